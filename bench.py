@@ -10,8 +10,14 @@ A "step" = one forward + one backward of that operator on every rank (grad reset
     python bench.py --gpus N --steps K --warmup W                      # launches its own N ranks (torch.distributed.run)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W   # or started as ranks
 
-Prints ONE JSON line (rank 0).  `value` = iterations/s of the whole job (max time over ranks).
-At every N the line carries
+Prints ONE JSON line (rank 0).  `value` = iterations/s of the whole job (max time over ranks), `ms_per_step` = the
+milliseconds of one timed step.  A plain run does only that: set-up, spin-up, warm-up, the timed steps, the line.
+    --dump-outputs DIR   after the timed steps, rank 0 writes what its last timed step returned to the caller (the
+                         output and the gradients of q and kv) as DIR/<name>.npy in float32; above 60 MB in all, the
+                         same fixed, seeded sample of token positions is kept from every array
+    --full               everything else the benchmark measures (below), after the timed steps
+With --full the line carries at every N
+  * `peak_device_memory_gib`, `power` (allocator peak and board power of the timed steps);
   * `roofline`   the dominant kernel (largest device time per launch) against the bf16 MFMA peak, timed with
                  HIP events INSIDE the real step at N = 1 (`kernels_in_step`: events between the launches of the
                  public function's own call sequence; their sum must stay below `ms_per_step`), and on this
@@ -21,7 +27,7 @@ At every N the line carries
                  (ring_flash_attn._testing.set_loopback), max over ranks;
   * `cpu_baseline` the CPU path on a bounded sample of the same workload on this box's host cores: N = 1 the oracle's
                  forward / backward ("port"); N > 1 the zigzag schedule over N gloo CPU processes with the oracle
-                 underneath (oracle/cpu_ring_baseline.py: the unmodified reference schedule where /root/reference
+                 underneath (oracle/cpu_ring_baseline.py: the unmodified reference schedule where the reference tree
                  exists — "reference" — else this repository's ring-form schedule — "port"), at the largest total
                  sequence the host finishes within --cpu-baseline-budget-s, stated in `sample`.
 Other rows of the reference's benchmark tables (README.md:82-98):
@@ -553,6 +559,31 @@ def comm_bytes_per_iter(mode, wire_fp32, world, hk):
     return (world - 1) * m + (world - 1) * contrib
 
 
+DUMP_MAX_BYTES = 60_000_000
+
+
+def dump_outputs(dirname, out, dq, dkv, seq_dim):
+    """--dump-outputs: what the caller of the timed path received in its last step, as float32 DIR/<name>.npy.  Above
+    DUMP_MAX_BYTES in all, every array keeps the same seeded sample of token positions (dimension `seq_dim`, sorted), so
+    that two builds run with the same arguments write arrays that compare element for element."""
+    import numpy as np
+
+    arrays = {"out": out, "q_grad": dq, "kv_grad": dkv}
+    arrays = {n: t.detach() for n, t in arrays.items() if t is not None}
+    total = sum(4 * t.numel() for t in arrays.values())
+    idx = None
+    if total > DUMP_MAX_BYTES:
+        n = out.shape[seq_dim]
+        keep = max(1, n * DUMP_MAX_BYTES // total)
+        idx = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:keep].sort().values
+        sys.stderr.write(f"bench.py: --dump-outputs keeps {keep} of {n} token positions (seeded sample)\n")
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        if idx is not None:
+            t = t.index_select(seq_dim, idx.to(t.device))
+        np.save(os.path.join(dirname, name + ".npy"), t.float().cpu().numpy())
+
+
 def free_port():
     import socket
 
@@ -604,7 +635,15 @@ def main():
     ap.add_argument("--cpu-baseline-budget-s", type=float, default=60.0,
                     help="N > 1: seconds the timed CPU sample may be predicted to take (picks the total sequence length)")
     ap.add_argument("--no-breakdown", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything beyond the headline: peak memory, board power, "
+                         "kernels in the step and roofline, the CPU baseline, and (N > 1) the exchange accounting")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (out, q_grad, kv_grad) to DIR/<name>.npy in float32 "
+                         "(rank 0; a fixed, seeded sample of token positions above 60 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.exchange:
         os.environ["RFA_ZIGZAG_EXCHANGE"] = args.exchange
     if args.wire:
@@ -702,22 +741,26 @@ def main():
     def step():
         if fwd_only:
             with torch.no_grad():
-                call(counter[0])
+                out = call(counter[0])
             counter[0] += 1
-            return
+            return out
         q.grad = None
         kv.grad = None
         out = call(counter[0])
         counter[0] += 1
         out.backward(dout)
+        return out
+
+    last = {}            # the output of the last step of the latest timed() (only that one is kept alive)
 
     def timed(n):
         torch.cuda.synchronize()
         dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for _ in range(n):
+        for _ in range(n - 1):
             step()
+        last["out"] = step()
         torch.cuda.synchronize()
         dist.barrier()
         torch.cuda.synchronize()
@@ -740,7 +783,7 @@ def main():
             tune_rep = tuning.autotune_zigzag_exchange(None, q.detach(), kd, vd, iters=3, warm=2)
         except Exception as e:           # (then the shape rule decides; the tuning step must never sink the benchmark)
             tune_rep = {"error": f"{type(e).__name__}: {e}"}
-    if multi:
+    if multi and args.full:
         from ring_flash_attn import tuning
 
         try:
@@ -777,19 +820,26 @@ def main():
     for _ in range(args.warmup):
         step()
     counter[0] = 0
-    torch.cuda.reset_peak_memory_stats(dev)
-    power = PowerSampler() if rank == 0 else None
+    if args.full:
+        torch.cuda.reset_peak_memory_stats(dev)
+    power = PowerSampler() if rank == 0 and args.full else None
     if power:
         power.start()
     elapsed = timed(args.steps)
     watts = power.stop() if power else (None, None, 0)
     if power:
         power.close()
-    # peak device memory of the timed steps (the reference names memory as its known limitation, README.md:154; the
-    # gather exchange form trades O(S_total) scratch for fewer transfers): allocator peak incl. the inputs, max over ranks
-    peak = torch.tensor([float(torch.cuda.max_memory_allocated(dev))], dtype=torch.float64, device=dev if multi else "cpu")
-    dist.all_reduce(peak, op=dist.ReduceOp.MAX)
-    peak_gib = peak.item() / 2 ** 30
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last["out"], None if fwd_only else q.grad, None if fwd_only else kv.grad,
+                     1 if wl in DENSE else 0)
+    last.clear()
+    peak_gib = None
+    if args.full:
+        # peak device memory of the timed steps (the reference names memory as its known limitation, README.md:154; the
+        # gather exchange form trades O(S_total) scratch for fewer transfers): allocator peak incl. the inputs, max over ranks
+        peak = torch.tensor([float(torch.cuda.max_memory_allocated(dev))], dtype=torch.float64, device=dev if multi else "cpu")
+        dist.all_reduce(peak, op=dist.ReduceOp.MAX)
+        peak_gib = peak.item() / 2 ** 30
 
     ms = elapsed / args.steps * 1e3
     its = args.steps / elapsed
@@ -822,18 +872,20 @@ def main():
             "world_size": world,
             "forward_only": fwd_only,
         },
-        "peak_device_memory_gib": round(peak_gib, 3),
-        # board power over the timed region (hwmon, a ~1 s moving average: meaningful from a few hundred ms of steps on)
-        # and the energy of one step: at the 1400 W cap the step's time IS its energy / 1400 W
-        # `valid`: the sensor is a ~1 s moving average — a timed region shorter than 0.5 s (the driver's --steps 20 is 0.04 s)
-        # reads the tail of whatever ran before it (1293 W where 200-step runs read 1385-1400 W: VERDICT r5 weak #11)
-        "power": ({"avg_w": round(watts[0], 1), "max_w": round(watts[1], 1), "samples": watts[2],
-                   "joules_per_step": round(watts[0] * elapsed / args.steps, 4), "source": "amdgpu hwmon power1_input",
-                   "timed_region_s": round(elapsed, 3), "valid": bool(elapsed >= 0.5)}
-                  if watts[0] is not None else None),
         "algorithmic_tflops_per_gpu": per_gpu_flops * its / 1e12,
         "mfma_roofline_frac_end_to_end": per_gpu_flops * its / 1e12 / MFMA_PEAK_TFLOPS,
     }
+    if args.full:
+        result["peak_device_memory_gib"] = round(peak_gib, 3)
+        # board power over the timed region (hwmon, a ~1 s moving average: meaningful from a few hundred ms of steps on)
+        # and the energy of one step: at the 1400 W cap the step's time IS its energy / 1400 W
+        # `valid`: the sensor is a ~1 s moving average — a timed region shorter than 0.5 s (--steps 20 is 0.04 s)
+        # reads the tail of whatever ran before it (1293 W where 200-step runs read 1385-1400 W: VERDICT r5 weak #11)
+        result["power"] = ({"avg_w": round(watts[0], 1), "max_w": round(watts[1], 1), "samples": watts[2],
+                            "joules_per_step": round(watts[0] * elapsed / args.steps, 4),
+                            "source": "amdgpu hwmon power1_input",
+                            "timed_region_s": round(elapsed, 3), "valid": bool(elapsed >= 0.5)}
+                           if watts[0] is not None else None)
 
     # ---- exchange accounting (N > 1): the same rank-local kernel sequence with the exchange looped back
     if forced:
@@ -841,7 +893,7 @@ def main():
     # (everything below is reporting: the measured line must survive a failure in it — it has only ever run on one GPU —
     #  so each block records its error under "errors" instead of ending the run; all ranks take the same path)
     errors = {}
-    if multi:
+    if multi and args.full:
         mode = exchange_mode(kv.detach()[:, :, 0], world, q.detach()) if wl == "zigzag" else {"llama3": "allgather+reduce_scatter"}.get(wl, "ring")
         comp = float("nan")
         rfa_testing.set_loopback((rank, world))
@@ -893,7 +945,7 @@ def main():
 
     # ---- kernel times INSIDE the step (every rank runs the instrumented steps: collectives must stay matched)
     instep = None
-    if not args.no_breakdown:
+    if args.full and not args.no_breakdown:
         from ring_flash_attn import backend as rfa_backend
 
         timer = InStepTimer(rfa_backend.get_backend())
@@ -1032,7 +1084,7 @@ def main():
                 result["backward_tflops"] = 2.5 * f / (bwd_ms * 1e-3) / 1e12
         except Exception as e:
             errors["roofline"] = f"{type(e).__name__}: {e}"
-    if rank == 0 and not args.no_cpu_baseline and wl in DENSE:
+    if rank == 0 and args.full and not args.no_cpu_baseline and wl in DENSE:
         # every N carries the CPU path next to the GPU number: N = 1 the oracle directly, N > 1 the
         # zigzag schedule over N gloo CPU processes (a one-rank forced-RCCL test line runs the two-rank form)
         try:
@@ -1042,7 +1094,7 @@ def main():
                 result["cpu_baseline"] = cpu_baseline(hk, args.cpu_baseline_full, fwd_only)
         except Exception as e:
             errors["cpu_baseline"] = f"{type(e).__name__}: {e}"
-    if rank == 0 and "roofline" not in result and not args.no_breakdown:
+    if rank == 0 and args.full and "roofline" not in result and not args.no_breakdown:
         # the contract's object, from the isolated launches of the local block when the in-step path failed
         try:
             with torch.no_grad():

@@ -1,5 +1,5 @@
-"""oracle/reference_harness.py — TEST INFRASTRUCTURE ONLY; usable only where /root/reference exists
-(the build container), never on the GPU box.
+"""oracle/reference_harness.py — TEST INFRASTRUCTURE ONLY; usable where build() has byte-compiled the reference
+modules into oracle/_ref/ (build_ref(), out of git), or where the reference tree itself exists.
 
 Loads the UNMODIFIED reference modules from /root/reference/ring_flash_attn under the private
 package name `ref_ring_flash_attn`:
@@ -15,10 +15,12 @@ Bytecode writing is disabled so nothing is dropped into the read-only reference 
 """
 import importlib
 import os
+import py_compile
 import sys
 import types
 
 REF_ROOT = os.environ.get("RFA_REFERENCE_ROOT", "/root/reference")
+REF_BUILD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_ref")     # build_ref()'s output
 
 _MODULES = [
     "utils",
@@ -31,8 +33,31 @@ _MODULES = [
 ]
 
 
+def _package_dir():
+    """the reference's package directory: the byte-compiled copy build_ref() made, else the reference tree, else None"""
+    for d, ext in ((os.path.join(REF_BUILD, "ring_flash_attn"), ".pyc"), (os.path.join(REF_ROOT, "ring_flash_attn"), ".py")):
+        if all(os.path.isfile(os.path.join(d, m + ext)) for m in _MODULES):
+            return d
+    return None
+
+
 def available():
-    return os.path.isdir(os.path.join(REF_ROOT, "ring_flash_attn"))
+    return _package_dir() is not None
+
+
+def build_ref():
+    """byte-compile the reference's algorithm modules (unmodified) into oracle/_ref/ring_flash_attn/<module>.pyc, so
+    that the tests load them from the repository tree; nothing to do where the reference tree is absent.  Returns the
+    output directory or None."""
+    src = os.path.join(REF_ROOT, "ring_flash_attn")
+    if not os.path.isdir(src):
+        return None
+    dst = os.path.join(REF_BUILD, "ring_flash_attn")
+    os.makedirs(dst, exist_ok=True)
+    for m in _MODULES:
+        py_compile.compile(os.path.join(src, m + ".py"), cfile=os.path.join(dst, m + ".pyc"), doraise=True,
+                           invalidation_mode=py_compile.PycInvalidationMode.UNCHECKED_HASH)
+    return dst
 
 
 def load_reference(provider="oracle"):
@@ -44,7 +69,7 @@ def load_reference(provider="oracle"):
     unmodified reference schedules through the shipped operator interface (fresh process only: the
     reference modules bind `flash_attn` at import time)."""
     if not available():
-        raise RuntimeError(f"reference tree not found at {REF_ROOT}")
+        raise RuntimeError(f"reference modules not found ({REF_BUILD}: run build(); or the tree at {REF_ROOT})")
     sys.dont_write_bytecode = True
     if provider == "shim":
         pkg_root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "ring-flash-attention_amd")
@@ -60,7 +85,7 @@ def load_reference(provider="oracle"):
 
     if "ref_ring_flash_attn" not in sys.modules:
         pkg = types.ModuleType("ref_ring_flash_attn")
-        pkg.__path__ = [os.path.join(REF_ROOT, "ring_flash_attn")]
+        pkg.__path__ = [_package_dir()]
         sys.modules["ref_ring_flash_attn"] = pkg
     return {m: importlib.import_module("ref_ring_flash_attn." + m) for m in _MODULES}
 

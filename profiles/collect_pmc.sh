@@ -18,7 +18,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 cd /tmp && export TMPDIR=/tmp
 OUT=$R/gpurun_out/prof
 mkdir -p $OUT
-BENCH="python $R/bench.py --gpus 1 --steps 200 --warmup 20 --no-cpu-baseline"
+BENCH="python $R/bench.py --gpus 1 --steps 200 --warmup 20 --full --no-cpu-baseline"
 SHORT="python $R/bench.py --gpus 1 --steps 8 --warmup 2 --no-cpu-baseline --no-breakdown"
 run() { name=$1; extra=$2; shift 2; rocprofv3 --kernel-trace --pmc "$@" -d $OUT/$name -o $name -- $SHORT $extra > $OUT/$name.log 2>&1; }
 run sq    "" SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS SQ_INSTS_VALU_MFMA_MOPS_BF16

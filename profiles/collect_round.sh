@@ -13,9 +13,9 @@ export HSA_ENABLE_IPC_MODE_LEGACY=0
 python -c "import sys; sys.path.insert(0,'ring-flash-attention_amd'); from ring_flash_attn import _C; print('build id', _C.load().rfa_build_id().decode())" > $O/build_id.txt 2>&1
 bash profiles/collect_pmc.sh $TAG > $O/collect_pmc.log 2>&1
 cp $R/gpurun_out/prof/${TAG}_* $O/ 2>/dev/null
-B="python bench.py --no-cpu-baseline"
-timeout 300 python bench.py > $O/${TAG}_bench_n1_default_flags.json 2> $O/bench.err
-timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/${TAG}_bench_n1_driver_command.json 2>> $O/bench.err
+B="python bench.py --full --no-cpu-baseline"
+timeout 300 python bench.py --full > $O/${TAG}_bench_n1_default_flags.json 2> $O/bench.err
+timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/${TAG}_bench_n1_driver_command.json 2>> $O/bench.err
 timeout 200 $B --kv-heads 32 > $O/${TAG}_bench_n1_mha.json 2>> $O/bench.err
 timeout 200 $B --forward-only > $O/${TAG}_bench_n1_forward_only.json 2>> $O/bench.err
 for wl in ring stripe ring_varlen zigzag_varlen llama3; do timeout 200 $B --workload $wl > $O/${TAG}_bench_n1_$wl.json 2>> $O/bench.err; done

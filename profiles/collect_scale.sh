@@ -32,7 +32,7 @@ else
   PROBE="python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port 29613 $R/tools/xgmi_probe.py"
 fi
 # bench.py launches its own N ranks (torch.distributed.run on 127.0.0.1 and a free port): the driver's command line
-BENCH="python $R/bench.py --gpus $N"
+BENCH="python $R/bench.py --gpus $N --full"
 # (round 6) every run first takes 2 AUDITED steps (--exchange-check-steps: each received K/V and dK/dV buffer checksummed
 # against its sender, ring_flash_attn.config.exchange_check) — this is the first execution of the RCCL orderings with more
 # than one rank, and a wrong exchange must fail with rank / step / buffer named instead of producing a fast wrong number

@@ -5,8 +5,10 @@ Targets (all in-tree, so the artefacts travel with the repo snapshot to the GPU 
   lib      ring-flash-attention_amd/ring_flash_attn/librfa_hip.so   hipcc, HIP kernels + C ABI
   oracle   oracle/libattn_ref.so                                     gcc -fopenmp, CPU checker
   selftest tests/native/selftest                                     hipcc, torch-free GPU test
+  ref      oracle/_ref/ring_flash_attn/*.pyc                         the reference's modules, byte-compiled (tests only;
+                                                                     skipped where the reference tree is absent)
 
-`python ring-flash-attention_amd/build.py [lib] [oracle] [selftest] [--force]`
+`python ring-flash-attention_amd/build.py [lib] [oracle] [selftest] [ref] [--force]`
 hipcc cross-compiles for gfx950 without a GPU, so this runs in the build container.
 """
 import hashlib
@@ -109,6 +111,15 @@ def build_selftest(force=False):
     return SELFTEST_BIN
 
 
+def build_ref(force=False):
+    """oracle/reference_harness.build_ref(): the unmodified reference modules the CPU tests run, compiled into the tree"""
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    from oracle import reference_harness
+
+    return reference_harness.build_ref()
+
+
 def main(argv):
     force = "--force" in argv
     targets = [a for a in argv if not a.startswith("-")] or ["lib", "oracle"]
@@ -116,7 +127,7 @@ def main(argv):
         if t == "lib":
             build_lib(force)
         else:
-            {"oracle": build_oracle, "selftest": build_selftest}[t](force)
+            {"oracle": build_oracle, "selftest": build_selftest, "ref": build_ref}[t](force)
 
 
 if __name__ == "__main__":

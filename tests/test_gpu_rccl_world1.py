@@ -33,7 +33,7 @@ def test_bench_multi_rank_branches_on_rccl_world_size_1(workload, exchange):
     env["RFA_BENCH_FORCE_RCCL"] = "1"
     env["MASTER_PORT"] = str(__import__("conftest").free_port())
     cmd = [sys.executable, os.path.join(os.path.dirname(HERE), "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-           "--no-breakdown", "--workload", workload]
+           "--full", "--no-breakdown", "--workload", workload]
     # the N > 1 line's CPU baseline (the zigzag schedule over gloo CPU processes, oracle/cpu_ring_baseline.py) rides on one
     # of the cases, with a budget that keeps it to the 2048-token probe
     cmd += ["--cpu-baseline-budget-s", "1"] if exchange == "gather" else ["--no-cpu-baseline"]

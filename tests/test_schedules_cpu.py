@@ -378,14 +378,14 @@ def test_schedules_under_torch_compile_at_world_size_gt_1(W, monkeypatch):
 
 
 def test_unmodified_reference_runs_on_the_flash_attn_shim():
-    """INTEGRATION.md route B: the reference's own schedule code (loaded unmodified from /root/reference)
-    on top of the shipped `flash_attn` compatibility package reproduces the golden vectors.  Build
-    container only (the reference tree does not travel); the kernels underneath are the CPU oracle
-    here — the same shim over the HIP kernels is covered by tests/test_gpu_flash_attn_shim.py."""
+    """INTEGRATION.md route B: the reference's own schedule code (loaded unmodified: the modules build() byte-compiled
+    into oracle/_ref/) on top of the shipped `flash_attn` compatibility package reproduces the golden vectors.  The
+    kernels underneath are the CPU oracle here — the same shim over the HIP kernels is covered by
+    tests/test_gpu_flash_attn_shim.py."""
     from oracle import reference_harness
 
     if not reference_harness.available():
-        pytest.skip("/root/reference not present")
+        pytest.skip("the reference's modules are not built (oracle/_ref/: build() found no reference tree)")
     names = [n for n, c in MG.CASES.items() if c["W"] == 2]
     errs = RW.run_world(2, names, use_hip=False, port=free_port(), via_reference=True)
     assert not errs, "\n".join(errs)

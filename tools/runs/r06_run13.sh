@@ -4,7 +4,7 @@ timeout 600 python tools/bal_check.py 2,8192,32,8 1,8192,64,8 1,8192,32,16 4,409
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 RFA_DKDV_WIDE=2 timeout 300 rocprofv3 --kernel-trace --stats -d $O/prof_bal -o run -- python tools/shape_sweep.py 1,8192,32,8,128,1 > $O/prof_bal.log 2>&1
 python profiles/summarize_rocpd.py $(find $O/prof_bal -name '*.db' | head -1) > $O/prof_bal.txt 2>&1; rm -rf $O/prof_bal; head -8 $O/prof_bal.txt
-timeout 300 python bench.py --steps 200 --warmup 10 --no-cpu-baseline > $O/bench_bal.json 2> $O/bench_bal.err; echo "bench rc $?"; python - <<'P'
+timeout 300 python bench.py --full --steps 200 --warmup 10 --no-cpu-baseline > $O/bench_bal.json 2> $O/bench_bal.err; echo "bench rc $?"; python - <<'P'
 import json
 d=json.loads(open('gpurun_out/r06b/bench_bal.json').read().strip().splitlines()[-1])
 print(d['value'], d['ms_per_step'], d['kernels_in_step']['ms'], d['roofline']['frac'], d['power'])
