@@ -36,7 +36,8 @@
  *     (B, H, Sq).  Varlen mode: q is (Tq, H, D), k/v (Tk, Hk, D), lse is (H, Tq); `B` is the
  *     number of packed sequences, `Sq`/`Sk` the max sequence lengths, *_batch strides unused.
  *   - Causal masks are bottom-right aligned: key j is visible to query i iff
- *     j <= i + (len_k - len_q)  (flash_attn >= 2.1 semantics).
+ *     j <= i + (len_k - len_q)  (flash_attn >= 2.1 semantics); `mask_shift` (ABI 7) moves the diagonal for a block
+ *     of a longer sequence.
  *   - Rows with no visible key produce out = 0 and lse = +inf (flash_attn semantics); in
  *     accumulate mode such rows leave the accumulators untouched.
  *   - `q_half` / `k_half` select, per packed (or dense) sequence, the whole sequence (0), its
@@ -54,7 +55,7 @@
 extern "C" {
 #endif
 
-#define RFA_ABI_VERSION 6
+#define RFA_ABI_VERSION 7
 
 typedef enum {
   RFA_OK = 0,
@@ -151,6 +152,20 @@ typedef struct {
   void *workspace;
   int32_t kv_nsplit;
   int64_t total_q;
+  /* ABI 7 — where this block sits in a longer sequence.  The band of the call (the plain causal bound included) becomes
+   *     i + (len_k - len_q) + mask_shift - window_left <= j <= i + (len_k - len_q) + mask_shift + window_right ,
+   * mask_shift = (global position of q row 0 + len_q) - (global position of k row 0 + len_k); for blocks of equal length
+   * simply q_start - k_start.  A rank of a ring that holds rows [rS, (r+1)S) and has the K/V of rank r - d on hand passes
+   * d * S and gets its share of ONE sliding-window attention over the whole sequence.  0 (a zero-initialised struct): the
+   * block's own diagonal, as before.  Ignored without `causal` and without `window`.  Dense input without dropout only
+   * (cu_seqlens != NULL or dropout_p > 0 with a non-zero shift: RFA_ERR_ARGS).  Any 64-bit value is accepted: the library
+   * normalises the band before it plans or launches — a bound no element of the block can reach is
+   * dropped, so a block wholly inside the window IS the unwindowed non-causal call (same instance, plan and dS-spill
+   * form, bit for bit); a block with no visible element launches nothing in accumulate mode and writes out = 0,
+   * lse = +inf / zero gradients in plain mode; what is left is re-expressed in numbers that fit the kernels' 32 bits.
+   * The persistent forward, the balanced dK/dV schedule and split-KV plans keyed on the block's own diagonal decline a
+   * shifted causal band; the triangular ds_scratch layout follows it. */
+  int64_t mask_shift;
 } rfa_fwd_args;
 
 enum { RFA_FWD_AUTO = 0, RFA_FWD_8x32 = 1, RFA_FWD_RETIRED_2 = 2, RFA_FWD_4x32 = 3, RFA_FWD_P8x32 = 4 };
@@ -248,6 +263,8 @@ typedef struct {
    * H * (total_q / 32 + B) * ceil(max_seqlen_k / 32) blocks of 2 KiB — bounded by the packed row count, not by
    * B x the longest sequence. */
   int64_t total_q;
+  /* ABI 7: as in rfa_fwd_args, with the forward's value */
+  int64_t mask_shift;
 } rfa_bwd_args;
 
 enum { RFA_DKDV_AUTO = 0, RFA_DKDV_128 = 1, RFA_DKDV_256 = 2, RFA_DKDV_BAL = 3 };

@@ -48,6 +48,69 @@ inline float drop_rescale(float p) {
   const unsigned k = drop_threshold(p);
   return k >= 256u ? 1.f : (k == 0u ? 0.f : 256.f / (float)k);
 }
+// ---- band normalisation (dense input) ------------------------------------------------------------------------------
+// A call's band is  i + off - wl <= j <= i + off + wr  with off = len_k - len_q + mask_shift (rfa.h).  Before anything is
+// planned or launched it is brought to a canonical form, so that blocks of a sharded sequence that differ only in how far
+// they lie from the diagonal run what an equivalent unsharded call would:
+//   * a left bound no row can reach (row len_q - 1 already starts at key <= 0) and a right bound row 0 already clears
+//     (off + wr >= len_k - 1) are dropped — a block wholly inside the window IS the unwindowed non-causal call: same
+//     instance, same plan, same dS-spill form, bit for bit;
+//   * a block no element of which is visible is flagged `empty` and given ONE canonical band (nothing visible, small
+//     numbers) for the callers that still have to write zeros;
+//   * what is left is re-expressed with small numbers where the caller's are large (the kernels keep off, off - wl and
+//     off + wr in 32 bits): only the two edges off - wl and off + wr matter, and for a non-empty block with live bounds both
+//     lie inside (-len_q, len_k).
+// Packed (cu_seqlens) input is not normalised — the lengths live on the device — and takes no shift (RFA_ERR_ARGS).
+struct Band { int causal, window, wl, wr; int64_t shift; bool empty; };
+inline int dense_len(int S, int half) { return half == RFA_HALF_FULL ? S : (half == RFA_HALF_FRONT ? S / 2 : S - S / 2); }
+inline Band norm_band(int Sq, int q_half, int Sk, int k_half, int causal, int window, int wl_in, int wr_in, int64_t shift) {
+  Band b{causal ? 1 : 0, window ? 1 : 0, wl_in, wr_in, 0, false};
+  int64_t wl = (window && wl_in >= 0) ? wl_in : -1;
+  int64_t wr = causal ? 0 : ((window && wr_in >= 0) ? wr_in : -1);
+  if (wl < 0 && wr < 0) return Band{0, 0, -1, -1, 0, false};          // no band: the shift is ignored
+  const int64_t lq = dense_len(Sq, q_half), lk = dense_len(Sk, k_half);
+  if (lq <= 0 || lk <= 0) { b.shift = 0; return b; }                  // (nothing to compute: the callers' own early returns)
+  const int64_t off = lk - lq + shift;
+  bool changed = false;
+  if (wl >= 0 && lq - 1 + off - wl <= 0) { wl = -1; changed = true; }
+  if (wr >= 0 && off + wr >= lk - 1) { wr = -1; changed = true; }
+  if ((wr >= 0 && lq - 1 + off + wr < 0) || (wl >= 0 && off - wl > lk - 1))
+    return Band{0, 1, -1, 0, -lk, true};                              // off' = -len_q, wr = 0: row i would see keys <= i - len_q
+  if (wl < 0 && wr < 0) return Band{0, 0, -1, -1, 0, false};
+  const int64_t big = (int64_t)1 << 28;
+  int64_t s = shift;
+  if (off > big || off < -big || wl > big || wr > big) {
+    // same two edges, small numbers: anchored at the live right edge (wr = 0, so a causal call stays one), else at the left
+    const int64_t lo_e = off - wl, hi_e = off + wr;
+    if (wr >= 0) { s = hi_e - (lk - lq); if (wl >= 0) wl = hi_e - lo_e; wr = 0; }
+    else { s = lo_e - (lk - lq); wl = 0; }
+    changed = true;
+  }
+  if (!changed) { b.shift = shift; return b; }                        // (the caller's own fields, untouched)
+  const int c = (causal && wr >= 0) ? 1 : 0;                          // (causal: wr was 0 and the bound is still live)
+  return Band{c, (wl >= 0 || (wr >= 0 && !c)) ? 1 : 0, (int)wl, (int)wr, s, false};
+}
+// the call with its band normalised (what every plan / size / launch below looks at)
+template <typename A>
+inline A norm_args(const A& a) {
+  A n = a;
+  if (a.cu_seqlens_q != nullptr || a.cu_seqlens_k != nullptr || a.dropout_p > 0.f) return n;   // (dropout: no window, no shift)
+  const Band b = norm_band(a.Sq, a.q_half, a.Sk, a.k_half, a.causal, a.window, a.window_left, a.window_right, a.mask_shift);
+  n.causal = b.causal; n.window = b.window; n.window_left = b.wl; n.window_right = b.wr; n.mask_shift = b.shift;
+  return n;
+}
+template <typename A>
+inline bool band_empty(const A& a) {
+  if (a.cu_seqlens_q != nullptr || a.cu_seqlens_k != nullptr || a.dropout_p > 0.f) return false;
+  return norm_band(a.Sq, a.q_half, a.Sk, a.k_half, a.causal, a.window, a.window_left, a.window_right, a.mask_shift).empty;
+}
+// a shift needs dense input and no dropout (the keep mask has position offsets of its own)
+template <typename A>
+inline bool shift_args_ok(const A& a) {
+  if (a.mask_shift == 0) return true;
+  return a.cu_seqlens_q == nullptr && a.cu_seqlens_k == nullptr && !(a.dropout_p > 0.f);
+}
+
 inline bool drop_args_ok(float p, int window, int wl, int wr, int causal) {
   if (!(p >= 0.f) || p >= 1.f) return false;
   const bool win = window && (wl >= 0 || (wr >= 0 && !causal));
@@ -190,6 +253,7 @@ static bool fwd_persist_eligible(const rfa_fwd_args* a) {
   if (a->D != kHeadDim || a->cu_seqlens_q != nullptr || a->out_acc != nullptr || a->dropout_p > 0.f) return false;
   if (a->window && (a->window_left >= 0 || (a->window_right >= 0 && !a->causal))) return false;
   if (a->B <= 0 || a->Sq <= 0 || a->Sk <= 0) return false;
+  if (a->mask_shift != 0) return false;                      // (its item deal and 'off >= 0' assume the block's own diagonal)
   return eff_len(a->Sk, a->k_half) >= eff_len(a->Sq, a->q_half);
 }
 static FwdPlan fwd_plan_base(const rfa_fwd_args* a);
@@ -294,7 +358,7 @@ static FwdPlan fwd_plan_base(const rfa_fwd_args* a) {
   }
   pl.rows = 256;
   if (!can_split) return pl;
-  const int64_t key[8] = {1, a->B, a->H, sq, sk, a->causal ? 1 : 0, 0, 0};
+  const int64_t key[8] = {1, a->B, a->H, sq, sk, a->causal ? 1 : 0, a->causal ? a->mask_shift : 0, 0};
   const uint64_t h = plan_hash(key, 8);
   int code;
   if (plan_lookup(h, &code)) {
@@ -302,7 +366,7 @@ static FwdPlan fwd_plan_base(const rfa_fwd_args* a) {
     return pl;
   }
   // workgroups of the 256-row form: block i of every (batch, head) sees the key tiles below its causal edge
-  const int off = sk - sq, nq = (sq + 255) / 256;
+  const int off = sk - sq + (int)a->mask_shift, nq = (sq + 255) / 256;
   const int64_t mult = (int64_t)a->B * a->H;
   double best = -1;
   static const int cand[] = {1, 2, 3, 4, 6, 8};
@@ -340,7 +404,9 @@ static int64_t fwd_rows_total(const rfa_fwd_args* a) {
 
 int64_t rfa_fwd_workspace_bytes(const rfa_fwd_args* a, int32_t* nsplit) {
   if (nsplit) *nsplit = 1;
-  if (!a || check_common(a->dtype, a->H, a->Hk, a->D, a->B)) return 0;
+  if (!a || check_common(a->dtype, a->H, a->Hk, a->D, a->B) || !shift_args_ok(*a)) return 0;
+  const rfa_fwd_args na = norm_args(*a);
+  a = &na;
   const int ns = fwd_kv_nsplit(a);
   const int64_t rows = fwd_rows_total(a);
   if (ns <= 1 || rows <= 0) return 0;
@@ -362,6 +428,12 @@ int rfa_fwd(const rfa_fwd_args* a, void* stream) {
   }
   if ((a->cu_seqlens_q == nullptr) != (a->cu_seqlens_k == nullptr)) return RFA_ERR_ARGS;
   if (!drop_args_ok(a->dropout_p, a->window, a->window_left, a->window_right, a->causal)) return RFA_ERR_ARGS;
+  if (!shift_args_ok(*a)) return RFA_ERR_ARGS;
+  // a block with no visible element: accumulate mode has nothing to merge; plain mode (and the first block of a ring)
+  // runs the canonical empty band, whose workgroups load no tile and write out = 0, lse = +inf (-inf into lse_acc)
+  if (a->out_acc && !a->acc_init && a->Sk > 0 && band_empty(*a)) return RFA_OK;
+  const rfa_fwd_args na = norm_args(*a);
+  a = &na;
   if (!aligned16(a->q) || !aligned16(a->k) || !aligned16(a->v)) return RFA_ERR_ALIGN;
   if (!stride_ok(a->q_st, 2) || !stride_ok(a->k_st, 2) || !stride_ok(a->v_st, 2)) return RFA_ERR_ALIGN;
   if (a->out_acc) {
@@ -383,6 +455,7 @@ int rfa_fwd(const rfa_fwd_args* a, void* stream) {
   p.causal = a->causal ? 1 : 0; p.acc_init = a->acc_init ? 1 : 0;
   p.wl = (a->window && a->window_left >= 0) ? a->window_left : -1;
   p.wr = a->causal ? 0 : ((a->window && a->window_right >= 0) ? a->window_right : -1);
+  p.shift = (p.causal || p.wl >= 0 || p.wr >= 0) ? (int)a->mask_shift : 0;
   p.scale = a->softmax_scale;
   p.drop_keep = drop_threshold(a->dropout_p);
   p.drop_scale = drop_rescale(a->dropout_p);
@@ -492,7 +565,7 @@ static int bwd_dkdv_cost_plan(const rfa_bwd_args* a, int hk_launch, bool only_wi
   }
   const bool big = a->D > kHeadDim;          // rfa_bigd.hip: 128-key workgroups (one wave per SIMD), 32-row Q/dO tiles; ONE form
   const int G = a->H / a->Hk;
-  const int64_t key[8] = {2, a->B, hk_launch, G, sq, sk, a->causal ? 1 : 0, (big ? 4 : 0) | (a->D == 64 ? 2 : 0) | (only_wide ? 1 : 0)};
+  const int64_t key[8] = {2 + 16 * (a->causal ? a->mask_shift : 0), a->B, hk_launch, G, sq, sk, a->causal ? 1 : 0, (big ? 4 : 0) | (a->D == 64 ? 2 : 0) | (only_wide ? 1 : 0)};
   const uint64_t h = plan_hash(key, 8);
   int code;
   if (plan_lookup(h, &code)) {
@@ -501,7 +574,7 @@ static int bwd_dkdv_cost_plan(const rfa_bwd_args* a, int hk_launch, bool only_wi
     return (code >> 4) & 1;
   }
   if (bal_out) *bal_out = 0;
-  const int off = sk - sq;
+  const int off = sk - sq + (int)a->mask_shift;
   const int64_t mult = (int64_t)a->B * hk_launch;
   const int trows = big ? 32 : 64;
   const int ntq = (sq + trows - 1) / trows;
@@ -560,7 +633,7 @@ static int bwd_dkdv_cost_plan(const rfa_bwd_args* a, int hk_launch, bool only_wi
   // B * Hk * nkb equal workgroups of (T/2 + 2) G tile-times; half of them cross one key-block seam (a second prologue /
   // epilogue) and every pair exchanges one partial: 14 tile-times of overhead on average instead of 8, no second pass
   int bal = 0;
-  if (!only_wide && !big && a->causal && sq == sk && sk >= 512 && sk % 512 == 0) {
+  if (!only_wide && !big && a->causal && a->mask_shift == 0 && sq == sk && sk >= 512 && sk % 512 == 0) {
     const int nkb = sk / 256;
     std::vector<int> sizes((size_t)(mult * nkb), (2 * nkb + 2) * G);
     double work = 0;
@@ -583,6 +656,7 @@ static int bwd_dkdv_cost_plan(const rfa_bwd_args* a, int hk_launch, bool only_wi
 static bool bwd_bal_eligible(const rfa_bwd_args* a, bool whole_call) {
   if ((a->D != kHeadDim && a->D != 64) || !a->causal || a->cu_seqlens_q != nullptr || a->dropout_p > 0.f) return false;
   if (a->window && (a->window_left >= 0 || a->window_right >= 0)) return false;
+  if (a->mask_shift != 0) return false;        // (the tile deal assumes the block's own diagonal)
   const int lq = eff_len(a->Sq, a->q_half), lk = eff_len(a->Sk, a->k_half);
   if (lq != lk || lk < 512 || (lk % 512) != 0) return false;
   if (!bwd_single_phase(a) || (a->phases & (RFA_BWD_SKIP_DKDV | RFA_BWD_SKIP_DQ))) return false;
@@ -659,7 +733,7 @@ static bool bwd_spill_eligible(const rfa_bwd_args* a) {
 static int bwd_ds_c(const rfa_bwd_args* a) {
   const int nkb = ds_blocks(a->Sk, a->k_half);
   if (!a->causal || a->cu_seqlens_q != nullptr) return nkb;
-  const int off = eff_len(a->Sk, a->k_half) - eff_len(a->Sq, a->q_half);
+  const int off = eff_len(a->Sk, a->k_half) - eff_len(a->Sq, a->q_half) + (int)a->mask_shift;   // (the triangle follows the shifted band)
   const int c = ((31 + off) >> 5) + 1;                   // (arithmetic shift: off may be negative)
   return c > nkb ? nkb : c;
 }
@@ -680,15 +754,24 @@ static int64_t bwd_ds_head_bytes(const rfa_bwd_args* a) {
   return (a->cu_seqlens_q != nullptr ? 1 : (int64_t)a->B) * bwd_ds_head_blocks(a) * kDsBlockBytes;
 }
 
-int64_t rfa_bwd_ds_scratch_bytes(const rfa_bwd_args* a) {
-  if (!a || !bwd_spill_eligible(a)) return 0;
+static int64_t bwd_ds_scratch_bytes(const rfa_bwd_args* a) {
+  if (!bwd_spill_eligible(a)) return 0;
   return (int64_t)a->H * bwd_ds_head_bytes(a);
 }
 
+int64_t rfa_bwd_ds_scratch_bytes(const rfa_bwd_args* a) {
+  if (!a || !shift_args_ok(*a)) return 0;
+  const rfa_bwd_args na = norm_args(*a);
+  return bwd_ds_scratch_bytes(&na);
+}
+
 int64_t rfa_bwd_ds_scratch_min_bytes(const rfa_bwd_args* a) {
-  if (!a || !bwd_spill_eligible(a)) return 0;
+  if (!a || !shift_args_ok(*a)) return 0;
+  const rfa_bwd_args na = norm_args(*a);
+  a = &na;
+  if (!bwd_spill_eligible(a)) return 0;
   // head dim 256 (rfa_bigd.hip) has no chunked form; two-phase calls (COMPUTE / REDUCE) chunk by whole K/V heads only
-  if (a->D != kHeadDim) return rfa_bwd_ds_scratch_bytes(a);
+  if (a->D != kHeadDim) return bwd_ds_scratch_bytes(a);
   const int G = a->H / a->Hk;
   return (bwd_single_phase(a) ? 1 : G) * bwd_ds_head_bytes(a);
 }
@@ -724,6 +807,9 @@ static DsChunks bwd_ds_chunking(const rfa_bwd_args* a) {
 int rfa_bwd_ds_chunks(const rfa_bwd_args* a, int32_t* nchunks, int32_t* kv_heads, int32_t* q_heads, int64_t* chunk_bytes) {
   if (!a) return RFA_ERR_NULL;
   if (int rc = check_common(a->dtype, a->H, a->Hk, a->D, a->B)) return rc;
+  if (!shift_args_ok(*a)) return RFA_ERR_ARGS;
+  const rfa_bwd_args na = norm_args(*a);
+  a = &na;
   const DsChunks ch = bwd_ds_chunking(a);
   if (nchunks) *nchunks = ch.nchunks;
   if (kv_heads) *kv_heads = ch.hc;
@@ -734,6 +820,9 @@ int rfa_bwd_ds_chunks(const rfa_bwd_args* a, int32_t* nchunks, int32_t* kv_heads
 
 int rfa_bwd_plan(const rfa_bwd_args* a, int32_t* form, int32_t* nsplit, int32_t* five_gemm) {
   if (!a) return RFA_ERR_NULL;
+  if (!shift_args_ok(*a)) return RFA_ERR_ARGS;
+  const rfa_bwd_args na = norm_args(*a);
+  a = &na;
   const DkdvPlan pl = bwd_dkdv_plan(a);
   if (form) *form = pl.bal ? RFA_DKDV_BAL : pl.wide ? RFA_DKDV_256 : RFA_DKDV_128;
   if (nsplit) *nsplit = pl.nsplit;
@@ -744,7 +833,10 @@ int rfa_bwd_plan(const rfa_bwd_args* a, int32_t* form, int32_t* nsplit, int32_t*
 static int64_t bal_flag_bytes(int64_t pairs) { return (pairs * 4 + 255) / 256 * 256; }
 
 int64_t rfa_bwd_workspace_bytes(const rfa_bwd_args* a) {
-  if (!a || !bwd_needs_ws(a)) return 0;
+  if (!a || !shift_args_ok(*a)) return 0;
+  const rfa_bwd_args na = norm_args(*a);
+  a = &na;
+  if (!bwd_needs_ws(a)) return 0;
   // balanced schedule: one fp32 pair slot (dK + dV accumulators of 256 keys) per key block of the lower half of every
   // (batch, K/V head) + one flag word per pair (rounded up to 256 bytes, in front of the slots)
   if (bwd_dkdv_plan(a).bal) {
@@ -770,6 +862,17 @@ int rfa_bwd(const rfa_bwd_args* a, void* stream) {
   if ((a->cu_seqlens_q == nullptr) != (a->cu_seqlens_k == nullptr)) return RFA_ERR_ARGS;
   if (a->dkdv_form < RFA_DKDV_AUTO || a->dkdv_form > RFA_DKDV_BAL || a->dkdv_nsplit < 0) return RFA_ERR_ARGS;
   if (!drop_args_ok(a->dropout_p, a->window, a->window_left, a->window_right, a->causal)) return RFA_ERR_ARGS;
+  if (!shift_args_ok(*a)) return RFA_ERR_ARGS;
+  // a block with no visible element adds nothing to accumulators (either phase of a two-phase call); where something has
+  // to be written — plain outputs, overwritten accumulators — the kernels run the canonical empty band and store zeros
+  if (a->dq_acc && a->dk_acc && !a->acc_init && !(a->phases & RFA_BWD_KV_OVERWRITE) && band_empty(*a)) {
+    if (a->prof_events)
+      for (int i = 0; i < 4; ++i)
+        if (a->prof_events[i]) (void)hipEventRecord((hipEvent_t)a->prof_events[i], (hipStream_t)stream);
+    return RFA_OK;
+  }
+  const rfa_bwd_args na = norm_args(*a);
+  a = &na;
   const bool ws = bwd_needs_ws(a);
   if (ws && !a->workspace) return RFA_ERR_NULL;
   if (!aligned16(a->dout) || !aligned16(a->q) || !aligned16(a->k) || !aligned16(a->v))
@@ -798,6 +901,7 @@ int rfa_bwd(const rfa_bwd_args* a, void* stream) {
   p.causal = a->causal ? 1 : 0; p.acc_init = a->acc_init ? 1 : 0;
   p.wl = (a->window && a->window_left >= 0) ? a->window_left : -1;
   p.wr = a->causal ? 0 : ((a->window && a->window_right >= 0) ? a->window_right : -1);
+  p.shift = (p.causal || p.wl >= 0 || p.wr >= 0) ? (int)a->mask_shift : 0;
   p.scale = a->softmax_scale;
   p.drop_keep = drop_threshold(a->dropout_p);
   p.drop_scale = drop_rescale(a->dropout_p);

@@ -147,7 +147,7 @@ __global__ __launch_bounds__(kBgThreads) void fwd_big_kernel(const FwdParams p) 
   const int lq = qs.len, lk = ks.len;
   const int qwg0 = qblk * kBgRows;
   if (qwg0 >= lq) return;
-  const int off = lk - lq;
+  const int off = lk - lq + p.shift;       // bottom-right alignment, moved by the block's place in the full sequence (rfa.h: mask_shift)
   const int qw0 = qwg0 + wave * 32;
   const int qrow = qw0 + l31;
   const int qrow_c = qrow < lq ? qrow : lq - 1;
@@ -174,8 +174,9 @@ __global__ __launch_bounds__(kBgThreads) void fwd_big_kernel(const FwdParams p) 
   if (hi && qend + off + wr < kmax) kmax = qend + off + wr;
   const int ntiles = kmax > 0 ? (kmax + kBgKV - 1) / kBgKV : 0;
   int kmin = lo ? qwg0 + off - wl : 0;
-  kmin = kmin > 0 ? kmin : 0;
+  kmin = kmin > 0 ? (kmin < lk ? kmin : lk) : 0;          // (a shifted band may start behind the last key)
   const int jt0 = kmin / kBgKV;
+  if (jt0 >= ntiles && p.out_acc != nullptr && !p.acc_init) return;  // rows wholly outside the band: nothing to merge
 
   int voff_k[kBgKV / 8], voff_v[kBgKV / 8];
   big_dma_offsets<kBgKV>(wave, lane, (int)p.k_st.row, p.D, voff_k);
@@ -418,7 +419,7 @@ __global__ __launch_bounds__(kBgThreads) void dq_big_kernel(const BwdParams p) {
   const int lq = qs.len, lk = ks.len;
   const int qwg0 = qblk * kBgRows;
   if (qwg0 >= lq) return;
-  const int off = lk - lq;
+  const int off = lk - lq + p.shift;       // bottom-right alignment, moved by the block's place in the full sequence (rfa.h: mask_shift)
   const int qw0 = qwg0 + wave * 32;
   const int qrow = qw0 + l31;
   const int qrow_c = qrow < lq ? qrow : lq - 1;
@@ -450,8 +451,9 @@ __global__ __launch_bounds__(kBgThreads) void dq_big_kernel(const BwdParams p) {
   if (hi && qend + off + wr < kmax) kmax = qend + off + wr;
   const int ntiles = kmax > 0 ? (kmax + kBgKV - 1) / kBgKV : 0;
   int kmin = lo ? qwg0 + off - wl : 0;
-  kmin = kmin > 0 ? kmin : 0;
+  kmin = kmin > 0 ? (kmin < lk ? kmin : lk) : 0;          // (a shifted band may start behind the last key)
   const int jt0 = kmin / kBgKV;
+  if (jt0 >= ntiles && p.dq_acc != nullptr && !p.acc_init) return;   // rows wholly outside the band add nothing to dq_acc
 
   int voff_k[kBgKV / 8], voff_v[kBgKV / 8];
   big_dma_offsets<kBgKV>(wave, lane, (int)p.k_st.row, p.D, voff_k);
@@ -642,7 +644,7 @@ __global__ __launch_bounds__(kBgThreads) void dkdv_big_kernel(const BwdParams p)
   const int lq = qs.len, lk = ks.len;
   const int kwg0 = kblk * kBgRows;
   if (kwg0 >= lk) return;
-  const int off = lk - lq;
+  const int off = lk - lq + p.shift;       // bottom-right alignment, moved by the block's place in the full sequence (rfa.h: mask_shift)
   const int kw0 = kwg0 + wave * 32;
   const int krow = kw0 + l31;
   const int64_t qbatch = p.cu_q ? 0 : (int64_t)b;
@@ -662,10 +664,11 @@ __global__ __launch_bounds__(kBgThreads) void dkdv_big_kernel(const BwdParams p)
   int qfirst = 0;
   if (hi) {
     qfirst = kwg0 - off - wr;
-    if (qfirst < 0) qfirst = 0;
+    qfirst = qfirst < 0 ? 0 : (qfirst < lq ? qfirst : lq);   // (a shifted band may start behind the last query row ...)
   }
   int qlast = lq;
   if (lo && kwg0 + kBgRows - off + wl < qlast) qlast = kwg0 + kBgRows - off + wl;
+  if (qlast < 0) qlast = 0;                    // (... or end in front of the first)
   const int jt0 = qfirst / kBgQ;
   int jt1 = (qlast + kBgQ - 1) / kBgQ;
   if (jt1 <= jt0) jt1 = jt0;
@@ -984,7 +987,7 @@ __global__ __launch_bounds__(kBgThreads) void dkdv_fused_big_kernel(const BwdPar
   const int lq = qs.len, lk = ks.len;
   const int kwg0 = kblk * kBgRows;
   if (kwg0 >= lk) return;
-  const int off = lk - lq;
+  const int off = lk - lq + p.shift;       // bottom-right alignment, moved by the block's place in the full sequence (rfa.h: mask_shift)
   const int kw0 = kwg0 + wave * 32;
   const int krow = kw0 + l31;
   const int64_t qbatch = p.cu_q ? 0 : (int64_t)b;
@@ -1004,10 +1007,11 @@ __global__ __launch_bounds__(kBgThreads) void dkdv_fused_big_kernel(const BwdPar
   int qfirst = 0;
   if (hi) {
     qfirst = kwg0 - off - wr;
-    if (qfirst < 0) qfirst = 0;
+    qfirst = qfirst < 0 ? 0 : (qfirst < lq ? qfirst : lq);   // (a shifted band may start behind the last query row ...)
   }
   int qlast = lq;
   if (lo && kwg0 + kBgRows - off + wl < qlast) qlast = kwg0 + kBgRows - off + wl;
+  if (qlast < 0) qlast = 0;                    // (... or end in front of the first)
   const int jt0 = qfirst / kBgQ;
   int jt1 = (qlast + kBgQ - 1) / kBgQ;
   if (jt1 <= jt0) jt1 = jt0;

@@ -125,7 +125,7 @@ __global__ __launch_bounds__(kDqThreads, 2) void dq_kernel(const BwdParams p) {
   const int lq = qs.len, lk = ks.len;
   const int qwg0 = qblk * kDqRows;
   if (qwg0 >= lq) return;
-  const int off = lk - lq;
+  const int off = lk - lq + p.shift;       // bottom-right alignment, moved by the block's place in the full sequence (rfa.h: mask_shift)
   const int qw0 = qwg0 + wave * 32;
   const int qrow = qw0 + l31;
   const int qrow_c = qrow < lq ? qrow : lq - 1;
@@ -160,8 +160,10 @@ __global__ __launch_bounds__(kDqThreads, 2) void dq_kernel(const BwdParams p) {
   if (hi && qend + off + wr < kmax) kmax = qend + off + wr;
   const int ntiles = kmax > 0 ? (kmax + kDqKV - 1) / kDqKV : 0;
   int kmin = lo ? qwg0 + off - wl : 0;
-  kmin = kmin > 0 ? kmin : 0;
+  kmin = kmin > 0 ? (kmin < lk ? kmin : lk) : 0;          // (a shifted band may start behind the last key)
   const int jt0 = (kmin / kDqKV) & ~1;                  // first tile (even: LDS stage = j & 1)
+  // rows wholly outside the band (a block of a longer sequence: p.shift) add nothing to dq_acc: no tile, no store
+  if (jt0 >= ntiles && p.dq_acc != nullptr && !p.acc_init) return;
 
   const int sc = tid % kChunks;
   const int sr = tid / kChunks;
@@ -484,7 +486,7 @@ __global__ __launch_bounds__(kKvThreads, 2) void dkdv_kernel(const BwdParams p) 
   const SeqSpan qs = resolve_span(p.cu_q, b, p.Sq, p.q_half);
   const SeqSpan ks = resolve_span(p.cu_k, b, p.Sk, p.k_half);
   const int lq = qs.len, lk = ks.len;
-  const int off = lk - lq;
+  const int off = lk - lq + p.shift;       // bottom-right alignment, moved by the block's place in the full sequence (rfa.h: mask_shift)
   const int64_t qbatch = p.cu_q ? 0 : (int64_t)b;
   const int64_t kbatch = p.cu_k ? 0 : (int64_t)b;
   // one pass per key block of this workgroup (two for a type-B workgroup of the balanced schedule, else one)
@@ -519,10 +521,11 @@ __global__ __launch_bounds__(kKvThreads, 2) void dkdv_kernel(const BwdParams p) 
   int qfirst = 0;
   if (hi) {
     qfirst = kwg0 - off - wr;
-    if (qfirst < 0) qfirst = 0;
+    qfirst = qfirst < 0 ? 0 : (qfirst < lq ? qfirst : lq);   // (a shifted band may start behind the last query row ...)
   }
   int qlast = lq;                              // exclusive
   if (lo && kwg0 + kKeys - off + wl < qlast) qlast = kwg0 + kKeys - off + wl;
+  if (qlast < 0) qlast = 0;                    // (... or end in front of the first)
   const int jt0 = qfirst / kKvQ;
   int jt1 = (qlast + kKvQ - 1) / kKvQ;         // exclusive
   if (jt1 <= jt0) jt1 = jt0;                   // nothing visible: no tiles (the unconditional prologue fetch below

@@ -127,7 +127,7 @@ __global__ __launch_bounds__(kW * 64, 2) void fwd_kernel(const FwdParams p) {
   const int lq = qs.len, lk = ks.len;
   const int qwg0 = qblk * kFwdQRows;
   if (qwg0 >= lq) return;
-  const int off = lk - lq;                 // bottom-right causal alignment
+  const int off = lk - lq + p.shift;       // bottom-right alignment, moved by the block's place in the full sequence (rfa.h: mask_shift)
   const int qw0 = qwg0 + wave * 32;
   const int qrow = qw0 + l31;
   const int qrow_c = qrow < lq ? qrow : lq - 1;
@@ -162,7 +162,7 @@ __global__ __launch_bounds__(kW * 64, 2) void fwd_kernel(const FwdParams p) {
   if (hi && qend + off + wr < kmax) kmax = qend + off + wr;
   int ntiles = kmax > 0 ? (kmax + kFwdKV - 1) / kFwdKV : 0;
   int kmin = lo ? qwg0 + off - wl : 0;
-  kmin = kmin > 0 ? kmin : 0;
+  kmin = kmin > 0 ? (kmin < lk ? kmin : lk) : 0;          // (a shifted band may start behind the last key)
   int jt0 = (kmin / kFwdKV) / kFwdStages * kFwdStages;   // first tile (aligned to the LDS ring: stage = j % stages)
   if (nsplit > 1) {
     // this workgroup's contiguous share of the tiles [jt0, ntiles), a multiple of the ring depth long (stage = j % stages)
@@ -171,6 +171,9 @@ __global__ __launch_bounds__(kW * 64, 2) void fwd_kernel(const FwdParams p) {
     jt0 += split * chunk;
     ntiles = jt0 + chunk < ntiles ? jt0 + chunk : ntiles;          // (an empty share: jt0 >= ntiles -> no tile, l = 0)
   }
+  // a workgroup whose rows lie wholly outside the band (a block of a longer sequence: p.shift) and that would only merge
+  // into the accumulators has nothing to add: no tile is fetched, nothing is stored
+  if (jt0 >= ntiles && nsplit == 1 && p.out_acc != nullptr && !p.acc_init) return;
 
   // ---- K/V tile staging.  Raw buffer loads: the per-thread byte offsets are fixed for the whole kernel,
   // the tile advance lives in the scalar descriptor, rows past the end of the sequence read as zero.

@@ -62,7 +62,7 @@ def _compilable(fn, lower, multi=None):
                 if _single_rank(bound.get("group", None)):
                     return lower(*args, **kwargs)
                 # several ranks: the whole schedule as one registered operator (_ops.py: rfa::sched_fwd / sched_bwd),
-                # where the schedule has one — windows raise over a multi-rank ring, llama3 keeps the graph break
+                # where the schedule has one — windowed calls and llama3 keep the eager path behind a graph break
                 if multi is not None and not has_window(bound.get("window_size", (-1, -1))):
                     return multi(*args, **kwargs)
         return eager(*args, **kwargs)
@@ -70,23 +70,30 @@ def _compilable(fn, lower, multi=None):
     return public
 
 
-def _check_unsupported(dropout_p, window_size, alibi_slopes, windows_ok=False):
+def _check_unsupported(dropout_p, window_size, alibi_slopes, windows_ok=False, dropout_ok=None):
     """Sliding windows and dropout are implemented in the kernels (flash_attn semantics; dropout: the counter-based
-    mask of include/rfa.h) and usable wherever ONE kernel call sees all the keys a query may attend to: every function
-    on a single-rank group, and llama3_flash_attn_varlen_func on any group (it gathers K/V) — the same coverage the
-    reference gets from forwarding window_size / dropout_p to flash_attn (llama3_flash_attn_varlen.py:131-147).  The
-    ring / zigzag / stripe schedules over several ranks would apply a window per block, which is wrong, and the
-    reference declares dropout unsupported there (README.md:158-159): they raise.  Both together are not available."""
+    mask of include/rfa.h).  Dropout is usable wherever ONE kernel call sees all the keys a query may attend to: every
+    function on a single-rank group, and llama3_flash_attn_varlen_func on any group (it gathers K/V) — the coverage the
+    reference gets from forwarding dropout_p to flash_attn (llama3_flash_attn_varlen.py:131-147); it declares dropout
+    over a ring unsupported (README.md:158-159) and so do the schedules here.  Windows are usable there too, and on any
+    group with the dense ring and zigzag schedules, which tell every block call where it sits in the full sequence
+    (`mask_shift`, include/rfa.h).  The stripe schedule and the two `*_varlen` ring families do not (a token's
+    neighbours are strided over the ranks / a per-sequence shift would be needed): they raise on a multi-rank group.
+    Dropout together with a window is not available anywhere."""
     assert alibi_slopes is None
+    if dropout_ok is None:
+        dropout_ok = windows_ok
     drop = bool(dropout_p) and dropout_p > 0
     if drop and not 0 < dropout_p < 1:
         raise ValueError("dropout_p must be in [0, 1)")
-    if drop and not windows_ok:
+    if drop and not dropout_ok:
         raise NotImplementedError("ring_flash_attn: dropout over a multi-rank ring is not supported (as in the "
                                   "reference); use llama3_flash_attn_varlen_func or a single-rank group")
     if not windows_ok and has_window(window_size):
-        raise NotImplementedError("ring_flash_attn: sliding window over a multi-rank ring is not supported (as in the "
-                                  "reference); use llama3_flash_attn_varlen_func or a single-rank group")
+        raise NotImplementedError("ring_flash_attn: sliding window over a multi-rank group is supported by the dense "
+                                  "ring_flash_attn_* and zigzag_ring_flash_attn_* functions only, not by the stripe "
+                                  "and *_varlen ring schedules; use one of those, llama3_flash_attn_varlen_func or a "
+                                  "single-rank group")
     if drop and has_window(window_size):
         raise NotImplementedError("ring_flash_attn: dropout together with a sliding window is not supported")
 
@@ -157,9 +164,10 @@ def _split_kept(ctx, more):
     return tensors_lead, ({"kept": tuple(kept)} if kept else {})
 
 
-def make_autograd_function(name, forward_impl, backward_impl, n_lead):
+def make_autograd_function(name, forward_impl, backward_impl, n_lead, window_ring=False):
     """n_lead: number of non-tensor positional arguments between (q,k,v) and the common tail
-    (0 for the batch API, 2 = (cu_seqlens, max_seqlen) for varlen)."""
+    (0 for the batch API, 2 = (cu_seqlens, max_seqlen) for varlen).  window_ring: the schedule serves a sliding window
+    on a multi-rank group (dense ring and zigzag)."""
 
     class _Fn(torch.autograd.Function):
         @staticmethod
@@ -169,7 +177,8 @@ def make_autograd_function(name, forward_impl, backward_impl, n_lead):
              return_softmax, group) = rest[n_lead:]
             if softmax_scale is None:
                 softmax_scale = q.shape[-1] ** (-0.5)
-            _check_unsupported(dropout_p, window_size, alibi_slopes, windows_ok=window_ok_for(group))
+            single = window_ok_for(group)
+            _check_unsupported(dropout_p, window_size, alibi_slopes, windows_ok=single or window_ring, dropout_ok=single)
             q, k, v = _prep_qkv(q, k, v, group)
             tensors_lead = ()
             if n_lead:
@@ -215,7 +224,8 @@ def make_autograd_function(name, forward_impl, backward_impl, n_lead):
     return _Fn
 
 
-def make_packed_function(name, base_fn, forward_impl, backward_impl, n_lead, pack_dim, n_packed, packed_travel=False):
+def make_packed_function(name, base_fn, forward_impl, backward_impl, n_lead, pack_dim, n_packed, packed_travel=False,
+                         window_ring=False):
     """autograd Function for the packed entry points (`kv` = 2 tensors, `qkv` = 3 tensors stacked on
     `pack_dim`).  Same math as `base_fn`; the only difference is where the gradients land: ONE packed
     buffer whose slices are handed to the schedule as output views (`out_grads`), instead of letting
@@ -235,7 +245,8 @@ def make_packed_function(name, base_fn, forward_impl, backward_impl, n_lead, pac
              return_softmax, group) = rest[n_lead:]
             if softmax_scale is None:
                 softmax_scale = q.shape[-1] ** (-0.5)
-            _check_unsupported(dropout_p, window_size, alibi_slopes, windows_ok=window_ok_for(group))
+            single = window_ok_for(group)
+            _check_unsupported(dropout_p, window_size, alibi_slopes, windows_ok=single or window_ring, dropout_ok=single)
             q, k, v = _prep_qkv(q, k, v, group, packed_travel=packed_travel and n_packed == 2)
             tensors_lead = ()
             if n_lead:
@@ -303,14 +314,16 @@ def _grad_buffers(out_grads, q, k, v):
             og[2] if og[2] is not None else torch.empty_like(v))
 
 
-def make_dense_api(fn, prefix, forward_impl=None, backward_impl=None, packed_travel=False):
+def make_dense_api(fn, prefix, forward_impl=None, backward_impl=None, packed_travel=False, window_ring=False):
     """(B,S,H,D) API: returns (func, kvpacked_func, qkvpacked_func).  packed_travel: the schedule exchanges a
-    packed `kv` as one buffer and writes dK/dV straight into the packed gradient (`out_grads`) at any world size."""
+    packed `kv` as one buffer and writes dK/dV straight into the packed gradient (`out_grads`) at any world size.
+    window_ring: as in make_autograd_function (pass the same value to both)."""
     kv_fn = qkv_fn = None
     if forward_impl is not None:
         kv_fn = make_packed_function(fn.__name__ + "KVPacked", fn, forward_impl, backward_impl, 0, 2, 2,
-                                     packed_travel=packed_travel)
-        qkv_fn = make_packed_function(fn.__name__ + "QKVPacked", fn, forward_impl, backward_impl, 0, 2, 3)
+                                     packed_travel=packed_travel, window_ring=window_ring)
+        qkv_fn = make_packed_function(fn.__name__ + "QKVPacked", fn, forward_impl, backward_impl, 0, 2, 3,
+                                      window_ring=window_ring)
 
     def func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
              alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None):

@@ -38,6 +38,31 @@ def _prep_qkv(q, k, v, group, packed_travel=False):
     return q, k, v
 
 
+def global_window(window_size, causal, total):
+    """The sides of `window_size` that cut something in a sequence of `total` rows, as (left, right) with -1 for a side
+    that does not, or None when neither does: a window that covers the whole sequence is dropped on the host, so that
+    such a call takes the unwindowed code path bit for bit.  `causal` bounds the right side itself (flash_attn: it
+    forces window_right = 0), so the right side of the window is then never needed."""
+    if window_size is None:
+        return None
+    wl, wr = int(window_size[0]), int(window_size[1])
+    if wl < 0 or wl >= total - 1:
+        wl = -1
+    if causal or wr < 0 or wr >= total - 1:
+        wr = -1
+    return None if wl < 0 and wr < 0 else (wl, wr)
+
+
+def require_mask_shift(be, what):
+    """A windowed call over several ranks needs a backend that can be told where a block sits in the full sequence
+    (`mask_shift`, include/rfa.h: HipBackend.serves_mask_shift).  One that cannot would band every block on its own, which
+    is wrong: refuse before anything is exchanged, on every rank alike."""
+    if not getattr(be, "serves_mask_shift", False):
+        raise NotImplementedError(f"ring_flash_attn: {what} with a sliding window on a multi-rank group needs a backend "
+                                  f"that serves `mask_shift`; {getattr(be, 'name', type(be).__name__)!r} does not (it would "
+                                  "apply the window per block)")
+
+
 def _as_cu(cu_seqlens, device):
     """cu_seqlens as an int32 tensor on the compute device (the kernels read it on device)."""
     import torch

@@ -55,6 +55,7 @@ class HipBackend:
     immediately; outputs are caller-allocated unless stated otherwise."""
 
     name = "hip"
+    serves_mask_shift = True        # fwd / bwd take `mask_shift` (include/rfa.h, ABI 7): what a windowed multi-rank schedule needs
 
     def __init__(self):
         self.lib = _C.load()
@@ -81,10 +82,13 @@ class HipBackend:
     # ------------------------------------------------------------------ forward
     def fwd(self, q, k, v, *, softmax_scale, causal, cu_seqlens_q=None, cu_seqlens_k=None,
             max_seqlen_q=None, max_seqlen_k=None, q_half=HALF_FULL, k_half=HALF_FULL,
-            out=None, lse=None, out_acc=None, lse_acc=None, acc_init=False, window=(-1, -1), dropout=None):
+            out=None, lse=None, out_acc=None, lse_acc=None, acc_init=False, window=(-1, -1), dropout=None,
+            mask_shift=0):
         """Block attention.  Plain mode fills (out, lse); accumulate mode merges into the fp32
         (out_acc, lse_acc) pair (fused update_out_and_lse).  Dense: q (B,Sq,H,D); varlen: (T,H,D).
-        dropout: (p, seed, q_pos_offset, k_pos_offset, head_offset) or None."""
+        dropout: (p, seed, q_pos_offset, k_pos_offset, head_offset) or None.
+        mask_shift: where the block sits in a longer sequence (include/rfa.h; dense input) — for blocks of equal length
+        the global position of q row 0 minus that of k row 0; moves the causal diagonal and the window alike."""
         self._check_dev(q, k, v, out, lse, out_acc, lse_acc)
         varlen = cu_seqlens_q is not None
         a = _C.FwdArgs()
@@ -114,6 +118,7 @@ class HipBackend:
         a.causal = 1 if causal else 0
         if window is not None and (window[0] >= 0 or window[1] >= 0):
             a.window, a.window_left, a.window_right = 1, int(window[0]), int(window[1])
+        a.mask_shift = int(mask_shift)
         a.dtype = self._dtype(q)
         _set_dropout(a, dropout)
         a.fwd_form = _fwd_form()
@@ -151,7 +156,7 @@ class HipBackend:
             cu_seqlens_k=None, max_seqlen_q=None, max_seqlen_k=None, q_half=HALF_FULL,
             k_half=HALF_FULL, dq=None, dk=None, dv=None, dq_acc=None, dk_acc=None, dv_acc=None,
             acc_init=False, deterministic=False, phases=_C.BWD_ALL, partials=None, ds_scratch=None,
-            window=(-1, -1), prof_events=None, dropout=None):
+            window=(-1, -1), prof_events=None, dropout=None, mask_shift=0):
         """dQ/dK/dV of one block.  Plain outputs (io dtype) or `+=` into fp32 accumulators.
         phases=BWD_COMPUTE / BWD_REDUCE splits the call so a ring step can overlap the kernels
         with the arrival of the dk/dv accumulators it adds into: the COMPUTE call RETURNS the buffer
@@ -197,6 +202,7 @@ class HipBackend:
         a.deterministic = 1 if deterministic else 0
         if window is not None and (window[0] >= 0 or window[1] >= 0):
             a.window, a.window_left, a.window_right = 1, int(window[0]), int(window[1])
+        a.mask_shift = int(mask_shift)
         a.dtype = self._dtype(q)
         a.phases = phases
         _set_dropout(a, dropout)

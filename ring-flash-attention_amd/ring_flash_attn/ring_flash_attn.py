@@ -6,14 +6,121 @@ the K/V of rank (r-s) mod W; with `causal` only steps s <= r compute and only st
 See zigzag_ring_flash_attn.py for the MI355X-first changes (fused fp32 merge / accumulate,
 strided views, two-phase backward, world_size==1 short-circuit).  One deliberate fix: dq is
 returned in q.dtype (the reference hard-codes bfloat16 at ring_flash_attn.py:154).
+
+Sliding windows over several ranks (no counterpart in the reference): the K/V on hand at step d belong to rank
+r - d, i.e. they lie d * S rows in front of this rank's queries — the kernels are told so (`mask_shift`, include/rfa.h)
+and band every block as ONE window over the whole sequence.  With a causal window of w rows only the
+d_max = (w - 1) // S + 1 ranks in front of a query hold visible keys, whatever the rank: every rank stops
+exchanging K/V after d_max hops and the dK/dV accumulators, d_max ranks from home by then, return in one direct
+transfer (`ring_window_plan`).  Calls without a window that cuts the global sequence take the unwindowed code, unchanged.
 """
 import torch
 
 from . import _C
 from .backend import get_backend
 from .utils import RingComm, single_rank
-from ._common import dropout_arg
+from ._common import dropout_arg, global_window, require_mask_shift
 from ._api import make_autograd_function, make_dense_api, _grad_buffers
+
+
+def ring_window_plan(rank, world_size, S, causal, window):
+    """The steps of a windowed ring: (n_steps, dists) — the ring runs steps 0 .. n_steps - 1 (n_steps - 1 K/V hops) and
+    dists[d] is the signed distance in RANKS between this rank's queries and the K/V on hand at step d (positive: keys
+    in front), or None where the step computes nothing.  `window` = (left, right) of the GLOBAL sequence, a side < 0
+    unbounded.  The block at distance t >= 1 has its nearest (query, key) pair (t - 1) S + 1 rows apart, so it holds a
+    visible key iff left < 0 or left >= (t - 1) S + 1 — the same for every rank, which is what lets a causal ring stop
+    early on all ranks at once; likewise the right side of keys behind the queries (never visible when causal)."""
+    wl, wr = window
+
+    def visible(t):
+        if t == 0:
+            return True
+        if t > 0:
+            return wl < 0 or wl >= (t - 1) * S + 1
+        return not causal and (wr < 0 or wr >= (-t - 1) * S + 1)
+
+    n_steps = world_size
+    if causal:
+        n_steps = world_size if wl < 0 else min(world_size, (wl - 1) // S + 2)
+    dists = []
+    for d in range(n_steps):
+        t = d if d <= rank else d - world_size
+        dists.append(t if visible(t) else None)
+    return n_steps, dists
+
+
+def _band(causal, window, t, S):
+    """keywords of a block call t ranks off the diagonal (the shift only where it is not zero: backends that predate
+    it serve the diagonal block unchanged)"""
+    kw = {"causal": causal, "window": window}
+    if t:
+        kw["mask_shift"] = t * S
+    return kw
+
+
+def _ring_window_forward(be, comm, q, k, v, softmax_scale, causal, window):
+    B, S, H, D = q.shape
+    n_steps, dists = ring_window_plan(comm.rank, comm.world_size, S, causal, window)
+    out_acc = torch.empty((B, S, H, D), dtype=torch.float32, device=q.device)
+    lse_acc = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
+    first = True
+    next_k, next_v = None, None
+    for step in range(n_steps):
+        if step + 1 != n_steps:
+            next_k, next_v = comm.send_recv_kv(k, v)
+        if dists[step] is not None:
+            be.fwd(q, k, v, softmax_scale=softmax_scale, out_acc=out_acc, lse_acc=lse_acc, acc_init=first,
+                   **_band(causal, window, dists[step], S))
+            first = False
+        if step + 1 != n_steps:
+            comm.wait()
+            k, v = next_k, next_v
+    return be.cast(out_acc, q.dtype), lse_acc
+
+
+def _ring_window_backward(be, process_group, kv_comm, d_kv_comm, dout, q, k, v, softmax_lse, delta, softmax_scale,
+                          causal, window, deterministic):
+    B, S, H, D = q.shape
+    world = kv_comm.world_size
+    n_steps, dists = ring_window_plan(kv_comm.rank, world, S, causal, window)
+    dq = None
+    dk = torch.empty(k.shape, dtype=torch.float32, device=q.device)
+    dv = torch.empty(v.shape, dtype=torch.float32, device=q.device)
+    next_dk, next_dv = None, None
+    next_k, next_v = None, None
+    for step in range(n_steps):
+        if step + 1 != n_steps:
+            next_k, next_v = kv_comm.send_recv_kv(k, v)
+        if dists[step] is not None:
+            band = _band(causal, window, dists[step], S)
+            if dq is None:                       # step 0: the diagonal block always computes
+                dq = torch.empty((B, S, H, D), dtype=torch.float32, device=q.device)
+                be.bwd(dout, q, k, v, softmax_lse, delta, softmax_scale=softmax_scale,
+                       dq_acc=dq, dk_acc=dk, dv_acc=dv, acc_init=True, deterministic=deterministic, **band)
+            else:
+                part = be.bwd(dout, q, k, v, softmax_lse, delta, softmax_scale=softmax_scale,
+                              dq_acc=dq, dk_acc=dk, dv_acc=dv, deterministic=deterministic,
+                              phases=_C.BWD_COMPUTE, **band)
+                d_kv_comm.wait()
+                dk, dv = next_dk, next_dv
+                be.bwd(dout, q, k, v, softmax_lse, delta, softmax_scale=softmax_scale,
+                       dq_acc=dq, dk_acc=dk, dv_acc=dv, deterministic=deterministic,
+                       phases=_C.BWD_REDUCE, partials=part, **band)
+        elif step != 0:
+            d_kv_comm.wait()
+            dk, dv = next_dk, next_dv
+        if step + 1 != n_steps:
+            kv_comm.wait()
+            k, v = next_k, next_v
+            next_dk, next_dv = d_kv_comm.send_recv_kv(dk, dv)
+    # the accumulators are n_steps - 1 ranks in front of their owners: home in ONE transfer (a full rotation: the
+    # ring's own last hop, distance 1)
+    back = (n_steps - 1) % world
+    if back:
+        home = RingComm(process_group, distance=-back)
+        dk, dv = home.send_recv_kv(dk, dv)
+        home.wait()
+    return be.cast(dq, q.dtype), be.cast(dk, q.dtype), be.cast(dv, q.dtype)
 
 
 def ring_flash_attn_forward(
@@ -39,6 +146,11 @@ def ring_flash_attn_forward(
         be.fwd(q, k, v, softmax_scale=softmax_scale, causal=causal, out=out, lse=lse, window=window_size, dropout=dropout_arg(dropout_p, dropout_seed))
         return out, lse
     assert not dropout_p, "dropout over a multi-rank ring is not supported (as in the reference)"
+
+    win = global_window(window_size, causal, comm.world_size * S)
+    if win is not None:
+        require_mask_shift(be, "ring_flash_attn")
+        return _ring_window_forward(be, comm, q, k, v, softmax_scale, causal, win)
 
     out_acc = torch.empty((B, S, H, D), dtype=torch.float32, device=q.device)
     lse_acc = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
@@ -98,6 +210,11 @@ def ring_flash_attn_backward(
         return dq, dk, dv
     assert not dropout_p, "dropout over a multi-rank ring is not supported (as in the reference)"
 
+    win = global_window(window_size, causal, kv_comm.world_size * S)
+    if win is not None:
+        return _ring_window_backward(be, process_group, kv_comm, d_kv_comm, dout, q, k, v, softmax_lse, delta,
+                                     softmax_scale, causal, win, deterministic)
+
     dq = None
     dk = torch.empty(k.shape, dtype=torch.float32, device=q.device)
     dv = torch.empty(v.shape, dtype=torch.float32, device=q.device)
@@ -139,9 +256,9 @@ def ring_flash_attn_backward(
 
 
 RingFlashAttnFunc = make_autograd_function(
-    "RingFlashAttnFunc", ring_flash_attn_forward, ring_flash_attn_backward, 0)
+    "RingFlashAttnFunc", ring_flash_attn_forward, ring_flash_attn_backward, 0, window_ring=True)
 (
     ring_flash_attn_func,
     ring_flash_attn_kvpacked_func,
     ring_flash_attn_qkvpacked_func,
-) = make_dense_api(RingFlashAttnFunc, "ring_flash_attn", ring_flash_attn_forward, ring_flash_attn_backward)
+) = make_dense_api(RingFlashAttnFunc, "ring_flash_attn", ring_flash_attn_forward, ring_flash_attn_backward, window_ring=True)

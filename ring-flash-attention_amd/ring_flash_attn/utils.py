@@ -249,10 +249,14 @@ class RingComm:
         comm.wait(); k, v = nk, nv
     """
 
-    def __init__(self, process_group: dist.ProcessGroup):
+    def __init__(self, process_group: dist.ProcessGroup, distance: int = 1):
+        """distance: send to rank + distance, receive from rank - distance (mod world size; 1 = the ring's neighbours).
+        Other values are single direct transfers — a windowed ring that stopped after d hops sends its dK/dV
+        accumulators home with distance = -d."""
         self._process_group = process_group
         self._ops = []
         self.rank, self.world_size = group_rank_world(process_group)
+        self.distance = distance
         self._reqs = None
         self._staged = []          # (host_recv, device_recv) pairs for the gloo staging path
         self._local = []           # (src, dst) pairs of the loopback measurement hook
@@ -261,8 +265,8 @@ class RingComm:
         self._audit = []           # (entry index, receive buffer) of the pending transfer (config.exchange_check)
         self._nhops = 0
 
-        self.send_rank = (self.rank + 1) % self.world_size
-        self.recv_rank = (self.rank - 1) % self.world_size
+        self.send_rank = (self.rank + distance) % self.world_size
+        self.recv_rank = (self.rank - distance) % self.world_size
 
         if process_group is not None and _loopback() is None:
             self.send_rank = dist.get_global_rank(self._process_group, self.send_rank)
@@ -349,7 +353,7 @@ class RingComm:
             _TEST.corrupt(self._audit[0][1])          # (tests: a receive buffer that something overwrote after it landed)
         if self._audit:
             # the ring neighbour posts its transfers in the same order: entry i of ITS table is what arrived here
-            src = (self.rank - 1) % self.world_size
+            src = (self.rank - self.distance) % self.world_size
             for j, (idx, buf) in enumerate(self._audit):
                 _audit(self._process_group).expect(idx, src, buf, f"ring hop {self._nhops}, buffer {j} (from rank {src})")
             self._audit = []

@@ -52,7 +52,7 @@ from . import _C, config
 from .backend import get_backend
 from .utils import Agreement, AllGatherComm, RingComm, SourceArrivals, all_to_all_async, reduce_scatter_async, single_rank
 from ._api import make_autograd_function, make_dense_api, _grad_buffers
-from ._common import packed_pair, dropout_arg
+from ._common import packed_pair, dropout_arg, global_window, require_mask_shift
 
 
 def gather_scratch_bytes(k: torch.Tensor, world: int, wire_fp32: bool) -> int:
@@ -161,6 +161,134 @@ def _gather_kv(comm_group, k, v, world, per_source=False):
     return (gather, bufs) + _kv_views(bufs, k, world)
 
 
+# ---------------------------------------------------------------------------------------------
+# Sliding windows over several ranks.  A rank's two chunks are not neighbours in the sequence (chunk r and chunk
+# 2W-1-r of C = S/2 rows each), so no single shift describes a call over both halves: a windowed step is issued per
+# (query chunk cq, key chunk ck <= cq) pair on slices of the same tensors, each a causal call that is told its distance
+# from the diagonal (mask_shift = (cq - ck) C, include/rfa.h) and merged through the same fp32 accumulators.  Pairs
+# further apart than the window reaches are skipped, so the COMPUTE follows the window; the traffic does not — the
+# zigzag layout spreads every neighbourhood of the sequence over all ranks by construction (the contiguous ring,
+# ring_flash_attn.py, is the layout whose exchange stops early).  Kept deliberately plain: zero-initialised fp32
+# gradient accumulators, single-phase block calls, fp32 reduce-scatter of the dK/dV slots in the gather forms.
+def zigzag_window_pairs(rank, src, world, C, window_left):
+    """the (query half, key half, mask_shift) block calls of rank `rank` against the K/V of rank `src`, diagonal
+    blocks first (they initialise the accumulators of their half)"""
+    qc = (rank, 2 * world - 1 - rank)
+    kc = (src, 2 * world - 1 - src)
+    pairs = []
+    for hq in (0, 1):
+        for hk in (0, 1):
+            d = qc[hq] - kc[hk]
+            if d < 0 or (window_left >= 0 and d * C - window_left > C - 1):
+                continue
+            pairs.append((hq, hk, d * C))
+    return sorted(pairs, key=lambda p: p[2] != 0)
+
+
+def _halves(S):
+    C = S // 2
+    return (slice(0, C), slice(C, S))
+
+
+def _zigzag_window_forward(be, process_group, comm, q, k, v, softmax_scale, window):
+    B, S, H, D = q.shape
+    W, rank = comm.world_size, comm.rank
+    hs = _halves(S)
+    out_acc = torch.empty((B, S, H, D), dtype=torch.float32, device=q.device)
+    lse_acc = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
+    started = [False, False]
+
+    def blocks(src, ks, vs):
+        for hq, hk, shift in zigzag_window_pairs(rank, src, W, S // 2, window[0]):
+            band = {"mask_shift": shift} if shift else {}
+            be.fwd(q[:, hs[hq]], ks[:, hs[hk]], vs[:, hs[hk]], softmax_scale=softmax_scale, causal=True, window=window,
+                   out_acc=out_acc[:, hs[hq]], lse_acc=lse_acc[:, :, hs[hq]], acc_init=not started[hq], **band)
+            started[hq] = True
+
+    mode = exchange_mode(k, W, q, process_group, v)
+    if mode in ("gather", "gather_ps"):
+        gather, _, k_all, v_all = _gather_kv(process_group, k, v, W, per_source=mode == "gather_ps")
+        blocks(rank, k, v)                                                 # runs beside the exchange
+        if mode == "gather":
+            gather.wait()
+        for step in range(1, W):
+            src = (rank - step) % W
+            if mode == "gather_ps":
+                gather.wait(step)
+            blocks(src, k_all[src], v_all[src])
+        return be.cast(out_acc, q.dtype), lse_acc
+    next_k, next_v = None, None
+    for step in range(W):
+        if step + 1 != W:
+            next_k, next_v = comm.send_recv_kv(k, v)
+        blocks((rank - step) % W, k, v)
+        if step + 1 != W:
+            comm.wait()
+            k, v = next_k, next_v
+    return be.cast(out_acc, q.dtype), lse_acc
+
+
+def _zigzag_window_backward(be, process_group, kv_comm, d_kv_comm, dout, q, k, v, softmax_lse, delta, softmax_scale,
+                            window, deterministic, kept):
+    B, S, H, D = q.shape
+    W, rank = kv_comm.world_size, kv_comm.rank
+    hs = _halves(S)
+    dq = torch.zeros((B, S, H, D), dtype=torch.float32, device=q.device)
+    lse_h = [softmax_lse[:, :, h].contiguous() for h in hs]
+    delta_h = [delta[:, :, h].contiguous() for h in hs]
+
+    def blocks(src, ks, vs, dk, dv):
+        for hq, hk, shift in zigzag_window_pairs(rank, src, W, S // 2, window[0]):
+            band = {"mask_shift": shift} if shift else {}
+            be.bwd(dout[:, hs[hq]], q[:, hs[hq]], ks[:, hs[hk]], vs[:, hs[hk]], lse_h[hq], delta_h[hq],
+                   softmax_scale=softmax_scale, causal=True, window=window, dq_acc=dq[:, hs[hq]],
+                   dk_acc=dk[:, hs[hk]], dv_acc=dv[:, hs[hk]], deterministic=deterministic, **band)
+
+    mode = exchange_mode(k, W, q, process_group, v)
+    if mode in ("gather", "gather_ps"):
+        per_source = mode == "gather_ps"
+        if kept:
+            gather, (k_all, v_all) = None, _kv_views(kept, k, W)
+        else:
+            gather, _, k_all, v_all = _gather_kv(process_group, k, v, W, per_source=per_source)
+        # slot c: this rank's dK/dV for the chunks owned by rank c, fp32, summed over the ranks by a reduce-scatter
+        dk_cat = torch.zeros((W * k.shape[0],) + tuple(k.shape[1:]), dtype=torch.float32, device=q.device)
+        dv_cat = torch.zeros((W * v.shape[0],) + tuple(v.shape[1:]), dtype=torch.float32, device=q.device)
+        dk_all, dv_all = dk_cat.view((W,) + tuple(k.shape)), dv_cat.view((W,) + tuple(v.shape))
+        blocks(rank, k, v, dk_all[rank], dv_all[rank])
+        if gather is not None and not per_source:
+            gather.wait()
+        for step in range(1, W):
+            src = (rank - step) % W
+            if gather is not None and per_source:
+                gather.wait(step)
+            blocks(src, k_all[src], v_all[src], dk_all[src], dv_all[src])
+        sums = [torch.empty(t.shape, dtype=torch.float32, device=q.device) for t in (k, v)]
+        works = [reduce_scatter_async(s_, c, group=process_group) for s_, c in zip(sums, (dk_cat, dv_cat))]
+        dq_out = be.cast(dq, q.dtype)                                      # runs beside the exchange
+        for w_ in works:
+            w_.wait()
+        return dq_out, be.cast(sums[0], q.dtype), be.cast(sums[1], q.dtype)
+
+    dk = torch.zeros(k.shape, dtype=torch.float32, device=q.device)
+    dv = torch.zeros(v.shape, dtype=torch.float32, device=q.device)
+    next_dk, next_dv = None, None
+    next_k, next_v = None, None
+    for step in range(W):
+        if step + 1 != W:
+            next_k, next_v = kv_comm.send_recv_kv(k, v)
+        if step != 0:
+            d_kv_comm.wait()
+            dk, dv = next_dk, next_dv
+        blocks((rank - step) % W, k, v, dk, dv)
+        if step + 1 != W:
+            kv_comm.wait()
+            k, v = next_k, next_v
+        next_dk, next_dv = d_kv_comm.send_recv_kv(dk, dv)
+    d_kv_comm.wait()
+    return be.cast(dq, q.dtype), be.cast(next_dk, q.dtype), be.cast(next_dv, q.dtype)
+
+
 def zigzag_ring_flash_attn_forward(
     process_group,
     q: torch.Tensor,
@@ -189,6 +317,11 @@ def zigzag_ring_flash_attn_forward(
         be.fwd(q, k, v, softmax_scale=softmax_scale, causal=True, out=out, lse=lse, window=window_size, dropout=dropout_arg(dropout_p, dropout_seed))
         return out, lse
     assert not dropout_p, "dropout over a multi-rank ring is not supported (as in the reference)"
+
+    win = global_window(window_size, True, comm.world_size * S)
+    if win is not None:
+        require_mask_shift(be, "zigzag_ring_flash_attn")
+        return _zigzag_window_forward(be, process_group, comm, q, k, v, softmax_scale, win)
 
     out_acc = torch.empty((B, S, H, D), dtype=torch.float32, device=q.device)
     lse_acc = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
@@ -277,6 +410,11 @@ def zigzag_ring_flash_attn_backward(
                dq=dq, dk=dk, dv=dv, deterministic=deterministic, window=window_size, dropout=dropout_arg(dropout_p, dropout_seed))
         return dq, dk, dv
     assert not dropout_p, "dropout over a multi-rank ring is not supported (as in the reference)"
+
+    win = global_window(window_size, True, kv_comm.world_size * S)
+    if win is not None:
+        return _zigzag_window_backward(be, process_group, kv_comm, d_kv_comm, dout, q, k, v, softmax_lse, delta,
+                                       softmax_scale, win, deterministic, kept)
 
     dq = torch.empty((B, S, H, D), dtype=torch.float32, device=q.device)
 
@@ -440,10 +578,10 @@ def zigzag_ring_flash_attn_backward(
 zigzag_ring_flash_attn_forward.keeps_for_backward = True
 
 ZigZagRingFlashAttnFunc = make_autograd_function(
-    "ZigZagRingFlashAttnFunc", zigzag_ring_flash_attn_forward, zigzag_ring_flash_attn_backward, 0)
+    "ZigZagRingFlashAttnFunc", zigzag_ring_flash_attn_forward, zigzag_ring_flash_attn_backward, 0, window_ring=True)
 (
     zigzag_ring_flash_attn_func,
     zigzag_ring_flash_attn_kvpacked_func,
     zigzag_ring_flash_attn_qkvpacked_func,
 ) = make_dense_api(ZigZagRingFlashAttnFunc, "zigzag_ring_flash_attn", zigzag_ring_flash_attn_forward,
-                   zigzag_ring_flash_attn_backward, packed_travel=True)
+                   zigzag_ring_flash_attn_backward, packed_travel=True, window_ring=True)
