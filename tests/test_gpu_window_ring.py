@@ -7,6 +7,7 @@ import os
 import sys
 
 import pytest
+import torch
 
 pytestmark = pytest.mark.gpu
 
@@ -26,11 +27,19 @@ def _case(kind, W, wl, n, causal=True, wr=0, forms=("kvpacked",)):
                 window=(wl, wr), forms=forms, check=("counts",))
 
 
+def _ragged(kind, rows, window, causal, n, D=128, dtype=torch.bfloat16):
+    return dict(name=f"{kind}_w4_s{rows}_{window[0]}_{window[1]}", kind=kind, W=4, S=rows, B=2, H=8, Hk=2, D=D, dtype=dtype,
+                seed=900 + n, causal=causal, window=window, forms=("func",), check=("counts",))
+
+
 @pytest.mark.parametrize("W", [2, 4, 8])
 def test_ring_window_on_the_hip_kernels(W):
     """windows below a tile, cutting a shard, spanning shards; the last also two-sided without `causal`"""
     cases = [_case("ring", W, 100, 0, forms=("func", "kvpacked")), _case("ring", W, S + 200, 1), _case("ring", W, 2 * S, 2),
              _case("ring", W, 300, 3, causal=False, wr=S + 50, forms=("func",))]
+    if W == 4:
+        # shards that are no multiple of 32 rows (every mask_shift unaligned: 328, 656, 984), batch 2; head dim 64 and fp16 once
+        cases += [_ragged("ring", 328, (413, 0), True, 4, D=64), _ragged("ring", 328, (150, 411), False, 5, dtype=torch.float16)]
     errs, _ = WW.run_world(W, cases, use_hip=True, port=free_port())
     assert not errs, "\n".join(errs)
 
@@ -48,5 +57,7 @@ def test_zigzag_window_on_the_hip_kernels(W, form, monkeypatch):
     cases = [_case("zigzag", W, 100, 0), _case("zigzag", W, S + 200, 1, forms=("func",))]
     if form == "ring":
         cases.append(_case("zigzag", W, 256, 2, forms=("qkvpacked",)))
+    if W == 4 and form in ("ring", "gather"):
+        cases.append(_ragged("zigzag", 336, (413, 0), True, 6))          # chunks of 168 rows
     errs, _ = WW.run_world(W, cases, use_hip=True, port=free_port())
     assert not errs, "\n".join(errs)

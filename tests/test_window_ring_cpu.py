@@ -35,16 +35,28 @@ def _cases(kind, W):
     return cases
 
 
+# shards that are not powers of two (appended to the W = 4 worlds below): 328 rows per rank is no multiple of 32, so every
+# mask_shift of the ring (328, 656, 984) is unaligned; zigzag chunks of 168 rows likewise; batch 2
+RAGGED_RING_CAUSAL = dict(name="ring_w4_s328_413", kind="ring", W=4, S=328, B=2, H=4, Hk=2, D=64, seed=911, causal=True,
+                          window=(413, 0), forms=("func",), check=("counts",))
+RAGGED_RING_TWO_SIDED = dict(name="ring_nc_w4_s328_150_411", kind="ring", W=4, S=328, B=2, H=4, Hk=2, D=32, seed=912,
+                             causal=False, window=(150, 411), dtype=torch.float16, forms=("func",), check=("counts",))
+RAGGED_ZIGZAG = dict(name="zigzag_w4_s336_413", kind="zigzag", W=4, S=336, B=2, H=4, Hk=2, D=32, seed=913, causal=True,
+                     window=(413, 0), forms=("func",), check=("counts",))
+
+
 @pytest.mark.parametrize("W", [2, 3, 4, 8])
 def test_ring_causal_window(W):
-    errs, _ = WW.run_world(W, _cases("ring", W), use_hip=False, port=free_port())
+    cases = _cases("ring", W) + ([RAGGED_RING_CAUSAL] if W == 4 else [])
+    errs, _ = WW.run_world(W, cases, use_hip=False, port=free_port())
     assert not errs, "\n".join(errs)
 
 
 @pytest.mark.parametrize("W", [2, 3, 4, 8])
 def test_zigzag_window(W, monkeypatch):
     monkeypatch.setenv("RFA_ZIGZAG_EXCHANGE", "ring")
-    errs, _ = WW.run_world(W, _cases("zigzag", W), use_hip=False, port=free_port())
+    cases = _cases("zigzag", W) + ([RAGGED_ZIGZAG] if W == 4 else [])
+    errs, _ = WW.run_world(W, cases, use_hip=False, port=free_port())
     assert not errs, "\n".join(errs)
 
 
@@ -52,7 +64,8 @@ def test_zigzag_window(W, monkeypatch):
 @pytest.mark.parametrize("W", [2, 4])
 def test_zigzag_window_gather_forms(W, form, monkeypatch):
     monkeypatch.setenv("RFA_ZIGZAG_EXCHANGE", form)
-    errs, _ = WW.run_world(W, _cases("zigzag", W), use_hip=False, port=free_port())
+    cases = _cases("zigzag", W) + ([RAGGED_ZIGZAG] if (W, form) == (4, "gather") else [])
+    errs, _ = WW.run_world(W, cases, use_hip=False, port=free_port())
     assert not errs, "\n".join(errs)
 
 
@@ -62,6 +75,8 @@ def test_ring_two_sided_window(W):
     cases = [dict(name=f"ring_nc_w{W}_{wl}_{wr}", kind="ring", W=W, S=S, H=4, Hk=2, D=32, seed=300 + 7 * W + n, causal=False,
                   window=(wl, wr), forms=("func", "kvpacked") if n == 0 else ("func",), check=("counts",))
              for n, (wl, wr) in enumerate([(5, 3), (S, 2 * S + 1), (-1, 4), (0, 0), (2 * S, -1), (W * S, W * S)])]
+    if W == 4:
+        cases.append(RAGGED_RING_TWO_SIDED)
     errs, _ = WW.run_world(W, cases, use_hip=False, port=free_port())
     assert not errs, "\n".join(errs)
 
