@@ -55,7 +55,7 @@
 extern "C" {
 #endif
 
-#define RFA_ABI_VERSION 7
+#define RFA_ABI_VERSION 8
 
 typedef enum {
   RFA_OK = 0,
@@ -158,7 +158,7 @@ typedef struct {
    * simply q_start - k_start.  A rank of a ring that holds rows [rS, (r+1)S) and has the K/V of rank r - d on hand passes
    * d * S and gets its share of ONE sliding-window attention over the whole sequence.  0 (a zero-initialised struct): the
    * block's own diagonal, as before.  Ignored without `causal` and without `window`.  Dense input without dropout only
-   * (cu_seqlens != NULL or dropout_p > 0 with a non-zero shift: RFA_ERR_ARGS).  Any 64-bit value is accepted: the library
+   * (cu_seqlens != NULL or dropout_p > 0 with a non-zero shift: RFA_ERR_ARGS; packed input takes mask_shift_lens, below).  Any 64-bit value is accepted: the library
    * normalises the band before it plans or launches — a bound no element of the block can reach is
    * dropped, so a block wholly inside the window IS the unwindowed non-causal call (same instance, plan and dS-spill
    * form, bit for bit); a block with no visible element launches nothing in accumulate mode and writes out = 0,
@@ -166,6 +166,26 @@ typedef struct {
    * The persistent forward, the balanced dK/dV schedule and split-KV plans keyed on the block's own diagonal decline a
    * shifted causal band; the triangular ds_scratch layout follows it. */
   int64_t mask_shift;
+  /* ABI 8 — the same, in units of each sequence's own key length, so that it also serves packed (cu_seqlens) input, whose
+   * lengths live on the device.  For sequence b of the call the band becomes
+   *     i + off_b - window_left <= j <= i + off_b + window_right ,
+   *     off_b = (len_k(b) - len_q(b)) + mask_shift + mask_shift_lens * len_k(b)
+   * (len_*: the effective lengths after q_half / k_half).  A rank that holds the l_b local rows of every packed sequence and
+   * has the K/V of the rank t places in front on hand passes t: every sequence is banded as its part of one window over
+   * its full length.  In one packed launch some sequences may then be wholly dark, some wholly lit and some cut; a dark
+   * sequence leaves accumulators untouched, writes out = 0 / lse = +inf in plain mode (out 0 / lse -inf with acc_init) and
+   * exact-zero gradients in the plain and overwrite modes — the contracts of a dense shifted block.  0 (a zero-initialised
+   * struct): as before.  Ignored without `causal` and without `window`.
+   *   packed input: accepted with causal and / or window; the absolute mask_shift stays RFA_ERR_ARGS there (it has no
+   *     meaning per sequence).  The band is not normalised on the host.  A bounded window runs the windowed instances; a
+   *     causal call without a window keeps the default ones, the packed-row dS hand-off and the 256-key dK/dV form.
+   *   dense input: mask_shift_lens * len_k is folded into mask_shift before the band is normalised — the call IS the call
+   *     with mask_shift = n * len_k, bit for bit (same normalisation, plan and instance).
+   *   dropout_p > 0 with a non-zero value, or |mask_shift_lens| * Sk >= 2^30 (the kernels keep off, off - window_left and
+   *     off + window_right in 32 bits): RFA_ERR_ARGS.
+   * The plans that decline a non-zero mask_shift decline this field too; estimates and memo keys take
+   * mask_shift_lens * Sk as the stand-in shift of packed input. */
+  int32_t mask_shift_lens;
 } rfa_fwd_args;
 
 enum { RFA_FWD_AUTO = 0, RFA_FWD_8x32 = 1, RFA_FWD_RETIRED_2 = 2, RFA_FWD_4x32 = 3, RFA_FWD_P8x32 = 4 };
@@ -265,6 +285,8 @@ typedef struct {
   int64_t total_q;
   /* ABI 7: as in rfa_fwd_args, with the forward's value */
   int64_t mask_shift;
+  /* ABI 8: as in rfa_fwd_args, with the forward's value */
+  int32_t mask_shift_lens;
 } rfa_bwd_args;
 
 enum { RFA_DKDV_AUTO = 0, RFA_DKDV_128 = 1, RFA_DKDV_256 = 2, RFA_DKDV_BAL = 3 };

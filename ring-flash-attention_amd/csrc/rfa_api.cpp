@@ -60,7 +60,10 @@ inline float drop_rescale(float p) {
 //   * what is left is re-expressed with small numbers where the caller's are large (the kernels keep off, off - wl and
 //     off + wr in 32 bits): only the two edges off - wl and off + wr matter, and for a non-empty block with live bounds both
 //     lie inside (-len_q, len_k).
-// Packed (cu_seqlens) input is not normalised — the lengths live on the device — and takes no shift (RFA_ERR_ARGS).
+// Packed (cu_seqlens) input is not normalised — the lengths live on the device — and takes no absolute shift (RFA_ERR_ARGS);
+// its shift is mask_shift_lens, in units of each sequence's own key length, applied by the kernels.  Dense input folds
+// mask_shift_lens * len_k into mask_shift first (fold_lens), so a dense call with mask_shift_lens = n IS the call with
+// mask_shift = n * len_k.
 struct Band { int causal, window, wl, wr; int64_t shift; bool empty; };
 inline int dense_len(int S, int half) { return half == RFA_HALF_FULL ? S : (half == RFA_HALF_FRONT ? S / 2 : S - S / 2); }
 inline Band norm_band(int Sq, int q_half, int Sk, int k_half, int causal, int window, int wl_in, int wr_in, int64_t shift) {
@@ -90,9 +93,27 @@ inline Band norm_band(int Sq, int q_half, int Sk, int k_half, int causal, int wi
   const int c = (causal && wr >= 0) ? 1 : 0;                          // (causal: wr was 0 and the bound is still live)
   return Band{c, (wl >= 0 || (wr >= 0 && !c)) ? 1 : 0, (int)wl, (int)wr, s, false};
 }
+template <typename A>
+inline bool has_band(const A& a) {
+  return a.causal || (a.window && (a.window_left >= 0 || a.window_right >= 0));
+}
+// mask_shift_lens made canonical: dense input folds it into mask_shift; a call without a band ignores it (as mask_shift)
+template <typename A>
+inline A fold_lens(const A& a) {
+  A n = a;
+  if (a.mask_shift_lens == 0) return n;
+  if (a.cu_seqlens_q == nullptr && a.cu_seqlens_k == nullptr) {
+    n.mask_shift = a.mask_shift + (int64_t)a.mask_shift_lens * dense_len(a.Sk, a.k_half);
+    n.mask_shift_lens = 0;
+  } else if (!has_band(a)) {
+    n.mask_shift_lens = 0;
+  }
+  return n;
+}
 // the call with its band normalised (what every plan / size / launch below looks at)
 template <typename A>
-inline A norm_args(const A& a) {
+inline A norm_args(const A& a0) {
+  const A a = fold_lens(a0);
   A n = a;
   if (a.cu_seqlens_q != nullptr || a.cu_seqlens_k != nullptr || a.dropout_p > 0.f) return n;   // (dropout: no window, no shift)
   const Band b = norm_band(a.Sq, a.q_half, a.Sk, a.k_half, a.causal, a.window, a.window_left, a.window_right, a.mask_shift);
@@ -100,16 +121,27 @@ inline A norm_args(const A& a) {
   return n;
 }
 template <typename A>
-inline bool band_empty(const A& a) {
-  if (a.cu_seqlens_q != nullptr || a.cu_seqlens_k != nullptr || a.dropout_p > 0.f) return false;
+inline bool band_empty(const A& a0) {
+  if (a0.cu_seqlens_q != nullptr || a0.cu_seqlens_k != nullptr || a0.dropout_p > 0.f) return false;
+  const A a = fold_lens(a0);
   return norm_band(a.Sq, a.q_half, a.Sk, a.k_half, a.causal, a.window, a.window_left, a.window_right, a.mask_shift).empty;
 }
-// a shift needs dense input and no dropout (the keep mask has position offsets of its own)
+// an absolute shift needs dense input, either shift no dropout (the keep mask has position offsets of its own); the
+// per-sequence shift must leave the kernels' 32-bit off, off - wl, off + wr room: |mask_shift_lens| * Sk < 2^30
 template <typename A>
 inline bool shift_args_ok(const A& a) {
+  if (a.mask_shift_lens != 0) {
+    if (a.dropout_p > 0.f) return false;
+    const int64_t n = a.mask_shift_lens < 0 ? -(int64_t)a.mask_shift_lens : (int64_t)a.mask_shift_lens;
+    if (n * (int64_t)(a.Sk > 0 ? a.Sk : 0) >= ((int64_t)1 << 30)) return false;
+  }
   if (a.mask_shift == 0) return true;
   return a.cu_seqlens_q == nullptr && a.cu_seqlens_k == nullptr && !(a.dropout_p > 0.f);
 }
+// the shift the plans reason with: the normalised mask_shift of dense input; packed input — whose lengths live on the
+// device — stands in mask_shift_lens * Sk (the longest sequence's shift)
+template <typename A>
+inline int64_t plan_shift(const A* a) { return a->mask_shift + (int64_t)a->mask_shift_lens * a->Sk; }
 
 inline bool drop_args_ok(float p, int window, int wl, int wr, int causal) {
   if (!(p >= 0.f) || p >= 1.f) return false;
@@ -253,7 +285,7 @@ static bool fwd_persist_eligible(const rfa_fwd_args* a) {
   if (a->D != kHeadDim || a->cu_seqlens_q != nullptr || a->out_acc != nullptr || a->dropout_p > 0.f) return false;
   if (a->window && (a->window_left >= 0 || (a->window_right >= 0 && !a->causal))) return false;
   if (a->B <= 0 || a->Sq <= 0 || a->Sk <= 0) return false;
-  if (a->mask_shift != 0) return false;                      // (its item deal and 'off >= 0' assume the block's own diagonal)
+  if (plan_shift(a) != 0) return false;                      // (its item deal and 'off >= 0' assume the block's own diagonal)
   return eff_len(a->Sk, a->k_half) >= eff_len(a->Sq, a->q_half);
 }
 static FwdPlan fwd_plan_base(const rfa_fwd_args* a);
@@ -358,7 +390,7 @@ static FwdPlan fwd_plan_base(const rfa_fwd_args* a) {
   }
   pl.rows = 256;
   if (!can_split) return pl;
-  const int64_t key[8] = {1, a->B, a->H, sq, sk, a->causal ? 1 : 0, a->causal ? a->mask_shift : 0, 0};
+  const int64_t key[8] = {1, a->B, a->H, sq, sk, a->causal ? 1 : 0, a->causal ? plan_shift(a) : 0, 0};
   const uint64_t h = plan_hash(key, 8);
   int code;
   if (plan_lookup(h, &code)) {
@@ -366,7 +398,7 @@ static FwdPlan fwd_plan_base(const rfa_fwd_args* a) {
     return pl;
   }
   // workgroups of the 256-row form: block i of every (batch, head) sees the key tiles below its causal edge
-  const int off = sk - sq + (int)a->mask_shift, nq = (sq + 255) / 256;
+  const int off = sk - sq + (int)plan_shift(a), nq = (sq + 255) / 256;
   const int64_t mult = (int64_t)a->B * a->H;
   double best = -1;
   static const int cand[] = {1, 2, 3, 4, 6, 8};
@@ -456,6 +488,7 @@ int rfa_fwd(const rfa_fwd_args* a, void* stream) {
   p.wl = (a->window && a->window_left >= 0) ? a->window_left : -1;
   p.wr = a->causal ? 0 : ((a->window && a->window_right >= 0) ? a->window_right : -1);
   p.shift = (p.causal || p.wl >= 0 || p.wr >= 0) ? (int)a->mask_shift : 0;
+  p.shift_lens = (p.causal || p.wl >= 0 || p.wr >= 0) ? a->mask_shift_lens : 0;
   p.scale = a->softmax_scale;
   p.drop_keep = drop_threshold(a->dropout_p);
   p.drop_scale = drop_rescale(a->dropout_p);
@@ -565,7 +598,7 @@ static int bwd_dkdv_cost_plan(const rfa_bwd_args* a, int hk_launch, bool only_wi
   }
   const bool big = a->D > kHeadDim;          // rfa_bigd.hip: 128-key workgroups (one wave per SIMD), 32-row Q/dO tiles; ONE form
   const int G = a->H / a->Hk;
-  const int64_t key[8] = {2 + 16 * (a->causal ? a->mask_shift : 0), a->B, hk_launch, G, sq, sk, a->causal ? 1 : 0, (big ? 4 : 0) | (a->D == 64 ? 2 : 0) | (only_wide ? 1 : 0)};
+  const int64_t key[8] = {2 + 16 * (a->causal ? plan_shift(a) : 0), a->B, hk_launch, G, sq, sk, a->causal ? 1 : 0, (big ? 4 : 0) | (a->D == 64 ? 2 : 0) | (only_wide ? 1 : 0)};
   const uint64_t h = plan_hash(key, 8);
   int code;
   if (plan_lookup(h, &code)) {
@@ -574,7 +607,7 @@ static int bwd_dkdv_cost_plan(const rfa_bwd_args* a, int hk_launch, bool only_wi
     return (code >> 4) & 1;
   }
   if (bal_out) *bal_out = 0;
-  const int off = sk - sq + (int)a->mask_shift;
+  const int off = sk - sq + (int)plan_shift(a);
   const int64_t mult = (int64_t)a->B * hk_launch;
   const int trows = big ? 32 : 64;
   const int ntq = (sq + trows - 1) / trows;
@@ -633,7 +666,7 @@ static int bwd_dkdv_cost_plan(const rfa_bwd_args* a, int hk_launch, bool only_wi
   // B * Hk * nkb equal workgroups of (T/2 + 2) G tile-times; half of them cross one key-block seam (a second prologue /
   // epilogue) and every pair exchanges one partial: 14 tile-times of overhead on average instead of 8, no second pass
   int bal = 0;
-  if (!only_wide && !big && a->causal && a->mask_shift == 0 && sq == sk && sk >= 512 && sk % 512 == 0) {
+  if (!only_wide && !big && a->causal && plan_shift(a) == 0 && sq == sk && sk >= 512 && sk % 512 == 0) {
     const int nkb = sk / 256;
     std::vector<int> sizes((size_t)(mult * nkb), (2 * nkb + 2) * G);
     double work = 0;
@@ -656,7 +689,7 @@ static int bwd_dkdv_cost_plan(const rfa_bwd_args* a, int hk_launch, bool only_wi
 static bool bwd_bal_eligible(const rfa_bwd_args* a, bool whole_call) {
   if ((a->D != kHeadDim && a->D != 64) || !a->causal || a->cu_seqlens_q != nullptr || a->dropout_p > 0.f) return false;
   if (a->window && (a->window_left >= 0 || a->window_right >= 0)) return false;
-  if (a->mask_shift != 0) return false;        // (the tile deal assumes the block's own diagonal)
+  if (plan_shift(a) != 0) return false;        // (the tile deal assumes the block's own diagonal)
   const int lq = eff_len(a->Sq, a->q_half), lk = eff_len(a->Sk, a->k_half);
   if (lq != lk || lk < 512 || (lk % 512) != 0) return false;
   if (!bwd_single_phase(a) || (a->phases & (RFA_BWD_SKIP_DKDV | RFA_BWD_SKIP_DQ))) return false;
@@ -902,6 +935,7 @@ int rfa_bwd(const rfa_bwd_args* a, void* stream) {
   p.wl = (a->window && a->window_left >= 0) ? a->window_left : -1;
   p.wr = a->causal ? 0 : ((a->window && a->window_right >= 0) ? a->window_right : -1);
   p.shift = (p.causal || p.wl >= 0 || p.wr >= 0) ? (int)a->mask_shift : 0;
+  p.shift_lens = (p.causal || p.wl >= 0 || p.wr >= 0) ? a->mask_shift_lens : 0;
   p.scale = a->softmax_scale;
   p.drop_keep = drop_threshold(a->dropout_p);
   p.drop_scale = drop_rescale(a->dropout_p);

@@ -147,7 +147,7 @@ __global__ __launch_bounds__(kBgThreads) void fwd_big_kernel(const FwdParams p) 
   const int lq = qs.len, lk = ks.len;
   const int qwg0 = qblk * kBgRows;
   if (qwg0 >= lq) return;
-  const int off = lk - lq + p.shift;       // bottom-right alignment, moved by the block's place in the full sequence (rfa.h: mask_shift)
+  const int off = lk - lq + p.shift + p.shift_lens * lk;   // bottom-right alignment, moved by the block's place in the full sequence (rfa.h: mask_shift, mask_shift_lens)
   const int qw0 = qwg0 + wave * 32;
   const int qrow = qw0 + l31;
   const int qrow_c = qrow < lq ? qrow : lq - 1;
@@ -419,7 +419,7 @@ __global__ __launch_bounds__(kBgThreads) void dq_big_kernel(const BwdParams p) {
   const int lq = qs.len, lk = ks.len;
   const int qwg0 = qblk * kBgRows;
   if (qwg0 >= lq) return;
-  const int off = lk - lq + p.shift;       // bottom-right alignment, moved by the block's place in the full sequence (rfa.h: mask_shift)
+  const int off = lk - lq + p.shift + p.shift_lens * lk;   // bottom-right alignment, moved by the block's place in the full sequence (rfa.h: mask_shift, mask_shift_lens)
   const int qw0 = qwg0 + wave * 32;
   const int qrow = qw0 + l31;
   const int qrow_c = qrow < lq ? qrow : lq - 1;
@@ -644,7 +644,7 @@ __global__ __launch_bounds__(kBgThreads) void dkdv_big_kernel(const BwdParams p)
   const int lq = qs.len, lk = ks.len;
   const int kwg0 = kblk * kBgRows;
   if (kwg0 >= lk) return;
-  const int off = lk - lq + p.shift;       // bottom-right alignment, moved by the block's place in the full sequence (rfa.h: mask_shift)
+  const int off = lk - lq + p.shift + p.shift_lens * lk;   // bottom-right alignment, moved by the block's place in the full sequence (rfa.h: mask_shift, mask_shift_lens)
   const int kw0 = kwg0 + wave * 32;
   const int krow = kw0 + l31;
   const int64_t qbatch = p.cu_q ? 0 : (int64_t)b;
@@ -987,7 +987,7 @@ __global__ __launch_bounds__(kBgThreads) void dkdv_fused_big_kernel(const BwdPar
   const int lq = qs.len, lk = ks.len;
   const int kwg0 = kblk * kBgRows;
   if (kwg0 >= lk) return;
-  const int off = lk - lq + p.shift;       // bottom-right alignment, moved by the block's place in the full sequence (rfa.h: mask_shift)
+  const int off = lk - lq + p.shift + p.shift_lens * lk;   // bottom-right alignment, moved by the block's place in the full sequence (rfa.h: mask_shift, mask_shift_lens)
   const int kw0 = kwg0 + wave * 32;
   const int krow = kw0 + l31;
   const int64_t qbatch = p.cu_q ? 0 : (int64_t)b;

@@ -125,7 +125,7 @@ __global__ __launch_bounds__(kDqThreads, 2) void dq_kernel(const BwdParams p) {
   const int lq = qs.len, lk = ks.len;
   const int qwg0 = qblk * kDqRows;
   if (qwg0 >= lq) return;
-  const int off = lk - lq + p.shift;       // bottom-right alignment, moved by the block's place in the full sequence (rfa.h: mask_shift)
+  const int off = lk - lq + p.shift + p.shift_lens * lk;   // bottom-right alignment, moved by the block's place in the full sequence (rfa.h: mask_shift, mask_shift_lens)
   const int qw0 = qwg0 + wave * 32;
   const int qrow = qw0 + l31;
   const int qrow_c = qrow < lq ? qrow : lq - 1;
@@ -486,7 +486,7 @@ __global__ __launch_bounds__(kKvThreads, 2) void dkdv_kernel(const BwdParams p) 
   const SeqSpan qs = resolve_span(p.cu_q, b, p.Sq, p.q_half);
   const SeqSpan ks = resolve_span(p.cu_k, b, p.Sk, p.k_half);
   const int lq = qs.len, lk = ks.len;
-  const int off = lk - lq + p.shift;       // bottom-right alignment, moved by the block's place in the full sequence (rfa.h: mask_shift)
+  const int off = lk - lq + p.shift + p.shift_lens * lk;   // bottom-right alignment, moved by the block's place in the full sequence (rfa.h: mask_shift, mask_shift_lens)
   const int64_t qbatch = p.cu_q ? 0 : (int64_t)b;
   const int64_t kbatch = p.cu_k ? 0 : (int64_t)b;
   // one pass per key block of this workgroup (two for a type-B workgroup of the balanced schedule, else one)

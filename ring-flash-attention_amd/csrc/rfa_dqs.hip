@@ -104,7 +104,7 @@ __global__ __launch_bounds__(DsGeo<kW>::kThreads, 2) void dq_ds_kernel(const Bwd
   const int64_t kbatch = p.cu_k ? 0 : (int64_t)b;
   const int qwg0 = qblk * kDsRows;
   if (qwg0 >= lq) return;
-  const int off = lk - lq + p.shift;       // bottom-right alignment, moved by the block's place in the full sequence (rfa.h: mask_shift)
+  const int off = lk - lq + p.shift + p.shift_lens * lk;   // bottom-right alignment, moved by the block's place in the full sequence (rfa.h: mask_shift, mask_shift_lens)
   const int qw0 = qwg0 + wave * 32;
   const int qrow = qw0 + l31;
 

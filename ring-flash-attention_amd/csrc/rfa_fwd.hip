@@ -127,7 +127,7 @@ __global__ __launch_bounds__(kW * 64, 2) void fwd_kernel(const FwdParams p) {
   const int lq = qs.len, lk = ks.len;
   const int qwg0 = qblk * kFwdQRows;
   if (qwg0 >= lq) return;
-  const int off = lk - lq + p.shift;       // bottom-right alignment, moved by the block's place in the full sequence (rfa.h: mask_shift)
+  const int off = lk - lq + p.shift + p.shift_lens * lk;   // bottom-right alignment, moved by the block's place in the full sequence (rfa.h: mask_shift, mask_shift_lens)
   const int qw0 = qwg0 + wave * 32;
   const int qrow = qw0 + l31;
   const int qrow_c = qrow < lq ? qrow : lq - 1;

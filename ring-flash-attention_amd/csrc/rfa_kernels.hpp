@@ -46,6 +46,8 @@ struct FwdParams {
   int wl, wr;          // visible keys of query i: i + (Sk - Sq) + shift - wl <= j <= i + (Sk - Sq) + shift + wr; -1 = unbounded
                        // (causal is folded in by the API layer: wr = 0)
   int shift;           // rfa.h: mask_shift after the API layer's band normalisation (dense input only; the plain causal bound too)
+  int shift_lens;      // rfa.h: mask_shift_lens — packed input only (dense calls fold it into shift): sequence b's band is moved by
+                       // shift_lens * len_k(b), so every derived tile range / dark-workgroup exit follows the sequence's own length
   int nqblk;
   int qrows;           // query rows per workgroup the launch was sized for: 256 (8 waves) or 128 (4 waves, small grids)
   int persist_grid;    // > 0: the persistent 256-row form (fwd_persist_kernel) with this many workgroups
@@ -89,6 +91,7 @@ struct BwdParams {
   int causal, acc_init;
   int wl, wr;          // attention window as in FwdParams (causal: wr = 0)
   int shift;           // as in FwdParams
+  int shift_lens;      // as in FwdParams
   int kv_f32;          // dk / dv point to fp32 buffers (overwritten), strides in fp32 elements
   void* ds;            // dS spill scratch (rfa_dqs.hip) or nullptr: dkdv_kernel stores its packed dS blocks there
   int ds_tri, ds_c;    // scratch rows are triangular (dense causal calls): row qt holds key blocks 0 .. min(nKb, qt + ds_c) - 1

@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # RFA_LIB_PATH: A/B tooling only (tools/ab_variants.py builds tuning variants of the same library)
 LIB_PATH = os.environ.get("RFA_LIB_PATH") or os.path.join(_HERE, "librfa_hip.so")
 
-RFA_ABI_VERSION = 7
+RFA_ABI_VERSION = 8
 RFA_BF16, RFA_F16 = 0, 1
 HALF_FULL, HALF_FRONT, HALF_BACK = 0, 1, 2
 BWD_ALL, BWD_COMPUTE, BWD_REDUCE = 0, 1, 2
@@ -46,6 +46,7 @@ class FwdArgs(C.Structure):
         ("fwd_form", C.c_int32),
         ("workspace", C.c_void_p), ("kv_nsplit", C.c_int32), ("total_q", C.c_int64),
         ("mask_shift", C.c_int64),
+        ("mask_shift_lens", C.c_int32),
     ]
 
 
@@ -92,6 +93,7 @@ class BwdArgs(C.Structure):
         ("ds_scratch_bytes", C.c_int64),
         ("total_q", C.c_int64),
         ("mask_shift", C.c_int64),
+        ("mask_shift_lens", C.c_int32),
     ]
 
 

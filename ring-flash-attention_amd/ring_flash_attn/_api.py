@@ -76,9 +76,11 @@ def _check_unsupported(dropout_p, window_size, alibi_slopes, windows_ok=False, d
     function on a single-rank group, and llama3_flash_attn_varlen_func on any group (it gathers K/V) — the coverage the
     reference gets from forwarding dropout_p to flash_attn (llama3_flash_attn_varlen.py:131-147); it declares dropout
     over a ring unsupported (README.md:158-159) and so do the schedules here.  Windows are usable there too, and on any
-    group with the dense ring and zigzag schedules, which tell every block call where it sits in the full sequence
-    (`mask_shift`, include/rfa.h).  The stripe schedule and the two `*_varlen` ring families do not (a token's
-    neighbours are strided over the ranks / a per-sequence shift would be needed): they raise on a multi-rank group.
+    group with every ring schedule, each of which tells every block call where it sits in the full sequence: the dense
+    ring and zigzag schedules in rows (`mask_shift`, include/rfa.h), the two `*_varlen` ring families in units of every
+    packed sequence's own length (`mask_shift_lens`), the stripe schedule — token i of rank r is global token i W + r —
+    as a dense shifted band in local rows.  These schedules pass windows_ok=True for such calls; windows_ok=False (the
+    `torch.compile` whole-schedule operator, which has no windowed form) still raises.
     Dropout together with a window is not available anywhere."""
     assert alibi_slopes is None
     if dropout_ok is None:
@@ -90,10 +92,9 @@ def _check_unsupported(dropout_p, window_size, alibi_slopes, windows_ok=False, d
         raise NotImplementedError("ring_flash_attn: dropout over a multi-rank ring is not supported (as in the "
                                   "reference); use llama3_flash_attn_varlen_func or a single-rank group")
     if not windows_ok and has_window(window_size):
-        raise NotImplementedError("ring_flash_attn: sliding window over a multi-rank group is supported by the dense "
-                                  "ring_flash_attn_* and zigzag_ring_flash_attn_* functions only, not by the stripe "
-                                  "and *_varlen ring schedules; use one of those, llama3_flash_attn_varlen_func or a "
-                                  "single-rank group")
+        raise NotImplementedError("ring_flash_attn: sliding window over a multi-rank group is served by the eager ring, "
+                                  "zigzag, stripe and *_varlen ring functions and by llama3_flash_attn_varlen_func, not "
+                                  "by this entry (the whole-schedule operator has no windowed form)")
     if drop and has_window(window_size):
         raise NotImplementedError("ring_flash_attn: dropout together with a sliding window is not supported")
 
@@ -167,7 +168,7 @@ def _split_kept(ctx, more):
 def make_autograd_function(name, forward_impl, backward_impl, n_lead, window_ring=False):
     """n_lead: number of non-tensor positional arguments between (q,k,v) and the common tail
     (0 for the batch API, 2 = (cu_seqlens, max_seqlen) for varlen).  window_ring: the schedule serves a sliding window
-    on a multi-rank group (dense ring and zigzag)."""
+    on a multi-rank group (every ring family does: dense and varlen ring and zigzag, stripe)."""
 
     class _Fn(torch.autograd.Function):
         @staticmethod
@@ -386,13 +387,16 @@ def make_dense_api(fn, prefix, forward_impl=None, backward_impl=None, packed_tra
             _compilable(qkvpacked_func, lower_qkv, multi_qkv))
 
 
-def make_varlen_api(fn, prefix, forward_impl=None, backward_impl=None):
+def make_varlen_api(fn, prefix, forward_impl=None, backward_impl=None, window_ring=False):
     """(T,H,D) + (cu_seqlens, max_seqlen) API.  With the schedule's forward / backward the packed entry points get
-    their own autograd Function (gradients land in ONE packed buffer, see make_packed_function)."""
+    their own autograd Function (gradients land in ONE packed buffer, see make_packed_function).
+    window_ring: as in make_autograd_function (pass the same value to both)."""
     kv_fn = qkv_fn = None
     if forward_impl is not None:
-        kv_fn = make_packed_function(fn.__name__ + "KVPacked", fn, forward_impl, backward_impl, 2, 1, 2)
-        qkv_fn = make_packed_function(fn.__name__ + "QKVPacked", fn, forward_impl, backward_impl, 2, 1, 3)
+        kv_fn = make_packed_function(fn.__name__ + "KVPacked", fn, forward_impl, backward_impl, 2, 1, 2,
+                                     window_ring=window_ring)
+        qkv_fn = make_packed_function(fn.__name__ + "QKVPacked", fn, forward_impl, backward_impl, 2, 1, 3,
+                                      window_ring=window_ring)
 
     def func(q, k, v, cu_seqlens, max_seqlen, dropout_p=0.0, softmax_scale=None, causal=False,
              window_size=(-1, -1), alibi_slopes=None, deterministic=False, return_attn_probs=False,

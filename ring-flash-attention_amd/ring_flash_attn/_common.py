@@ -63,6 +63,16 @@ def require_mask_shift(be, what):
                                   "apply the window per block)")
 
 
+def require_mask_shift_lens(be, what):
+    """The packed (varlen) counterpart of require_mask_shift: the lengths of packed sequences differ, so a block's place
+    in the full sequences is a multiple of every sequence's own length (`mask_shift_lens`, include/rfa.h:
+    HipBackend.serves_mask_shift_lens).  Refused before anything is exchanged, on every rank alike."""
+    if not getattr(be, "serves_mask_shift_lens", False):
+        raise NotImplementedError(f"ring_flash_attn: {what} with a sliding window on a multi-rank group needs a backend "
+                                  f"that serves `mask_shift_lens`; {getattr(be, 'name', type(be).__name__)!r} does not (it "
+                                  "would apply the window per block)")
+
+
 def _as_cu(cu_seqlens, device):
     """cu_seqlens as an int32 tensor on the compute device (the kernels read it on device)."""
     import torch

@@ -56,6 +56,7 @@ class HipBackend:
 
     name = "hip"
     serves_mask_shift = True        # fwd / bwd take `mask_shift` (include/rfa.h, ABI 7): what a windowed multi-rank schedule needs
+    serves_mask_shift_lens = True   # ... and `mask_shift_lens` (ABI 8), the per-sequence shift the packed (varlen) ring schedules need
 
     def __init__(self):
         self.lib = _C.load()
@@ -83,12 +84,14 @@ class HipBackend:
     def fwd(self, q, k, v, *, softmax_scale, causal, cu_seqlens_q=None, cu_seqlens_k=None,
             max_seqlen_q=None, max_seqlen_k=None, q_half=HALF_FULL, k_half=HALF_FULL,
             out=None, lse=None, out_acc=None, lse_acc=None, acc_init=False, window=(-1, -1), dropout=None,
-            mask_shift=0):
+            mask_shift=0, mask_shift_lens=0):
         """Block attention.  Plain mode fills (out, lse); accumulate mode merges into the fp32
         (out_acc, lse_acc) pair (fused update_out_and_lse).  Dense: q (B,Sq,H,D); varlen: (T,H,D).
         dropout: (p, seed, q_pos_offset, k_pos_offset, head_offset) or None.
         mask_shift: where the block sits in a longer sequence (include/rfa.h; dense input) — for blocks of equal length
-        the global position of q row 0 minus that of k row 0; moves the causal diagonal and the window alike."""
+        the global position of q row 0 minus that of k row 0; moves the causal diagonal and the window alike.
+        mask_shift_lens: the same in units of every sequence's own key length (include/rfa.h, ABI 8): the shift of packed
+        (cu_seqlens) input; dense input folds it into mask_shift."""
         self._check_dev(q, k, v, out, lse, out_acc, lse_acc)
         varlen = cu_seqlens_q is not None
         a = _C.FwdArgs()
@@ -119,6 +122,7 @@ class HipBackend:
         if window is not None and (window[0] >= 0 or window[1] >= 0):
             a.window, a.window_left, a.window_right = 1, int(window[0]), int(window[1])
         a.mask_shift = int(mask_shift)
+        a.mask_shift_lens = int(mask_shift_lens)
         a.dtype = self._dtype(q)
         _set_dropout(a, dropout)
         a.fwd_form = _fwd_form()
@@ -156,7 +160,7 @@ class HipBackend:
             cu_seqlens_k=None, max_seqlen_q=None, max_seqlen_k=None, q_half=HALF_FULL,
             k_half=HALF_FULL, dq=None, dk=None, dv=None, dq_acc=None, dk_acc=None, dv_acc=None,
             acc_init=False, deterministic=False, phases=_C.BWD_ALL, partials=None, ds_scratch=None,
-            window=(-1, -1), prof_events=None, dropout=None, mask_shift=0):
+            window=(-1, -1), prof_events=None, dropout=None, mask_shift=0, mask_shift_lens=0):
         """dQ/dK/dV of one block.  Plain outputs (io dtype) or `+=` into fp32 accumulators.
         phases=BWD_COMPUTE / BWD_REDUCE splits the call so a ring step can overlap the kernels
         with the arrival of the dk/dv accumulators it adds into: the COMPUTE call RETURNS the buffer
@@ -203,6 +207,7 @@ class HipBackend:
         if window is not None and (window[0] >= 0 or window[1] >= 0):
             a.window, a.window_left, a.window_right = 1, int(window[0]), int(window[1])
         a.mask_shift = int(mask_shift)
+        a.mask_shift_lens = int(mask_shift_lens)
         a.dtype = self._dtype(q)
         a.phases = phases
         _set_dropout(a, dropout)

@@ -6,14 +6,35 @@ autograd :195-265, wrappers :268-358).  Every packed sequence is sharded contigu
 ring, so the local `cu_seqlens` are identical for q and k at every step.  lse is produced
 natively as (nheads, total) — the layout of flash_attn >= 2.7 — so the reference's
 flatten/unflatten shims (triton_utils.py) are never needed on this path.
+
+Sliding windows over several ranks (no counterpart in the reference): the K/V on hand at step d belong to rank
+r - d, which holds the l_b rows in front of this rank's l_b rows of EVERY packed sequence b — d times the sequence's own
+local length, a different number of rows for every sequence.  The kernels are told so in those units
+(`mask_shift_lens`, include/rfa.h ABI 8) and band every sequence as its part of one window over its full length.
+The exchange stays a full rotation: the host does not know the shortest sequence, so it cannot prove a hop dark for
+all of them — the COMPUTE follows the window inside the kernels (dark sequences and tiles are skipped there), the
+traffic does not.  A window that covers the whole of the longest sequence is dropped on the host and takes the
+unwindowed path unchanged.
 """
 import torch
 
 from . import _C
 from .backend import get_backend
 from .utils import RingComm, single_rank
-from ._common import dropout_arg
+from ._common import dropout_arg, global_window, require_mask_shift_lens
 from ._api import make_autograd_function, make_varlen_api, _grad_buffers
+
+
+def _band(causal, win, step, rank, world):
+    """band keywords of the block call of ring step `step`: unwindowed, only the diagonal block is masked; windowed, every
+    block is told how many ranks (= local sequence lengths) its keys lie in front of its queries"""
+    if win is None:
+        return {"causal": causal and step == 0}
+    t = step if step <= rank else step - world
+    kw = {"causal": causal, "window": win}
+    if t:
+        kw["mask_shift_lens"] = t
+    return kw
 
 
 def ring_flash_attn_varlen_forward(
@@ -42,6 +63,9 @@ def ring_flash_attn_varlen_forward(
         be.fwd(q, k, v, softmax_scale=softmax_scale, causal=causal, out=out, lse=lse, window=window_size, dropout=dropout_arg(dropout_p, dropout_seed), **vl)
         return out, lse
     assert not dropout_p, "dropout over a multi-rank ring is not supported (as in the reference)"
+    win = global_window(window_size, causal, comm.world_size * int(max_seqlen))
+    if win is not None:
+        require_mask_shift_lens(be, "ring_flash_attn_varlen")
 
     out_acc = torch.empty((T, H, D), dtype=torch.float32, device=q.device)
     lse_acc = torch.empty((H, T), dtype=torch.float32, device=q.device)
@@ -51,8 +75,8 @@ def ring_flash_attn_varlen_forward(
         if step + 1 != comm.world_size:
             next_k, next_v = comm.send_recv_kv(k, v)
         if not causal or step <= comm.rank:
-            be.fwd(q, k, v, softmax_scale=softmax_scale, causal=causal and step == 0,
-                   out_acc=out_acc, lse_acc=lse_acc, acc_init=first, **vl)
+            be.fwd(q, k, v, softmax_scale=softmax_scale, out_acc=out_acc, lse_acc=lse_acc, acc_init=first,
+                   **_band(causal, win, step, comm.rank, comm.world_size), **vl)
             first = False
         if step + 1 != comm.world_size:
             comm.wait()
@@ -99,6 +123,9 @@ def ring_flash_attn_varlen_backward(
                dq=dq, dk=dk, dv=dv, deterministic=deterministic, window=window_size, dropout=dropout_arg(dropout_p, dropout_seed), **vl)
         return dq, dk, dv
     assert not dropout_p, "dropout over a multi-rank ring is not supported (as in the reference)"
+    win = global_window(window_size, causal, kv_comm.world_size * int(max_seqlen))
+    if win is not None:
+        require_mask_shift_lens(be, "ring_flash_attn_varlen")
 
     dq = None
     dk = torch.empty(k.shape, dtype=torch.float32, device=q.device)
@@ -110,8 +137,8 @@ def ring_flash_attn_varlen_backward(
             next_k, next_v = kv_comm.send_recv_kv(k, v)
 
         if step <= kv_comm.rank or not causal:
-            bwd_causal = causal and step == 0
-            common = dict(softmax_scale=softmax_scale, causal=bwd_causal, deterministic=deterministic, **vl)
+            common = dict(softmax_scale=softmax_scale, deterministic=deterministic,
+                          **_band(causal, win, step, kv_comm.rank, kv_comm.world_size), **vl)
             if dq is None:
                 dq = torch.empty((T, H, D), dtype=torch.float32, device=q.device)
                 be.bwd(dout, q, k, v, softmax_lse, delta, dq_acc=dq, dk_acc=dk, dv_acc=dv, acc_init=True, **common)
@@ -138,9 +165,10 @@ def ring_flash_attn_varlen_backward(
 
 
 RingFlashAttnVarlenFunc = make_autograd_function(
-    "RingFlashAttnVarlenFunc", ring_flash_attn_varlen_forward, ring_flash_attn_varlen_backward, 2)
+    "RingFlashAttnVarlenFunc", ring_flash_attn_varlen_forward, ring_flash_attn_varlen_backward, 2, window_ring=True)
 (
     ring_flash_attn_varlen_func,
     ring_flash_attn_varlen_kvpacked_func,
     ring_flash_attn_varlen_qkvpacked_func,
-) = make_varlen_api(RingFlashAttnVarlenFunc, "ring_flash_attn_varlen", ring_flash_attn_varlen_forward, ring_flash_attn_varlen_backward)
+) = make_varlen_api(RingFlashAttnVarlenFunc, "ring_flash_attn_varlen", ring_flash_attn_varlen_forward, ring_flash_attn_varlen_backward,
+                    window_ring=True)

@@ -6,14 +6,88 @@ an ordinary causal block; at step s > rank the incoming keys are "one token ahea
 causal on the SHIFTED views q[:, 1:] x k[:, :-1] (:63-93), merged into rows [1:].
 Built from the same kernels as the zigzag path: the shifted views are pointer offsets into the same
 tensors (no copies), merged by the fused fp32 epilogue; dQ / dK / dV accumulate in fp32 in place.
+
+Sliding windows over several ranks (no counterpart in the reference): token i of rank r is global token i W + r, so for
+the queries of rank rq against the keys of rank rk (a = rq - rk) a causal window (wl, 0) of the global sequence is, in
+LOCAL rows, the band  i + ceil((a - wl) / W) <= j <= i + floor(a / W)  — an ordinary dense shifted block
+(`stripe_window_band`: mask_shift = floor(a / W), 0 or -1, causal, and a local left bound).  A block whose local left
+bound comes out negative holds no visible element and is skipped — on every rank alike, it depends on (a, wl, W)
+only.  The exchange stays a full rotation: a token's neighbours are strided over ALL ranks, so the compute follows the
+window and the traffic does not.  The unwindowed code, with its sliced views, is untouched; a window that covers the
+whole sequence (wl >= W S - 1) is dropped on the host and takes it.
 """
 import torch
 
 from . import _C
 from .backend import get_backend
 from .utils import RingComm, single_rank
-from ._common import dropout_arg
+from ._common import dropout_arg, global_window, require_mask_shift
 from ._api import make_autograd_function, make_dense_api, _grad_buffers
+
+
+def stripe_window_band(rank, src, world, window_left):
+    """(mask_shift, local window_left) of the block of rank `rank`'s queries against rank `src`'s keys under a causal
+    window of `window_left` global tokens, or None where no element of the block is visible"""
+    a = rank - src
+    hi = a // world                                  # floor(a / W): 0 (keys of a rank in front or this one) or -1
+    lo = -((window_left - a) // world)               # ceil((a - wl) / W)
+    return None if hi - lo < 0 else (hi, hi - lo)
+
+
+def _stripe_window_forward(be, comm, q, k, v, softmax_scale, wl):
+    B, S, H, D = q.shape
+    W, rank = comm.world_size, comm.rank
+    out_acc = torch.empty((B, S, H, D), dtype=torch.float32, device=q.device)
+    lse_acc = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
+    next_k, next_v = None, None
+    for step in range(W):
+        if step + 1 != W:
+            next_k, next_v = comm.send_recv_kv(k, v)
+        band = stripe_window_band(rank, (rank - step) % W, W, wl)
+        if band is not None:                         # (step 0, a = 0, is always visible: it initialises the accumulators)
+            shift = {"mask_shift": band[0]} if band[0] else {}
+            be.fwd(q, k, v, softmax_scale=softmax_scale, causal=True, window=(band[1], -1),
+                   out_acc=out_acc, lse_acc=lse_acc, acc_init=(step == 0), **shift)
+        if step + 1 != W:
+            comm.wait()
+            k, v = next_k, next_v
+    return be.cast(out_acc, q.dtype), lse_acc
+
+
+def _stripe_window_backward(be, kv_comm, d_kv_comm, dout, q, k, v, softmax_lse, delta, softmax_scale, wl, deterministic):
+    B, S, H, D = q.shape
+    W, rank = kv_comm.world_size, kv_comm.rank
+    dq = torch.empty((B, S, H, D), dtype=torch.float32, device=q.device)
+    dk = torch.empty(k.shape, dtype=torch.float32, device=q.device)
+    dv = torch.empty(v.shape, dtype=torch.float32, device=q.device)
+    next_dk, next_dv = None, None
+    next_k, next_v = None, None
+    for step in range(W):
+        if step + 1 != W:
+            next_k, next_v = kv_comm.send_recv_kv(k, v)
+        band = stripe_window_band(rank, (rank - step) % W, W, wl)
+        if band is not None:
+            common = dict(softmax_scale=softmax_scale, causal=True, window=(band[1], -1), deterministic=deterministic)
+            if band[0]:
+                common["mask_shift"] = band[0]
+            if step == 0:
+                be.bwd(dout, q, k, v, softmax_lse, delta, dq_acc=dq, dk_acc=dk, dv_acc=dv, acc_init=True, **common)
+            else:
+                part = be.bwd(dout, q, k, v, softmax_lse, delta, dq_acc=dq, dk_acc=dk, dv_acc=dv,
+                              phases=_C.BWD_COMPUTE, **common)
+                d_kv_comm.wait()
+                dk, dv = next_dk, next_dv
+                be.bwd(dout, q, k, v, softmax_lse, delta, dq_acc=dq, dk_acc=dk, dv_acc=dv,
+                       phases=_C.BWD_REDUCE, partials=part, **common)
+        elif step != 0:
+            d_kv_comm.wait()
+            dk, dv = next_dk, next_dv
+        if step + 1 != W:
+            kv_comm.wait()
+            k, v = next_k, next_v
+        next_dk, next_dv = d_kv_comm.send_recv_kv(dk, dv)
+    d_kv_comm.wait()
+    return be.cast(dq, q.dtype), be.cast(next_dk, q.dtype), be.cast(next_dv, q.dtype)
 
 
 def stripe_flash_attn_forward(
@@ -42,6 +116,10 @@ def stripe_flash_attn_forward(
         be.fwd(q, k, v, softmax_scale=softmax_scale, causal=True, out=out, lse=lse, window=window_size, dropout=dropout_arg(dropout_p, dropout_seed))
         return out, lse
     assert not dropout_p, "dropout over a multi-rank ring is not supported (as in the reference)"
+    win = global_window(window_size, True, comm.world_size * S)
+    if win is not None:
+        require_mask_shift(be, "stripe_flash_attn")
+        return _stripe_window_forward(be, comm, q, k, v, softmax_scale, win[0])
 
     out_acc = torch.empty((B, S, H, D), dtype=torch.float32, device=q.device)
     lse_acc = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
@@ -102,6 +180,11 @@ def stripe_flash_attn_backward(
                dq=dq, dk=dk, dv=dv, deterministic=deterministic, window=window_size, dropout=dropout_arg(dropout_p, dropout_seed))
         return dq, dk, dv
     assert not dropout_p, "dropout over a multi-rank ring is not supported (as in the reference)"
+    win = global_window(window_size, True, kv_comm.world_size * S)
+    if win is not None:
+        require_mask_shift(be, "stripe_flash_attn")
+        return _stripe_window_backward(be, kv_comm, d_kv_comm, dout, q, k, v, softmax_lse, delta, softmax_scale, win[0],
+                                       deterministic)
 
     dq = torch.empty((B, S, H, D), dtype=torch.float32, device=q.device)
     dk = torch.empty(k.shape, dtype=torch.float32, device=q.device)
@@ -149,9 +232,10 @@ def stripe_flash_attn_backward(
 
 
 StripeFlashAttnFunc = make_autograd_function(
-    "StripeFlashAttnFunc", stripe_flash_attn_forward, stripe_flash_attn_backward, 0)
+    "StripeFlashAttnFunc", stripe_flash_attn_forward, stripe_flash_attn_backward, 0, window_ring=True)
 (
     stripe_flash_attn_func,
     stripe_flash_attn_kvpacked_func,
     stripe_flash_attn_qkvpacked_func,
-) = make_dense_api(StripeFlashAttnFunc, "stripe_flash_attn", stripe_flash_attn_forward, stripe_flash_attn_backward)
+) = make_dense_api(StripeFlashAttnFunc, "stripe_flash_attn", stripe_flash_attn_forward, stripe_flash_attn_backward,
+                   window_ring=True)

@@ -18,13 +18,22 @@ protocol; `gather` is the mesh-aware form of the dense zigzag path (zigzag_ring_
 sequences — one all-gather of K/V beside the local block, every rank's dK/dV contribution for the rows of rank
 c written into slot c (a "front" step fills only the front half of every sequence: the slot is zeroed first),
 one all-to-all, fp32 sum of the W arrivals at the owner (rfa_sum_slots).  Same kernels, same step order.
+
+Sliding windows over several ranks (no counterpart in the reference): as in the dense windowed zigzag
+(zigzag_ring_flash_attn.py: zigzag_window_pairs) a windowed step is one causal call per (query chunk cq, key chunk
+ck <= cq) pair — here with the kernels' q_half / k_half selectors instead of slices, and with the distance from the
+diagonal given in chunks of every sequence's own length (`mask_shift_lens = cq - ck`, include/rfa.h ABI 8).  The host does
+not know the lengths, so no pair is skipped and the exchange is a full rotation (either form): the COMPUTE follows the
+window inside the kernels, the traffic does not.  Kept as plain as the dense form: zero-initialised fp32 gradient
+accumulators, single-phase block calls, an fp32 reduce-scatter of the dK/dV slots in the gather form.  A window that
+covers the whole of the longest sequence is dropped on the host and takes the unwindowed path unchanged.
 """
 import torch
 
 from . import _C, config
 from .backend import get_backend, HALF_FRONT, HALF_BACK
-from .utils import AllGatherComm, RingComm, all_to_all_async, single_rank
-from ._common import dropout_arg
+from .utils import AllGatherComm, RingComm, all_to_all_async, reduce_scatter_async, single_rank
+from ._common import dropout_arg, global_window, require_mask_shift_lens
 from ._api import make_autograd_function, make_varlen_api, _grad_buffers
 
 
@@ -78,6 +87,104 @@ def get_half_lse(lse, cu_seqlens, *, front: bool):
     return new_lse
 
 
+_HALVES = (HALF_FRONT, HALF_BACK)
+
+
+def zigzag_varlen_window_pairs(rank, src, world):
+    """the (query half, key half, mask_shift_lens) block calls of rank `rank` against the K/V of rank `src`, diagonal
+    blocks first (they initialise the accumulators of their half).  Unlike zigzag_window_pairs no pair is dropped for
+    lying beyond the window: that depends on every sequence's own chunk length, which only the kernels see."""
+    qc = (rank, 2 * world - 1 - rank)
+    kc = (src, 2 * world - 1 - src)
+    pairs = [(hq, hk, qc[hq] - kc[hk]) for hq in (0, 1) for hk in (0, 1) if qc[hq] - kc[hk] >= 0]
+    return sorted(pairs, key=lambda p: p[2] != 0)
+
+
+def _band_lens(d):
+    return {"mask_shift_lens": d} if d else {}
+
+
+def _zigzag_varlen_window_forward(be, process_group, comm, q, k, v, vl, softmax_scale, window):
+    T, H, D = q.shape
+    W, rank = comm.world_size, comm.rank
+    out_acc = torch.empty((T, H, D), dtype=torch.float32, device=q.device)
+    lse_acc = torch.empty((H, T), dtype=torch.float32, device=q.device)
+    started = [False, False]
+
+    def blocks(src, ks, vs):
+        for hq, hk, d in zigzag_varlen_window_pairs(rank, src, W):
+            be.fwd(q, ks, vs, softmax_scale=softmax_scale, causal=True, window=window, q_half=_HALVES[hq],
+                   k_half=_HALVES[hk], out_acc=out_acc, lse_acc=lse_acc, acc_init=not started[hq], **_band_lens(d), **vl)
+            started[hq] = True
+
+    if varlen_exchange_mode() == "gather":
+        gather, k_all, v_all = _gather_kv(process_group, k, v, W)
+        blocks(rank, k, v)                                                 # beside the all-gather
+        gather.wait()
+        for step in range(1, W):
+            src = (rank - step) % W
+            blocks(src, k_all[src], v_all[src])
+        return be.cast(out_acc, q.dtype), lse_acc
+    next_k, next_v = None, None
+    for step in range(W):
+        if step + 1 != W:
+            next_k, next_v = comm.send_recv_kv(k, v)
+        blocks((rank - step) % W, k, v)
+        if step + 1 != W:
+            comm.wait()
+            k, v = next_k, next_v
+    return be.cast(out_acc, q.dtype), lse_acc
+
+
+def _zigzag_varlen_window_backward(be, process_group, kv_comm, d_kv_comm, dout, q, k, v, softmax_lse, delta, vl,
+                                   softmax_scale, window, deterministic):
+    T, H, D = q.shape
+    W, rank = kv_comm.world_size, kv_comm.rank
+    dq = torch.zeros((T, H, D), dtype=torch.float32, device=q.device)
+
+    def blocks(src, ks, vs, dk, dv):
+        for hq, hk, d in zigzag_varlen_window_pairs(rank, src, W):
+            be.bwd(dout, q, ks, vs, softmax_lse, delta, softmax_scale=softmax_scale, causal=True, window=window,
+                   q_half=_HALVES[hq], k_half=_HALVES[hk], dq_acc=dq, dk_acc=dk, dv_acc=dv,
+                   deterministic=deterministic, **_band_lens(d), **vl)
+
+    if varlen_exchange_mode() == "gather":
+        gather, k_all, v_all = _gather_kv(process_group, k, v, W)
+        # slot c: this rank's dK/dV for the rows of rank c, fp32, summed over the ranks by a reduce-scatter
+        dk_cat = torch.zeros((W * k.shape[0],) + tuple(k.shape[1:]), dtype=torch.float32, device=q.device)
+        dv_cat = torch.zeros((W * v.shape[0],) + tuple(v.shape[1:]), dtype=torch.float32, device=q.device)
+        dk_all, dv_all = dk_cat.view((W,) + tuple(k.shape)), dv_cat.view((W,) + tuple(v.shape))
+        blocks(rank, k, v, dk_all[rank], dv_all[rank])                     # beside the all-gather
+        gather.wait()
+        for step in range(1, W):
+            src = (rank - step) % W
+            blocks(src, k_all[src], v_all[src], dk_all[src], dv_all[src])
+        sums = [torch.empty(t.shape, dtype=torch.float32, device=q.device) for t in (k, v)]
+        works = [reduce_scatter_async(s_, c, group=process_group) for s_, c in zip(sums, (dk_cat, dv_cat))]
+        dq_out = be.cast(dq, q.dtype)                                      # beside the exchange
+        for w_ in works:
+            w_.wait()
+        return dq_out, be.cast(sums[0], q.dtype), be.cast(sums[1], q.dtype)
+
+    dk = torch.zeros(k.shape, dtype=torch.float32, device=q.device)
+    dv = torch.zeros(v.shape, dtype=torch.float32, device=q.device)
+    next_dk, next_dv = None, None
+    next_k, next_v = None, None
+    for step in range(W):
+        if step + 1 != W:
+            next_k, next_v = kv_comm.send_recv_kv(k, v)
+        if step != 0:
+            d_kv_comm.wait()
+            dk, dv = next_dk, next_dv
+        blocks((rank - step) % W, k, v, dk, dv)
+        if step + 1 != W:
+            kv_comm.wait()
+            k, v = next_k, next_v
+        next_dk, next_dv = d_kv_comm.send_recv_kv(dk, dv)
+    d_kv_comm.wait()
+    return be.cast(dq, q.dtype), be.cast(next_dk, q.dtype), be.cast(next_dv, q.dtype)
+
+
 def zigzag_ring_flash_attn_varlen_forward(
     process_group,
     q: torch.Tensor,
@@ -105,6 +212,10 @@ def zigzag_ring_flash_attn_varlen_forward(
         be.fwd(q, k, v, softmax_scale=softmax_scale, causal=True, out=out, lse=lse, window=window_size, dropout=dropout_arg(dropout_p, dropout_seed), **vl)
         return out, lse
     assert not dropout_p, "dropout over a multi-rank ring is not supported (as in the reference)"
+    win = global_window(window_size, True, comm.world_size * int(max_seqlen))
+    if win is not None:
+        require_mask_shift_lens(be, "zigzag_ring_flash_attn_varlen")
+        return _zigzag_varlen_window_forward(be, process_group, comm, q, k, v, vl, softmax_scale, win)
 
     out_acc = torch.empty((T, H, D), dtype=torch.float32, device=q.device)
     lse_acc = torch.empty((H, T), dtype=torch.float32, device=q.device)
@@ -183,6 +294,11 @@ def zigzag_ring_flash_attn_varlen_backward(
                dq=dq, dk=dk, dv=dv, deterministic=deterministic, window=window_size, dropout=dropout_arg(dropout_p, dropout_seed), **vl)
         return dq, dk, dv
     assert not dropout_p, "dropout over a multi-rank ring is not supported (as in the reference)"
+    win = global_window(window_size, True, kv_comm.world_size * int(max_seqlen))
+    if win is not None:
+        require_mask_shift_lens(be, "zigzag_ring_flash_attn_varlen")
+        return _zigzag_varlen_window_backward(be, process_group, kv_comm, d_kv_comm, dout, q, k, v, softmax_lse, delta, vl,
+                                              softmax_scale, win, deterministic)
 
     dq = torch.empty((T, H, D), dtype=torch.float32, device=q.device)
     dk = torch.empty(k.shape, dtype=torch.float32, device=q.device)
@@ -261,9 +377,10 @@ def zigzag_ring_flash_attn_varlen_backward(
 
 ZigZagRingFlashAttnVarlenFunc = make_autograd_function(
     "ZigZagRingFlashAttnVarlenFunc", zigzag_ring_flash_attn_varlen_forward,
-    zigzag_ring_flash_attn_varlen_backward, 2)
+    zigzag_ring_flash_attn_varlen_backward, 2, window_ring=True)
 (
     zigzag_ring_flash_attn_varlen_func,
     zigzag_ring_flash_attn_varlen_kvpacked_func,
     zigzag_ring_flash_attn_varlen_qkvpacked_func,
-) = make_varlen_api(ZigZagRingFlashAttnVarlenFunc, "zigzag_ring_flash_attn_varlen", zigzag_ring_flash_attn_varlen_forward, zigzag_ring_flash_attn_varlen_backward)
+) = make_varlen_api(ZigZagRingFlashAttnVarlenFunc, "zigzag_ring_flash_attn_varlen", zigzag_ring_flash_attn_varlen_forward, zigzag_ring_flash_attn_varlen_backward,
+                    window_ring=True)
