@@ -130,6 +130,17 @@ typedef struct {
   float dropout_p;
   uint64_t dropout_seed;
   int64_t q_pos_offset, k_pos_offset;
+  /* ABI 8, revision 1 — position map of the dropout mask, for local tensors whose rows are not ONE contiguous run of the
+   * global sequence (a zigzag rank holds two distant chunks, a stripe rank every W-th token).  Local row i of q (of k)
+   * sits at global position
+   *     pos(i) = (split == 0 || i < split) ? offset + i * stride : offset2 + (i - split) * stride      (mod 2^32)
+   * stride 0 reads as 1, split 0 as "one piece": a zero-initialised map is the plain offset of before, through the same
+   * code path, bit for bit.  Read only when dropout_p > 0; positions feed the mask hash ONLY — causal and window masks keep
+   * working on local rows.  RFA_ERR_ARGS: a non-default map (stride > 1 or split != 0) with cu_seqlens input or with
+   * q_half / k_half != RFA_HALF_FULL, a negative stride, a split outside [1, S - 1]. */
+  int32_t q_pos_stride, k_pos_stride;
+  int32_t q_pos_split, k_pos_split;
+  int64_t q_pos_offset2, k_pos_offset2;
   int32_t head_offset;
   /* Kernel form (tuning / tests; 0 = chosen by the library): RFA_FWD_8x32 = 8 waves x 32 query rows, two waves per SIMD
    * (csrc/rfa_fwd.hip: every head dim, windows, dropout; 256 query rows per workgroup — RFA_FWD_AUTO also launches the
@@ -270,6 +281,10 @@ typedef struct {
   float dropout_p;
   uint64_t dropout_seed;
   int64_t q_pos_offset, k_pos_offset;
+  /* position map of the dropout mask: as in rfa_fwd_args, with the forward's values */
+  int32_t q_pos_stride, k_pos_stride;
+  int32_t q_pos_split, k_pos_split;
+  int64_t q_pos_offset2, k_pos_offset2;
   int32_t head_offset;
   /* ABI 5: size of the buffer `ds_scratch` points to.  0 = at least rfa_bwd_ds_scratch_bytes().  A SMALLER buffer does
    * not switch the 5-GEMM form off: the call then runs it in HEAD-GROUP CHUNKS that reuse the one buffer — chunks of
@@ -324,6 +339,10 @@ typedef struct {
 } rfa_merge_args;
 
 int rfa_abi_version(void);
+/* Revision of the structs WITHIN one RFA_ABI_VERSION (fields added in the middle of a struct leave the version number
+ * alone): 1 = the dropout position map.  A binding must find this symbol and this value, or refuse the library. */
+#define RFA_ABI_REVISION 1
+int rfa_abi_revision(void);
 /* identity of this build: the first 16 hex digits of the sha256 over the library's sources, compiled into the binary by
  * the build recipe (ring-flash-attention_amd/build.py).  Measurement files (profiles/r*_traffic.json) record the id of
  * the library they were collected on; bench.py only quotes them for a library with the same id. */

@@ -149,6 +149,33 @@ inline bool drop_args_ok(float p, int window, int wl, int wr, int causal) {
   return !(p > 0.f && win);
 }
 
+// dropout position map (rfa.h: q_pos_stride ...): a non-default map needs dense, unhalved input and a split inside the tensor
+inline bool pos_map_default(int stride, int split) { return (stride == 0 || stride == 1) && split == 0; }
+template <typename A>
+inline bool pos_map_ok(const A& a) {
+  if (!(a.dropout_p > 0.f)) return true;                       // the fields are read with dropout only
+  if (a.q_pos_stride < 0 || a.k_pos_stride < 0) return false;
+  const bool qd = pos_map_default(a.q_pos_stride, a.q_pos_split), kd = pos_map_default(a.k_pos_stride, a.k_pos_split);
+  if (qd && kd) return true;
+  if (a.cu_seqlens_q != nullptr || a.cu_seqlens_k != nullptr) return false;
+  if (a.q_half != RFA_HALF_FULL || a.k_half != RFA_HALF_FULL) return false;
+  if (a.q_pos_split != 0 && (a.q_pos_split < 1 || a.q_pos_split > a.Sq - 1)) return false;
+  if (a.k_pos_split != 0 && (a.k_pos_split < 1 || a.k_pos_split > a.Sk - 1)) return false;
+  return true;
+}
+// kernel parameters of the map: strides normalised to >= 1, drop_mapped = "not the identity" (the kernels' run-time branch)
+template <typename P, typename A>
+inline void set_pos_map(P& p, const A& a) {
+  p.q_pos0 = (unsigned)a.q_pos_offset; p.k_pos0 = (unsigned)a.k_pos_offset; p.head0 = (unsigned)a.head_offset;
+  p.q_pstride = 1u; p.k_pstride = 1u;
+  if (!(a.dropout_p > 0.f)) return;
+  p.q_pstride = a.q_pos_stride > 0 ? (unsigned)a.q_pos_stride : 1u;
+  p.k_pstride = a.k_pos_stride > 0 ? (unsigned)a.k_pos_stride : 1u;
+  p.q_psplit = a.q_pos_split; p.k_psplit = a.k_pos_split;
+  p.q_pos2 = (unsigned)a.q_pos_offset2; p.k_pos2 = (unsigned)a.k_pos_offset2;
+  p.drop_mapped = (p.q_pstride != 1u || p.k_pstride != 1u || p.q_psplit != 0 || p.k_psplit != 0) ? 1 : 0;
+}
+
 }  // namespace
 
 // the library is built with -fvisibility=hidden: the C ABI below (include/rfa.h) is everything a loader can bind —
@@ -157,6 +184,7 @@ inline bool drop_args_ok(float p, int window, int wl, int wr, int causal) {
 extern "C" {
 
 int rfa_abi_version(void) { return RFA_ABI_VERSION; }
+int rfa_abi_revision(void) { return RFA_ABI_REVISION; }
 
 #ifndef RFA_BUILD_ID
 #define RFA_BUILD_ID "unstamped"
@@ -436,7 +464,7 @@ static int64_t fwd_rows_total(const rfa_fwd_args* a) {
 
 int64_t rfa_fwd_workspace_bytes(const rfa_fwd_args* a, int32_t* nsplit) {
   if (nsplit) *nsplit = 1;
-  if (!a || check_common(a->dtype, a->H, a->Hk, a->D, a->B) || !shift_args_ok(*a)) return 0;
+  if (!a || check_common(a->dtype, a->H, a->Hk, a->D, a->B) || !shift_args_ok(*a) || !pos_map_ok(*a)) return 0;
   const rfa_fwd_args na = norm_args(*a);
   a = &na;
   const int ns = fwd_kv_nsplit(a);
@@ -460,6 +488,7 @@ int rfa_fwd(const rfa_fwd_args* a, void* stream) {
   }
   if ((a->cu_seqlens_q == nullptr) != (a->cu_seqlens_k == nullptr)) return RFA_ERR_ARGS;
   if (!drop_args_ok(a->dropout_p, a->window, a->window_left, a->window_right, a->causal)) return RFA_ERR_ARGS;
+  if (!pos_map_ok(*a)) return RFA_ERR_ARGS;
   if (!shift_args_ok(*a)) return RFA_ERR_ARGS;
   // a block with no visible element: accumulate mode has nothing to merge; plain mode (and the first block of a ring)
   // runs the canonical empty band, whose workgroups load no tile and write out = 0, lse = +inf (-inf into lse_acc)
@@ -493,7 +522,7 @@ int rfa_fwd(const rfa_fwd_args* a, void* stream) {
   p.drop_keep = drop_threshold(a->dropout_p);
   p.drop_scale = drop_rescale(a->dropout_p);
   p.drop_seed = a->dropout_seed;
-  p.q_pos0 = (unsigned)a->q_pos_offset; p.k_pos0 = (unsigned)a->k_pos_offset; p.head0 = (unsigned)a->head_offset;
+  set_pos_map(p, *a);
   // 256 query rows per workgroup (8 waves) or 128 (4 waves, two workgroups per CU), and the split-KV shares: fwd_plan()
   const FwdPlan plan = fwd_plan(a);
   int rows = plan.rows;
@@ -793,13 +822,13 @@ static int64_t bwd_ds_scratch_bytes(const rfa_bwd_args* a) {
 }
 
 int64_t rfa_bwd_ds_scratch_bytes(const rfa_bwd_args* a) {
-  if (!a || !shift_args_ok(*a)) return 0;
+  if (!a || !shift_args_ok(*a) || !pos_map_ok(*a)) return 0;
   const rfa_bwd_args na = norm_args(*a);
   return bwd_ds_scratch_bytes(&na);
 }
 
 int64_t rfa_bwd_ds_scratch_min_bytes(const rfa_bwd_args* a) {
-  if (!a || !shift_args_ok(*a)) return 0;
+  if (!a || !shift_args_ok(*a) || !pos_map_ok(*a)) return 0;
   const rfa_bwd_args na = norm_args(*a);
   a = &na;
   if (!bwd_spill_eligible(a)) return 0;
@@ -840,7 +869,7 @@ static DsChunks bwd_ds_chunking(const rfa_bwd_args* a) {
 int rfa_bwd_ds_chunks(const rfa_bwd_args* a, int32_t* nchunks, int32_t* kv_heads, int32_t* q_heads, int64_t* chunk_bytes) {
   if (!a) return RFA_ERR_NULL;
   if (int rc = check_common(a->dtype, a->H, a->Hk, a->D, a->B)) return rc;
-  if (!shift_args_ok(*a)) return RFA_ERR_ARGS;
+  if (!shift_args_ok(*a) || !pos_map_ok(*a)) return RFA_ERR_ARGS;
   const rfa_bwd_args na = norm_args(*a);
   a = &na;
   const DsChunks ch = bwd_ds_chunking(a);
@@ -853,7 +882,7 @@ int rfa_bwd_ds_chunks(const rfa_bwd_args* a, int32_t* nchunks, int32_t* kv_heads
 
 int rfa_bwd_plan(const rfa_bwd_args* a, int32_t* form, int32_t* nsplit, int32_t* five_gemm) {
   if (!a) return RFA_ERR_NULL;
-  if (!shift_args_ok(*a)) return RFA_ERR_ARGS;
+  if (!shift_args_ok(*a) || !pos_map_ok(*a)) return RFA_ERR_ARGS;
   const rfa_bwd_args na = norm_args(*a);
   a = &na;
   const DkdvPlan pl = bwd_dkdv_plan(a);
@@ -866,7 +895,7 @@ int rfa_bwd_plan(const rfa_bwd_args* a, int32_t* form, int32_t* nsplit, int32_t*
 static int64_t bal_flag_bytes(int64_t pairs) { return (pairs * 4 + 255) / 256 * 256; }
 
 int64_t rfa_bwd_workspace_bytes(const rfa_bwd_args* a) {
-  if (!a || !shift_args_ok(*a)) return 0;
+  if (!a || !shift_args_ok(*a) || !pos_map_ok(*a)) return 0;
   const rfa_bwd_args na = norm_args(*a);
   a = &na;
   if (!bwd_needs_ws(a)) return 0;
@@ -895,6 +924,7 @@ int rfa_bwd(const rfa_bwd_args* a, void* stream) {
   if ((a->cu_seqlens_q == nullptr) != (a->cu_seqlens_k == nullptr)) return RFA_ERR_ARGS;
   if (a->dkdv_form < RFA_DKDV_AUTO || a->dkdv_form > RFA_DKDV_BAL || a->dkdv_nsplit < 0) return RFA_ERR_ARGS;
   if (!drop_args_ok(a->dropout_p, a->window, a->window_left, a->window_right, a->causal)) return RFA_ERR_ARGS;
+  if (!pos_map_ok(*a)) return RFA_ERR_ARGS;
   if (!shift_args_ok(*a)) return RFA_ERR_ARGS;
   // a block with no visible element adds nothing to accumulators (either phase of a two-phase call); where something has
   // to be written — plain outputs, overwritten accumulators — the kernels run the canonical empty band and store zeros
@@ -940,7 +970,7 @@ int rfa_bwd(const rfa_bwd_args* a, void* stream) {
   p.drop_keep = drop_threshold(a->dropout_p);
   p.drop_scale = drop_rescale(a->dropout_p);
   p.drop_seed = a->dropout_seed;
-  p.q_pos0 = (unsigned)a->q_pos_offset; p.k_pos0 = (unsigned)a->k_pos_offset; p.head0 = (unsigned)a->head_offset;
+  set_pos_map(p, *a);
   p.nqblk = (eff_len(a->Sq, a->q_half) + bwd_dq_rows_per_block() - 1) / bwd_dq_rows_per_block();
   const DsChunks chunks = bwd_ds_chunking(a);
   const int Gfull = a->H / a->Hk;

@@ -220,7 +220,7 @@ __global__ __launch_bounds__(kBgThreads) void fwd_big_kernel(const FwdParams p) 
 
   const bool drop = p.drop_keep < 256;
   const uint32_t drop_key = drop ? drop_head_key(p.drop_seed, p.cu_q ? 0u : (uint32_t)b, p.head0 + (uint32_t)h) : 0u;
-  const uint32_t drop_i = drop ? p.q_pos0 + (uint32_t)(p.cu_q ? qs.row0 : 0) + (uint32_t)qrow : 0u;
+  const uint32_t drop_i = drop ? drop_pos(p.q_pos0 + (uint32_t)(p.cu_q ? qs.row0 : 0), p.q_pstride, p.q_psplit, p.q_pos2, qrow) : 0u;   // per row: a wave's rows can straddle the split
   const uint32_t drop_j0 = drop ? p.k_pos0 + (uint32_t)(p.cu_k ? ks.row0 : 0) : 0u;
   const float c = p.scale * kLog2e;
   float m = -INFINITY;
@@ -307,17 +307,30 @@ __global__ __launch_bounds__(kBgThreads) void fwd_big_kernel(const FwdParams p) 
       if (drop) {
         // the forward kernel's mask (rfa_fwd.hip): row sum and lse stay those of the undropped softmax
         const int mis = __builtin_amdgcn_readfirstlane((int)(drop_j0 & 3u));
+        auto mask4 = [&](int t, int mm, uint32_t w) {
 #pragma unroll
-        for (int t = 0; t < 2; ++t)
+          for (int e = 0; e < 4; ++e)
+            if (!drop_keep(w, e, p.drop_keep)) s[t][4 * mm + e] = 0.f;
+        };
+        if (p.drop_mapped) {      // a position map (rfa_common.hpp: drop_words_mapped); wave-uniform, the identity keeps the path below
 #pragma unroll
-          for (int mm = 0; mm < 4; ++mm) {
-            const uint32_t jg = drop_j0 + (uint32_t)(kt0 + 32 * t + 8 * mm + 4 * g);
-            uint32_t w = drop_word(drop_key, drop_i, jg >> 2);
-            if (mis) w = __builtin_amdgcn_alignbyte(drop_word(drop_key, drop_i, (jg >> 2) + 1), w, (uint32_t)mis);
+          for (int t = 0; t < 2; ++t) {
+            uint32_t w[4];
+            drop_words_mapped(drop_key, drop_i, kt0 + 32 * t, g, p.k_pos0, p.k_pstride, p.k_psplit, p.k_pos2, w);
 #pragma unroll
-            for (int e = 0; e < 4; ++e)
-              if (!drop_keep(w, e, p.drop_keep)) s[t][4 * mm + e] = 0.f;
+            for (int mm = 0; mm < 4; ++mm) mask4(t, mm, w[mm]);
           }
+        } else {
+#pragma unroll
+          for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int mm = 0; mm < 4; ++mm) {
+              const uint32_t jg = drop_j0 + (uint32_t)(kt0 + 32 * t + 8 * mm + 4 * g);
+              uint32_t w = drop_word(drop_key, drop_i, jg >> 2);
+              if (mis) w = __builtin_amdgcn_alignbyte(drop_word(drop_key, drop_i, (jg >> 2) + 1), w, (uint32_t)mis);
+              mask4(t, mm, w);
+            }
+        }
       }
       {
         vec8<T> pb[4];                                  // [t][ks2]
@@ -479,7 +492,7 @@ __global__ __launch_bounds__(kBgThreads) void dq_big_kernel(const BwdParams p) {
 
   const bool drop = p.drop_keep < 256;
   const uint32_t drop_key = drop ? drop_head_key(p.drop_seed, p.cu_q ? 0u : (uint32_t)b, p.head0 + (uint32_t)h) : 0u;
-  const uint32_t drop_i = drop ? p.q_pos0 + (uint32_t)(p.cu_q ? qs.row0 : 0) + (uint32_t)qrow : 0u;
+  const uint32_t drop_i = drop ? drop_pos(p.q_pos0 + (uint32_t)(p.cu_q ? qs.row0 : 0), p.q_pstride, p.q_psplit, p.q_pos2, qrow) : 0u;   // per row: a wave's rows can straddle the split
   const uint32_t drop_j0 = drop ? p.k_pos0 + (uint32_t)(p.cu_k ? ks.row0 : 0) : 0u;
   const float c = p.scale * kLog2e;
   f32x16 dq[kNB];
@@ -529,13 +542,23 @@ __global__ __launch_bounds__(kBgThreads) void dq_big_kernel(const BwdParams p) {
         }
         if (drop) {
           const int mis = __builtin_amdgcn_readfirstlane((int)(drop_j0 & 3u));
-#pragma unroll
-          for (int mm = 0; mm < 4; ++mm) {
-            const uint32_t jg = drop_j0 + (uint32_t)(kt0 + 32 * t + 8 * mm + 4 * g);
-            uint32_t w = drop_word(drop_key, drop_i, jg >> 2);
-            if (mis) w = __builtin_amdgcn_alignbyte(drop_word(drop_key, drop_i, (jg >> 2) + 1), w, (uint32_t)mis);
+          auto mask4 = [&](int mm, uint32_t w) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) dp[4 * mm + e] = drop_keep(w, e, p.drop_keep) ? dp[4 * mm + e] * p.drop_scale : 0.f;
+          };
+          if (p.drop_mapped) {    // a position map (rfa_common.hpp: drop_words_mapped); wave-uniform, the identity keeps the path below
+            uint32_t w[4];
+            drop_words_mapped(drop_key, drop_i, kt0 + 32 * t, g, p.k_pos0, p.k_pstride, p.k_psplit, p.k_pos2, w);
+#pragma unroll
+            for (int mm = 0; mm < 4; ++mm) mask4(mm, w[mm]);
+          } else {
+#pragma unroll
+            for (int mm = 0; mm < 4; ++mm) {
+              const uint32_t jg = drop_j0 + (uint32_t)(kt0 + 32 * t + 8 * mm + 4 * g);
+              uint32_t w = drop_word(drop_key, drop_i, jg >> 2);
+              if (mis) w = __builtin_amdgcn_alignbyte(drop_word(drop_key, drop_i, (jg >> 2) + 1), w, (uint32_t)mis);
+              mask4(mm, w);
+            }
           }
         }
 #pragma unroll
@@ -758,7 +781,7 @@ __global__ __launch_bounds__(kBgThreads) void dkdv_big_kernel(const BwdParams p)
   const int sa0 = lds_addr(smem) + kBgOffStat + 4 * g * 4;           // row statistics, stage 0
 
   const bool drop = p.drop_keep < 256;
-  const uint32_t drop_j = drop ? p.k_pos0 + (uint32_t)(p.cu_k ? ks.row0 : 0) + (uint32_t)krow : 0u;
+  const uint32_t drop_j = drop ? drop_pos(p.k_pos0 + (uint32_t)(p.cu_k ? ks.row0 : 0), p.k_pstride, p.k_psplit, p.k_pos2, krow) : 0u;
   const uint32_t drop_i0 = drop ? p.q_pos0 + (uint32_t)(p.cu_q ? qs.row0 : 0) : 0u;
   const float c = p.scale * kLog2e;
   f32x16 acck[kDoK ? kNB : 1], accv[kDoV ? kNB : 1];   // dK^T / dV^T of this wave's 32 keys
@@ -837,21 +860,29 @@ __global__ __launch_bounds__(kBgThreads) void dkdv_big_kernel(const BwdParams p)
       if (drop) {
         // the dK/dV kernel's dropout (rfa_bwd.hip): dP = keep ? dO V^T / (1 - p) : 0, dS = P (dP - delta), dV takes keep ? P / (1 - p) : 0
         const uint32_t hkey = drop_head_key(p.drop_seed, p.cu_q ? 0u : (uint32_t)b, p.head0 + (uint32_t)(h0 + cg));
+        // kMapped: the query rows go through the position map (rfa_bwd.hip: dkdv_kernel); wave-uniform choice
+        auto drop_rows = [&](auto mapped_t) {
+          constexpr bool kMapped = decltype(mapped_t)::value;
 #pragma unroll
-        for (int jj = 0; jj < 4; ++jj) {
-          const f32x4 dl = *(__attribute__((address_space(3))) f32x4*)(lds_ptr(sa) + 256 + 8 * jj * 4);
+          for (int jj = 0; jj < 4; ++jj) {
+            const f32x4 dl = *(__attribute__((address_space(3))) f32x4*)(lds_ptr(sa) + 256 + 8 * jj * 4);
 #pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const int r = 4 * jj + e;
-            const uint32_t w = drop_word(hkey, drop_i0 + (uint32_t)(qs0 + crow(r, g)), drop_j >> 2);
-            const bool keep = drop_keep(w, (int)(drop_j & 3u), p.drop_keep);
-            if (kDoV) pv[r] = keep ? s[r] * p.drop_scale : 0.f;   // dropped, rescaled P
-            if (kDoK) {
-              const float dpd = keep ? (dp[r] + dl[e]) * p.drop_scale - dl[e] : -dl[e];
-              s[r] = dpd * s[r];                       // dS
+            for (int e = 0; e < 4; ++e) {
+              const int r = 4 * jj + e;
+              const uint32_t ipos = kMapped ? drop_pos(p.q_pos0, p.q_pstride, p.q_psplit, p.q_pos2, qs0 + crow(r, g))
+                                            : drop_i0 + (uint32_t)(qs0 + crow(r, g));
+              const uint32_t w = drop_word(hkey, ipos, drop_j >> 2);
+              const bool keep = drop_keep(w, (int)(drop_j & 3u), p.drop_keep);
+              if (kDoV) pv[r] = keep ? s[r] * p.drop_scale : 0.f;   // dropped, rescaled P
+              if (kDoK) {
+                const float dpd = keep ? (dp[r] + dl[e]) * p.drop_scale - dl[e] : -dl[e];
+                s[r] = dpd * s[r];                       // dS
+              }
             }
           }
-        }
+        };
+        if (p.drop_mapped) drop_rows(std::true_type{});
+        else drop_rows(std::false_type{});
       } else if (kDoV) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) pv[r] = s[r];
@@ -1088,7 +1119,7 @@ __global__ __launch_bounds__(kBgThreads) void dkdv_fused_big_kernel(const BwdPar
   const int sa0 = lds_addr(smem) + kFuOffStat + 4 * g * 4;
 
   constexpr bool drop = kDrop;
-  const uint32_t drop_j = drop ? p.k_pos0 + (uint32_t)(p.cu_k ? ks.row0 : 0) + (uint32_t)krow : 0u;
+  const uint32_t drop_j = drop ? drop_pos(p.k_pos0 + (uint32_t)(p.cu_k ? ks.row0 : 0), p.k_pstride, p.k_psplit, p.k_pos2, krow) : 0u;
   const uint32_t drop_i0 = drop ? p.q_pos0 + (uint32_t)(p.cu_q ? qs.row0 : 0) : 0u;
   const float c = p.scale * kLog2e;
   f32x16 acck[kNB], accv[kNB];
@@ -1209,19 +1240,26 @@ __global__ __launch_bounds__(kBgThreads) void dkdv_fused_big_kernel(const BwdPar
       if (drop) {
         const uint32_t hkey = drop_head_key(p.drop_seed, p.cu_q ? 0u : (uint32_t)b, p.head0 + (uint32_t)(h0 + cg));
         f32x16 pv;
+        auto drop_rows = [&](auto mapped_t) {          // kMapped: as in dkdv_big_kernel
+          constexpr bool kMapped = decltype(mapped_t)::value;
 #pragma unroll
-        for (int jj = 0; jj < 4; ++jj) {
-          const f32x4 dl = *(__attribute__((address_space(3))) f32x4*)(lds_ptr(sa) + 256 + 8 * jj * 4);
+          for (int jj = 0; jj < 4; ++jj) {
+            const f32x4 dl = *(__attribute__((address_space(3))) f32x4*)(lds_ptr(sa) + 256 + 8 * jj * 4);
 #pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const int r = 4 * jj + e;
-            const uint32_t w = drop_word(hkey, drop_i0 + (uint32_t)(qs0 + crow(r, g)), drop_j >> 2);
-            const bool keep = drop_keep(w, (int)(drop_j & 3u), p.drop_keep);
-            pv[r] = keep ? s[r] * p.drop_scale : 0.f;
-            const float dpd = keep ? (dp[r] + dl[e]) * p.drop_scale - dl[e] : -dl[e];
-            s[r] = dpd * s[r];
+            for (int e = 0; e < 4; ++e) {
+              const int r = 4 * jj + e;
+              const uint32_t ipos = kMapped ? drop_pos(p.q_pos0, p.q_pstride, p.q_psplit, p.q_pos2, qs0 + crow(r, g))
+                                            : drop_i0 + (uint32_t)(qs0 + crow(r, g));
+              const uint32_t w = drop_word(hkey, ipos, drop_j >> 2);
+              const bool keep = drop_keep(w, (int)(drop_j & 3u), p.drop_keep);
+              pv[r] = keep ? s[r] * p.drop_scale : 0.f;
+              const float dpd = keep ? (dp[r] + dl[e]) * p.drop_scale - dl[e] : -dl[e];
+              s[r] = dpd * s[r];
+            }
           }
-        }
+        };
+        if (p.drop_mapped) drop_rows(std::true_type{});
+        else drop_rows(std::false_type{});
         pbv[0] = pack8<T>(pv, 0);
         pbv[1] = pack8<T>(pv, 8);
       } else {

@@ -242,7 +242,7 @@ __global__ __launch_bounds__(kDqThreads, 2) void dq_kernel(const BwdParams p) {
       }
 
   const uint32_t drop_key = kDrop ? drop_head_key(p.drop_seed, p.cu_q ? 0u : (uint32_t)b, p.head0 + (uint32_t)h) : 0u;
-  const uint32_t drop_i = kDrop ? p.q_pos0 + (uint32_t)(p.cu_q ? qs.row0 : 0) + (uint32_t)qrow : 0u;
+  const uint32_t drop_i = kDrop ? drop_pos(p.q_pos0 + (uint32_t)(p.cu_q ? qs.row0 : 0), p.q_pstride, p.q_psplit, p.q_pos2, qrow) : 0u;   // per row: a wave's rows can straddle the split
   const uint32_t drop_j0 = kDrop ? p.k_pos0 + (uint32_t)(p.cu_k ? ks.row0 : 0) : 0u;
   const float c = p.scale * kLog2e;
   f32x16 dq[kNB];
@@ -316,13 +316,23 @@ __global__ __launch_bounds__(kDqThreads, 2) void dq_kernel(const BwdParams p) {
           // dP = mask ∘ (dO V^T) / (1 - p): the gradient of the DROPPED probabilities; dS = P ∘ (dP - delta) keeps the
           // undropped P (a dropped element still contributes -P delta)
           const int mis = __builtin_amdgcn_readfirstlane((int)(drop_j0 & 3u));
-#pragma unroll
-          for (int mm = 0; mm < 4; ++mm) {
-            const uint32_t jg = drop_j0 + (uint32_t)(kt0 + 32 * t + 8 * mm + 4 * g);
-            uint32_t w = drop_word(drop_key, drop_i, jg >> 2);
-            if (mis) w = __builtin_amdgcn_alignbyte(drop_word(drop_key, drop_i, (jg >> 2) + 1), w, (uint32_t)mis);
+          auto mask4 = [&](int mm, uint32_t w) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) dp[4 * mm + e] = drop_keep(w, e, p.drop_keep) ? dp[4 * mm + e] * p.drop_scale : 0.f;
+          };
+          if (p.drop_mapped) {    // a position map (rfa_common.hpp: drop_words_mapped); wave-uniform, the identity keeps the path below
+            uint32_t w[4];
+            drop_words_mapped(drop_key, drop_i, kt0 + 32 * t, g, p.k_pos0, p.k_pstride, p.k_psplit, p.k_pos2, w);
+#pragma unroll
+            for (int mm = 0; mm < 4; ++mm) mask4(mm, w[mm]);
+          } else {
+#pragma unroll
+            for (int mm = 0; mm < 4; ++mm) {
+              const uint32_t jg = drop_j0 + (uint32_t)(kt0 + 32 * t + 8 * mm + 4 * g);
+              uint32_t w = drop_word(drop_key, drop_i, jg >> 2);
+              if (mis) w = __builtin_amdgcn_alignbyte(drop_word(drop_key, drop_i, (jg >> 2) + 1), w, (uint32_t)mis);
+              mask4(mm, w);
+            }
           }
         }
 #pragma unroll
@@ -414,7 +424,10 @@ template <int kD> constexpr int kv_smem() {        // 129 KiB (65 KiB at kD = 64
 // partials (fp32, workspace) are summed by reduce_kernel (rfa_api.cpp).
 // kDrop: dropout — dV takes the dropped, rescaled probabilities, dS the masked dP (128-key form without spill / window)
 // kBal (round 6, kWide only): the BALANCED causal schedule — see "balanced schedule" below the work decode
-template <typename T, int kD, bool kFullD, bool kSpill, bool kWin, bool kWide, bool kDrop = false, bool kBal = false>
+// kMap (kDrop only): the dropout mask's positions go through the position map (include/rfa.h: q_pos_stride ...).  An
+// instance of its own, not a run-time branch like in the forward and dQ kernels: the kDrop instances of head dim 128 sit
+// at 256 registers, and a second copy of the mask loop put them on the scratch.  kDrop without kMap is the code of before.
+template <typename T, int kD, bool kFullD, bool kSpill, bool kWin, bool kWide, bool kDrop = false, bool kBal = false, bool kMap = false>
 __global__ __launch_bounds__(kKvThreads, 2) void dkdv_kernel(const BwdParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   lds_t* smem = (lds_t*)smem_raw;
@@ -422,6 +435,7 @@ __global__ __launch_bounds__(kKvThreads, 2) void dkdv_kernel(const BwdParams p) 
   static_assert(!kWide || ((kD == 128 || kD == 64) && kFullD && !kWin), "the 256-key form: head dim 128 / 64 exactly, no window");
   static_assert(!kDrop || (!kSpill && !kWin && !kWide), "dropout: the plain 128-key instances");
   static_assert(!kBal || kWide, "the balanced schedule: the 256-key form");
+  static_assert(!kMap || kDrop, "a position map belongs to the dropout mask");
   constexpr int kKeys = kWide ? 2 * kKvKeys : kKvKeys;       // keys per workgroup
   typedef HeadGeo<kD> Geo;
   constexpr int kRowBytes = Geo::kRowBytes;                  // (shadows the 128-wide namespace constant)
@@ -725,8 +739,11 @@ __global__ __launch_bounds__(kKvThreads, 2) void dkdv_kernel(const BwdParams p) 
   const int ds_kb = __builtin_amdgcn_readfirstlane(kblk * (kKeys / 32) + kbw);
 
   // dropout: this lane's key position; the mask word of (query i, key j) is word(i, j >> 2), byte j & 3
-  const uint32_t drop_j = kDrop ? p.k_pos0 + (uint32_t)(p.cu_k ? ks.row0 : 0) + (uint32_t)krow : 0u;
+  // (kMap: dense input — rfa_api.cpp —, positions through the map; the query rows' are taken per row in the tile loop)
+  const uint32_t drop_j = !kDrop ? 0u : kMap ? drop_pos(p.k_pos0, p.k_pstride, p.k_psplit, p.k_pos2, krow)
+                                             : p.k_pos0 + (uint32_t)(p.cu_k ? ks.row0 : 0) + (uint32_t)krow;
   const uint32_t drop_i0 = kDrop ? p.q_pos0 + (uint32_t)(p.cu_q ? qs.row0 : 0) : 0u;
+  uint32_t drop_g4s = kMap ? (uint32_t)(4 * g) * p.q_pstride : 0u;      // this lane's share of a query row's position
   const float c = p.scale * kLog2e;
   f32x16 dk[kNB], dv[kNB];
 #pragma unroll
@@ -855,7 +872,18 @@ __global__ __launch_bounds__(kKvThreads, 2) void dkdv_kernel(const BwdParams p) 
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             const int r = 4 * jj + e;
-            const uint32_t w = drop_word(hkey, drop_i0 + (uint32_t)(qs0 + crow(r, g)), drop_j >> 2);
+            uint32_t ipos;
+            if (kMap) {
+              // query row sq + 4 g, sq wave-uniform (as in the mask above): both pieces' positions of row sq are scalars,
+              // the lane picks its piece — the 32 rows of a block can straddle the split — and adds its own 4 g strides
+              const int sq = qs0 + crow(r, 0);
+              const uint32_t i1 = p.q_pos0 + (uint32_t)sq * p.q_pstride, i2 = p.q_pos2 + (uint32_t)(sq - p.q_psplit) * p.q_pstride;
+              const bool front = (p.q_psplit == 0) | (mask_g4 < p.q_psplit - sq);
+              ipos = (front ? i1 : i2) + drop_g4s;
+            } else {
+              ipos = drop_i0 + (uint32_t)(qs0 + crow(r, g));
+            }
+            const uint32_t w = drop_word(hkey, ipos, drop_j >> 2);
             const bool keep = drop_keep(w, (int)(drop_j & 3u), p.drop_keep);
             const float dpd = keep ? (dp[r] - nd[e]) * p.drop_scale + nd[e] : nd[e];
             dp[r] = dpd * s[r];
@@ -1143,10 +1171,10 @@ __global__ void zero_words_kernel(unsigned* w, int n) {
   if (i < n) w[i] = 0u;
 }
 
-template <typename T, int kD, bool kFullD, bool kSpill, bool kWin, bool kWide = false, bool kDrop = false, bool kBal = false>
+template <typename T, int kD, bool kFullD, bool kSpill, bool kWin, bool kWide = false, bool kDrop = false, bool kBal = false, bool kMap = false>
 static int launch_dkdv_t(const BwdParams& p, hipStream_t stream) {
   static std::atomic<unsigned long long> attr_done{0};
-  if (int rc = opt_in_dynamic_lds((const void*)dkdv_kernel<T, kD, kFullD, kSpill, kWin, kWide, kDrop, kBal>, kv_smem<kD>(), attr_done)) return rc;
+  if (int rc = opt_in_dynamic_lds((const void*)dkdv_kernel<T, kD, kFullD, kSpill, kWin, kWide, kDrop, kBal, kMap>, kv_smem<kD>(), attr_done)) return rc;
   // one workgroup per (key block, K/V head) [x tile-range split of the 256-key form]
   const int64_t nblocks = (int64_t)p.nkblk * p.Hk * p.B * ((kWide && !kBal) ? p.nsplit : 1);
   if (nblocks <= 0) return 0;
@@ -1158,7 +1186,7 @@ static int launch_dkdv_t(const BwdParams& p, hipStream_t stream) {
     hipLaunchKernelGGL(zero_words_kernel, dim3((unsigned)((nflags + 255) / 256)), dim3(256), 0, stream, p.pair_flags, nflags);
     if (hipGetLastError() != hipSuccess) return kLaunchFailed;
   }
-  hipLaunchKernelGGL((dkdv_kernel<T, kD, kFullD, kSpill, kWin, kWide, kDrop, kBal>), dim3((unsigned)nblocks), dim3(kKvThreads), kv_smem<kD>(), stream, p);
+  hipLaunchKernelGGL((dkdv_kernel<T, kD, kFullD, kSpill, kWin, kWide, kDrop, kBal, kMap>), dim3((unsigned)nblocks), dim3(kKvThreads), kv_smem<kD>(), stream, p);
   return hipGetLastError() == hipSuccess ? kLaunchOk : kLaunchFailed;
 }
 
@@ -1179,8 +1207,14 @@ int launch_bwd_dq(const BwdParams& p, int dtype, hipStream_t stream) {
   if (windowed(p.causal, p.wl, p.wr)) return dtype == 0 ? launch_dq_d<bf16_t, true, false>(p, stream) : launch_dq_d<f16_t, true, false>(p, stream);
   return dtype == 0 ? launch_dq_d<bf16_t, false, false>(p, stream) : launch_dq_d<f16_t, false, false>(p, stream);
 }
-template <typename T, bool kWin, bool kDrop>
+template <typename T, bool kWin, bool kDrop, bool kMap = false>
 static int launch_dkdv_d(const BwdParams& p, hipStream_t stream) {
+  if constexpr (kMap) {                     // dropout under a position map: the kMap instances
+    if (p.D == 128) return launch_dkdv_t<T, 128, true, false, false, false, true, false, true>(p, stream);
+    if (p.D > 64) return launch_dkdv_t<T, 128, false, false, false, false, true, false, true>(p, stream);
+    if (p.D == 64) return launch_dkdv_t<T, 64, true, false, false, false, true, false, true>(p, stream);
+    return launch_dkdv_t<T, 64, false, false, false, false, true, false, true>(p, stream);
+  }
   if (p.D == 128) return launch_dkdv_t<T, 128, true, false, kWin, false, kDrop>(p, stream);
   if constexpr (!kWin && !kDrop) {          // 64 < D <= 96: the 128-wide layout with three quarters of the MFMA work
     if (p.D == 96) return launch_dkdv_t<T, 96, true, false, kWin, false, kDrop>(p, stream);
@@ -1193,6 +1227,8 @@ static int launch_dkdv_d(const BwdParams& p, hipStream_t stream) {
 int launch_bwd_dkdv(const BwdParams& p, int dtype, hipStream_t stream) {
   if (p.D > 128) return launch_bwd_dkdv_big(p, dtype, stream);          // rfa_bigd.hip (rfa_api.cpp: no spill, no 256-key form)
   const bool win = windowed(p.causal, p.wl, p.wr);
+  if (p.drop_keep < 256 && p.drop_mapped)         // ... with a position map: instances of their own (dkdv_kernel: kMap)
+    return dtype == 0 ? launch_dkdv_d<bf16_t, false, true, true>(p, stream) : launch_dkdv_d<f16_t, false, true, true>(p, stream);
   if (p.drop_keep < 256)                          // rfa_api.cpp: dropout calls run the 128-key form without spill / window
     return dtype == 0 ? launch_dkdv_d<bf16_t, false, true>(p, stream) : launch_dkdv_d<f16_t, false, true>(p, stream);
   if (p.wide && p.D == 64 && p.bal)               // (round 6: its balanced causal schedule)

@@ -344,6 +344,47 @@ __device__ __forceinline__ bool drop_keep(uint32_t word, int byte, uint32_t keep
   return ((word >> (8 * byte)) & 0xffu) < keep;
 }
 
+// Position map (include/rfa.h: q_pos_stride ...): local row i of a tensor that is not one contiguous run of the global
+// sequence — two distant chunks (zigzag) or every W-th token (stripe) — sits at
+//     pos(i) = (split == 0 || i < split) ? pos0 + i * stride : pos2 + (i - split) * stride          (mod 2^32)
+__device__ __forceinline__ uint32_t drop_pos(uint32_t pos0, uint32_t stride, int split, uint32_t pos2, int i) {
+  return (split == 0 || i < split) ? pos0 + (uint32_t)i * stride : pos2 + (uint32_t)(i - split) * stride;
+}
+// Mask words of one 32-key sub-tile under a key map that is not the identity: w[mm] holds, in the byte order of the
+// identity path's word, the mask bytes of the 4 consecutive LOCAL keys jt + 8 mm + 4 g + (0..3) (jt % 32 == 0: the
+// sub-tile's first key) of the query at position i.  Every branch is wave-uniform:
+//   * stride 1 and the sub-tile not cut inside a 4-key group: a group lies in ONE piece, its keys are consecutive
+//     positions and share mask words — one hash, or the bytes of two when the piece's positions are misaligned against
+//     its local rows.  The misalignment is a constant of the piece (pos0 & 3 in front of the split, (pos2 - split) & 3
+//     behind it), no longer of the call; a lane picks its piece's.
+//   * otherwise (a stride: no two local keys share a word; or the split cuts a group of this sub-tile): one hash per key.
+__device__ __forceinline__ void drop_words_mapped(uint32_t head_key, uint32_t i, int jt, int g, uint32_t pos0, uint32_t stride,
+                                                  int split, uint32_t pos2, uint32_t (&w)[4]) {
+  const bool per_key = stride != 1u || ((split & 3) != 0 && split > jt && split < jt + 32);
+  if (per_key) {
+#pragma unroll
+    for (int mm = 0; mm < 4; ++mm) {
+      uint32_t x = 0;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const uint32_t pe = drop_pos(pos0, stride, split, pos2, jt + 8 * mm + 4 * g + e);
+        x |= ((drop_word(head_key, i, pe >> 2) >> (8 * (pe & 3u))) & 0xffu) << (8 * e);
+      }
+      w[mm] = x;
+    }
+    return;
+  }
+  const bool two = ((pos0 | (split ? pos2 - (uint32_t)split : 0u)) & 3u) != 0u;
+#pragma unroll
+  for (int mm = 0; mm < 4; ++mm) {
+    const uint32_t pos = drop_pos(pos0, 1u, split, pos2, jt + 8 * mm + 4 * g);
+    uint32_t x = drop_word(head_key, i, pos >> 2);
+    // (word index of the next 4 positions, mod 2^30 like the positions themselves are mod 2^32)
+    if (two) x = __builtin_amdgcn_alignbyte(drop_word(head_key, i, ((pos >> 2) + 1u) & 0x3fffffffu), x, pos & 3u);
+    w[mm] = x;
+  }
+}
+
 __device__ __forceinline__ float shfl_xor32(float v) { return __shfl_xor(v, 32, 64); }
 // max / sum of a value over the two half-waves (lane l and lane l ^ 32) WITHOUT the LDS round trip of a
 // ds_bpermute: v_permlane32_swap of a register with a copy of itself leaves {lower half, lower half} in one and

@@ -269,7 +269,7 @@ __global__ __launch_bounds__(kW * 64, 2) void fwd_kernel(const FwdParams p) {
 
   // dropout: global positions of this lane's query row and of key 0 of the sequence (packed input: absolute rows)
   const uint32_t drop_key = kDrop ? drop_head_key(p.drop_seed, p.cu_q ? 0u : (uint32_t)b, p.head0 + (uint32_t)h) : 0u;
-  const uint32_t drop_i = kDrop ? p.q_pos0 + (uint32_t)(p.cu_q ? qs.row0 : 0) + (uint32_t)qrow : 0u;
+  const uint32_t drop_i = kDrop ? drop_pos(p.q_pos0 + (uint32_t)(p.cu_q ? qs.row0 : 0), p.q_pstride, p.q_psplit, p.q_pos2, qrow) : 0u;   // per row: a wave's rows can straddle the split
   const uint32_t drop_j0 = kDrop ? p.k_pos0 + (uint32_t)(p.cu_k ? ks.row0 : 0) : 0u;
   const float c = p.scale * kLog2e;
   float m = -INFINITY;
@@ -421,17 +421,32 @@ __global__ __launch_bounds__(kW * 64, 2) void fwd_kernel(const FwdParams p) {
         // per (t, mm), 4 consecutive keys of its row: one mask word, or the bytes of two when the sequence's
         // first key position is not a multiple of 4 (wave-uniform)
         const int mis = __builtin_amdgcn_readfirstlane((int)(drop_j0 & 3u));
+        auto mask4 = [&](int t, int mm, uint32_t w) {
 #pragma unroll
-        for (int t = 0; t < kFwdSub; ++t)
+          for (int e = 0; e < 4; ++e)
+            if (!drop_keep(w, e, p.drop_keep)) s[t][4 * mm + e] = 0.f;
+        };
+        if (p.drop_mapped) {
+          // a position map (dense input): the keys of a group, a sub-tile or a tile need not be consecutive positions
+          // (rfa_common.hpp: drop_words_mapped); wave-uniform branch, the identity keeps the path below
 #pragma unroll
-          for (int mm = 0; mm < 4; ++mm) {
-            const uint32_t jg = drop_j0 + (uint32_t)(kt0 + 32 * t + 8 * mm + 4 * g);
-            uint32_t w = drop_word(drop_key, drop_i, jg >> 2);
-            if (mis) w = __builtin_amdgcn_alignbyte(drop_word(drop_key, drop_i, (jg >> 2) + 1), w, (uint32_t)mis);
+          for (int t = 0; t < kFwdSub; ++t) {
+            uint32_t w[4];
+            drop_words_mapped(drop_key, drop_i, kt0 + 32 * t, g, p.k_pos0, p.k_pstride, p.k_psplit, p.k_pos2, w);
 #pragma unroll
-            for (int e = 0; e < 4; ++e)
-              if (!drop_keep(w, e, p.drop_keep)) s[t][4 * mm + e] = 0.f;
+            for (int mm = 0; mm < 4; ++mm) mask4(t, mm, w[mm]);
           }
+        } else {
+#pragma unroll
+          for (int t = 0; t < kFwdSub; ++t)
+#pragma unroll
+            for (int mm = 0; mm < 4; ++mm) {
+              const uint32_t jg = drop_j0 + (uint32_t)(kt0 + 32 * t + 8 * mm + 4 * g);
+              uint32_t w = drop_word(drop_key, drop_i, jg >> 2);
+              if (mis) w = __builtin_amdgcn_alignbyte(drop_word(drop_key, drop_i, (jg >> 2) + 1), w, (uint32_t)mis);
+              mask4(t, mm, w);
+            }
+        }
       }
 
       // ---------------- O^T += V^T P^T ----------------

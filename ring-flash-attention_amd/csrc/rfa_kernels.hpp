@@ -66,6 +66,12 @@ struct FwdParams {
   float drop_scale;
   unsigned long long drop_seed;
   unsigned q_pos0, k_pos0, head0;
+  // position map of the mask (rfa.h: q_pos_stride ...; rfa_common.hpp: drop_pos): strides >= 1, split 0 = one piece;
+  // drop_mapped = some field is not the identity's — the kernels then leave the word-per-four-keys path
+  unsigned q_pstride, k_pstride;
+  int q_psplit, k_psplit;
+  unsigned q_pos2, k_pos2;
+  int drop_mapped;
 };
 
 struct PreParams {
@@ -117,6 +123,12 @@ struct BwdParams {
   float drop_scale;
   unsigned long long drop_seed;
   unsigned q_pos0, k_pos0, head0;
+  // position map of the mask (rfa.h: q_pos_stride ...; rfa_common.hpp: drop_pos): strides >= 1, split 0 = one piece;
+  // drop_mapped = some field is not the identity's — the kernels then leave the word-per-four-keys path
+  unsigned q_pstride, k_pstride;
+  int q_psplit, k_psplit;
+  unsigned q_pos2, k_pos2;
+  int drop_mapped;
 };
 
 // dst[b, row, hk, :] (=|+=) sum_g src[b, row, hk*G+g, :]

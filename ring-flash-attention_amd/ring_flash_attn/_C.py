@@ -11,6 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RFA_LIB_PATH") or os.path.join(_HERE, "librfa_hip.so")
 
 RFA_ABI_VERSION = 8
+RFA_ABI_REVISION = 1      # struct revision inside ABI 8 (include/rfa.h: rfa_abi_revision): the dropout position map
 RFA_BF16, RFA_F16 = 0, 1
 HALF_FULL, HALF_FRONT, HALF_BACK = 0, 1, 2
 BWD_ALL, BWD_COMPUTE, BWD_REDUCE = 0, 1, 2
@@ -42,7 +43,11 @@ class FwdArgs(C.Structure):
         ("dtype", C.c_int32),
         ("window", C.c_int32), ("window_left", C.c_int32), ("window_right", C.c_int32),
         ("dropout_p", C.c_float), ("dropout_seed", C.c_uint64),
-        ("q_pos_offset", C.c_int64), ("k_pos_offset", C.c_int64), ("head_offset", C.c_int32),
+        ("q_pos_offset", C.c_int64), ("k_pos_offset", C.c_int64),
+        ("q_pos_stride", C.c_int32), ("k_pos_stride", C.c_int32),          # dropout position map (ABI 8, revision 1)
+        ("q_pos_split", C.c_int32), ("k_pos_split", C.c_int32),
+        ("q_pos_offset2", C.c_int64), ("k_pos_offset2", C.c_int64),
+        ("head_offset", C.c_int32),
         ("fwd_form", C.c_int32),
         ("workspace", C.c_void_p), ("kv_nsplit", C.c_int32), ("total_q", C.c_int64),
         ("mask_shift", C.c_int64),
@@ -89,7 +94,11 @@ class BwdArgs(C.Structure):
         ("dkdv_form", C.c_int32), ("dkdv_nsplit", C.c_int32),
         ("prof_events", C.POINTER(C.c_void_p)),
         ("dropout_p", C.c_float), ("dropout_seed", C.c_uint64),
-        ("q_pos_offset", C.c_int64), ("k_pos_offset", C.c_int64), ("head_offset", C.c_int32),
+        ("q_pos_offset", C.c_int64), ("k_pos_offset", C.c_int64),
+        ("q_pos_stride", C.c_int32), ("k_pos_stride", C.c_int32),          # dropout position map (ABI 8, revision 1)
+        ("q_pos_split", C.c_int32), ("k_pos_split", C.c_int32),
+        ("q_pos_offset2", C.c_int64), ("k_pos_offset2", C.c_int64),
+        ("head_offset", C.c_int32),
         ("ds_scratch_bytes", C.c_int64),
         ("total_q", C.c_int64),
         ("mask_shift", C.c_int64),
@@ -123,6 +132,7 @@ class SumSlotsArgs(C.Structure):
 # every symbol include/rfa.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "rfa_abi_version": (C.c_int, []),
+    "rfa_abi_revision": (C.c_int, []),
     "rfa_build_id": (C.c_char_p, []),
     "rfa_strerror": (C.c_char_p, [C.c_int]),
     "rfa_fwd": (C.c_int, [C.POINTER(FwdArgs), C.c_void_p]),
@@ -162,6 +172,10 @@ def load():
         lib = C.CDLL(LIB_PATH)
     except OSError as e:  # missing libamdhip64 etc.
         raise RuntimeError(f"ring_flash_attn: cannot load {LIB_PATH}: {e}") from e
+    # the revision first: fields were added in the MIDDLE of the ABI 8 structs, so a library from before them reports the
+    # same version number and would read every later field from the wrong place
+    if not hasattr(lib, "rfa_abi_revision"):
+        raise RuntimeError(f"ring_flash_attn: librfa_hip.so has no rfa_abi_revision (binding revision {RFA_ABI_REVISION}); rebuild")
     for name, (res, args) in SYMBOLS.items():
         fn = getattr(lib, name)  # AttributeError if the .so is stale
         fn.restype = res
@@ -169,6 +183,9 @@ def load():
     ver = lib.rfa_abi_version()
     if ver != RFA_ABI_VERSION:
         raise RuntimeError(f"ring_flash_attn: librfa_hip.so ABI {ver} != binding {RFA_ABI_VERSION}; rebuild")
+    rev = lib.rfa_abi_revision()
+    if rev != RFA_ABI_REVISION:
+        raise RuntimeError(f"ring_flash_attn: librfa_hip.so ABI {ver} revision {rev} != binding revision {RFA_ABI_REVISION}; rebuild")
     _lib = lib
     return lib
 

@@ -6,8 +6,9 @@ The generated callables keep the exact keyword surface of the reference package
     dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1), alibi_slopes=None,
     deterministic=False, return_attn_probs=False, group=None
 with the reference's semantics: softmax_scale None -> head_dim ** -0.5; alibi_slopes must be
-None; dropout_p / window_size work wherever one kernel call sees all keys (single-rank groups, llama3) and raise
-on a multi-rank ring (unsupported there in the reference too, README.md:158-159);
+None; dropout_p works on single-rank groups, on the llama3 path and over several ranks with the dense ring, zigzag and
+stripe schedules (the reference declares dropout over a ring unsupported, README.md:158-159; the `*_varlen` ring families
+still raise here); window_size works with every schedule; the two together raise;
 return_attn_probs=True -> (out, softmax_lse, None); `group=None` is the default process group;
 inputs are the caller's LOCAL shard.
 """
@@ -75,7 +76,12 @@ def _check_unsupported(dropout_p, window_size, alibi_slopes, windows_ok=False, d
     mask of include/rfa.h).  Dropout is usable wherever ONE kernel call sees all the keys a query may attend to: every
     function on a single-rank group, and llama3_flash_attn_varlen_func on any group (it gathers K/V) — the coverage the
     reference gets from forwarding dropout_p to flash_attn (llama3_flash_attn_varlen.py:131-147); it declares dropout
-    over a ring unsupported (README.md:158-159) and so do the schedules here.  Windows are usable there too, and on any
+    over a ring unsupported (README.md:158-159).  Here the dense ring, zigzag (every exchange form) and stripe schedules
+    serve it on any group as well: the mask is a function of global positions, and those schedules tell every block
+    call where its rows sit (the position maps of `dropout=`, _common.dropout_arg), so the un-sharded result is the
+    single-device dropout call's with the same seed; they pass dropout_ok=True.  The two `*_varlen` ring families
+    (position maps for packed input do not exist) and the `torch.compile` whole-schedule operator still raise.
+    Windows are usable there too, and on any
     group with every ring schedule, each of which tells every block call where it sits in the full sequence: the dense
     ring and zigzag schedules in rows (`mask_shift`, include/rfa.h), the two `*_varlen` ring families in units of every
     packed sequence's own length (`mask_shift_lens`), the stripe schedule — token i of rank r is global token i W + r —
@@ -89,8 +95,10 @@ def _check_unsupported(dropout_p, window_size, alibi_slopes, windows_ok=False, d
     if drop and not 0 < dropout_p < 1:
         raise ValueError("dropout_p must be in [0, 1)")
     if drop and not dropout_ok:
-        raise NotImplementedError("ring_flash_attn: dropout over a multi-rank ring is not supported (as in the "
-                                  "reference); use llama3_flash_attn_varlen_func or a single-rank group")
+        raise NotImplementedError("ring_flash_attn: dropout over a multi-rank group is served by the dense ring, zigzag "
+                                  "and stripe functions and by llama3_flash_attn_varlen_func, not by the *_varlen ring "
+                                  "functions (position maps for packed input are not implemented) nor under "
+                                  "torch.compile's whole-schedule operator; use one of those or a single-rank group")
     if not windows_ok and has_window(window_size):
         raise NotImplementedError("ring_flash_attn: sliding window over a multi-rank group is served by the eager ring, "
                                   "zigzag, stripe and *_varlen ring functions and by llama3_flash_attn_varlen_func, not "
@@ -165,10 +173,12 @@ def _split_kept(ctx, more):
     return tensors_lead, ({"kept": tuple(kept)} if kept else {})
 
 
-def make_autograd_function(name, forward_impl, backward_impl, n_lead, window_ring=False):
+def make_autograd_function(name, forward_impl, backward_impl, n_lead, window_ring=False, dropout_ring=False):
     """n_lead: number of non-tensor positional arguments between (q,k,v) and the common tail
     (0 for the batch API, 2 = (cu_seqlens, max_seqlen) for varlen).  window_ring: the schedule serves a sliding window
-    on a multi-rank group (every ring family does: dense and varlen ring and zigzag, stripe)."""
+    on a multi-rank group (every ring family does: dense and varlen ring and zigzag, stripe).  dropout_ring: it serves
+    dropout there (the dense ring, zigzag and stripe schedules: every block call is told the global positions of its
+    rows, _common.dropout_arg)."""
 
     class _Fn(torch.autograd.Function):
         @staticmethod
@@ -179,7 +189,7 @@ def make_autograd_function(name, forward_impl, backward_impl, n_lead, window_rin
             if softmax_scale is None:
                 softmax_scale = q.shape[-1] ** (-0.5)
             single = window_ok_for(group)
-            _check_unsupported(dropout_p, window_size, alibi_slopes, windows_ok=single or window_ring, dropout_ok=single)
+            _check_unsupported(dropout_p, window_size, alibi_slopes, windows_ok=single or window_ring, dropout_ok=single or dropout_ring)
             q, k, v = _prep_qkv(q, k, v, group)
             tensors_lead = ()
             if n_lead:
@@ -226,7 +236,7 @@ def make_autograd_function(name, forward_impl, backward_impl, n_lead, window_rin
 
 
 def make_packed_function(name, base_fn, forward_impl, backward_impl, n_lead, pack_dim, n_packed, packed_travel=False,
-                         window_ring=False):
+                         window_ring=False, dropout_ring=False):
     """autograd Function for the packed entry points (`kv` = 2 tensors, `qkv` = 3 tensors stacked on
     `pack_dim`).  Same math as `base_fn`; the only difference is where the gradients land: ONE packed
     buffer whose slices are handed to the schedule as output views (`out_grads`), instead of letting
@@ -247,7 +257,7 @@ def make_packed_function(name, base_fn, forward_impl, backward_impl, n_lead, pac
             if softmax_scale is None:
                 softmax_scale = q.shape[-1] ** (-0.5)
             single = window_ok_for(group)
-            _check_unsupported(dropout_p, window_size, alibi_slopes, windows_ok=single or window_ring, dropout_ok=single)
+            _check_unsupported(dropout_p, window_size, alibi_slopes, windows_ok=single or window_ring, dropout_ok=single or dropout_ring)
             q, k, v = _prep_qkv(q, k, v, group, packed_travel=packed_travel and n_packed == 2)
             tensors_lead = ()
             if n_lead:
@@ -315,16 +325,17 @@ def _grad_buffers(out_grads, q, k, v):
             og[2] if og[2] is not None else torch.empty_like(v))
 
 
-def make_dense_api(fn, prefix, forward_impl=None, backward_impl=None, packed_travel=False, window_ring=False):
+def make_dense_api(fn, prefix, forward_impl=None, backward_impl=None, packed_travel=False, window_ring=False,
+                   dropout_ring=False):
     """(B,S,H,D) API: returns (func, kvpacked_func, qkvpacked_func).  packed_travel: the schedule exchanges a
     packed `kv` as one buffer and writes dK/dV straight into the packed gradient (`out_grads`) at any world size.
-    window_ring: as in make_autograd_function (pass the same value to both)."""
+    window_ring, dropout_ring: as in make_autograd_function (pass the same values to both)."""
     kv_fn = qkv_fn = None
     if forward_impl is not None:
         kv_fn = make_packed_function(fn.__name__ + "KVPacked", fn, forward_impl, backward_impl, 0, 2, 2,
-                                     packed_travel=packed_travel, window_ring=window_ring)
+                                     packed_travel=packed_travel, window_ring=window_ring, dropout_ring=dropout_ring)
         qkv_fn = make_packed_function(fn.__name__ + "QKVPacked", fn, forward_impl, backward_impl, 0, 2, 3,
-                                      window_ring=window_ring)
+                                      window_ring=window_ring, dropout_ring=dropout_ring)
 
     def func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
              alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None):

@@ -85,14 +85,70 @@ def _as_cu(cu_seqlens, device):
     return cu_seqlens.contiguous()
 
 
-def dropout_arg(dropout_p, dropout_seed, q_pos_offset=0, k_pos_offset=0, head_offset=0):
+def require_dropout_positions(be, what):
+    """Dropout over several ranks needs a backend that can be told where the rows of a block sit in the full sequence
+    even when they are not one contiguous run (the position maps of `dropout=`, include/rfa.h: q_pos_stride ...;
+    HipBackend.serves_dropout_positions).  One that cannot would draw another mask than the unsharded call — and, in the
+    backward of a block whose keys came from another rank, another mask than that rank's forward: refuse before anything
+    is exchanged, on every rank alike.  The contiguous ring asks for it too, although offsets alone would serve it, so
+    that one flag tells whether a backend serves dropout over a multi-rank group."""
+    if not getattr(be, "serves_dropout_positions", False):
+        raise NotImplementedError(f"ring_flash_attn: {what} with dropout on a multi-rank group needs a backend that serves "
+                                  f"dropout position maps; {getattr(be, 'name', type(be).__name__)!r} does not (it would "
+                                  "draw the mask per block)")
+
+
+IDENTITY_MAP = (1, 0, 0)
+
+
+def pos_map(offset=0, stride=1, split=0, offset2=0):
+    """(offset, (stride, split, offset2)) of a tensor whose local row i is global position
+    `offset + i * stride` for i < split (or split == 0), `offset2 + (i - split) * stride` from row `split` on"""
+    return int(offset), (int(stride), int(split), int(offset2))
+
+
+def map_positions(pm, n):
+    """the global positions of local rows 0 .. n-1 under pos_map `pm` (tests, documentation: the kernels' arithmetic)"""
+    off, (stride, split, off2) = pm
+    stride = stride or 1
+    return [off + i * stride if (split == 0 or i < split) else off2 + (i - split) * stride for i in range(n)]
+
+
+def zigzag_map(x, W, c, part="all"):
+    """pos_map of rank x's zigzag tensor with chunk length c: chunks x and 2W-1-x of the sequence (part "all"), its
+    front chunk alone ("front": `k[:, :c]`) or its back chunk alone ("back": `q[:, c:]`)"""
+    if part == "front":
+        return pos_map(x * c)
+    if part == "back":
+        return pos_map((2 * W - 1 - x) * c)
+    return pos_map(x * c, 1, c, (2 * W - 1 - x) * c)
+
+
+def stripe_map(x, W, skip=0):
+    """pos_map of rank x's stripe tensor (local row i is global token i W + x), `skip` leading rows sliced off"""
+    return pos_map(x + skip * W, W)
+
+
+def dropout_arg(dropout_p, dropout_seed, q_pos_offset=0, k_pos_offset=0, head_offset=0, q_map=None, k_map=None):
     """backend `dropout=` argument (p, seed, q_pos_offset, k_pos_offset, head_offset), or None when dropout is off.
-    The seed comes from the autograd Function (one draw per forward, reused by its backward)."""
+    The seed comes from the autograd Function (one draw per forward, reused by its backward).
+    q_map / k_map: a pos_map() each, for tensors whose rows are not one contiguous run of the global sequence; they
+    replace the offsets.  When both are the identity (stride 1, one piece) the result is the 5-tuple every backend
+    serves; otherwise the 7-tuple (..., (stride, split, offset2) of q, of k) that needs `serves_dropout_positions`."""
     if not dropout_p or not dropout_p > 0:
         return None
     if dropout_seed is None:
         raise ValueError("ring_flash_attn: dropout_p > 0 needs a dropout_seed (the public functions draw one)")
-    return (float(dropout_p), int(dropout_seed), int(q_pos_offset), int(k_pos_offset), int(head_offset))
+    qm = km = IDENTITY_MAP
+    if q_map is not None:
+        q_pos_offset, qm = q_map
+    if k_map is not None:
+        k_pos_offset, km = k_map
+    qm, km = ((m[0] or 1, m[1], m[2] if m[1] else 0) for m in (qm, km))
+    base = (float(dropout_p), int(dropout_seed), int(q_pos_offset), int(k_pos_offset), int(head_offset))
+    if qm == IDENTITY_MAP and km == IDENTITY_MAP:
+        return base
+    return base + (qm, km)
 
 
 _DROPOUT_SOURCE = {"generator": None, "group": None, "sync": False}

@@ -57,6 +57,7 @@ class HipBackend:
     name = "hip"
     serves_mask_shift = True        # fwd / bwd take `mask_shift` (include/rfa.h, ABI 7): what a windowed multi-rank schedule needs
     serves_mask_shift_lens = True   # ... and `mask_shift_lens` (ABI 8), the per-sequence shift the packed (varlen) ring schedules need
+    serves_dropout_positions = True  # `dropout=` takes the position maps (q_map, k_map): what dropout over a dense ring, zigzag or stripe schedule needs
 
     def __init__(self):
         self.lib = _C.load()
@@ -87,7 +88,8 @@ class HipBackend:
             mask_shift=0, mask_shift_lens=0):
         """Block attention.  Plain mode fills (out, lse); accumulate mode merges into the fp32
         (out_acc, lse_acc) pair (fused update_out_and_lse).  Dense: q (B,Sq,H,D); varlen: (T,H,D).
-        dropout: (p, seed, q_pos_offset, k_pos_offset, head_offset) or None.
+        dropout: (p, seed, q_pos_offset, k_pos_offset, head_offset), the same plus the position maps (q_map, k_map) —
+        each (stride, split, offset2), _common.dropout_arg — or None.
         mask_shift: where the block sits in a longer sequence (include/rfa.h; dense input) — for blocks of equal length
         the global position of q row 0 minus that of k row 0; moves the causal diagonal and the window alike.
         mask_shift_lens: the same in units of every sequence's own key length (include/rfa.h, ABI 8): the shift of packed
@@ -437,12 +439,17 @@ class HipBackend:
 
 
 def _set_dropout(a, dropout):
-    """dropout = (p, seed, q_pos_offset, k_pos_offset, head_offset) or None (include/rfa.h: rfa_fwd_args.dropout_p)"""
+    """dropout = (p, seed, q_pos_offset, k_pos_offset, head_offset) or None (include/rfa.h: rfa_fwd_args.dropout_p), or
+    the 7-tuple that adds the position maps (q_map, k_map) of tensors whose rows are not one contiguous run of the
+    sequence: each (stride, split, offset2) — include/rfa.h: q_pos_stride ... (_common.dropout_arg builds both)"""
     if dropout is None or not dropout[0] > 0:
         return
-    p, seed, q0, k0, h0 = dropout
+    p, seed, q0, k0, h0 = dropout[:5]
     a.dropout_p, a.dropout_seed = float(p), int(seed) & 0xFFFFFFFFFFFFFFFF
     a.q_pos_offset, a.k_pos_offset, a.head_offset = int(q0), int(k0), int(h0)
+    if len(dropout) > 5:
+        (a.q_pos_stride, a.q_pos_split, a.q_pos_offset2), (a.k_pos_stride, a.k_pos_split, a.k_pos_offset2) = (
+            tuple(int(x) for x in m) for m in dropout[5:7])
 
 
 _FWD_FORMS = {"auto": _C.FWD_AUTO, "8x32": _C.FWD_8x32, "4x32": _C.FWD_4x32, "p8x32": _C.FWD_P8x32}

@@ -19,7 +19,7 @@ import torch
 from . import _C
 from .backend import get_backend
 from .utils import RingComm, single_rank
-from ._common import dropout_arg, global_window, require_mask_shift
+from ._common import dropout_arg, global_window, pos_map, require_dropout_positions, require_mask_shift
 from ._api import make_autograd_function, make_dense_api, _grad_buffers
 
 
@@ -123,6 +123,19 @@ def _ring_window_backward(be, process_group, kv_comm, d_kv_comm, dout, q, k, v, 
     return be.cast(dq, q.dtype), be.cast(dk, q.dtype), be.cast(dv, q.dtype)
 
 
+def _ring_dropout(be, comm, S, dropout_p, dropout_seed):
+    """step -> the `dropout=` keyword of that step's block call (nothing without dropout).  The mask is a function of
+    GLOBAL positions (include/rfa.h): this rank's queries are rows rank * S ..., the K/V on hand at step d those of rank
+    rank - d — every block draws the bits the unsharded call draws there, and the backward, which walks the same steps
+    with the forward's seed, the forward's.  (Dropout together with a window never gets here: _api._check_unsupported.)"""
+    if not dropout_p or not dropout_p > 0:
+        return lambda step: {}
+    require_dropout_positions(be, "ring_flash_attn")
+    rank, world = comm.rank, comm.world_size
+    return lambda step: {"dropout": dropout_arg(dropout_p, dropout_seed, q_map=pos_map(rank * S),
+                                                k_map=pos_map(((rank - step) % world) * S))}
+
+
 def ring_flash_attn_forward(
     process_group,
     q: torch.Tensor,
@@ -145,7 +158,7 @@ def ring_flash_attn_forward(
         lse = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
         be.fwd(q, k, v, softmax_scale=softmax_scale, causal=causal, out=out, lse=lse, window=window_size, dropout=dropout_arg(dropout_p, dropout_seed))
         return out, lse
-    assert not dropout_p, "dropout over a multi-rank ring is not supported (as in the reference)"
+    drop = _ring_dropout(be, comm, S, dropout_p, dropout_seed)
 
     win = global_window(window_size, causal, comm.world_size * S)
     if win is not None:
@@ -163,7 +176,7 @@ def ring_flash_attn_forward(
 
         if not causal or step <= comm.rank:
             be.fwd(q, k, v, softmax_scale=softmax_scale, causal=causal and step == 0,
-                   out_acc=out_acc, lse_acc=lse_acc, acc_init=first)
+                   out_acc=out_acc, lse_acc=lse_acc, acc_init=first, **drop(step))
             first = False
 
         if step + 1 != comm.world_size:
@@ -208,7 +221,7 @@ def ring_flash_attn_backward(
         be.bwd(dout, q, k, v, softmax_lse, delta, softmax_scale=softmax_scale, causal=causal,
                dq=dq, dk=dk, dv=dv, deterministic=deterministic, window=window_size, dropout=dropout_arg(dropout_p, dropout_seed))
         return dq, dk, dv
-    assert not dropout_p, "dropout over a multi-rank ring is not supported (as in the reference)"
+    drop = _ring_dropout(be, kv_comm, S, dropout_p, dropout_seed)
 
     win = global_window(window_size, causal, kv_comm.world_size * S)
     if win is not None:
@@ -230,16 +243,16 @@ def ring_flash_attn_backward(
             if dq is None:
                 dq = torch.empty((B, S, H, D), dtype=torch.float32, device=q.device)
                 be.bwd(dout, q, k, v, softmax_lse, delta, softmax_scale=softmax_scale, causal=bwd_causal,
-                       dq_acc=dq, dk_acc=dk, dv_acc=dv, acc_init=True, deterministic=deterministic)
+                       dq_acc=dq, dk_acc=dk, dv_acc=dv, acc_init=True, deterministic=deterministic, **drop(step))
             else:
                 part = be.bwd(dout, q, k, v, softmax_lse, delta, softmax_scale=softmax_scale, causal=bwd_causal,
                               dq_acc=dq, dk_acc=dk, dv_acc=dv, deterministic=deterministic,
-                              phases=_C.BWD_COMPUTE)
+                              phases=_C.BWD_COMPUTE, **drop(step))
                 d_kv_comm.wait()
                 dk, dv = next_dk, next_dv
                 be.bwd(dout, q, k, v, softmax_lse, delta, softmax_scale=softmax_scale, causal=bwd_causal,
                        dq_acc=dq, dk_acc=dk, dv_acc=dv, deterministic=deterministic,
-                       phases=_C.BWD_REDUCE, partials=part)
+                       phases=_C.BWD_REDUCE, partials=part, **drop(step))
         elif step != 0:
             d_kv_comm.wait()
             dk, dv = next_dk, next_dv
@@ -256,9 +269,10 @@ def ring_flash_attn_backward(
 
 
 RingFlashAttnFunc = make_autograd_function(
-    "RingFlashAttnFunc", ring_flash_attn_forward, ring_flash_attn_backward, 0, window_ring=True)
+    "RingFlashAttnFunc", ring_flash_attn_forward, ring_flash_attn_backward, 0, window_ring=True, dropout_ring=True)
 (
     ring_flash_attn_func,
     ring_flash_attn_kvpacked_func,
     ring_flash_attn_qkvpacked_func,
-) = make_dense_api(RingFlashAttnFunc, "ring_flash_attn", ring_flash_attn_forward, ring_flash_attn_backward, window_ring=True)
+) = make_dense_api(RingFlashAttnFunc, "ring_flash_attn", ring_flash_attn_forward, ring_flash_attn_backward, window_ring=True,
+                   dropout_ring=True)

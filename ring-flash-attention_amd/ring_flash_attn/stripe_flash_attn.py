@@ -21,7 +21,7 @@ import torch
 from . import _C
 from .backend import get_backend
 from .utils import RingComm, single_rank
-from ._common import dropout_arg, global_window, require_mask_shift
+from ._common import dropout_arg, global_window, require_dropout_positions, require_mask_shift, stripe_map
 from ._api import make_autograd_function, make_dense_api, _grad_buffers
 
 
@@ -90,6 +90,20 @@ def _stripe_window_backward(be, kv_comm, d_kv_comm, dout, q, k, v, softmax_lse, 
     return be.cast(dq, q.dtype), be.cast(next_dk, q.dtype), be.cast(next_dv, q.dtype)
 
 
+def _stripe_dropout(be, rank, world, dropout_p, dropout_seed):
+    """(src, shifted) -> the `dropout=` keyword of a block call against the K/V of rank `src` (nothing without dropout).
+    The mask is a function of GLOBAL positions (include/rfa.h); local row i of rank x is global token i W + x — a
+    position map with stride W (_common.stripe_map).  shifted: the `q[:, 1:]` x `k[:, :-1]` views of a step whose keys
+    are one token ahead — the queries then start one stride later, the keys where they always start.
+    The backward passes the forward's map with the forward's seed.  (Dropout with a window: _api._check_unsupported.)"""
+    if not dropout_p or not dropout_p > 0:
+        return lambda src, shifted: {}
+    require_dropout_positions(be, "stripe_flash_attn")
+    return lambda src, shifted: {"dropout": dropout_arg(dropout_p, dropout_seed,
+                                                        q_map=stripe_map(rank, world, skip=1 if shifted else 0),
+                                                        k_map=stripe_map(src, world))}
+
+
 def stripe_flash_attn_forward(
     process_group,
     q: torch.Tensor,
@@ -115,7 +129,7 @@ def stripe_flash_attn_forward(
         lse = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
         be.fwd(q, k, v, softmax_scale=softmax_scale, causal=True, out=out, lse=lse, window=window_size, dropout=dropout_arg(dropout_p, dropout_seed))
         return out, lse
-    assert not dropout_p, "dropout over a multi-rank ring is not supported (as in the reference)"
+    drop = _stripe_dropout(be, comm.rank, comm.world_size, dropout_p, dropout_seed)
     win = global_window(window_size, True, comm.world_size * S)
     if win is not None:
         require_mask_shift(be, "stripe_flash_attn")
@@ -128,12 +142,13 @@ def stripe_flash_attn_forward(
         if step + 1 != comm.world_size:
             next_k, next_v = comm.send_recv_kv(k, v)
 
+        src = (comm.rank - step) % comm.world_size                     # whose K/V are on hand
         if step <= comm.rank:
             be.fwd(q, k, v, softmax_scale=softmax_scale, causal=True,
-                   out_acc=out_acc, lse_acc=lse_acc, acc_init=(step == 0))
+                   out_acc=out_acc, lse_acc=lse_acc, acc_init=(step == 0), **drop(src, False))
         else:
             be.fwd(q[:, 1:], k[:, :-1], v[:, :-1], softmax_scale=softmax_scale, causal=True,
-                   out_acc=out_acc[:, 1:], lse_acc=lse_acc[:, :, 1:])
+                   out_acc=out_acc[:, 1:], lse_acc=lse_acc[:, :, 1:], **drop(src, True))
 
         if step + 1 != comm.world_size:
             comm.wait()
@@ -179,7 +194,7 @@ def stripe_flash_attn_backward(
         be.bwd(dout, q, k, v, softmax_lse, delta, softmax_scale=softmax_scale, causal=True,
                dq=dq, dk=dk, dv=dv, deterministic=deterministic, window=window_size, dropout=dropout_arg(dropout_p, dropout_seed))
         return dq, dk, dv
-    assert not dropout_p, "dropout over a multi-rank ring is not supported (as in the reference)"
+    drop = _stripe_dropout(be, kv_comm.rank, kv_comm.world_size, dropout_p, dropout_seed)
     win = global_window(window_size, True, kv_comm.world_size * S)
     if win is not None:
         require_mask_shift(be, "stripe_flash_attn")
@@ -204,7 +219,8 @@ def stripe_flash_attn_backward(
         else:
             args = (dout, q, k, v, softmax_lse, delta)
             dq_view = dq
-        common = dict(softmax_scale=softmax_scale, causal=True, deterministic=deterministic)
+        common = dict(softmax_scale=softmax_scale, causal=True, deterministic=deterministic,
+                      **drop((kv_comm.rank - step) % kv_comm.world_size, shift_causal))
 
         if step == 0:
             be.bwd(*args, dq_acc=dq, dk_acc=dk, dv_acc=dv, acc_init=True, **common)
@@ -232,10 +248,10 @@ def stripe_flash_attn_backward(
 
 
 StripeFlashAttnFunc = make_autograd_function(
-    "StripeFlashAttnFunc", stripe_flash_attn_forward, stripe_flash_attn_backward, 0, window_ring=True)
+    "StripeFlashAttnFunc", stripe_flash_attn_forward, stripe_flash_attn_backward, 0, window_ring=True, dropout_ring=True)
 (
     stripe_flash_attn_func,
     stripe_flash_attn_kvpacked_func,
     stripe_flash_attn_qkvpacked_func,
 ) = make_dense_api(StripeFlashAttnFunc, "stripe_flash_attn", stripe_flash_attn_forward, stripe_flash_attn_backward,
-                   window_ring=True)
+                   window_ring=True, dropout_ring=True)

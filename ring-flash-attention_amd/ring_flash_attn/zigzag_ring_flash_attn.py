@@ -52,7 +52,7 @@ from . import _C, config
 from .backend import get_backend
 from .utils import Agreement, AllGatherComm, RingComm, SourceArrivals, all_to_all_async, reduce_scatter_async, single_rank
 from ._api import make_autograd_function, make_dense_api, _grad_buffers
-from ._common import packed_pair, dropout_arg, global_window, require_mask_shift
+from ._common import packed_pair, dropout_arg, global_window, require_dropout_positions, require_mask_shift, zigzag_map
 
 
 def gather_scratch_bytes(k: torch.Tensor, world: int, wire_fp32: bool) -> int:
@@ -289,6 +289,27 @@ def _zigzag_window_backward(be, process_group, kv_comm, d_kv_comm, dout, q, k, v
     return be.cast(dq, q.dtype), be.cast(next_dk, q.dtype), be.cast(next_dv, q.dtype)
 
 
+def _zigzag_dropout(be, rank, world, half, dropout_p, dropout_seed):
+    """(kind, src) -> the `dropout=` keyword of a block call against the K/V of rank `src` (nothing without dropout).
+    The mask is a function of GLOBAL positions (include/rfa.h) and a rank's tensor is two distant chunks of the
+    sequence — chunk r and chunk 2W-1-r —, which a position map describes (_common.zigzag_map).  The three kinds are the
+    three block calls every exchange form makes:
+        "local"  all queries x all keys of this rank          both sides two pieces
+        "front"  all queries x `k[:, :half]` of rank src      keys: the front chunk, one piece
+        "back"   `q[:, half:]` x all keys of rank src         queries: the back chunk, one piece
+    The backward passes the forward's map with the forward's seed.  (Dropout with a window: _api._check_unsupported.)"""
+    if not dropout_p or not dropout_p > 0:
+        return lambda kind, src: {}
+    require_dropout_positions(be, "zigzag_ring_flash_attn")
+
+    def drop(kind, src):
+        q_map = zigzag_map(rank, world, half, "back" if kind == "back" else "all")
+        k_map = zigzag_map(src, world, half, "front" if kind == "front" else "all")
+        return {"dropout": dropout_arg(dropout_p, dropout_seed, q_map=q_map, k_map=k_map)}
+
+    return drop
+
+
 def zigzag_ring_flash_attn_forward(
     process_group,
     q: torch.Tensor,
@@ -316,7 +337,7 @@ def zigzag_ring_flash_attn_forward(
         lse = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
         be.fwd(q, k, v, softmax_scale=softmax_scale, causal=True, out=out, lse=lse, window=window_size, dropout=dropout_arg(dropout_p, dropout_seed))
         return out, lse
-    assert not dropout_p, "dropout over a multi-rank ring is not supported (as in the reference)"
+    drop = _zigzag_dropout(be, comm.rank, comm.world_size, half, dropout_p, dropout_seed)
 
     win = global_window(window_size, True, comm.world_size * S)
     if win is not None:
@@ -330,7 +351,7 @@ def zigzag_ring_flash_attn_forward(
     if mode in ("gather", "gather_ps"):
         gather, bufs, k_all, v_all = _gather_kv(process_group, k, v, comm.world_size, per_source=mode == "gather_ps")
         be.fwd(q, k, v, softmax_scale=softmax_scale, causal=True,          # runs beside the exchange
-               out_acc=out_acc, lse_acc=lse_acc, acc_init=True)
+               out_acc=out_acc, lse_acc=lse_acc, acc_init=True, **drop("local", comm.rank))
         if mode == "gather":
             gather.wait()                                                  # one collective: everything or nothing
         _try_keep(keep, bufs, process_group)
@@ -341,10 +362,10 @@ def zigzag_ring_flash_attn_forward(
             ks, vs = k_all[src], v_all[src]
             if step <= comm.rank:
                 be.fwd(q, ks[:, :half], vs[:, :half], softmax_scale=softmax_scale, causal=False,
-                       out_acc=out_acc, lse_acc=lse_acc)
+                       out_acc=out_acc, lse_acc=lse_acc, **drop("front", src))
             else:
                 be.fwd(q[:, half:], ks, vs, softmax_scale=softmax_scale, causal=False,
-                       out_acc=out_acc[:, half:], lse_acc=lse_acc[:, :, half:])
+                       out_acc=out_acc[:, half:], lse_acc=lse_acc[:, :, half:], **drop("back", src))
         return be.cast(out_acc, q.dtype), lse_acc
 
     next_k, next_v = None, None
@@ -353,15 +374,16 @@ def zigzag_ring_flash_attn_forward(
         if step + 1 != comm.world_size:
             next_k, next_v = comm.send_recv_kv(k, v)
 
+        src = (comm.rank - step) % comm.world_size                     # whose K/V are on hand
         if step == 0:
             be.fwd(q, k, v, softmax_scale=softmax_scale, causal=True,
-                   out_acc=out_acc, lse_acc=lse_acc, acc_init=True)
+                   out_acc=out_acc, lse_acc=lse_acc, acc_init=True, **drop("local", src))
         elif step <= comm.rank:
             be.fwd(q, k[:, :half], v[:, :half], softmax_scale=softmax_scale, causal=False,
-                   out_acc=out_acc, lse_acc=lse_acc)
+                   out_acc=out_acc, lse_acc=lse_acc, **drop("front", src))
         else:
             be.fwd(q[:, half:], k, v, softmax_scale=softmax_scale, causal=False,
-                   out_acc=out_acc[:, half:], lse_acc=lse_acc[:, :, half:])
+                   out_acc=out_acc[:, half:], lse_acc=lse_acc[:, :, half:], **drop("back", src))
 
         if step + 1 != comm.world_size:
             comm.wait()
@@ -409,7 +431,7 @@ def zigzag_ring_flash_attn_backward(
         be.bwd(dout, q, k, v, softmax_lse, delta, softmax_scale=softmax_scale, causal=True,
                dq=dq, dk=dk, dv=dv, deterministic=deterministic, window=window_size, dropout=dropout_arg(dropout_p, dropout_seed))
         return dq, dk, dv
-    assert not dropout_p, "dropout over a multi-rank ring is not supported (as in the reference)"
+    drop = _zigzag_dropout(be, kv_comm.rank, kv_comm.world_size, half, dropout_p, dropout_seed)
 
     win = global_window(window_size, True, kv_comm.world_size * S)
     if win is not None:
@@ -457,7 +479,7 @@ def zigzag_ring_flash_attn_backward(
         full = slice(None)
         if not local_last:
             be.bwd(dout, q, k, v, softmax_lse, delta, softmax_scale=softmax_scale, causal=True,
-                   dq_acc=dq, acc_init=True, deterministic=deterministic, **slots(rank, full))   # beside the all-gather
+                   dq_acc=dq, acc_init=True, deterministic=deterministic, **slots(rank, full), **drop("local", rank))   # beside the all-gather
             if gather is not None and not per_source:
                 gather.wait()
         elif rank == 0:
@@ -477,11 +499,11 @@ def zigzag_ring_flash_attn_backward(
                     dv_all[src][:, half:].zero_()
                 be.bwd(dout, q, ks[:, :half], vs[:, :half], softmax_lse, delta, softmax_scale=softmax_scale,
                        causal=False, dq_acc=dq, acc_init=init, deterministic=deterministic,
-                       phases=_C.BWD_KV_OVERWRITE, **slots(src, slice(0, half)))
+                       phases=_C.BWD_KV_OVERWRITE, **slots(src, slice(0, half)), **drop("front", src))
             else:
                 be.bwd(dout[:, half:], q[:, half:], ks, vs, softmax_lse[:, :, half:], delta[:, :, half:],
                        softmax_scale=softmax_scale, causal=False, dq_acc=dq[:, half:], acc_init=init,
-                       deterministic=deterministic, phases=_C.BWD_KV_OVERWRITE, **slots(src, full))
+                       deterministic=deterministic, phases=_C.BWD_KV_OVERWRITE, **slots(src, full), **drop("back", src))
         if wire32:
             sums = [torch.empty((c.shape[0] // W,) + tuple(c.shape[1:]), dtype=torch.float32, device=q.device) for c in cats]
             works = [reduce_scatter_async(s_, c, group=process_group) for s_, c in zip(sums, cats)]
@@ -503,7 +525,7 @@ def zigzag_ring_flash_attn_backward(
             # (a one-rank group on the forced multi-step path has no remote step: the local block is then the first —
             #  and only — kernel that touches dq)
             be.bwd(dout, q, k, v, softmax_lse, delta, softmax_scale=softmax_scale, causal=True,
-                   dq_acc=dq, acc_init=W == 1, deterministic=deterministic, **own_kv)
+                   dq_acc=dq, acc_init=W == 1, deterministic=deterministic, **own_kv, **drop("local", rank))
         dq_out = be.cast(dq, q.dtype)                                      # runs beside the exchange
         for w_ in works:
             w_.wait()
@@ -537,9 +559,11 @@ def zigzag_ring_flash_attn_backward(
 
         if step == 0:
             be.bwd(dout, q, k, v, softmax_lse, delta, softmax_scale=softmax_scale, causal=True,
-                   dq_acc=dq, dk_acc=dk, dv_acc=dv, acc_init=True, deterministic=deterministic)
+                   dq_acc=dq, dk_acc=dk, dv_acc=dv, acc_init=True, deterministic=deterministic,
+                   **drop("local", kv_comm.rank))
         else:
             front = step <= kv_comm.rank
+            dkw = drop("front" if front else "back", (kv_comm.rank - step) % kv_comm.world_size)
             if front:
                 args = (dout, q, k[:, :half], v[:, :half], softmax_lse, delta)
                 dq_view = dq
@@ -548,7 +572,7 @@ def zigzag_ring_flash_attn_backward(
                 dq_view = dq[:, half:]
             # phase 1: dQ (+= in fp32) and per-head dK/dV partials — overlaps the dk/dv transfer
             part = be.bwd(*args, softmax_scale=softmax_scale, causal=False, dq_acc=dq_view,
-                          dk_acc=dk, dv_acc=dv, deterministic=deterministic, phases=_C.BWD_COMPUTE)
+                          dk_acc=dk, dv_acc=dv, deterministic=deterministic, phases=_C.BWD_COMPUTE, **dkw)
 
             d_kv_comm.wait()
             dk_comm_buffer, dv_comm_buffer = dk, dv
@@ -558,11 +582,11 @@ def zigzag_ring_flash_attn_backward(
             if front:
                 be.bwd(*args, softmax_scale=softmax_scale, causal=False, dq_acc=dq_view,
                        dk_acc=dk[:, :half], dv_acc=dv[:, :half], deterministic=deterministic,
-                       phases=_C.BWD_REDUCE, partials=part)
+                       phases=_C.BWD_REDUCE, partials=part, **dkw)
             else:
                 be.bwd(*args, softmax_scale=softmax_scale, causal=False, dq_acc=dq_view,
                        dk_acc=dk, dv_acc=dv, deterministic=deterministic, phases=_C.BWD_REDUCE,
-                       partials=part)
+                       partials=part, **dkw)
 
         if step + 1 != kv_comm.world_size:
             kv_comm.wait()
@@ -578,10 +602,11 @@ def zigzag_ring_flash_attn_backward(
 zigzag_ring_flash_attn_forward.keeps_for_backward = True
 
 ZigZagRingFlashAttnFunc = make_autograd_function(
-    "ZigZagRingFlashAttnFunc", zigzag_ring_flash_attn_forward, zigzag_ring_flash_attn_backward, 0, window_ring=True)
+    "ZigZagRingFlashAttnFunc", zigzag_ring_flash_attn_forward, zigzag_ring_flash_attn_backward, 0, window_ring=True,
+    dropout_ring=True)
 (
     zigzag_ring_flash_attn_func,
     zigzag_ring_flash_attn_kvpacked_func,
     zigzag_ring_flash_attn_qkvpacked_func,
 ) = make_dense_api(ZigZagRingFlashAttnFunc, "zigzag_ring_flash_attn", zigzag_ring_flash_attn_forward,
-                   zigzag_ring_flash_attn_backward, packed_travel=True, window_ring=True)
+                   zigzag_ring_flash_attn_backward, packed_travel=True, window_ring=True, dropout_ring=True)
