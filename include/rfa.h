@@ -44,6 +44,12 @@
  *     front half (1) or its back half (2) WITHOUT gathering — the offset arithmetic that
  *     replaces get_half_index/get_half_lse (zigzag_ring_flash_attn_varlen.py:24-71).  Outputs
  *     (out, lse, dq, delta) are addressed like q; dk/dv like k.
+ *   - ALiBi (flash_attn's alibi_slopes) is an EXTENSION argument (rfa_ext_args, below): per batch b, query head h, query row i
+ *     and key j of a block call
+ *         score = softmax_scale * q.k  -  slope[b,h] * | i + (len_k - len_q) + alibi_shift - j |
+ *     added before masking and softmax (len_*: the effective lengths after q_half / k_half, per sequence for packed
+ *     input).  lse is the log-sum-exp of the biased scores, the whole bias included, so blocks of a ring merge; the
+ *     backward recomputes P with the same bias, the slopes get no gradient.
  *   - Return value: 0 on success, negative rfa_status otherwise; rfa_strerror() explains.
  */
 #ifndef RFA_H_
@@ -350,6 +356,42 @@ const char *rfa_build_id(void);
 const char *rfa_strerror(int status);
 
 int rfa_fwd(const rfa_fwd_args *args, void *stream);
+
+/* Extension arguments: per-call features that arrive after the structs above were frozen (ABI 8 revision 1 stays — no
+ * existing struct changes) ride on this struct and the two *_ex entry points instead of new fields there.
+ *   rfa_fwd(a, s) IS rfa_fwd_ex(a, NULL, s), rfa_bwd likewise; a NULL `ext`, or one whose features are all off, runs the
+ *   instance, plan and bits of the plain call.
+ *   struct_bytes: sizeof(rfa_ext_args) as the CALLER compiled it.  Smaller than the library's: the missing tail reads as
+ *   zero.  Larger: accepted while the tail the library does not know is zero.  RFA_ERR_ARGS: a larger struct with a
+ *   non-zero tail, struct_bytes below the fixed head (struct_bytes + reserved), a non-zero `reserved`.  The extension is
+ *   validated before any pointer of the base struct is looked at; rfa_ext_args_bytes() is the library's sizeof.
+ * ALiBi (Conventions, above): alibi_slopes — fp32, DEVICE, one slope per query head (GQA changes nothing): (H,) with
+ *   alibi_batch_stride = 0, or (B, H) with the element stride between batch entries (packed input: between sequences); a
+ *   head-group slice is a pointer offset made by the caller.  NULL: off (stride and shift are then not read).
+ *   alibi_shift: where the block sits in a longer sequence, with mask_shift's meaning for blocks of equal length — global
+ *   position of q row 0 minus that of k row 0, in rows — but a field of its own: it is independent of the mask, is read
+ *   without a band and is never rewritten by the band normalisation.  A ring rank that has the K/V of the rank t places in
+ *   front on hand passes t * S.
+ *   The distance is formed in integers per row and only the per-element part in fp32: exact up to 2^24 rows; beyond that
+ *   it carries a relative rounding of 6e-8 (the forward and the backward kernels may round it differently there).
+ *   The slopes enter the kernels in score units (slope / softmax_scale: their row max runs on unscaled scores).
+ *   RFA_ERR_ARGS with a bias: a bounded window that survives the band normalisation; dropout_p > 0; head_dim > 128;
+ *   a non-zero alibi_shift with cu_seqlens; |alibi_shift| + Sq + Sk >= 2^31; softmax_scale <= 0; a negative
+ *   alibi_batch_stride.  (A block whose band is empty has nothing to bias: it runs as the call without the extension.)
+ *   Forward: one kernel form, 8 waves x 32 rows; fwd_form values that do not exist for a bias (RFA_FWD_4x32,
+ *   RFA_FWD_P8x32) and split-KV read as RFA_FWD_AUTO / never split, as for dropout; `workspace` is ignored.
+ *   Backward: the plain 128-key dK/dV kernel and the 7-GEMM dQ kernel, as for dropout.  rfa_bwd_workspace_bytes and
+ *   rfa_bwd_plan do not see the extension, so rfa_bwd_ex returns RFA_ERR_ARGS unless the BASE arguments already plan to
+ *   exactly that — dkdv_form = RFA_DKDV_128, ds_scratch = NULL — and the three can never disagree. */
+typedef struct {
+  uint32_t struct_bytes;        /* sizeof as the caller compiled it */
+  uint32_t reserved;            /* 0 */
+  const float *alibi_slopes;    /* NULL: off */
+  int64_t alibi_batch_stride;   /* 0: one (H,) row for every batch entry */
+  int64_t alibi_shift;
+} rfa_ext_args;
+int rfa_fwd_ex(const rfa_fwd_args *args, const rfa_ext_args *ext, void *stream);
+int64_t rfa_ext_args_bytes(void);
 /* bytes of rfa_fwd_args.workspace the call can use (0: the call is never split); *nsplit (may be NULL) = the number of
  * key-range shares the call runs with when given that workspace.  Pure function of the arguments. */
 int64_t rfa_fwd_workspace_bytes(const rfa_fwd_args *args, int32_t *nsplit);
@@ -369,6 +411,7 @@ int64_t rfa_bwd_ds_scratch_min_bytes(const rfa_bwd_args *args);
  * of one chunk, *chunk_bytes = scratch bytes one chunk uses.  Pure function of the arguments. */
 int rfa_bwd_ds_chunks(const rfa_bwd_args *args, int32_t *nchunks, int32_t *kv_heads, int32_t *q_heads, int64_t *chunk_bytes);
 int rfa_bwd(const rfa_bwd_args *args, void *stream);
+int rfa_bwd_ex(const rfa_bwd_args *args, const rfa_ext_args *ext, void *stream);
 int rfa_merge(const rfa_merge_args *args, void *stream);
 
 /* dst(io dtype) = (io)src(fp32), n elements, both contiguous */

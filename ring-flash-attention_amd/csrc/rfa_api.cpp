@@ -176,6 +176,42 @@ inline void set_pos_map(P& p, const A& a) {
   p.drop_mapped = (p.q_pstride != 1u || p.k_pstride != 1u || p.q_psplit != 0 || p.k_psplit != 0) ? 1 : 0;
 }
 
+
+// ---- extension arguments (rfa.h: rfa_ext_args) -----------------------------------------------------------------------------
+// The caller's struct may be shorter (an older caller: the missing tail reads as zero) or longer (a newer one: accepted while
+// the tail this library does not know is zero) than ours.  Parsed before any pointer of the base struct is looked at.
+struct Ext { const float* slopes; int64_t bstride, shift; };
+constexpr uint32_t kExtHead = 2 * sizeof(uint32_t);              // struct_bytes + reserved
+inline int parse_ext(const rfa_ext_args* e, Ext* out) {
+  *out = Ext{nullptr, 0, 0};
+  if (e == nullptr) return RFA_OK;
+  const uint32_t n = e->struct_bytes;
+  if (n < kExtHead || e->reserved != 0) return RFA_ERR_ARGS;
+  rfa_ext_args x{};
+  const unsigned char* src = reinterpret_cast<const unsigned char*>(e);
+  unsigned char* dst = reinterpret_cast<unsigned char*>(&x);
+  for (uint32_t i = 0; i < n && i < sizeof(x); ++i) dst[i] = src[i];
+  for (uint32_t i = sizeof(x); i < n; ++i)
+    if (src[i] != 0) return RFA_ERR_ARGS;
+  if (x.alibi_slopes == nullptr) return RFA_OK;                  // off: the shift and the stride are not read
+  if (x.alibi_batch_stride < 0) return RFA_ERR_ARGS;
+  *out = Ext{x.alibi_slopes, x.alibi_batch_stride, x.alibi_shift};
+  return RFA_OK;
+}
+// what a call with a bias must look like (rfa.h), checked on the call as given and on its normalised band `n`
+template <typename A>
+inline bool bias_args_ok(const A& a, const A& n, const Ext& e) {
+  if (a.dropout_p > 0.f || a.D > kHeadDim || !(a.softmax_scale > 0.f)) return false;
+  if (n.window && (n.window_left >= 0 || (n.window_right >= 0 && !n.causal))) return false;   // a bound that survived
+  if (e.shift != 0 && (a.cu_seqlens_q != nullptr || a.cu_seqlens_k != nullptr)) return false;
+  if (e.shift <= -((int64_t)1 << 31) || e.shift >= ((int64_t)1 << 31)) return false;
+  return (e.shift < 0 ? -e.shift : e.shift) + a.Sq + a.Sk < ((int64_t)1 << 31);
+}
+template <typename P>
+inline void set_bias(P& p, const Ext& e, float scale) {
+  p.alibi = e.slopes; p.alibi_bstride = e.bstride; p.alibi_shift = (int)e.shift; p.alibi_rscale = 1.f / scale;
+}
+
 }  // namespace
 
 // the library is built with -fvisibility=hidden: the C ABI below (include/rfa.h) is everything a loader can bind —
@@ -474,11 +510,22 @@ int64_t rfa_fwd_workspace_bytes(const rfa_fwd_args* a, int32_t* nsplit) {
   return (int64_t)ns * rows * a->H * ((int64_t)a->D + 1) * 4;      // fp32 partial outs + partial lse
 }
 
-int rfa_fwd(const rfa_fwd_args* a, void* stream) {
+int64_t rfa_ext_args_bytes(void) { return (int64_t)sizeof(rfa_ext_args); }
+
+int rfa_fwd(const rfa_fwd_args* a, void* stream) { return rfa_fwd_ex(a, nullptr, stream); }
+
+int rfa_fwd_ex(const rfa_fwd_args* a, const rfa_ext_args* ext, void* stream) {
   if (!a) return RFA_ERR_NULL;
+  Ext e;
+  if (int rce = parse_ext(ext, &e)) return rce;
   int rc = check_common(a->dtype, a->H, a->Hk, a->D, a->B);
   if (rc) return rc;
   if (a->Sq < 0 || a->Sk < 0) return RFA_ERR_SHAPE;
+  if (e.slopes != nullptr) {
+    if (!shift_args_ok(*a)) return RFA_ERR_ARGS;
+    if (band_empty(*a)) e.slopes = nullptr;        // nothing visible: the bias has nothing to act on — the call without it
+    else if (!bias_args_ok(*a, norm_args(*a), e)) return RFA_ERR_ARGS;
+  }
   if (a->B == 0 || a->Sq == 0) return RFA_OK;
   if (!a->q || !a->k || !a->v) return RFA_ERR_NULL;
   if (a->out_acc) {
@@ -524,10 +571,14 @@ int rfa_fwd(const rfa_fwd_args* a, void* stream) {
   p.drop_seed = a->dropout_seed;
   set_pos_map(p, *a);
   // 256 query rows per workgroup (8 waves) or 128 (4 waves, two workgroups per CU), and the split-KV shares: fwd_plan()
-  const FwdPlan plan = fwd_plan(a);
+  // a bias runs the 256-row form: the persistent form, the 4-wave form and split-KV shares do not exist for it and read as
+  // RFA_FWD_AUTO / "never split" (`workspace` is ignored), as they do for dropout
+  const bool bias = e.slopes != nullptr;
+  if (bias) set_bias(p, e, a->softmax_scale);
+  const FwdPlan plan = bias ? FwdPlan{fwd_qrows_per_block(), 1, 0} : fwd_plan(a);
   int rows = plan.rows;
   // split-KV (needs the caller's workspace): the 128-row form with the key tiles of a workgroup shared by kv_nsplit
-  const int ns = (a->workspace != nullptr && fwd_rows_total(a) > 0) ? plan.ns : 1;
+  const int ns = (a->workspace != nullptr && fwd_rows_total(a) > 0 && !bias) ? plan.ns : 1;
   if (a->kv_nsplit < 0) return RFA_ERR_ARGS;
   if (ns <= 1 && plan.ns > 1) {                              // planned with shares but called without a workspace: the unsplit plan
     rfa_fwd_args b = *a;
@@ -911,11 +962,23 @@ int64_t rfa_bwd_workspace_bytes(const rfa_bwd_args* a) {
   return 2 * a->total_k * (int64_t)a->Hk * a->D * (f32 ? 4 * ns : 2);
 }
 
-int rfa_bwd(const rfa_bwd_args* a, void* stream) {
+int rfa_bwd(const rfa_bwd_args* a, void* stream) { return rfa_bwd_ex(a, nullptr, stream); }
+
+int rfa_bwd_ex(const rfa_bwd_args* a, const rfa_ext_args* ext, void* stream) {
   if (!a) return RFA_ERR_NULL;
+  Ext e;
+  if (int rce = parse_ext(ext, &e)) return rce;
   int rc = check_common(a->dtype, a->H, a->Hk, a->D, a->B);
   if (rc) return rc;
   if (a->Sq < 0 || a->Sk < 0) return RFA_ERR_SHAPE;
+  if (e.slopes != nullptr) {
+    if (!shift_args_ok(*a)) return RFA_ERR_ARGS;
+    if (band_empty(*a)) e.slopes = nullptr;        // nothing visible: zero gradients with or without a bias
+    else if (!bias_args_ok(*a, norm_args(*a), e)) return RFA_ERR_ARGS;
+    // a bias runs the plain 128-key dK/dV kernel and the 7-GEMM dQ kernel.  rfa_bwd_plan / rfa_bwd_workspace_bytes do not see
+    // the extension, so the BASE arguments must already plan to that: the two can then never disagree with this call
+    else if (a->dkdv_form != RFA_DKDV_128 || a->ds_scratch != nullptr) return RFA_ERR_ARGS;
+  }
   if (a->B == 0 || a->Sq == 0 || a->Sk == 0) return RFA_OK;
   if (!a->dout || !a->q || !a->k || !a->v || !a->lse || !a->delta) return RFA_ERR_NULL;
   if (!a->dq && !a->dq_acc) return RFA_ERR_NULL;
@@ -971,6 +1034,7 @@ int rfa_bwd(const rfa_bwd_args* a, void* stream) {
   p.drop_scale = drop_rescale(a->dropout_p);
   p.drop_seed = a->dropout_seed;
   set_pos_map(p, *a);
+  if (e.slopes != nullptr) set_bias(p, e, a->softmax_scale);
   p.nqblk = (eff_len(a->Sq, a->q_half) + bwd_dq_rows_per_block() - 1) / bwd_dq_rows_per_block();
   const DsChunks chunks = bwd_ds_chunking(a);
   const int Gfull = a->H / a->Hk;

@@ -91,8 +91,11 @@ template <int kD> constexpr int dq_smem() { return 4 * kDqKV * HeadGeo<kD>::kRow
 
 // kD: compiled head dim (128 / 64); kFullD: D == kD (LDS-DMA staging), else zero padded (register staging)
 // kDrop: dropout (the forward's mask, rfa_common.hpp: drop_word) applied to dP; instances without a window only
-template <typename T, int kD, bool kFullD, bool kWin, bool kDrop = false>
+// kBias: ALiBi (rfa.h: rfa_ext_args) — P is recomputed from the biased scores, by the forward's expression (rfa_fwd.hip: the
+// bias enters the UNSCALED scores, slope / softmax_scale); dS needs nothing else.  Instances without a window or dropout only.
+template <typename T, int kD, bool kFullD, bool kWin, bool kDrop = false, bool kBias = false>
 __global__ __launch_bounds__(kDqThreads, 2) void dq_kernel(const BwdParams p) {
+  static_assert(!kBias || (!kWin && !kDrop), "ALiBi: the instances without a window or dropout");
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   lds_t* smem = (lds_t*)smem_raw;
   typedef HeadGeo<kD> Geo;
@@ -244,6 +247,8 @@ __global__ __launch_bounds__(kDqThreads, 2) void dq_kernel(const BwdParams p) {
   const uint32_t drop_key = kDrop ? drop_head_key(p.drop_seed, p.cu_q ? 0u : (uint32_t)b, p.head0 + (uint32_t)h) : 0u;
   const uint32_t drop_i = kDrop ? drop_pos(p.q_pos0 + (uint32_t)(p.cu_q ? qs.row0 : 0), p.q_pstride, p.q_psplit, p.q_pos2, qrow) : 0u;   // per row: a wave's rows can straddle the split
   const uint32_t drop_j0 = kDrop ? p.k_pos0 + (uint32_t)(p.cu_k ? ks.row0 : 0) : 0u;
+  const float bias_slope = kBias ? p.alibi[(int64_t)b * p.alibi_bstride + h] * p.alibi_rscale : 0.f;   // once per workgroup, score units
+  const int bias_row = kBias ? qrow + (lk - lq) + p.alibi_shift - 4 * g : 0;
   const float c = p.scale * kLog2e;
   f32x16 dq[kNB];
 #pragma unroll
@@ -302,6 +307,11 @@ __global__ __launch_bounds__(kDqThreads, 2) void dq_kernel(const BwdParams p) {
             __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
           }
           __builtin_amdgcn_sched_group_barrier(0x008, kAhead, 0);
+        }
+        if (kBias) {
+          const float dist0 = (float)(bias_row - kt0 - 32 * t);
+#pragma unroll
+          for (int r = 0; r < 16; ++r) s[r] = __builtin_fmaf(-bias_slope, __builtin_fabsf(dist0 - (float)crow(r, 0)), s[r]);
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) s[r] = fast_exp2(__builtin_fmaf(s[r], c, -L2));
@@ -427,8 +437,12 @@ template <int kD> constexpr int kv_smem() {        // 129 KiB (65 KiB at kD = 64
 // kMap (kDrop only): the dropout mask's positions go through the position map (include/rfa.h: q_pos_stride ...).  An
 // instance of its own, not a run-time branch like in the forward and dQ kernels: the kDrop instances of head dim 128 sit
 // at 256 registers, and a second copy of the mask loop put them on the scratch.  kDrop without kMap is the code of before.
-template <typename T, int kD, bool kFullD, bool kSpill, bool kWin, bool kWide, bool kDrop = false, bool kBal = false, bool kMap = false>
+// kBias: ALiBi, as in dq_kernel (the plain 128-key instances; the slopes of the G query heads of the K/V head are wave-uniform
+// loads, one per head step)
+template <typename T, int kD, bool kFullD, bool kSpill, bool kWin, bool kWide, bool kDrop = false, bool kBal = false, bool kMap = false,
+          bool kBias = false>
 __global__ __launch_bounds__(kKvThreads, 2) void dkdv_kernel(const BwdParams p) {
+  static_assert(!kBias || (!kSpill && !kWin && !kWide && !kDrop), "ALiBi: the plain 128-key instances");
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   lds_t* smem = (lds_t*)smem_raw;
   static_assert(!kSpill || (kD == 128 && !kWin), "the dS spill path: head dim 128, no window");
@@ -744,6 +758,9 @@ __global__ __launch_bounds__(kKvThreads, 2) void dkdv_kernel(const BwdParams p) 
                                              : p.k_pos0 + (uint32_t)(p.cu_k ? ks.row0 : 0) + (uint32_t)krow;
   const uint32_t drop_i0 = kDrop ? p.q_pos0 + (uint32_t)(p.cu_q ? qs.row0 : 0) : 0u;
   uint32_t drop_g4s = kMap ? (uint32_t)(4 * g) * p.q_pstride : 0u;      // this lane's share of a query row's position
+  // ALiBi: distance of (query sq + 4 g, key krow) = sq + bias_off - (krow - 4 g) — an integer per sub-tile, as the mask's
+  const int bias_off = kBias ? (lk - lq) + p.alibi_shift : 0;
+  const float* bias_slopes = kBias ? p.alibi + (int64_t)b * p.alibi_bstride + h0 : nullptr;
   const float c = p.scale * kLog2e;
   f32x16 dk[kNB], dv[kNB];
 #pragma unroll
@@ -804,7 +821,8 @@ __global__ __launch_bounds__(kKvThreads, 2) void dkdv_kernel(const BwdParams p) 
       {
         // dP - delta = dO V_w^T (+ init; V_w fragments from LDS) then S = Q K_w^T (K_w in registers):
         // 2 kNK MFMAs, LDS operands read kAhead steps ahead
-        constexpr int kAhead = RFA_KV_AHEAD;
+        // (the zero-padded 128-wide ALiBi instances read one pair less ahead: they hold their staging registers on top of a full file)
+        constexpr int kAhead = (kBias && !kFullD && kD == 128) ? RFA_KV_AHEAD - 1 : RFA_KV_AHEAD;
         constexpr int kN = 2 * kNK;
         vec8<T> a[kN], w[kNK];
         auto fa = [&](int i) {
@@ -840,6 +858,16 @@ __global__ __launch_bounds__(kKvThreads, 2) void dkdv_kernel(const BwdParams p) 
 #endif
       }
       if (RFA_KV_PRIO == 3 || RFA_KV_PRIO == 5) __builtin_amdgcn_s_setprio(0);
+      if (kBias) {
+        const float bias_slope = bias_slopes[cg] * p.alibi_rscale;          // (head h0 + cg: wave-uniform)
+        // (the scalar part through an opaque copy: hoisted out of the tile loop, bias_off - mask_kg would be one more
+        //  register live across it — the zero-padded 128-wide instance has none to spare)
+        int dist_s = qs0 + bias_off;
+        asm volatile("" : "+s"(dist_s));
+        const float dist0 = (float)(dist_s - mask_kg);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) s[r] = __builtin_fmaf(-bias_slope, __builtin_fabsf(dist0 + (float)crow(r, 0)), s[r]);
+      }
       // lse is read only now: holding it across GEMM 1 would cost 16 registers
       f32x4 l2v[4];
 #pragma unroll
@@ -915,7 +943,7 @@ __global__ __launch_bounds__(kKvThreads, 2) void dkdv_kernel(const BwdParams p) 
         };
         if (RFA_SPILL_PROBE != 2) spill();
         if (RFA_KV_PRIO == 4 || RFA_KV_PRIO == 5) __builtin_amdgcn_s_setprio(1);
-        constexpr int kAhead = RFA_KV_AHEAD2;
+        constexpr int kAhead = (kBias && !kFullD && kD == 128) ? RFA_KV_AHEAD2 - 1 : RFA_KV_AHEAD2;
         constexpr int kN2 = 4 * kNB;                   // [ks2][which: 0 = dO^T (dV), 1 = Q^T (dK)][dblk]
         vec8<T> a[kN2];
         auto frag = [&](int i) {
@@ -1156,13 +1184,13 @@ __global__ __launch_bounds__(kKvThreads, 2) void dkdv_kernel(const BwdParams p) 
   }   // segment loop
 }
 
-template <typename T, int kD, bool kFullD, bool kWin, bool kDrop = false>
+template <typename T, int kD, bool kFullD, bool kWin, bool kDrop = false, bool kBias = false>
 static int launch_dq_t(const BwdParams& p, hipStream_t stream) {
   static std::atomic<unsigned long long> attr_done{0};
-  if (int rc = opt_in_dynamic_lds((const void*)dq_kernel<T, kD, kFullD, kWin, kDrop>, dq_smem<kD>(), attr_done)) return rc;
+  if (int rc = opt_in_dynamic_lds((const void*)dq_kernel<T, kD, kFullD, kWin, kDrop, kBias>, dq_smem<kD>(), attr_done)) return rc;
   const int64_t nblocks = (int64_t)p.nqblk * p.H * p.B;
   if (nblocks <= 0) return 0;
-  hipLaunchKernelGGL((dq_kernel<T, kD, kFullD, kWin, kDrop>), dim3((unsigned)nblocks), dim3(kDqThreads), dq_smem<kD>(), stream, p);
+  hipLaunchKernelGGL((dq_kernel<T, kD, kFullD, kWin, kDrop, kBias>), dim3((unsigned)nblocks), dim3(kDqThreads), dq_smem<kD>(), stream, p);
   return hipGetLastError() == hipSuccess ? kLaunchOk : kLaunchFailed;
 }
 
@@ -1171,10 +1199,11 @@ __global__ void zero_words_kernel(unsigned* w, int n) {
   if (i < n) w[i] = 0u;
 }
 
-template <typename T, int kD, bool kFullD, bool kSpill, bool kWin, bool kWide = false, bool kDrop = false, bool kBal = false, bool kMap = false>
+template <typename T, int kD, bool kFullD, bool kSpill, bool kWin, bool kWide = false, bool kDrop = false, bool kBal = false, bool kMap = false,
+          bool kBias = false>
 static int launch_dkdv_t(const BwdParams& p, hipStream_t stream) {
   static std::atomic<unsigned long long> attr_done{0};
-  if (int rc = opt_in_dynamic_lds((const void*)dkdv_kernel<T, kD, kFullD, kSpill, kWin, kWide, kDrop, kBal, kMap>, kv_smem<kD>(), attr_done)) return rc;
+  if (int rc = opt_in_dynamic_lds((const void*)dkdv_kernel<T, kD, kFullD, kSpill, kWin, kWide, kDrop, kBal, kMap, kBias>, kv_smem<kD>(), attr_done)) return rc;
   // one workgroup per (key block, K/V head) [x tile-range split of the 256-key form]
   const int64_t nblocks = (int64_t)p.nkblk * p.Hk * p.B * ((kWide && !kBal) ? p.nsplit : 1);
   if (nblocks <= 0) return 0;
@@ -1186,7 +1215,7 @@ static int launch_dkdv_t(const BwdParams& p, hipStream_t stream) {
     hipLaunchKernelGGL(zero_words_kernel, dim3((unsigned)((nflags + 255) / 256)), dim3(256), 0, stream, p.pair_flags, nflags);
     if (hipGetLastError() != hipSuccess) return kLaunchFailed;
   }
-  hipLaunchKernelGGL((dkdv_kernel<T, kD, kFullD, kSpill, kWin, kWide, kDrop, kBal, kMap>), dim3((unsigned)nblocks), dim3(kKvThreads), kv_smem<kD>(), stream, p);
+  hipLaunchKernelGGL((dkdv_kernel<T, kD, kFullD, kSpill, kWin, kWide, kDrop, kBal, kMap, kBias>), dim3((unsigned)nblocks), dim3(kKvThreads), kv_smem<kD>(), stream, p);
   return hipGetLastError() == hipSuccess ? kLaunchOk : kLaunchFailed;
 }
 
@@ -1201,8 +1230,25 @@ static int launch_dq_d(const BwdParams& p, hipStream_t stream) {
   if (p.D == 64) return launch_dq_t<T, 64, true, kWin, kDrop>(p, stream);
   return launch_dq_t<T, 64, false, kWin, kDrop>(p, stream);
 }
+// ALiBi (rfa_api.cpp: head dim <= 128, no window, no dropout, the 128-key dK/dV form without the dS hand-off): 128 and 64 full,
+// every other head dim through the zero-padded 128- / 64-wide layouts
+template <typename T>
+static int launch_dq_bias(const BwdParams& p, hipStream_t stream) {
+  if (p.D == 128) return launch_dq_t<T, 128, true, false, false, true>(p, stream);
+  if (p.D > 64) return launch_dq_t<T, 128, false, false, false, true>(p, stream);
+  if (p.D == 64) return launch_dq_t<T, 64, true, false, false, true>(p, stream);
+  return launch_dq_t<T, 64, false, false, false, true>(p, stream);
+}
+template <typename T>
+static int launch_dkdv_bias(const BwdParams& p, hipStream_t stream) {
+  if (p.D == 128) return launch_dkdv_t<T, 128, true, false, false, false, false, false, false, true>(p, stream);
+  if (p.D > 64) return launch_dkdv_t<T, 128, false, false, false, false, false, false, false, true>(p, stream);
+  if (p.D == 64) return launch_dkdv_t<T, 64, true, false, false, false, false, false, false, true>(p, stream);
+  return launch_dkdv_t<T, 64, false, false, false, false, false, false, false, true>(p, stream);
+}
 int launch_bwd_dq(const BwdParams& p, int dtype, hipStream_t stream) {
   if (p.D > 128) return launch_bwd_dq_big(p, dtype, stream);            // rfa_bigd.hip
+  if (p.alibi != nullptr) return dtype == 0 ? launch_dq_bias<bf16_t>(p, stream) : launch_dq_bias<f16_t>(p, stream);
   if (p.drop_keep < 256) return dtype == 0 ? launch_dq_d<bf16_t, false, true>(p, stream) : launch_dq_d<f16_t, false, true>(p, stream);
   if (windowed(p.causal, p.wl, p.wr)) return dtype == 0 ? launch_dq_d<bf16_t, true, false>(p, stream) : launch_dq_d<f16_t, true, false>(p, stream);
   return dtype == 0 ? launch_dq_d<bf16_t, false, false>(p, stream) : launch_dq_d<f16_t, false, false>(p, stream);
@@ -1226,6 +1272,7 @@ static int launch_dkdv_d(const BwdParams& p, hipStream_t stream) {
 }
 int launch_bwd_dkdv(const BwdParams& p, int dtype, hipStream_t stream) {
   if (p.D > 128) return launch_bwd_dkdv_big(p, dtype, stream);          // rfa_bigd.hip (rfa_api.cpp: no spill, no 256-key form)
+  if (p.alibi != nullptr) return dtype == 0 ? launch_dkdv_bias<bf16_t>(p, stream) : launch_dkdv_bias<f16_t>(p, stream);
   const bool win = windowed(p.causal, p.wl, p.wr);
   if (p.drop_keep < 256 && p.drop_mapped)         // ... with a position map: instances of their own (dkdv_kernel: kMap)
     return dtype == 0 ? launch_dkdv_d<bf16_t, false, true, true>(p, stream) : launch_dkdv_d<f16_t, false, true, true>(p, stream);

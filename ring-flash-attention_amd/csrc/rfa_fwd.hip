@@ -88,8 +88,12 @@ template <int kD> constexpr int fwd_smem() { return 2 * kFwdStages * kFwdKV * He
 // kD: compiled head dim (128 or 64: half the MFMAs, half the LDS bytes per tile); kFullD: D == kD (LDS-DMA
 // staging, no conditional loads), otherwise D < kD is zero padded through the register staging path
 // kDrop: dropout on the probabilities that enter P·V (instances without a window only)
-template <typename T, int kD, bool kFullD, bool kWin, bool kDrop = false, int kW = kFwdWavesMax>
+// kBias: ALiBi (rfa.h: rfa_ext_args) — score -= slope * |i + (len_k - len_q) + alibi_shift - j|, added to the UNSCALED scores in
+// front of the mask and the row max (slope / softmax_scale: the max, the deferred rescale and lse = m scale + log l then
+// see the biased scores and need no change).  Instances without a window or dropout only.
+template <typename T, int kD, bool kFullD, bool kWin, bool kDrop = false, int kW = kFwdWavesMax, bool kBias = false>
 __global__ __launch_bounds__(kW * 64, 2) void fwd_kernel(const FwdParams p) {
+  static_assert(!kBias || (!kWin && !kDrop), "ALiBi: the instances without a window or dropout");
   constexpr int kFwdWaves = kW, kFwdThreads = kW * 64, kFwdQRows = kW * 32;   // (query rows per workgroup)
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   lds_t* smem = (lds_t*)smem_raw;
@@ -271,6 +275,10 @@ __global__ __launch_bounds__(kW * 64, 2) void fwd_kernel(const FwdParams p) {
   const uint32_t drop_key = kDrop ? drop_head_key(p.drop_seed, p.cu_q ? 0u : (uint32_t)b, p.head0 + (uint32_t)h) : 0u;
   const uint32_t drop_i = kDrop ? drop_pos(p.q_pos0 + (uint32_t)(p.cu_q ? qs.row0 : 0), p.q_pstride, p.q_psplit, p.q_pos2, qrow) : 0u;   // per row: a wave's rows can straddle the split
   const uint32_t drop_j0 = kDrop ? p.k_pos0 + (uint32_t)(p.cu_k ? ks.row0 : 0) : 0u;
+  // ALiBi: the slope of this workgroup's (batch, head), read once (wave-uniform), in score units; the row's distance to key 0
+  // as an integer — only the per-element part below is float (exact up to 2^24 rows, rfa.h)
+  const float bias_slope = kBias ? p.alibi[(int64_t)b * p.alibi_bstride + h] * p.alibi_rscale : 0.f;
+  const int bias_row = kBias ? qrow + (lk - lq) + p.alibi_shift - 4 * g : 0;
   const float c = p.scale * kLog2e;
   float m = -INFINITY;
   float mthr = -INFINITY, mc_run = 0.f;      // RFA_FWD_LEAN: rescale threshold m + DEFER / c, and m c (0 while m is -inf)
@@ -339,6 +347,16 @@ __global__ __launch_bounds__(kW * 64, 2) void fwd_kernel(const FwdParams p) {
           __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
         }
         __builtin_amdgcn_sched_group_barrier(0x008, kAhead, 0);
+      }
+      if (kBias) {
+        // key = kt0 + 32 t + crow(r, 0) + 4 g: one integer subtract and convert per sub-tile, then per score one subtract of
+        // a constant and one FMA with |x| as a source modifier
+#pragma unroll
+        for (int t = 0; t < kFwdSub; ++t) {
+          const float dist0 = (float)(bias_row - kt0 - 32 * t);
+#pragma unroll
+          for (int r = 0; r < 16; ++r) s[t][r] = __builtin_fmaf(-bias_slope, __builtin_fabsf(dist0 - (float)crow(r, 0)), s[t][r]);
+        }
       }
       // ---------------- mask ----------------
       const bool need_mask = (kt0 + kFwdKV > lk) || (hi && kt0 + kFwdKV - 1 > qw0 + off + wr) ||
@@ -903,13 +921,13 @@ static int launch_fwd_persist(const FwdParams& p, hipStream_t stream) {
   return hipGetLastError() == hipSuccess ? kLaunchOk : kLaunchFailed;
 }
 
-template <typename T, int kD, bool kFullD, bool kWin, bool kDrop = false, int kW = kFwdWavesMax>
+template <typename T, int kD, bool kFullD, bool kWin, bool kDrop = false, int kW = kFwdWavesMax, bool kBias = false>
 static int launch_fwd_w(const FwdParams& p, hipStream_t stream) {
   static std::atomic<unsigned long long> attr_done{0};
-  if (int rc = opt_in_dynamic_lds((const void*)fwd_kernel<T, kD, kFullD, kWin, kDrop, kW>, fwd_smem<kD>(), attr_done)) return rc;
+  if (int rc = opt_in_dynamic_lds((const void*)fwd_kernel<T, kD, kFullD, kWin, kDrop, kW, kBias>, fwd_smem<kD>(), attr_done)) return rc;
   const int64_t nblocks = (int64_t)p.nqblk * p.H * p.B * (p.kv_nsplit > 1 ? p.kv_nsplit : 1);
   if (nblocks <= 0) return 0;
-  hipLaunchKernelGGL((fwd_kernel<T, kD, kFullD, kWin, kDrop, kW>), dim3((unsigned)nblocks), dim3(kW * 64), fwd_smem<kD>(), stream, p);
+  hipLaunchKernelGGL((fwd_kernel<T, kD, kFullD, kWin, kDrop, kW, kBias>), dim3((unsigned)nblocks), dim3(kW * 64), fwd_smem<kD>(), stream, p);
   return hipGetLastError() == hipSuccess ? kLaunchOk : kLaunchFailed;
 }
 template <typename T, int kD, bool kFullD, bool kWin, bool kDrop = false>
@@ -933,7 +951,18 @@ static int launch_fwd_d(const FwdParams& p, hipStream_t stream) {
   return launch_fwd_t<T, 64, false, kWin, kDrop>(p, stream);
 }
 
+// ALiBi (rfa_api.cpp: head dim <= 128, no window, no dropout, the 256-row form): 128 and 64 full, every other head dim through
+// the zero-padded 128- / 64-wide layouts, as windowed calls
+template <typename T>
+static int launch_fwd_bias(const FwdParams& p, hipStream_t stream) {
+  if (p.D == 128) return launch_fwd_w<T, 128, true, false, false, kFwdWavesMax, true>(p, stream);
+  if (p.D > 64) return launch_fwd_w<T, 128, false, false, false, kFwdWavesMax, true>(p, stream);
+  if (p.D == 64) return launch_fwd_w<T, 64, true, false, false, kFwdWavesMax, true>(p, stream);
+  return launch_fwd_w<T, 64, false, false, false, kFwdWavesMax, true>(p, stream);
+}
+
 int launch_fwd(const FwdParams& p, int dtype, hipStream_t stream) {
+  if (p.alibi != nullptr) return dtype == 0 ? launch_fwd_bias<bf16_t>(p, stream) : launch_fwd_bias<f16_t>(p, stream);
   if (p.persist_grid > 0)                                      // rfa_api.cpp: head dim 128, dense, plain outputs, 256-row form, no shares
     return dtype == 0 ? launch_fwd_persist<bf16_t>(p, stream) : launch_fwd_persist<f16_t>(p, stream);
   if (p.drop_keep < 256)                                       // (rfa_api.cpp rejects dropout together with a window)

@@ -72,6 +72,13 @@ struct FwdParams {
   int q_psplit, k_psplit;
   unsigned q_pos2, k_pos2;
   int drop_mapped;
+  // ALiBi (rfa.h: rfa_ext_args; the kBias instances only): alibi = nullptr is off.  The slope of (batch b, head h) is
+  // alibi[b * alibi_bstride + h]; the kernels take it in SCORE units (slope * alibi_rscale, alibi_rscale = 1 / softmax_scale,
+  // prepared by the API layer) because their row max runs on unscaled scores; alibi_shift as rfa.h (fits 32 bits: API layer)
+  const float* alibi;
+  int64_t alibi_bstride;
+  int alibi_shift;
+  float alibi_rscale;
 };
 
 struct PreParams {
@@ -129,6 +136,13 @@ struct BwdParams {
   int q_psplit, k_psplit;
   unsigned q_pos2, k_pos2;
   int drop_mapped;
+  // ALiBi (rfa.h: rfa_ext_args; the kBias instances only): alibi = nullptr is off.  The slope of (batch b, head h) is
+  // alibi[b * alibi_bstride + h]; the kernels take it in SCORE units (slope * alibi_rscale, alibi_rscale = 1 / softmax_scale,
+  // prepared by the API layer) because their row max runs on unscaled scores; alibi_shift as rfa.h (fits 32 bits: API layer)
+  const float* alibi;
+  int64_t alibi_bstride;
+  int alibi_shift;
+  float alibi_rscale;
 };
 
 // dst[b, row, hk, :] (=|+=) sum_g src[b, row, hk*G+g, :]

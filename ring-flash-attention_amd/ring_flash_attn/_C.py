@@ -106,6 +106,19 @@ class BwdArgs(C.Structure):
     ]
 
 
+class ExtArgs(C.Structure):
+    """rfa_ext_args: per-call features added after the ABI 8 structs were frozen (ALiBi); struct_bytes is filled in here"""
+    _fields_ = [
+        ("struct_bytes", C.c_uint32), ("reserved", C.c_uint32),
+        ("alibi_slopes", C.c_void_p), ("alibi_batch_stride", C.c_int64), ("alibi_shift", C.c_int64),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if not self.struct_bytes:
+            self.struct_bytes = C.sizeof(ExtArgs)
+
+
 class MergeArgs(C.Structure):
     _fields_ = [
         ("out_acc", C.c_void_p), ("out_acc_st", Strides),
@@ -136,6 +149,8 @@ SYMBOLS = {
     "rfa_build_id": (C.c_char_p, []),
     "rfa_strerror": (C.c_char_p, [C.c_int]),
     "rfa_fwd": (C.c_int, [C.POINTER(FwdArgs), C.c_void_p]),
+    "rfa_fwd_ex": (C.c_int, [C.POINTER(FwdArgs), C.POINTER(ExtArgs), C.c_void_p]),
+    "rfa_ext_args_bytes": (C.c_int64, []),
     "rfa_fwd_workspace_bytes": (C.c_int64, [C.POINTER(FwdArgs), C.POINTER(C.c_int32)]),
     "rfa_bwd_preprocess": (C.c_int, [C.POINTER(BwdPreArgs), C.c_void_p]),
     "rfa_bwd_workspace_bytes": (C.c_int64, [C.POINTER(BwdArgs)]),
@@ -145,6 +160,7 @@ SYMBOLS = {
                                     C.POINTER(C.c_int64)]),
     "rfa_bwd_plan": (C.c_int, [C.POINTER(BwdArgs), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "rfa_bwd": (C.c_int, [C.POINTER(BwdArgs), C.c_void_p]),
+    "rfa_bwd_ex": (C.c_int, [C.POINTER(BwdArgs), C.POINTER(ExtArgs), C.c_void_p]),
     "rfa_merge": (C.c_int, [C.POINTER(MergeArgs), C.c_void_p]),
     "rfa_sum_slots": (C.c_int, [C.POINTER(SumSlotsArgs), C.c_void_p]),
     "rfa_cast": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
@@ -176,6 +192,11 @@ def load():
     # same version number and would read every later field from the wrong place
     if not hasattr(lib, "rfa_abi_revision"):
         raise RuntimeError(f"ring_flash_attn: librfa_hip.so has no rfa_abi_revision (binding revision {RFA_ABI_REVISION}); rebuild")
+    # the extension entry points arrived without a version or revision bump (no existing struct changed): a library from
+    # before them reports 8 / 1 as well
+    for name in ("rfa_fwd_ex", "rfa_bwd_ex", "rfa_ext_args_bytes"):
+        if not hasattr(lib, name):
+            raise RuntimeError(f"ring_flash_attn: librfa_hip.so has no {name} (the extension entry points); rebuild")
     for name, (res, args) in SYMBOLS.items():
         fn = getattr(lib, name)  # AttributeError if the .so is stale
         fn.restype = res
@@ -186,6 +207,9 @@ def load():
     rev = lib.rfa_abi_revision()
     if rev != RFA_ABI_REVISION:
         raise RuntimeError(f"ring_flash_attn: librfa_hip.so ABI {ver} revision {rev} != binding revision {RFA_ABI_REVISION}; rebuild")
+    ext = lib.rfa_ext_args_bytes()
+    if ext != C.sizeof(ExtArgs):
+        raise RuntimeError(f"ring_flash_attn: librfa_hip.so rfa_ext_args is {ext} bytes, the binding's {C.sizeof(ExtArgs)}; rebuild")
     _lib = lib
     return lib
 

@@ -5,8 +5,9 @@ The generated callables keep the exact keyword surface of the reference package
 (/root/reference/ring_flash_attn/__init__.py:1-35 and SURVEY.md Appendix A):
     dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1), alibi_slopes=None,
     deterministic=False, return_attn_probs=False, group=None
-with the reference's semantics: softmax_scale None -> head_dim ** -0.5; alibi_slopes must be
-None; dropout_p works on single-rank groups, on the llama3 path and over several ranks with the dense ring, zigzag and
+with the reference's semantics: softmax_scale None -> head_dim ** -0.5; alibi_slopes (flash_attn's: fp32, (H,) or
+(B, H)) works on single-rank groups with every function and over several ranks with the dense ring and zigzag schedules and
+with causal llama3 (not together with a window or dropout, head dims <= 128); dropout_p works on single-rank groups, on the llama3 path and over several ranks with the dense ring, zigzag and
 stripe schedules (the reference declares dropout over a ring unsupported, README.md:158-159; the `*_varlen` ring families
 still raise here); window_size works with every schedule; the two together raise;
 return_attn_probs=True -> (out, softmax_lse, None); `group=None` is the default process group;
@@ -14,7 +15,7 @@ inputs are the caller's LOCAL shard.
 """
 import torch
 
-from ._common import _prep_qkv, _as_cu, draw_dropout_seed
+from ._common import _prep_qkv, _as_cu, check_alibi_slopes, draw_dropout_seed, require_alibi
 from .utils import audit_verify
 
 
@@ -59,7 +60,8 @@ def _compilable(fn, lower, multi=None):
             # `group` may be passed positionally: resolve it the way the call itself would
             bound = sig.bind(*args, **kwargs).arguments
             # (dropout draws a host-side seed per call: such calls run eagerly behind a graph break)
-            if not bound.get("dropout_p", 0.0):
+            # (a bias runs the eager autograd path too: the registered operators have no biased form)
+            if not bound.get("dropout_p", 0.0) and bound.get("alibi_slopes", None) is None:
                 if _single_rank(bound.get("group", None)):
                     return lower(*args, **kwargs)
                 # several ranks: the whole schedule as one registered operator (_ops.py: rfa::sched_fwd / sched_bwd),
@@ -71,7 +73,7 @@ def _compilable(fn, lower, multi=None):
     return public
 
 
-def _check_unsupported(dropout_p, window_size, alibi_slopes, windows_ok=False, dropout_ok=None):
+def _check_unsupported(dropout_p, window_size, alibi_slopes, windows_ok=False, dropout_ok=None, alibi_ok=False):
     """Sliding windows and dropout are implemented in the kernels (flash_attn semantics; dropout: the counter-based
     mask of include/rfa.h).  Dropout is usable wherever ONE kernel call sees all the keys a query may attend to: every
     function on a single-rank group, and llama3_flash_attn_varlen_func on any group (it gathers K/V) — the coverage the
@@ -87,8 +89,14 @@ def _check_unsupported(dropout_p, window_size, alibi_slopes, windows_ok=False, d
     packed sequence's own length (`mask_shift_lens`), the stripe schedule — token i of rank r is global token i W + r —
     as a dense shifted band in local rows.  These schedules pass windows_ok=True for such calls; windows_ok=False (the
     `torch.compile` whole-schedule operator, which has no windowed form) still raises.
-    Dropout together with a window is not available anywhere."""
-    assert alibi_slopes is None
+    Dropout together with a window is not available anywhere.
+    ALiBi (alibi_slopes) is implemented in the kernels as well (include/rfa.h: rfa_ext_args).  The bias is a function of
+    the GLOBAL distance i - j, so it is usable wherever ONE call sees whole sequences (every function on a single-rank group)
+    and wherever the schedule tells every block call where it sits (`alibi_shift`): the dense ring (the block at signed rank
+    distance t: t S), the zigzag schedule (per chunk pair, (cq - ck) C) and causal llama3 (bottom-right alignment against
+    the truncated cu_seqlens_k IS the global distance); those pass alibi_ok=True.  Everything else — stripe, the *_varlen
+    ring families and zigzag_llama3 over several ranks, non-causal llama3 over several ranks, the torch.compile operators
+    — raises, as does a bias together with a window or dropout."""
     if dropout_ok is None:
         dropout_ok = windows_ok
     drop = bool(dropout_p) and dropout_p > 0
@@ -105,6 +113,29 @@ def _check_unsupported(dropout_p, window_size, alibi_slopes, windows_ok=False, d
                                   "by this entry (the whole-schedule operator has no windowed form)")
     if drop and has_window(window_size):
         raise NotImplementedError("ring_flash_attn: dropout together with a sliding window is not supported")
+    if alibi_slopes is not None:
+        if not alibi_ok:
+            raise NotImplementedError("ring_flash_attn: alibi_slopes over a multi-rank group is served by the eager dense "
+                                      "ring and zigzag functions and by causal llama3_flash_attn_varlen_func, not by this "
+                                      "entry (stripe, the *_varlen ring functions, zigzag_llama3, non-causal llama3 and "
+                                      "torch.compile's operators have no biased form); use one of those or a single-rank group")
+        if drop or has_window(window_size):
+            raise NotImplementedError("ring_flash_attn: alibi_slopes together with dropout or a sliding window is not supported")
+
+
+def checked_alibi(alibi_slopes, q, batch, what):
+    """alibi_slopes validated once per public call (ValueError: _common.check_alibi_slopes) and the refusals that need the
+    tensors: head dims above 128 and a backend that does not serve a bias — NotImplementedError, before anything is
+    exchanged, on every rank alike.  None stays None."""
+    if alibi_slopes is None:
+        return None
+    slopes = check_alibi_slopes(alibi_slopes, q, batch)
+    if q.shape[-1] > 128:
+        raise NotImplementedError(f"ring_flash_attn: {what} with alibi_slopes serves head dims up to 128, not {q.shape[-1]}")
+    from .backend import get_backend
+
+    require_alibi(get_backend(), what)
+    return slopes
 
 
 def has_window(window_size) -> bool:
@@ -173,12 +204,13 @@ def _split_kept(ctx, more):
     return tensors_lead, ({"kept": tuple(kept)} if kept else {})
 
 
-def make_autograd_function(name, forward_impl, backward_impl, n_lead, window_ring=False, dropout_ring=False):
+def make_autograd_function(name, forward_impl, backward_impl, n_lead, window_ring=False, dropout_ring=False,
+                           alibi_ring=False):
     """n_lead: number of non-tensor positional arguments between (q,k,v) and the common tail
     (0 for the batch API, 2 = (cu_seqlens, max_seqlen) for varlen).  window_ring: the schedule serves a sliding window
     on a multi-rank group (every ring family does: dense and varlen ring and zigzag, stripe).  dropout_ring: it serves
     dropout there (the dense ring, zigzag and stripe schedules: every block call is told the global positions of its
-    rows, _common.dropout_arg)."""
+    rows, _common.dropout_arg).  alibi_ring: it serves alibi_slopes there (the dense ring and zigzag schedules)."""
 
     class _Fn(torch.autograd.Function):
         @staticmethod
@@ -189,7 +221,9 @@ def make_autograd_function(name, forward_impl, backward_impl, n_lead, window_rin
             if softmax_scale is None:
                 softmax_scale = q.shape[-1] ** (-0.5)
             single = window_ok_for(group)
-            _check_unsupported(dropout_p, window_size, alibi_slopes, windows_ok=single or window_ring, dropout_ok=single or dropout_ring)
+            _check_unsupported(dropout_p, window_size, alibi_slopes, windows_ok=single or window_ring, dropout_ok=single or dropout_ring,
+                               alibi_ok=single or alibi_ring)
+            alibi_slopes = checked_alibi(alibi_slopes, q, (len(lead[0]) - 1) if n_lead else q.shape[0], name)
             q, k, v = _prep_qkv(q, k, v, group)
             tensors_lead = ()
             if n_lead:
@@ -214,6 +248,7 @@ def make_autograd_function(name, forward_impl, backward_impl, n_lead, window_rin
             ctx.deterministic = deterministic
             ctx.group = group
             ctx.window_size = tuple(window_size)
+            ctx.alibi_slopes = alibi_slopes             # (no gradient, as in flash_attn: held, not saved for backward)
             return out if not return_softmax else (out, softmax_lse, None)
 
         @staticmethod
@@ -225,7 +260,7 @@ def make_autograd_function(name, forward_impl, backward_impl, n_lead, window_rin
             dq, dk, dv = backward_impl(
                 ctx.group, dout, q, k, v, out, softmax_lse, *tensors_lead, *ctx.lead_rest,
                 softmax_scale=ctx.softmax_scale, dropout_p=ctx.dropout[0], causal=ctx.causal,
-                window_size=ctx.window_size, alibi_slopes=None, deterministic=ctx.deterministic, **extra,
+                window_size=ctx.window_size, alibi_slopes=ctx.alibi_slopes, deterministic=ctx.deterministic, **extra,
             )
             _release_kept(ctx)
             audit_verify(ctx.group, f"{name} backward")
@@ -236,7 +271,7 @@ def make_autograd_function(name, forward_impl, backward_impl, n_lead, window_rin
 
 
 def make_packed_function(name, base_fn, forward_impl, backward_impl, n_lead, pack_dim, n_packed, packed_travel=False,
-                         window_ring=False, dropout_ring=False):
+                         window_ring=False, dropout_ring=False, alibi_ring=False):
     """autograd Function for the packed entry points (`kv` = 2 tensors, `qkv` = 3 tensors stacked on
     `pack_dim`).  Same math as `base_fn`; the only difference is where the gradients land: ONE packed
     buffer whose slices are handed to the schedule as output views (`out_grads`), instead of letting
@@ -257,7 +292,9 @@ def make_packed_function(name, base_fn, forward_impl, backward_impl, n_lead, pac
             if softmax_scale is None:
                 softmax_scale = q.shape[-1] ** (-0.5)
             single = window_ok_for(group)
-            _check_unsupported(dropout_p, window_size, alibi_slopes, windows_ok=single or window_ring, dropout_ok=single or dropout_ring)
+            _check_unsupported(dropout_p, window_size, alibi_slopes, windows_ok=single or window_ring, dropout_ok=single or dropout_ring,
+                               alibi_ok=single or alibi_ring)
+            alibi_slopes = checked_alibi(alibi_slopes, q, (len(lead[0]) - 1) if n_lead else q.shape[0], name)
             q, k, v = _prep_qkv(q, k, v, group, packed_travel=packed_travel and n_packed == 2)
             tensors_lead = ()
             if n_lead:
@@ -282,6 +319,7 @@ def make_packed_function(name, base_fn, forward_impl, backward_impl, n_lead, pac
             ctx.deterministic = deterministic
             ctx.group = group
             ctx.window_size = tuple(window_size)
+            ctx.alibi_slopes = alibi_slopes             # (no gradient, as in flash_attn: held, not saved for backward)
             ctx.packed_meta = (packed.shape, packed.dtype, packed.device)
             return out if not return_softmax else (out, softmax_lse, None)
 
@@ -301,7 +339,7 @@ def make_packed_function(name, base_fn, forward_impl, backward_impl, n_lead, pac
             dq, dk, dv = backward_impl(
                 ctx.group, dout, q, k, v, out, softmax_lse, *tensors_lead, *ctx.lead_rest,
                 softmax_scale=ctx.softmax_scale, dropout_p=ctx.dropout[0], causal=ctx.causal,
-                window_size=ctx.window_size, alibi_slopes=None, deterministic=ctx.deterministic,
+                window_size=ctx.window_size, alibi_slopes=ctx.alibi_slopes, deterministic=ctx.deterministic,
                 out_grads=out_grads, **extra,
             )
             got = (dq, dk, dv)[3 - n_packed:]
@@ -326,16 +364,17 @@ def _grad_buffers(out_grads, q, k, v):
 
 
 def make_dense_api(fn, prefix, forward_impl=None, backward_impl=None, packed_travel=False, window_ring=False,
-                   dropout_ring=False):
+                   dropout_ring=False, alibi_ring=False):
     """(B,S,H,D) API: returns (func, kvpacked_func, qkvpacked_func).  packed_travel: the schedule exchanges a
     packed `kv` as one buffer and writes dK/dV straight into the packed gradient (`out_grads`) at any world size.
-    window_ring, dropout_ring: as in make_autograd_function (pass the same values to both)."""
+    window_ring, dropout_ring, alibi_ring: as in make_autograd_function (pass the same values to both)."""
     kv_fn = qkv_fn = None
     if forward_impl is not None:
         kv_fn = make_packed_function(fn.__name__ + "KVPacked", fn, forward_impl, backward_impl, 0, 2, 2,
-                                     packed_travel=packed_travel, window_ring=window_ring, dropout_ring=dropout_ring)
+                                     packed_travel=packed_travel, window_ring=window_ring, dropout_ring=dropout_ring,
+                                     alibi_ring=alibi_ring)
         qkv_fn = make_packed_function(fn.__name__ + "QKVPacked", fn, forward_impl, backward_impl, 0, 2, 3,
-                                      window_ring=window_ring, dropout_ring=dropout_ring)
+                                      window_ring=window_ring, dropout_ring=dropout_ring, alibi_ring=alibi_ring)
 
     def func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
              alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None):

@@ -73,6 +73,41 @@ def require_mask_shift_lens(be, what):
                                   "would apply the window per block)")
 
 
+def require_alibi(be, what):
+    """A call with alibi_slopes needs a backend that adds the bias inside its kernels (`alibi=` of fwd / bwd, include/rfa.h:
+    rfa_ext_args; HipBackend.serves_alibi).  One that cannot would drop the bias silently: refuse before anything is
+    exchanged, on every rank alike."""
+    if not getattr(be, "serves_alibi", False):
+        raise NotImplementedError(f"ring_flash_attn: {what} with alibi_slopes needs a backend that serves `alibi`; "
+                                  f"{getattr(be, 'name', type(be).__name__)!r} does not (it would ignore the bias)")
+
+
+def check_alibi_slopes(alibi_slopes, q, batch):
+    """alibi_slopes as the kernels take them — fp32, on q's device, (H,) or (batch, H) with H = q's heads, innermost stride
+    1 — or None; ValueError otherwise.  Validated once per public call (flash_attn's contract: alibi_slopes is fp32)."""
+    if alibi_slopes is None:
+        return None
+    import torch
+    H = q.shape[-2]
+    if (not torch.is_tensor(alibi_slopes) or alibi_slopes.dtype != torch.float32 or alibi_slopes.device != q.device
+            or tuple(alibi_slopes.shape) not in ((H,), (batch, H))):
+        raise ValueError(f"ring_flash_attn: alibi_slopes must be a float32 tensor of shape ({H},) or ({batch}, {H}) on "
+                         f"{q.device}; got {getattr(alibi_slopes, 'dtype', type(alibi_slopes))} "
+                         f"{tuple(getattr(alibi_slopes, 'shape', ()))} on {getattr(alibi_slopes, 'device', None)}")
+    return alibi_slopes.detach().contiguous()
+
+
+def alibi_kw(alibi_slopes, shift=0, heads=None):
+    """the `alibi=` keyword of a block call whose q row 0 sits `shift` rows behind its k row 0 in the full sequence
+    (include/rfa.h: alibi_shift), for the query heads `heads` (a slice: a head group's slopes are a view); nothing without
+    slopes, so that backends that predate the keyword keep serving unbiased calls"""
+    if alibi_slopes is None:
+        return {}
+    if heads is not None:
+        alibi_slopes = alibi_slopes[..., heads]
+    return {"alibi": (alibi_slopes, int(shift))}
+
+
 def _as_cu(cu_seqlens, device):
     """cu_seqlens as an int32 tensor on the compute device (the kernels read it on device)."""
     import torch

@@ -57,6 +57,7 @@ class HipBackend:
     name = "hip"
     serves_mask_shift = True        # fwd / bwd take `mask_shift` (include/rfa.h, ABI 7): what a windowed multi-rank schedule needs
     serves_mask_shift_lens = True   # ... and `mask_shift_lens` (ABI 8), the per-sequence shift the packed (varlen) ring schedules need
+    serves_alibi = True             # fwd / bwd take `alibi=(slopes, shift)` (include/rfa.h: rfa_ext_args)
     serves_dropout_positions = True  # `dropout=` takes the position maps (q_map, k_map): what dropout over a dense ring, zigzag or stripe schedule needs
 
     def __init__(self):
@@ -85,7 +86,7 @@ class HipBackend:
     def fwd(self, q, k, v, *, softmax_scale, causal, cu_seqlens_q=None, cu_seqlens_k=None,
             max_seqlen_q=None, max_seqlen_k=None, q_half=HALF_FULL, k_half=HALF_FULL,
             out=None, lse=None, out_acc=None, lse_acc=None, acc_init=False, window=(-1, -1), dropout=None,
-            mask_shift=0, mask_shift_lens=0):
+            mask_shift=0, mask_shift_lens=0, alibi=None):
         """Block attention.  Plain mode fills (out, lse); accumulate mode merges into the fp32
         (out_acc, lse_acc) pair (fused update_out_and_lse).  Dense: q (B,Sq,H,D); varlen: (T,H,D).
         dropout: (p, seed, q_pos_offset, k_pos_offset, head_offset), the same plus the position maps (q_map, k_map) —
@@ -93,7 +94,9 @@ class HipBackend:
         mask_shift: where the block sits in a longer sequence (include/rfa.h; dense input) — for blocks of equal length
         the global position of q row 0 minus that of k row 0; moves the causal diagonal and the window alike.
         mask_shift_lens: the same in units of every sequence's own key length (include/rfa.h, ABI 8): the shift of packed
-        (cu_seqlens) input; dense input folds it into mask_shift."""
+        (cu_seqlens) input; dense input folds it into mask_shift.
+        alibi: (slopes, shift) or None — fp32 slopes (H,) or (B, H) on q's device and the block's alibi_shift
+        (include/rfa.h: rfa_ext_args; _common.alibi_arg validates and builds it)."""
         self._check_dev(q, k, v, out, lse, out_acc, lse_acc)
         varlen = cu_seqlens_q is not None
         a = _C.FwdArgs()
@@ -131,6 +134,10 @@ class HipBackend:
         a.kv_nsplit = config.get().fwd_kv_nsplit
         # split-KV launches (few query rows against many keys on an under-filled grid: include/rfa.h) need a small
         # workspace for the partial (out, lse) pairs: a few tens of MB, only for the calls that split
+        ext = _ext_args(alibi, q)
+        if ext is not None:                       # a bias is never split: no workspace (include/rfa.h)
+            _C.check(self.lib.rfa_fwd_ex(C.byref(a), C.byref(ext), _stream(q)), "rfa_fwd_ex")
+            return
         ws = None
         nbytes = self.lib.rfa_fwd_workspace_bytes(C.byref(a), None)
         if nbytes:
@@ -162,14 +169,16 @@ class HipBackend:
             cu_seqlens_k=None, max_seqlen_q=None, max_seqlen_k=None, q_half=HALF_FULL,
             k_half=HALF_FULL, dq=None, dk=None, dv=None, dq_acc=None, dk_acc=None, dv_acc=None,
             acc_init=False, deterministic=False, phases=_C.BWD_ALL, partials=None, ds_scratch=None,
-            window=(-1, -1), prof_events=None, dropout=None, mask_shift=0, mask_shift_lens=0):
+            window=(-1, -1), prof_events=None, dropout=None, mask_shift=0, mask_shift_lens=0, alibi=None):
         """dQ/dK/dV of one block.  Plain outputs (io dtype) or `+=` into fp32 accumulators.
         phases=BWD_COMPUTE / BWD_REDUCE splits the call so a ring step can overlap the kernels
         with the arrival of the dk/dv accumulators it adds into: the COMPUTE call RETURNS the buffer
         holding its dK/dV partials and the REDUCE call must be handed exactly that buffer (`partials=`),
         so interleaved backwards (other streams, re-entrant / checkpointed autograd, pipeline
         micro-batches) can never consume each other's partials.  Scratch comes from torch's caching
-        allocator on the current stream, per call; the C library itself never allocates."""
+        allocator on the current stream, per call; the C library itself never allocates.
+        alibi: as in fwd, with the forward's values; such a call names the 128-key dK/dV form and takes no dS scratch —
+        what rfa_bwd_ex asks of the base arguments (include/rfa.h)."""
         self._check_dev(dout, q, k, v, lse, delta, dq, dk, dv, dq_acc, dk_acc, dv_acc)
         varlen = cu_seqlens_q is not None
         a = _C.BwdArgs()
@@ -230,7 +239,10 @@ class HipBackend:
         # large: a hand-off that does not fit runs in head-group chunks over it (include/rfa.h: ds_scratch_bytes).
         # config.bwd_ds_spill = False (RFA_BWD_DS_SPILL=0) keeps the 7-GEMM form.  Callers that split one backward over
         # several calls (measurement: BWD_SKIP_DQ / BWD_SKIP_DKDV) pass the same `ds_scratch` to both.
-        if ds_scratch is None and not reduce_only and _spill_enabled():
+        ext = _ext_args(alibi, q)
+        if ext is not None:
+            a.dkdv_form, a.dkdv_nsplit, ds_scratch = _C.DKDV_128, 0, None
+        if ext is None and ds_scratch is None and not reduce_only and _spill_enabled():
             ds_scratch = self.bwd_ds_scratch(a, q.device)
         if ds_scratch is not None and not reduce_only:
             a.ds_scratch = ds_scratch.data_ptr()
@@ -249,7 +261,10 @@ class HipBackend:
             ws._rfa_plan = (form, ns if form == _C.DKDV_256 or a.D > 128 else 0)
         if ws is not None:
             a.workspace = ws.data_ptr()
-        _C.check(self.lib.rfa_bwd(C.byref(a), _stream(q)), "rfa_bwd")
+        if ext is not None:
+            _C.check(self.lib.rfa_bwd_ex(C.byref(a), C.byref(ext), _stream(q)), "rfa_bwd_ex")
+        else:
+            _C.check(self.lib.rfa_bwd(C.byref(a), _stream(q)), "rfa_bwd")
         return ws if (phases & _C.BWD_COMPUTE) else None
 
     def bwd_plan(self, a):
@@ -450,6 +465,20 @@ def _set_dropout(a, dropout):
     if len(dropout) > 5:
         (a.q_pos_stride, a.q_pos_split, a.q_pos_offset2), (a.k_pos_stride, a.k_pos_split, a.k_pos_offset2) = (
             tuple(int(x) for x in m) for m in dropout[5:7])
+
+
+def _ext_args(alibi, q):
+    """rfa_ext_args of a call with `alibi=(slopes, shift)`, or None: the call without the extension"""
+    if alibi is None or alibi[0] is None:
+        return None
+    slopes, shift = alibi
+    if slopes.dtype != torch.float32 or slopes.device != q.device or slopes.dim() not in (1, 2) or slopes.stride(-1) != 1:
+        raise ValueError("alibi slopes must be a float32 tensor of shape (H,) or (B, H), innermost stride 1, on q's device")
+    ext = _C.ExtArgs()
+    ext.alibi_slopes = slopes.data_ptr()
+    ext.alibi_batch_stride = slopes.stride(0) if slopes.dim() == 2 else 0
+    ext.alibi_shift = int(shift)
+    return ext
 
 
 _FWD_FORMS = {"auto": _C.FWD_AUTO, "8x32": _C.FWD_8x32, "4x32": _C.FWD_4x32, "p8x32": _C.FWD_P8x32}

@@ -27,8 +27,8 @@ import torch
 from . import config
 from .backend import get_backend
 from .utils import AllGatherComm as Comm, group_rank_world, reduce_scatter_async, single_rank
-from ._api import _check_unsupported, _opaque
-from ._common import _as_cu, dropout_arg, draw_dropout_seed, packed_pair
+from ._api import _check_unsupported, _opaque, checked_alibi, window_ok_for
+from ._common import alibi_kw, _as_cu, dropout_arg, draw_dropout_seed, packed_pair
 
 
 def fused_heads_k_stride(nheads_k: int, heads_k_stride: int, total_k: int, world: int, head_dim: int,
@@ -130,7 +130,7 @@ def llama3_flash_attn_varlen_forward(
 
     if single_rank(world_size):
         be.fwd(q, k[local_k_slice], v[local_k_slice], softmax_scale=softmax_scale, causal=causal,
-               out=out, lse=lse, window=window_size, dropout=drop(0), **vl)
+               out=out, lse=lse, window=window_size, dropout=drop(0), **alibi_kw(alibi_slopes), **vl)
         return out, lse
 
     hs = fused_heads_k_stride(nheads_k, heads_k_stride, total_k, world_size, head_dim, k.element_size())
@@ -145,7 +145,7 @@ def llama3_flash_attn_varlen_forward(
         comm.all_gather(buf, kvp)
         comm.wait()
         be.fwd(q, buf[local_k_slice, 0], buf[local_k_slice, 1], softmax_scale=softmax_scale, causal=causal,
-               out=out, lse=lse, window=window_size, dropout=drop(0), **vl)
+               out=out, lse=lse, window=window_size, dropout=drop(0), **alibi_kw(alibi_slopes), **vl)
         return out, lse
     groups = list(range(0, nheads_k, hs))
     bufs = [torch.empty((2, total_k * world_size, hs, head_dim), dtype=k.dtype, device=k.device)
@@ -168,7 +168,7 @@ def llama3_flash_attn_varlen_forward(
         q_slice = slice(g0 * nheads // nheads_k, (g0 + hs) * nheads // nheads_k)
         be.fwd(q[:, q_slice], buf[0][local_k_slice], buf[1][local_k_slice],
                softmax_scale=softmax_scale, causal=causal, out=out[:, q_slice], lse=lse[q_slice], window=window_size,
-               dropout=drop(q_slice.start), **vl)
+               dropout=drop(q_slice.start), **alibi_kw(alibi_slopes, heads=q_slice), **vl)
 
     return out, lse
 
@@ -230,7 +230,7 @@ def llama3_flash_attn_varlen_backward(
             dv.zero_()
         be.bwd(dout, q, k[local_k_slice], v[local_k_slice], softmax_lse, delta, softmax_scale=softmax_scale,
                causal=causal, dq=dq, dk=dk[local_k_slice], dv=dv[local_k_slice], deterministic=deterministic, window=window_size,
-               dropout=drop(0), **vl)
+               dropout=drop(0), **alibi_kw(alibi_slopes), **vl)
         return dq, dk, dv
 
     hs = fused_heads_k_stride(nheads_k, heads_k_stride, total_k, world_size, head_dim, k.element_size())
@@ -252,7 +252,7 @@ def llama3_flash_attn_varlen_backward(
         comm.wait()
         be.bwd(dout, q, buf[local_k_slice, 0], buf[local_k_slice, 1], softmax_lse, delta, softmax_scale=softmax_scale,
                causal=causal, dq=dq, dk=dkvc[local_k_slice, 0], dv=dkvc[local_k_slice, 1], deterministic=deterministic,
-               window=window_size, dropout=drop(0), **vl)
+               window=window_size, dropout=drop(0), **alibi_kw(alibi_slopes), **vl)
         dst = packed_pair(dk, dv)
         land = dst if dst is not None else torch.empty((total_k,) + tuple(kvp.shape[1:]), dtype=k.dtype, device=k.device)
         reduce_scatter_async(land, dkvc, group=process_group).wait()
@@ -300,7 +300,8 @@ def llama3_flash_attn_varlen_backward(
         be.bwd(dout[:, q_slice], q[:, q_slice], kv[0][local_k_slice], kv[1][local_k_slice],
                softmax_lse[q_slice], delta[q_slice], softmax_scale=softmax_scale, causal=causal,
                dq=dq[:, q_slice], dk=dkv[0][local_k_slice], dv=dkv[1][local_k_slice],
-               deterministic=deterministic, window=window_size, dropout=drop(q_slice.start), **vl)
+               deterministic=deterministic, window=window_size, dropout=drop(q_slice.start),
+               **alibi_kw(alibi_slopes, heads=q_slice), **vl)
         if job is not None:
             finish(job)                          # group gi-1's exchange ran beside the kernels just enqueued
         dst = (dk, dv) if whole else (rs_out[gi % 2][0], rs_out[gi % 2][1])
@@ -315,7 +316,10 @@ def _l3_forward(ctx, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seql
                 dropout_p, softmax_scale, causal, window_size, alibi_slopes, deterministic, return_softmax, group):
     if softmax_scale is None:
         softmax_scale = q.shape[-1] ** (-0.5)
-    _check_unsupported(dropout_p, window_size, alibi_slopes, windows_ok=True)   # K/V are gathered: one kernel sees them all
+    # K/V are gathered: one kernel sees them all.  A bias needs the global distance i - j: on several ranks the bottom-right
+    # alignment against the truncated cu_seqlens_k yields it for causal calls only (the slopes are sliced per head group)
+    _check_unsupported(dropout_p, window_size, alibi_slopes, windows_ok=True, alibi_ok=window_ok_for(group) or bool(causal))
+    alibi_slopes = checked_alibi(alibi_slopes, q, len(cu_seqlens_q) - 1, "llama3_flash_attn_varlen_func")
     # (strided views — the halves of a packed kv — are fine: the kernels take strides, and the all-gather sources are
     #  made contiguous per head group where they are posted)
     q, k, v = (t if t.stride(-1) == 1 else t.contiguous() for t in (q, k, v))
@@ -334,6 +338,7 @@ def _l3_forward(ctx, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seql
     ctx.deterministic = deterministic
     ctx.group = group
     ctx.window_size = tuple(window_size)
+    ctx.alibi_slopes = alibi_slopes
     return out if not return_softmax else (out, softmax_lse, None)
 
 
@@ -342,7 +347,7 @@ def _l3_backward(ctx, dout, grads=None):
     return llama3_flash_attn_varlen_backward(
         ctx.group, dout, q, k, v, out, softmax_lse, cu_seqlens_q, cu_seqlens_k, *ctx.static,
         softmax_scale=ctx.softmax_scale, dropout_p=ctx.dropout[0], causal=ctx.causal, window_size=ctx.window_size,
-        alibi_slopes=None, deterministic=ctx.deterministic, dropout_seed=ctx.dropout[1], grads=grads,
+        alibi_slopes=ctx.alibi_slopes, deterministic=ctx.deterministic, dropout_seed=ctx.dropout[1], grads=grads,
     )
 
 
@@ -448,7 +453,8 @@ def _make_llama3_api():
         def public(*args, **kwargs):
             if torch.compiler.is_compiling():
                 bound = sig.bind(*args, **kwargs).arguments
-                if not bound.get("dropout_p", 0.0) and isinstance(bound.get("local_k_slice"), slice):
+                if (not bound.get("dropout_p", 0.0) and bound.get("alibi_slopes", None) is None
+                        and isinstance(bound.get("local_k_slice"), slice)):
                     return low(*args, **kwargs)
             return eager(*args, **kwargs)
 

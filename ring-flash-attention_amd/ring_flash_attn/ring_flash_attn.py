@@ -13,13 +13,17 @@ and band every block as ONE window over the whole sequence.  With a causal windo
 d_max = (w - 1) // S + 1 ranks in front of a query hold visible keys, whatever the rank: every rank stops
 exchanging K/V after d_max hops and the dK/dV accumulators, d_max ranks from home by then, return in one direct
 transfer (`ring_window_plan`).  Calls without a window that cuts the global sequence take the unwindowed code, unchanged.
+
+ALiBi over several ranks rides on the same bookkeeping: the bias is a function of the global distance i - j, so the block
+at signed rank distance t is told alibi_shift = t * S (include/rfa.h: rfa_ext_args) — `ring_window_plan` with both sides
+unbounded walks all W steps, and the causal diagonal moves with the same t * S as a windowed call's.
 """
 import torch
 
 from . import _C
 from .backend import get_backend
 from .utils import RingComm, single_rank
-from ._common import dropout_arg, global_window, pos_map, require_dropout_positions, require_mask_shift
+from ._common import alibi_kw, dropout_arg, global_window, pos_map, require_dropout_positions, require_mask_shift
 from ._api import make_autograd_function, make_dense_api, _grad_buffers
 
 
@@ -49,16 +53,17 @@ def ring_window_plan(rank, world_size, S, causal, window):
     return n_steps, dists
 
 
-def _band(causal, window, t, S):
+def _band(causal, window, t, S, alibi_slopes=None):
     """keywords of a block call t ranks off the diagonal (the shift only where it is not zero: backends that predate
-    it serve the diagonal block unchanged)"""
+    it serve the diagonal block unchanged; the bias only where there is one)"""
     kw = {"causal": causal, "window": window}
     if t:
         kw["mask_shift"] = t * S
+    kw.update(alibi_kw(alibi_slopes, t * S))
     return kw
 
 
-def _ring_window_forward(be, comm, q, k, v, softmax_scale, causal, window):
+def _ring_window_forward(be, comm, q, k, v, softmax_scale, causal, window, alibi_slopes=None):
     B, S, H, D = q.shape
     n_steps, dists = ring_window_plan(comm.rank, comm.world_size, S, causal, window)
     out_acc = torch.empty((B, S, H, D), dtype=torch.float32, device=q.device)
@@ -70,7 +75,7 @@ def _ring_window_forward(be, comm, q, k, v, softmax_scale, causal, window):
             next_k, next_v = comm.send_recv_kv(k, v)
         if dists[step] is not None:
             be.fwd(q, k, v, softmax_scale=softmax_scale, out_acc=out_acc, lse_acc=lse_acc, acc_init=first,
-                   **_band(causal, window, dists[step], S))
+                   **_band(causal, window, dists[step], S, alibi_slopes))
             first = False
         if step + 1 != n_steps:
             comm.wait()
@@ -79,7 +84,7 @@ def _ring_window_forward(be, comm, q, k, v, softmax_scale, causal, window):
 
 
 def _ring_window_backward(be, process_group, kv_comm, d_kv_comm, dout, q, k, v, softmax_lse, delta, softmax_scale,
-                          causal, window, deterministic):
+                          causal, window, deterministic, alibi_slopes=None):
     B, S, H, D = q.shape
     world = kv_comm.world_size
     n_steps, dists = ring_window_plan(kv_comm.rank, world, S, causal, window)
@@ -92,7 +97,7 @@ def _ring_window_backward(be, process_group, kv_comm, d_kv_comm, dout, q, k, v, 
         if step + 1 != n_steps:
             next_k, next_v = kv_comm.send_recv_kv(k, v)
         if dists[step] is not None:
-            band = _band(causal, window, dists[step], S)
+            band = _band(causal, window, dists[step], S, alibi_slopes)
             if dq is None:                       # step 0: the diagonal block always computes
                 dq = torch.empty((B, S, H, D), dtype=torch.float32, device=q.device)
                 be.bwd(dout, q, k, v, softmax_lse, delta, softmax_scale=softmax_scale,
@@ -156,14 +161,17 @@ def ring_flash_attn_forward(
     if single_rank(comm.world_size):
         out = torch.empty_like(q)
         lse = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
-        be.fwd(q, k, v, softmax_scale=softmax_scale, causal=causal, out=out, lse=lse, window=window_size, dropout=dropout_arg(dropout_p, dropout_seed))
+        be.fwd(q, k, v, softmax_scale=softmax_scale, causal=causal, out=out, lse=lse, window=window_size, dropout=dropout_arg(dropout_p, dropout_seed),
+               **alibi_kw(alibi_slopes))
         return out, lse
     drop = _ring_dropout(be, comm, S, dropout_p, dropout_seed)
 
     win = global_window(window_size, causal, comm.world_size * S)
+    if alibi_slopes is not None:                 # (never together with a window: _api._check_unsupported)
+        win = (-1, -1)
     if win is not None:
         require_mask_shift(be, "ring_flash_attn")
-        return _ring_window_forward(be, comm, q, k, v, softmax_scale, causal, win)
+        return _ring_window_forward(be, comm, q, k, v, softmax_scale, causal, win, alibi_slopes)
 
     out_acc = torch.empty((B, S, H, D), dtype=torch.float32, device=q.device)
     lse_acc = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
@@ -219,14 +227,17 @@ def ring_flash_attn_backward(
     if single_rank(kv_comm.world_size):
         dq, dk, dv = _grad_buffers(out_grads, q, k, v)
         be.bwd(dout, q, k, v, softmax_lse, delta, softmax_scale=softmax_scale, causal=causal,
-               dq=dq, dk=dk, dv=dv, deterministic=deterministic, window=window_size, dropout=dropout_arg(dropout_p, dropout_seed))
+               dq=dq, dk=dk, dv=dv, deterministic=deterministic, window=window_size, dropout=dropout_arg(dropout_p, dropout_seed),
+               **alibi_kw(alibi_slopes))
         return dq, dk, dv
     drop = _ring_dropout(be, kv_comm, S, dropout_p, dropout_seed)
 
     win = global_window(window_size, causal, kv_comm.world_size * S)
+    if alibi_slopes is not None:
+        win = (-1, -1)
     if win is not None:
         return _ring_window_backward(be, process_group, kv_comm, d_kv_comm, dout, q, k, v, softmax_lse, delta,
-                                     softmax_scale, causal, win, deterministic)
+                                     softmax_scale, causal, win, deterministic, alibi_slopes)
 
     dq = None
     dk = torch.empty(k.shape, dtype=torch.float32, device=q.device)
@@ -269,10 +280,11 @@ def ring_flash_attn_backward(
 
 
 RingFlashAttnFunc = make_autograd_function(
-    "RingFlashAttnFunc", ring_flash_attn_forward, ring_flash_attn_backward, 0, window_ring=True, dropout_ring=True)
+    "RingFlashAttnFunc", ring_flash_attn_forward, ring_flash_attn_backward, 0, window_ring=True, dropout_ring=True,
+    alibi_ring=True)
 (
     ring_flash_attn_func,
     ring_flash_attn_kvpacked_func,
     ring_flash_attn_qkvpacked_func,
 ) = make_dense_api(RingFlashAttnFunc, "ring_flash_attn", ring_flash_attn_forward, ring_flash_attn_backward, window_ring=True,
-                   dropout_ring=True)
+                   dropout_ring=True, alibi_ring=True)

@@ -21,7 +21,7 @@ import torch
 from . import _C
 from .backend import get_backend
 from .utils import RingComm, single_rank
-from ._common import dropout_arg, global_window, require_dropout_positions, require_mask_shift, stripe_map
+from ._common import alibi_kw, dropout_arg, global_window, require_dropout_positions, require_mask_shift, stripe_map
 from ._api import make_autograd_function, make_dense_api, _grad_buffers
 
 
@@ -127,7 +127,7 @@ def stripe_flash_attn_forward(
     if single_rank(comm.world_size):
         out = torch.empty_like(q)
         lse = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
-        be.fwd(q, k, v, softmax_scale=softmax_scale, causal=True, out=out, lse=lse, window=window_size, dropout=dropout_arg(dropout_p, dropout_seed))
+        be.fwd(q, k, v, softmax_scale=softmax_scale, causal=True, out=out, lse=lse, window=window_size, dropout=dropout_arg(dropout_p, dropout_seed), **alibi_kw(alibi_slopes))
         return out, lse
     drop = _stripe_dropout(be, comm.rank, comm.world_size, dropout_p, dropout_seed)
     win = global_window(window_size, True, comm.world_size * S)
@@ -192,7 +192,7 @@ def stripe_flash_attn_backward(
     if single_rank(kv_comm.world_size):
         dq, dk, dv = _grad_buffers(out_grads, q, k, v)
         be.bwd(dout, q, k, v, softmax_lse, delta, softmax_scale=softmax_scale, causal=True,
-               dq=dq, dk=dk, dv=dv, deterministic=deterministic, window=window_size, dropout=dropout_arg(dropout_p, dropout_seed))
+               dq=dq, dk=dk, dv=dv, deterministic=deterministic, window=window_size, dropout=dropout_arg(dropout_p, dropout_seed), **alibi_kw(alibi_slopes))
         return dq, dk, dv
     drop = _stripe_dropout(be, kv_comm.rank, kv_comm.world_size, dropout_p, dropout_seed)
     win = global_window(window_size, True, kv_comm.world_size * S)

@@ -19,13 +19,15 @@ How it runs, with the pieces this package already has:
     llama3 split — so forward, backward and masks are the kernels' ordinary varlen paths;
   * backward: the two calls add their dK/dV contributions into fp32 stream-order buffers (`dk_acc +=`), which are
     put back into rank order and reduce-scattered; dQ is written per slice.
-Sliding windows work as in llama3 (one kernel sees all keys).  `heads_k_stride` is accepted for symmetry with
+Sliding windows work as in llama3 (one kernel sees all keys).  alibi_slopes — (H,) — are served on a single-rank group
+with `causal` (each slice's bottom-right alignment against its truncated cu_seqlens_k is then the global distance); several
+ranks, a non-causal call and per-sequence (B, H) slopes (the two slices hold different sequences) raise.  `heads_k_stride` is accepted for symmetry with
 llama3_flash_attn_varlen_func; all heads are processed per call.
 """
 import torch
 
-from ._api import _check_unsupported, _opaque
-from ._common import _as_cu
+from ._api import _check_unsupported, _opaque, checked_alibi, window_ok_for
+from ._common import _as_cu, alibi_kw
 from .backend import get_backend
 from .llama3_flash_attn_varlen import llama3_flash_attn_prepare_cu_seqlens
 from .utils import AllGatherComm, group_rank_world, reduce_scatter_async, single_rank
@@ -74,7 +76,7 @@ def _gathered_stream_kv(process_group, k, v, world):
 
 
 def zigzag_llama3_flash_attn_varlen_forward(process_group, q, k, v, params, softmax_scale, causal=True,
-                                            window_size=(-1, -1)):
+                                            window_size=(-1, -1), alibi_slopes=None):
     be = get_backend()
     T, H, _ = q.shape
     L = T // 2
@@ -86,12 +88,12 @@ def zigzag_llama3_flash_attn_varlen_forward(process_group, q, k, v, params, soft
         rows = slice(i * L, (i + 1) * L)
         be.fwd(q[rows], kg[ksl], vg[ksl], softmax_scale=softmax_scale, causal=causal, out=out[rows],
                lse=lse[:, rows], window=window_size, cu_seqlens_q=cu_q, cu_seqlens_k=cu_k, max_seqlen_q=mq,
-               max_seqlen_k=mk)
+               max_seqlen_k=mk, **alibi_kw(alibi_slopes))
     return out, lse
 
 
 def zigzag_llama3_flash_attn_varlen_backward(process_group, dout, q, k, v, out, softmax_lse, params, softmax_scale,
-                                             causal=True, window_size=(-1, -1), deterministic=False):
+                                             causal=True, window_size=(-1, -1), deterministic=False, alibi_slopes=None):
     be = get_backend()
     T, H, _ = q.shape
     L = T // 2
@@ -110,7 +112,7 @@ def zigzag_llama3_flash_attn_varlen_backward(process_group, dout, q, k, v, out, 
         be.bwd(dout[rows], q[rows], kg[ksl], vg[ksl], softmax_lse[:, rows], delta[:, rows],
                softmax_scale=softmax_scale, causal=causal, dq=dq[rows], dk_acc=dkg[ksl], dv_acc=dvg[ksl],
                acc_init=False, deterministic=deterministic, window=window_size, cu_seqlens_q=cu_q,
-               cu_seqlens_k=cu_k, max_seqlen_q=mq, max_seqlen_k=mk)
+               cu_seqlens_k=cu_k, max_seqlen_q=mq, max_seqlen_k=mk, **alibi_kw(alibi_slopes))
     if single_rank(world):
         return dq, be.cast(dkg, k.dtype), be.cast(dvg, v.dtype)
     dk = torch.empty(k.shape, dtype=torch.float32, device=q.device)
@@ -128,7 +130,12 @@ class ZigZagLlama3FlashAttnVarlenFunc(torch.autograd.Function):
                 deterministic, return_softmax, group):
         if softmax_scale is None:
             softmax_scale = q.shape[-1] ** (-0.5)
-        _check_unsupported(dropout_p, window_size, alibi_slopes, windows_ok=True)   # K/V are gathered
+        _check_unsupported(dropout_p, window_size, alibi_slopes, windows_ok=True,   # K/V are gathered
+                           alibi_ok=window_ok_for(group) and bool(causal))
+        if alibi_slopes is not None and alibi_slopes.dim() != 1:
+            raise NotImplementedError("zigzag_llama3_flash_attn_varlen_func: alibi_slopes per sequence, (B, H), are not "
+                                      "supported (the two stream slices hold different sequences); pass (H,)")
+        alibi_slopes = checked_alibi(alibi_slopes, q, 0, "zigzag_llama3_flash_attn_varlen_func")
         if dropout_p and dropout_p > 0:
             raise NotImplementedError("zigzag_llama3_flash_attn_varlen_func: dropout is not supported")
         if q.shape[0] % 2 != 0 or k.shape[0] != q.shape[0] or v.shape[0] != q.shape[0]:
@@ -143,7 +150,9 @@ class ZigZagLlama3FlashAttnVarlenFunc(torch.autograd.Function):
             raise ValueError(f"zigzag_llama3: cu_seqlens ends at {int(host[-1])}, the ranks hold {q.shape[0] * world} tokens")
         params = tuple((_as_cu(cq, q.device), _as_cu(ck, q.device), mq, mk, sl)
                        for cq, ck, mq, mk, sl in zigzag_llama3_flash_attn_prepare_cu_seqlens(host, causal, rank, world))
-        out, lse = zigzag_llama3_flash_attn_varlen_forward(group, q, k, v, params, softmax_scale, causal, window_size)
+        out, lse = zigzag_llama3_flash_attn_varlen_forward(group, q, k, v, params, softmax_scale, causal, window_size,
+                                                           alibi_slopes)
+        ctx.alibi_slopes = alibi_slopes
         ctx.save_for_backward(q, k, v, out, lse)
         ctx.params = params
         ctx.meta = (softmax_scale, causal, tuple(window_size), deterministic, group)
@@ -154,7 +163,7 @@ class ZigZagLlama3FlashAttnVarlenFunc(torch.autograd.Function):
         q, k, v, out, lse = ctx.saved_tensors
         softmax_scale, causal, window_size, deterministic, group = ctx.meta
         dq, dk, dv = zigzag_llama3_flash_attn_varlen_backward(group, dout, q, k, v, out, lse, ctx.params, softmax_scale,
-                                                              causal, window_size, deterministic)
+                                                              causal, window_size, deterministic, ctx.alibi_slopes)
         return (dq, dk, dv) + (None,) * 10
 
 

@@ -52,7 +52,7 @@ from . import _C, config
 from .backend import get_backend
 from .utils import Agreement, AllGatherComm, RingComm, SourceArrivals, all_to_all_async, reduce_scatter_async, single_rank
 from ._api import make_autograd_function, make_dense_api, _grad_buffers
-from ._common import packed_pair, dropout_arg, global_window, require_dropout_positions, require_mask_shift, zigzag_map
+from ._common import alibi_kw, packed_pair, dropout_arg, global_window, require_dropout_positions, require_mask_shift, zigzag_map
 
 
 def gather_scratch_bytes(k: torch.Tensor, world: int, wire_fp32: bool) -> int:
@@ -170,6 +170,8 @@ def _gather_kv(comm_group, k, v, world, per_source=False):
 # zigzag layout spreads every neighbourhood of the sequence over all ranks by construction (the contiguous ring,
 # ring_flash_attn.py, is the layout whose exchange stops early).  Kept deliberately plain: zero-initialised fp32
 # gradient accumulators, single-phase block calls, fp32 reduce-scatter of the dK/dV slots in the gather forms.
+# ALiBi over several ranks takes the same decomposition with an unbounded left window: the bias is a function of the global
+# distance i - j, which for the pair (cq, ck) is the block's own plus (cq - ck) C — its alibi_shift (include/rfa.h).
 def zigzag_window_pairs(rank, src, world, C, window_left):
     """the (query half, key half, mask_shift) block calls of rank `rank` against the K/V of rank `src`, diagonal
     blocks first (they initialise the accumulators of their half)"""
@@ -190,7 +192,7 @@ def _halves(S):
     return (slice(0, C), slice(C, S))
 
 
-def _zigzag_window_forward(be, process_group, comm, q, k, v, softmax_scale, window):
+def _zigzag_window_forward(be, process_group, comm, q, k, v, softmax_scale, window, alibi_slopes=None):
     B, S, H, D = q.shape
     W, rank = comm.world_size, comm.rank
     hs = _halves(S)
@@ -202,7 +204,8 @@ def _zigzag_window_forward(be, process_group, comm, q, k, v, softmax_scale, wind
         for hq, hk, shift in zigzag_window_pairs(rank, src, W, S // 2, window[0]):
             band = {"mask_shift": shift} if shift else {}
             be.fwd(q[:, hs[hq]], ks[:, hs[hk]], vs[:, hs[hk]], softmax_scale=softmax_scale, causal=True, window=window,
-                   out_acc=out_acc[:, hs[hq]], lse_acc=lse_acc[:, :, hs[hq]], acc_init=not started[hq], **band)
+                   out_acc=out_acc[:, hs[hq]], lse_acc=lse_acc[:, :, hs[hq]], acc_init=not started[hq], **band,
+                   **alibi_kw(alibi_slopes, shift))
             started[hq] = True
 
     mode = exchange_mode(k, W, q, process_group, v)
@@ -229,7 +232,7 @@ def _zigzag_window_forward(be, process_group, comm, q, k, v, softmax_scale, wind
 
 
 def _zigzag_window_backward(be, process_group, kv_comm, d_kv_comm, dout, q, k, v, softmax_lse, delta, softmax_scale,
-                            window, deterministic, kept):
+                            window, deterministic, kept, alibi_slopes=None):
     B, S, H, D = q.shape
     W, rank = kv_comm.world_size, kv_comm.rank
     hs = _halves(S)
@@ -242,7 +245,8 @@ def _zigzag_window_backward(be, process_group, kv_comm, d_kv_comm, dout, q, k, v
             band = {"mask_shift": shift} if shift else {}
             be.bwd(dout[:, hs[hq]], q[:, hs[hq]], ks[:, hs[hk]], vs[:, hs[hk]], lse_h[hq], delta_h[hq],
                    softmax_scale=softmax_scale, causal=True, window=window, dq_acc=dq[:, hs[hq]],
-                   dk_acc=dk[:, hs[hk]], dv_acc=dv[:, hs[hk]], deterministic=deterministic, **band)
+                   dk_acc=dk[:, hs[hk]], dv_acc=dv[:, hs[hk]], deterministic=deterministic, **band,
+                   **alibi_kw(alibi_slopes, shift))
 
     mode = exchange_mode(k, W, q, process_group, v)
     if mode in ("gather", "gather_ps"):
@@ -335,14 +339,17 @@ def zigzag_ring_flash_attn_forward(
     if single_rank(comm.world_size):
         out = torch.empty_like(q)
         lse = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
-        be.fwd(q, k, v, softmax_scale=softmax_scale, causal=True, out=out, lse=lse, window=window_size, dropout=dropout_arg(dropout_p, dropout_seed))
+        be.fwd(q, k, v, softmax_scale=softmax_scale, causal=True, out=out, lse=lse, window=window_size, dropout=dropout_arg(dropout_p, dropout_seed),
+               **alibi_kw(alibi_slopes))
         return out, lse
     drop = _zigzag_dropout(be, comm.rank, comm.world_size, half, dropout_p, dropout_seed)
 
     win = global_window(window_size, True, comm.world_size * S)
+    if alibi_slopes is not None:                 # (never together with a window: _api._check_unsupported)
+        win = (-1, -1)
     if win is not None:
         require_mask_shift(be, "zigzag_ring_flash_attn")
-        return _zigzag_window_forward(be, process_group, comm, q, k, v, softmax_scale, win)
+        return _zigzag_window_forward(be, process_group, comm, q, k, v, softmax_scale, win, alibi_slopes)
 
     out_acc = torch.empty((B, S, H, D), dtype=torch.float32, device=q.device)
     lse_acc = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
@@ -429,14 +436,17 @@ def zigzag_ring_flash_attn_backward(
     if single_rank(kv_comm.world_size):
         dq, dk, dv = _grad_buffers(out_grads, q, k, v)
         be.bwd(dout, q, k, v, softmax_lse, delta, softmax_scale=softmax_scale, causal=True,
-               dq=dq, dk=dk, dv=dv, deterministic=deterministic, window=window_size, dropout=dropout_arg(dropout_p, dropout_seed))
+               dq=dq, dk=dk, dv=dv, deterministic=deterministic, window=window_size, dropout=dropout_arg(dropout_p, dropout_seed),
+               **alibi_kw(alibi_slopes))
         return dq, dk, dv
     drop = _zigzag_dropout(be, kv_comm.rank, kv_comm.world_size, half, dropout_p, dropout_seed)
 
     win = global_window(window_size, True, kv_comm.world_size * S)
+    if alibi_slopes is not None:
+        win = (-1, -1)
     if win is not None:
         return _zigzag_window_backward(be, process_group, kv_comm, d_kv_comm, dout, q, k, v, softmax_lse, delta,
-                                       softmax_scale, win, deterministic, kept)
+                                       softmax_scale, win, deterministic, kept, alibi_slopes)
 
     dq = torch.empty((B, S, H, D), dtype=torch.float32, device=q.device)
 
@@ -603,10 +613,11 @@ zigzag_ring_flash_attn_forward.keeps_for_backward = True
 
 ZigZagRingFlashAttnFunc = make_autograd_function(
     "ZigZagRingFlashAttnFunc", zigzag_ring_flash_attn_forward, zigzag_ring_flash_attn_backward, 0, window_ring=True,
-    dropout_ring=True)
+    dropout_ring=True, alibi_ring=True)
 (
     zigzag_ring_flash_attn_func,
     zigzag_ring_flash_attn_kvpacked_func,
     zigzag_ring_flash_attn_qkvpacked_func,
 ) = make_dense_api(ZigZagRingFlashAttnFunc, "zigzag_ring_flash_attn", zigzag_ring_flash_attn_forward,
-                   zigzag_ring_flash_attn_backward, packed_travel=True, window_ring=True, dropout_ring=True)
+                   zigzag_ring_flash_attn_backward, packed_travel=True, window_ring=True, dropout_ring=True,
+                   alibi_ring=True)

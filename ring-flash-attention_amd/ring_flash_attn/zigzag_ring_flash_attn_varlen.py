@@ -33,7 +33,7 @@ import torch
 from . import _C, config
 from .backend import get_backend, HALF_FRONT, HALF_BACK
 from .utils import AllGatherComm, RingComm, all_to_all_async, reduce_scatter_async, single_rank
-from ._common import dropout_arg, global_window, require_mask_shift_lens
+from ._common import alibi_kw, dropout_arg, global_window, require_mask_shift_lens
 from ._api import make_autograd_function, make_varlen_api, _grad_buffers
 
 
@@ -209,7 +209,7 @@ def zigzag_ring_flash_attn_varlen_forward(
     if single_rank(comm.world_size):
         out = torch.empty_like(q)
         lse = torch.empty((H, T), dtype=torch.float32, device=q.device)
-        be.fwd(q, k, v, softmax_scale=softmax_scale, causal=True, out=out, lse=lse, window=window_size, dropout=dropout_arg(dropout_p, dropout_seed), **vl)
+        be.fwd(q, k, v, softmax_scale=softmax_scale, causal=True, out=out, lse=lse, window=window_size, dropout=dropout_arg(dropout_p, dropout_seed), **alibi_kw(alibi_slopes), **vl)
         return out, lse
     assert not dropout_p, "dropout over a multi-rank ring is not supported (as in the reference)"
     win = global_window(window_size, True, comm.world_size * int(max_seqlen))
@@ -291,7 +291,7 @@ def zigzag_ring_flash_attn_varlen_backward(
     if single_rank(kv_comm.world_size):
         dq, dk, dv = _grad_buffers(out_grads, q, k, v)
         be.bwd(dout, q, k, v, softmax_lse, delta, softmax_scale=softmax_scale, causal=True,
-               dq=dq, dk=dk, dv=dv, deterministic=deterministic, window=window_size, dropout=dropout_arg(dropout_p, dropout_seed), **vl)
+               dq=dq, dk=dk, dv=dv, deterministic=deterministic, window=window_size, dropout=dropout_arg(dropout_p, dropout_seed), **alibi_kw(alibi_slopes), **vl)
         return dq, dk, dv
     assert not dropout_p, "dropout over a multi-rank ring is not supported (as in the reference)"
     win = global_window(window_size, True, kv_comm.world_size * int(max_seqlen))
