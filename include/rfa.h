@@ -382,13 +382,34 @@ int rfa_fwd(const rfa_fwd_args *args, void *stream);
  *   RFA_FWD_P8x32) and split-KV read as RFA_FWD_AUTO / never split, as for dropout; `workspace` is ignored.
  *   Backward: the plain 128-key dK/dV kernel and the 7-GEMM dQ kernel, as for dropout.  rfa_bwd_workspace_bytes and
  *   rfa_bwd_plan do not see the extension, so rfa_bwd_ex returns RFA_ERR_ARGS unless the BASE arguments already plan to
- *   exactly that — dkdv_form = RFA_DKDV_128, ds_scratch = NULL — and the three can never disagree. */
+ *   exactly that — dkdv_form = RFA_DKDV_128, ds_scratch = NULL — and the three can never disagree.
+ * Logit soft-capping (flash_attn's softcap): with softcap > 0 every score becomes
+ *         s' = softcap * tanh(softmax_scale * q.k / softcap)
+ *   before masking and softmax; the mask (causal, window, mask_shift, mask_shift_lens, halves) is applied to s'.  lse is
+ *   the log-sum-exp of s', so blocks of a ring merge as before.  Backward, with t = tanh(...) recomputed by the forward's
+ *   expression: P = exp(s' - lse), dS = P (dP - delta) (1 - t^2), dQ = softmax_scale dS K, dK = softmax_scale dS^T Q; dV and
+ *   delta are unchanged.  softcap == 0: off — the instance, plan and bits of the plain call; a caller's struct that ends
+ *   in front of the field reads it as 0 (struct_bytes).  softcap_pad: explicit padding, must be 0.
+ *   tanh(x) = 1 - 2 / (1 + exp2(2 log2(e) x)) on the hardware exp2 and reciprocal, ONE expression for the three kernels:
+ *   no branch, finite at +-inf, absolute error a few 2^-23 — times softcap about 3e-6 in a capped score at softcap = 50.
+ *   RFA_ERR_ARGS, before any base pointer is looked at: a negative, NaN or infinite softcap; a non-zero softcap_pad;
+ *   softcap > 0 together with dropout_p > 0, a non-NULL alibi_slopes, head_dim > 128 or softmax_scale <= 0; softcap > 0
+ *   with a bounded window that survives the band normalisation at head dims 65 .. 127 (the zero-padded 128-wide windowed
+ *   dK/dV instance with a cap does not fit the register file: not built; refused by rfa_fwd_ex and rfa_bwd_ex alike).
+ *   Everything else combines with a cap: bounded windows, mask_shift, mask_shift_lens, q_half / k_half, cu_seqlens,
+ *   accumulate mode, two-phase backwards, RFA_BWD_KV_OVERWRITE.  (A block whose band is empty runs as the call without the
+ *   extension.)  Forward: the 8 waves x 32 rows form; RFA_FWD_4x32, RFA_FWD_P8x32 and split-KV read as RFA_FWD_AUTO / never
+ *   split, as for the bias; `workspace` is ignored.  Backward: the 128-key dK/dV kernel and the 7-GEMM dQ kernel;
+ *   rfa_bwd_ex returns RFA_ERR_ARGS unless the base arguments name dkdv_form = RFA_DKDV_128 and ds_scratch = NULL — the
+ *   same rule and reason as for the bias. */
 typedef struct {
   uint32_t struct_bytes;        /* sizeof as the caller compiled it */
   uint32_t reserved;            /* 0 */
   const float *alibi_slopes;    /* NULL: off */
   int64_t alibi_batch_stride;   /* 0: one (H,) row for every batch entry */
   int64_t alibi_shift;
+  float softcap;                /* 0: off */
+  uint32_t softcap_pad;         /* 0 */
 } rfa_ext_args;
 int rfa_fwd_ex(const rfa_fwd_args *args, const rfa_ext_args *ext, void *stream);
 int64_t rfa_ext_args_bytes(void);

@@ -5,6 +5,7 @@
 #include "rfa_kernels.hpp"
 
 #include <algorithm>
+#include <cfloat>
 #include <atomic>
 #include <vector>
 
@@ -180,10 +181,10 @@ inline void set_pos_map(P& p, const A& a) {
 // ---- extension arguments (rfa.h: rfa_ext_args) -----------------------------------------------------------------------------
 // The caller's struct may be shorter (an older caller: the missing tail reads as zero) or longer (a newer one: accepted while
 // the tail this library does not know is zero) than ours.  Parsed before any pointer of the base struct is looked at.
-struct Ext { const float* slopes; int64_t bstride, shift; };
+struct Ext { const float* slopes; int64_t bstride, shift; float cap; };   // ALiBi (slopes = nullptr: off) and the soft cap (0: off), independent
 constexpr uint32_t kExtHead = 2 * sizeof(uint32_t);              // struct_bytes + reserved
 inline int parse_ext(const rfa_ext_args* e, Ext* out) {
-  *out = Ext{nullptr, 0, 0};
+  *out = Ext{nullptr, 0, 0, 0.f};
   if (e == nullptr) return RFA_OK;
   const uint32_t n = e->struct_bytes;
   if (n < kExtHead || e->reserved != 0) return RFA_ERR_ARGS;
@@ -193,9 +194,11 @@ inline int parse_ext(const rfa_ext_args* e, Ext* out) {
   for (uint32_t i = 0; i < n && i < sizeof(x); ++i) dst[i] = src[i];
   for (uint32_t i = sizeof(x); i < n; ++i)
     if (src[i] != 0) return RFA_ERR_ARGS;
-  if (x.alibi_slopes == nullptr) return RFA_OK;                  // off: the shift and the stride are not read
+  if (!(x.softcap >= 0.f) || !(x.softcap <= FLT_MAX) || x.softcap_pad != 0) return RFA_ERR_ARGS;   // negative, NaN, infinite
+  out->cap = x.softcap;
+  if (x.alibi_slopes == nullptr) return RFA_OK;                  // bias off: the shift and the stride are not read
   if (x.alibi_batch_stride < 0) return RFA_ERR_ARGS;
-  *out = Ext{x.alibi_slopes, x.alibi_batch_stride, x.alibi_shift};
+  out->slopes = x.alibi_slopes; out->bstride = x.alibi_batch_stride; out->shift = x.alibi_shift;
   return RFA_OK;
 }
 // what a call with a bias must look like (rfa.h), checked on the call as given and on its normalised band `n`
@@ -206,6 +209,20 @@ inline bool bias_args_ok(const A& a, const A& n, const Ext& e) {
   if (e.shift != 0 && (a.cu_seqlens_q != nullptr || a.cu_seqlens_k != nullptr)) return false;
   if (e.shift <= -((int64_t)1 << 31) || e.shift >= ((int64_t)1 << 31)) return false;
   return (e.shift < 0 ? -e.shift : e.shift) + a.Sq + a.Sk < ((int64_t)1 << 31);
+}
+// what a call with a soft cap must look like (rfa.h); `n`: its normalised band.  A bounded window at head dims 65 .. 127
+// would need the zero-padded 128-wide windowed dK/dV instance with a cap, which is not built (rfa_bwd.hip: launch_dkdv_cap)
+// — refused in the forward too, so that no forward runs whose backward cannot
+template <typename A>
+inline bool cap_args_ok(const A& a, const A& n, const Ext& e) {
+  if (a.dropout_p > 0.f || e.slopes != nullptr || a.D > kHeadDim || !(a.softmax_scale > 0.f)) return false;
+  const bool win = n.window && (n.window_left >= 0 || (n.window_right >= 0 && !n.causal));
+  return kCapPaddedWin || !(win && a.D > 64 && a.D < kHeadDim);
+}
+// the kernels' two constants, made once here (rfa_kernels.hpp)
+template <typename P>
+inline void set_cap(P& p, const Ext& e, float scale) {
+  p.cap = e.cap; p.cap_in = 2.f * kLog2e * scale / e.cap; p.cap_c = e.cap * kLog2e;
 }
 template <typename P>
 inline void set_bias(P& p, const Ext& e, float scale) {
@@ -521,6 +538,10 @@ int rfa_fwd_ex(const rfa_fwd_args* a, const rfa_ext_args* ext, void* stream) {
   int rc = check_common(a->dtype, a->H, a->Hk, a->D, a->B);
   if (rc) return rc;
   if (a->Sq < 0 || a->Sk < 0) return RFA_ERR_SHAPE;
+  if (e.cap > 0.f) {
+    if (!cap_args_ok(*a, norm_args(*a), e)) return RFA_ERR_ARGS;     // (with a bias too: refused whatever the band)
+    if (shift_args_ok(*a) && band_empty(*a)) e.cap = 0.f;           // nothing visible: the call without the extension
+  }
   if (e.slopes != nullptr) {
     if (!shift_args_ok(*a)) return RFA_ERR_ARGS;
     if (band_empty(*a)) e.slopes = nullptr;        // nothing visible: the bias has nothing to act on — the call without it
@@ -573,8 +594,10 @@ int rfa_fwd_ex(const rfa_fwd_args* a, const rfa_ext_args* ext, void* stream) {
   // 256 query rows per workgroup (8 waves) or 128 (4 waves, two workgroups per CU), and the split-KV shares: fwd_plan()
   // a bias runs the 256-row form: the persistent form, the 4-wave form and split-KV shares do not exist for it and read as
   // RFA_FWD_AUTO / "never split" (`workspace` is ignored), as they do for dropout
-  const bool bias = e.slopes != nullptr;
-  if (bias) set_bias(p, e, a->softmax_scale);
+  // (a soft cap likewise: the 256-row instances with or without a window)
+  const bool bias = e.slopes != nullptr || e.cap > 0.f;
+  if (e.slopes != nullptr) set_bias(p, e, a->softmax_scale);
+  if (e.cap > 0.f) set_cap(p, e, a->softmax_scale);
   const FwdPlan plan = bias ? FwdPlan{fwd_qrows_per_block(), 1, 0} : fwd_plan(a);
   int rows = plan.rows;
   // split-KV (needs the caller's workspace): the 128-row form with the key tiles of a workgroup shared by kv_nsplit
@@ -971,6 +994,12 @@ int rfa_bwd_ex(const rfa_bwd_args* a, const rfa_ext_args* ext, void* stream) {
   int rc = check_common(a->dtype, a->H, a->Hk, a->D, a->B);
   if (rc) return rc;
   if (a->Sq < 0 || a->Sk < 0) return RFA_ERR_SHAPE;
+  if (e.cap > 0.f) {
+    if (!cap_args_ok(*a, norm_args(*a), e)) return RFA_ERR_ARGS;
+    if (shift_args_ok(*a) && band_empty(*a)) e.cap = 0.f;           // nothing visible: zero gradients with or without a cap
+    // as for the bias below: the capped kernels are the 128-key dK/dV and the 7-GEMM dQ, and the base arguments must say so
+    else if (a->dkdv_form != RFA_DKDV_128 || a->ds_scratch != nullptr) return RFA_ERR_ARGS;
+  }
   if (e.slopes != nullptr) {
     if (!shift_args_ok(*a)) return RFA_ERR_ARGS;
     if (band_empty(*a)) e.slopes = nullptr;        // nothing visible: zero gradients with or without a bias
@@ -1035,6 +1064,7 @@ int rfa_bwd_ex(const rfa_bwd_args* a, const rfa_ext_args* ext, void* stream) {
   p.drop_seed = a->dropout_seed;
   set_pos_map(p, *a);
   if (e.slopes != nullptr) set_bias(p, e, a->softmax_scale);
+  if (e.cap > 0.f) set_cap(p, e, a->softmax_scale);
   p.nqblk = (eff_len(a->Sq, a->q_half) + bwd_dq_rows_per_block() - 1) / bwd_dq_rows_per_block();
   const DsChunks chunks = bwd_ds_chunking(a);
   const int Gfull = a->H / a->Hk;

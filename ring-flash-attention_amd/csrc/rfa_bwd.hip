@@ -93,9 +93,13 @@ template <int kD> constexpr int dq_smem() { return 4 * kDqKV * HeadGeo<kD>::kRow
 // kDrop: dropout (the forward's mask, rfa_common.hpp: drop_word) applied to dP; instances without a window only
 // kBias: ALiBi (rfa.h: rfa_ext_args) — P is recomputed from the biased scores, by the forward's expression (rfa_fwd.hip: the
 // bias enters the UNSCALED scores, slope / softmax_scale); dS needs nothing else.  Instances without a window or dropout only.
-template <typename T, int kD, bool kFullD, bool kWin, bool kDrop = false, bool kBias = false>
+// kCap: logit soft-capping (rfa.h: rfa_ext_args.softcap) — t = tanh(softmax_scale s / softcap) by the forward's expression
+// (rfa_common.hpp: cap_tanh), dP - delta takes the factor 1 - t^2 BEFORE the exponential overwrites s, then P = exp2(t c - lse
+// log2 e) with softcap's exponent constant: no register lives across the GEMMs.  With or without a window; no dropout, no bias.
+template <typename T, int kD, bool kFullD, bool kWin, bool kDrop = false, bool kBias = false, bool kCap = false>
 __global__ __launch_bounds__(kDqThreads, 2) void dq_kernel(const BwdParams p) {
   static_assert(!kBias || (!kWin && !kDrop), "ALiBi: the instances without a window or dropout");
+  static_assert(!kCap || (!kDrop && !kBias), "soft-capping: the instances without dropout or bias");
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   lds_t* smem = (lds_t*)smem_raw;
   typedef HeadGeo<kD> Geo;
@@ -249,7 +253,7 @@ __global__ __launch_bounds__(kDqThreads, 2) void dq_kernel(const BwdParams p) {
   const uint32_t drop_j0 = kDrop ? p.k_pos0 + (uint32_t)(p.cu_k ? ks.row0 : 0) : 0u;
   const float bias_slope = kBias ? p.alibi[(int64_t)b * p.alibi_bstride + h] * p.alibi_rscale : 0.f;   // once per workgroup, score units
   const int bias_row = kBias ? qrow + (lk - lq) + p.alibi_shift - 4 * g : 0;
-  const float c = p.scale * kLog2e;
+  const float c = kCap ? p.cap_c : p.scale * kLog2e;
   f32x16 dq[kNB];
 #pragma unroll
   for (int i = 0; i < kNB; ++i)
@@ -313,6 +317,14 @@ __global__ __launch_bounds__(kDqThreads, 2) void dq_kernel(const BwdParams p) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) s[r] = __builtin_fmaf(-bias_slope, __builtin_fabsf(dist0 - (float)crow(r, 0)), s[r]);
         }
+        if (kCap) {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const float th = cap_tanh(s[r] * p.cap_in);
+            dp[r] = (dp[r] - dlt) * __builtin_fmaf(-th, th, 1.f);
+            s[r] = th;
+          }
+        }
 #pragma unroll
         for (int r = 0; r < 16; ++r) s[r] = fast_exp2(__builtin_fmaf(s[r], c, -L2));
         if (need_mask) {
@@ -346,7 +358,7 @@ __global__ __launch_bounds__(kDqThreads, 2) void dq_kernel(const BwdParams p) {
           }
         }
 #pragma unroll
-        for (int r = 0; r < 16; ++r) s[r] = s[r] * (dp[r] - dlt);
+        for (int r = 0; r < 16; ++r) s[r] = s[r] * (kCap ? dp[r] : dp[r] - dlt);
 #pragma unroll
         for (int ks2 = 0; ks2 < 2; ++ks2) {
           const vec8<T> dsb = pack8<T>(s, 8 * ks2);
@@ -439,10 +451,13 @@ template <int kD> constexpr int kv_smem() {        // 129 KiB (65 KiB at kD = 64
 // at 256 registers, and a second copy of the mask loop put them on the scratch.  kDrop without kMap is the code of before.
 // kBias: ALiBi, as in dq_kernel (the plain 128-key instances; the slopes of the G query heads of the K/V head are wave-uniform
 // loads, one per head step)
+// kCap: logit soft-capping, as in dq_kernel (the 128-key instances with or without a window; dp is dO V^T - delta when the
+// factor 1 - t^2 is applied)
 template <typename T, int kD, bool kFullD, bool kSpill, bool kWin, bool kWide, bool kDrop = false, bool kBal = false, bool kMap = false,
-          bool kBias = false>
+          bool kBias = false, bool kCap = false>
 __global__ __launch_bounds__(kKvThreads, 2) void dkdv_kernel(const BwdParams p) {
   static_assert(!kBias || (!kSpill && !kWin && !kWide && !kDrop), "ALiBi: the plain 128-key instances");
+  static_assert(!kCap || (!kSpill && !kWide && !kDrop && !kBias), "soft-capping: the 128-key instances without dS spill, dropout or bias");
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   lds_t* smem = (lds_t*)smem_raw;
   static_assert(!kSpill || (kD == 128 && !kWin), "the dS spill path: head dim 128, no window");
@@ -761,7 +776,7 @@ __global__ __launch_bounds__(kKvThreads, 2) void dkdv_kernel(const BwdParams p) 
   // ALiBi: distance of (query sq + 4 g, key krow) = sq + bias_off - (krow - 4 g) — an integer per sub-tile, as the mask's
   const int bias_off = kBias ? (lk - lq) + p.alibi_shift : 0;
   const float* bias_slopes = kBias ? p.alibi + (int64_t)b * p.alibi_bstride + h0 : nullptr;
-  const float c = p.scale * kLog2e;
+  const float c = kCap ? p.cap_c : p.scale * kLog2e;
   f32x16 dk[kNB], dv[kNB];
 #pragma unroll
   for (int i = 0; i < kNB; ++i)
@@ -821,8 +836,8 @@ __global__ __launch_bounds__(kKvThreads, 2) void dkdv_kernel(const BwdParams p) 
       {
         // dP - delta = dO V_w^T (+ init; V_w fragments from LDS) then S = Q K_w^T (K_w in registers):
         // 2 kNK MFMAs, LDS operands read kAhead steps ahead
-        // (the zero-padded 128-wide ALiBi instances read one pair less ahead: they hold their staging registers on top of a full file)
-        constexpr int kAhead = (kBias && !kFullD && kD == 128) ? RFA_KV_AHEAD - 1 : RFA_KV_AHEAD;
+        // (the zero-padded 128-wide ALiBi and soft-capping instances read one pair less ahead: they hold their staging registers on top of a full file)
+        constexpr int kAhead = ((kBias || kCap) && !kFullD && kD == 128) ? RFA_KV_AHEAD - 1 : RFA_KV_AHEAD;
         constexpr int kN = 2 * kNK;
         vec8<T> a[kN], w[kNK];
         auto fa = [&](int i) {
@@ -867,6 +882,14 @@ __global__ __launch_bounds__(kKvThreads, 2) void dkdv_kernel(const BwdParams p) 
         const float dist0 = (float)(dist_s - mask_kg);
 #pragma unroll
         for (int r = 0; r < 16; ++r) s[r] = __builtin_fmaf(-bias_slope, __builtin_fabsf(dist0 + (float)crow(r, 0)), s[r]);
+      }
+      if (kCap) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const float th = cap_tanh(s[r] * p.cap_in);
+          dp[r] *= __builtin_fmaf(-th, th, 1.f);
+          s[r] = th;
+        }
       }
       // lse is read only now: holding it across GEMM 1 would cost 16 registers
       f32x4 l2v[4];
@@ -943,7 +966,7 @@ __global__ __launch_bounds__(kKvThreads, 2) void dkdv_kernel(const BwdParams p) 
         };
         if (RFA_SPILL_PROBE != 2) spill();
         if (RFA_KV_PRIO == 4 || RFA_KV_PRIO == 5) __builtin_amdgcn_s_setprio(1);
-        constexpr int kAhead = (kBias && !kFullD && kD == 128) ? RFA_KV_AHEAD2 - 1 : RFA_KV_AHEAD2;
+        constexpr int kAhead = ((kBias || kCap) && !kFullD && kD == 128) ? RFA_KV_AHEAD2 - 1 : RFA_KV_AHEAD2;
         constexpr int kN2 = 4 * kNB;                   // [ks2][which: 0 = dO^T (dV), 1 = Q^T (dK)][dblk]
         vec8<T> a[kN2];
         auto frag = [&](int i) {
@@ -1184,13 +1207,13 @@ __global__ __launch_bounds__(kKvThreads, 2) void dkdv_kernel(const BwdParams p) 
   }   // segment loop
 }
 
-template <typename T, int kD, bool kFullD, bool kWin, bool kDrop = false, bool kBias = false>
+template <typename T, int kD, bool kFullD, bool kWin, bool kDrop = false, bool kBias = false, bool kCap = false>
 static int launch_dq_t(const BwdParams& p, hipStream_t stream) {
   static std::atomic<unsigned long long> attr_done{0};
-  if (int rc = opt_in_dynamic_lds((const void*)dq_kernel<T, kD, kFullD, kWin, kDrop, kBias>, dq_smem<kD>(), attr_done)) return rc;
+  if (int rc = opt_in_dynamic_lds((const void*)dq_kernel<T, kD, kFullD, kWin, kDrop, kBias, kCap>, dq_smem<kD>(), attr_done)) return rc;
   const int64_t nblocks = (int64_t)p.nqblk * p.H * p.B;
   if (nblocks <= 0) return 0;
-  hipLaunchKernelGGL((dq_kernel<T, kD, kFullD, kWin, kDrop, kBias>), dim3((unsigned)nblocks), dim3(kDqThreads), dq_smem<kD>(), stream, p);
+  hipLaunchKernelGGL((dq_kernel<T, kD, kFullD, kWin, kDrop, kBias, kCap>), dim3((unsigned)nblocks), dim3(kDqThreads), dq_smem<kD>(), stream, p);
   return hipGetLastError() == hipSuccess ? kLaunchOk : kLaunchFailed;
 }
 
@@ -1200,10 +1223,10 @@ __global__ void zero_words_kernel(unsigned* w, int n) {
 }
 
 template <typename T, int kD, bool kFullD, bool kSpill, bool kWin, bool kWide = false, bool kDrop = false, bool kBal = false, bool kMap = false,
-          bool kBias = false>
+          bool kBias = false, bool kCap = false>
 static int launch_dkdv_t(const BwdParams& p, hipStream_t stream) {
   static std::atomic<unsigned long long> attr_done{0};
-  if (int rc = opt_in_dynamic_lds((const void*)dkdv_kernel<T, kD, kFullD, kSpill, kWin, kWide, kDrop, kBal, kMap, kBias>, kv_smem<kD>(), attr_done)) return rc;
+  if (int rc = opt_in_dynamic_lds((const void*)dkdv_kernel<T, kD, kFullD, kSpill, kWin, kWide, kDrop, kBal, kMap, kBias, kCap>, kv_smem<kD>(), attr_done)) return rc;
   // one workgroup per (key block, K/V head) [x tile-range split of the 256-key form]
   const int64_t nblocks = (int64_t)p.nkblk * p.Hk * p.B * ((kWide && !kBal) ? p.nsplit : 1);
   if (nblocks <= 0) return 0;
@@ -1215,7 +1238,7 @@ static int launch_dkdv_t(const BwdParams& p, hipStream_t stream) {
     hipLaunchKernelGGL(zero_words_kernel, dim3((unsigned)((nflags + 255) / 256)), dim3(256), 0, stream, p.pair_flags, nflags);
     if (hipGetLastError() != hipSuccess) return kLaunchFailed;
   }
-  hipLaunchKernelGGL((dkdv_kernel<T, kD, kFullD, kSpill, kWin, kWide, kDrop, kBal, kMap, kBias>), dim3((unsigned)nblocks), dim3(kKvThreads), kv_smem<kD>(), stream, p);
+  hipLaunchKernelGGL((dkdv_kernel<T, kD, kFullD, kSpill, kWin, kWide, kDrop, kBal, kMap, kBias, kCap>), dim3((unsigned)nblocks), dim3(kKvThreads), kv_smem<kD>(), stream, p);
   return hipGetLastError() == hipSuccess ? kLaunchOk : kLaunchFailed;
 }
 
@@ -1246,8 +1269,34 @@ static int launch_dkdv_bias(const BwdParams& p, hipStream_t stream) {
   if (p.D == 64) return launch_dkdv_t<T, 64, true, false, false, false, false, false, false, true>(p, stream);
   return launch_dkdv_t<T, 64, false, false, false, false, false, false, false, true>(p, stream);
 }
+// soft-capping (rfa_api.cpp: head dim <= 128, no dropout, no bias, the 128-key dK/dV form without the dS hand-off), with or
+// without a window: 128 and 64 full, every other head dim through the zero-padded 128- / 64-wide layouts
+template <typename T, bool kWin>
+static int launch_dq_cap(const BwdParams& p, hipStream_t stream) {
+  if (p.D == 128) return launch_dq_t<T, 128, true, kWin, false, false, true>(p, stream);
+  if (p.D > 64) return launch_dq_t<T, 128, false, kWin, false, false, true>(p, stream);
+  if (p.D == 64) return launch_dq_t<T, 64, true, kWin, false, false, true>(p, stream);
+  return launch_dq_t<T, 64, false, kWin, false, false, true>(p, stream);
+}
+template <typename T, bool kWin>
+static int launch_dkdv_cap(const BwdParams& p, hipStream_t stream) {
+  if (p.D == 128) return launch_dkdv_t<T, 128, true, false, kWin, false, false, false, false, false, true>(p, stream);
+  // (the zero-padded 128-wide instance with a window AND a cap is not built — rfa_kernels.hpp: kCapPaddedWin — and the API
+  //  layer refuses such calls, forward and backward alike)
+  if constexpr (kWin && !kCapPaddedWin) {
+    if (p.D > 64) return kLaunchFailed;
+  } else {
+    if (p.D > 64) return launch_dkdv_t<T, 128, false, false, kWin, false, false, false, false, false, true>(p, stream);
+  }
+  if (p.D == 64) return launch_dkdv_t<T, 64, true, false, kWin, false, false, false, false, false, true>(p, stream);
+  return launch_dkdv_t<T, 64, false, false, kWin, false, false, false, false, false, true>(p, stream);
+}
 int launch_bwd_dq(const BwdParams& p, int dtype, hipStream_t stream) {
   if (p.D > 128) return launch_bwd_dq_big(p, dtype, stream);            // rfa_bigd.hip
+  if (p.cap > 0.f) {
+    if (windowed(p.causal, p.wl, p.wr)) return dtype == 0 ? launch_dq_cap<bf16_t, true>(p, stream) : launch_dq_cap<f16_t, true>(p, stream);
+    return dtype == 0 ? launch_dq_cap<bf16_t, false>(p, stream) : launch_dq_cap<f16_t, false>(p, stream);
+  }
   if (p.alibi != nullptr) return dtype == 0 ? launch_dq_bias<bf16_t>(p, stream) : launch_dq_bias<f16_t>(p, stream);
   if (p.drop_keep < 256) return dtype == 0 ? launch_dq_d<bf16_t, false, true>(p, stream) : launch_dq_d<f16_t, false, true>(p, stream);
   if (windowed(p.causal, p.wl, p.wr)) return dtype == 0 ? launch_dq_d<bf16_t, true, false>(p, stream) : launch_dq_d<f16_t, true, false>(p, stream);
@@ -1272,6 +1321,10 @@ static int launch_dkdv_d(const BwdParams& p, hipStream_t stream) {
 }
 int launch_bwd_dkdv(const BwdParams& p, int dtype, hipStream_t stream) {
   if (p.D > 128) return launch_bwd_dkdv_big(p, dtype, stream);          // rfa_bigd.hip (rfa_api.cpp: no spill, no 256-key form)
+  if (p.cap > 0.f) {
+    if (windowed(p.causal, p.wl, p.wr)) return dtype == 0 ? launch_dkdv_cap<bf16_t, true>(p, stream) : launch_dkdv_cap<f16_t, true>(p, stream);
+    return dtype == 0 ? launch_dkdv_cap<bf16_t, false>(p, stream) : launch_dkdv_cap<f16_t, false>(p, stream);
+  }
   if (p.alibi != nullptr) return dtype == 0 ? launch_dkdv_bias<bf16_t>(p, stream) : launch_dkdv_bias<f16_t>(p, stream);
   const bool win = windowed(p.causal, p.wl, p.wr);
   if (p.drop_keep < 256 && p.drop_mapped)         // ... with a position map: instances of their own (dkdv_kernel: kMap)

@@ -406,4 +406,13 @@ __device__ __forceinline__ float sum_xor32(float v) {
 
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 
+// tanh(x) = 1 - 2 / (1 + exp2(2 log2(e) x)) for logit soft-capping (rfa.h: rfa_ext_args.softcap): the hardware exp2 and
+// reciprocal, no branch, finite at +-inf (exp2 -> inf gives 1, exp2 -> 0 gives -1).  The ONE expression the forward, dQ and
+// dK/dV kernels call, so that all three round alike.  Absolute error a few 2^-23 (exp2 and rcp: 1 ulp each, of a value in
+// (0, 2]); times softcap that is about 3e-6 in a capped score at softcap = 50.
+// The argument arrives as y = 2 log2(e) x: the factor is folded into the per-call constant on the host (cap_in).
+__device__ __forceinline__ float cap_tanh(float y) {
+  return __builtin_fmaf(-2.f, __builtin_amdgcn_rcpf(1.f + fast_exp2(y)), 1.f);
+}
+
 }  // namespace rfa

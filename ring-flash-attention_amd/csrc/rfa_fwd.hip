@@ -91,9 +91,14 @@ template <int kD> constexpr int fwd_smem() { return 2 * kFwdStages * kFwdKV * He
 // kBias: ALiBi (rfa.h: rfa_ext_args) — score -= slope * |i + (len_k - len_q) + alibi_shift - j|, added to the UNSCALED scores in
 // front of the mask and the row max (slope / softmax_scale: the max, the deferred rescale and lse = m scale + log l then
 // see the biased scores and need no change).  Instances without a window or dropout only.
-template <typename T, int kD, bool kFullD, bool kWin, bool kDrop = false, int kW = kFwdWavesMax, bool kBias = false>
+// kCap: logit soft-capping (rfa.h: rfa_ext_args.softcap) — s = tanh(softmax_scale s / softcap) right behind the S GEMM, in front
+// of the mask; from there on the scores are in units of softcap (the exponent constant and the lse factor are softcap's
+// instead of softmax_scale's), the row max, the deferred rescale and the merge epilogue are unchanged.  With or without a
+// window; no dropout, no bias.
+template <typename T, int kD, bool kFullD, bool kWin, bool kDrop = false, int kW = kFwdWavesMax, bool kBias = false, bool kCap = false>
 __global__ __launch_bounds__(kW * 64, 2) void fwd_kernel(const FwdParams p) {
   static_assert(!kBias || (!kWin && !kDrop), "ALiBi: the instances without a window or dropout");
+  static_assert(!kCap || (!kDrop && !kBias && kW == kFwdWavesMax), "soft-capping: the 256-row instances without dropout or bias");
   constexpr int kFwdWaves = kW, kFwdThreads = kW * 64, kFwdQRows = kW * 32;   // (query rows per workgroup)
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   lds_t* smem = (lds_t*)smem_raw;
@@ -279,7 +284,7 @@ __global__ __launch_bounds__(kW * 64, 2) void fwd_kernel(const FwdParams p) {
   // as an integer — only the per-element part below is float (exact up to 2^24 rows, rfa.h)
   const float bias_slope = kBias ? p.alibi[(int64_t)b * p.alibi_bstride + h] * p.alibi_rscale : 0.f;
   const int bias_row = kBias ? qrow + (lk - lq) + p.alibi_shift - 4 * g : 0;
-  const float c = p.scale * kLog2e;
+  const float c = kCap ? p.cap_c : p.scale * kLog2e;
   float m = -INFINITY;
   float mthr = -INFINITY, mc_run = 0.f;      // RFA_FWD_LEAN: rescale threshold m + DEFER / c, and m c (0 while m is -inf)
   float lsum = 0.f;
@@ -357,6 +362,12 @@ __global__ __launch_bounds__(kW * 64, 2) void fwd_kernel(const FwdParams p) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) s[t][r] = __builtin_fmaf(-bias_slope, __builtin_fabsf(dist0 - (float)crow(r, 0)), s[t][r]);
         }
+      }
+      if (kCap) {
+#pragma unroll
+        for (int t = 0; t < kFwdSub; ++t)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) s[t][r] = cap_tanh(s[t][r] * p.cap_in);
       }
       // ---------------- mask ----------------
       const bool need_mask = (kt0 + kFwdKV > lk) || (hi && kt0 + kFwdKV - 1 > qw0 + off + wr) ||
@@ -511,7 +522,7 @@ __global__ __launch_bounds__(kW * 64, 2) void fwd_kernel(const FwdParams p) {
   const float l = RFA_FWD_MAXFORM ? sum_xor32(lsum) : lsum + shfl_xor32(lsum);
   const bool has = l > 0.f;
   const float inv = has ? (kDrop ? p.drop_scale : 1.f) / l : 0.f;      // kept probabilities are scaled by 1 / (1 - p)
-  const float blse = has ? m * p.scale + __logf(l) : INFINITY;   // natural log
+  const float blse = has ? m * (kCap ? p.cap : p.scale) + __logf(l) : INFINITY;   // natural log
   const int64_t orow = qs.row0 + qrow;
 
   if (p.out_acc == nullptr && nsplit == 1) {
@@ -921,13 +932,13 @@ static int launch_fwd_persist(const FwdParams& p, hipStream_t stream) {
   return hipGetLastError() == hipSuccess ? kLaunchOk : kLaunchFailed;
 }
 
-template <typename T, int kD, bool kFullD, bool kWin, bool kDrop = false, int kW = kFwdWavesMax, bool kBias = false>
+template <typename T, int kD, bool kFullD, bool kWin, bool kDrop = false, int kW = kFwdWavesMax, bool kBias = false, bool kCap = false>
 static int launch_fwd_w(const FwdParams& p, hipStream_t stream) {
   static std::atomic<unsigned long long> attr_done{0};
-  if (int rc = opt_in_dynamic_lds((const void*)fwd_kernel<T, kD, kFullD, kWin, kDrop, kW, kBias>, fwd_smem<kD>(), attr_done)) return rc;
+  if (int rc = opt_in_dynamic_lds((const void*)fwd_kernel<T, kD, kFullD, kWin, kDrop, kW, kBias, kCap>, fwd_smem<kD>(), attr_done)) return rc;
   const int64_t nblocks = (int64_t)p.nqblk * p.H * p.B * (p.kv_nsplit > 1 ? p.kv_nsplit : 1);
   if (nblocks <= 0) return 0;
-  hipLaunchKernelGGL((fwd_kernel<T, kD, kFullD, kWin, kDrop, kW, kBias>), dim3((unsigned)nblocks), dim3(kW * 64), fwd_smem<kD>(), stream, p);
+  hipLaunchKernelGGL((fwd_kernel<T, kD, kFullD, kWin, kDrop, kW, kBias, kCap>), dim3((unsigned)nblocks), dim3(kW * 64), fwd_smem<kD>(), stream, p);
   return hipGetLastError() == hipSuccess ? kLaunchOk : kLaunchFailed;
 }
 template <typename T, int kD, bool kFullD, bool kWin, bool kDrop = false>
@@ -961,7 +972,21 @@ static int launch_fwd_bias(const FwdParams& p, hipStream_t stream) {
   return launch_fwd_w<T, 64, false, false, false, kFwdWavesMax, true>(p, stream);
 }
 
+// soft-capping (rfa_api.cpp: head dim <= 128, no dropout, no bias, the 256-row form), with or without a window: 128 and 64
+// full, every other head dim through the zero-padded 128- / 64-wide layouts
+template <typename T, bool kWin>
+static int launch_fwd_cap(const FwdParams& p, hipStream_t stream) {
+  if (p.D == 128) return launch_fwd_w<T, 128, true, kWin, false, kFwdWavesMax, false, true>(p, stream);
+  if (p.D > 64) return launch_fwd_w<T, 128, false, kWin, false, kFwdWavesMax, false, true>(p, stream);
+  if (p.D == 64) return launch_fwd_w<T, 64, true, kWin, false, kFwdWavesMax, false, true>(p, stream);
+  return launch_fwd_w<T, 64, false, kWin, false, kFwdWavesMax, false, true>(p, stream);
+}
+
 int launch_fwd(const FwdParams& p, int dtype, hipStream_t stream) {
+  if (p.cap > 0.f) {
+    if (windowed(p.causal, p.wl, p.wr)) return dtype == 0 ? launch_fwd_cap<bf16_t, true>(p, stream) : launch_fwd_cap<f16_t, true>(p, stream);
+    return dtype == 0 ? launch_fwd_cap<bf16_t, false>(p, stream) : launch_fwd_cap<f16_t, false>(p, stream);
+  }
   if (p.alibi != nullptr) return dtype == 0 ? launch_fwd_bias<bf16_t>(p, stream) : launch_fwd_bias<f16_t>(p, stream);
   if (p.persist_grid > 0)                                      // rfa_api.cpp: head dim 128, dense, plain outputs, 256-row form, no shares
     return dtype == 0 ? launch_fwd_persist<bf16_t>(p, stream) : launch_fwd_persist<f16_t>(p, stream);

@@ -79,6 +79,10 @@ struct FwdParams {
   int64_t alibi_bstride;
   int alibi_shift;
   float alibi_rscale;
+  // logit soft-capping (rfa.h: rfa_ext_args.softcap; the kCap instances only): cap = softcap, 0 is off.  The two constants
+  // of the kernels, made once by the API layer: t = cap_tanh(s * cap_in) with cap_in = 2 log2(e) softmax_scale / softcap
+  // (rfa_common.hpp), and the exponent constant cap_c = softcap log2(e) that takes the place of softmax_scale log2(e)
+  float cap, cap_in, cap_c;
 };
 
 struct PreParams {
@@ -143,6 +147,10 @@ struct BwdParams {
   int64_t alibi_bstride;
   int alibi_shift;
   float alibi_rscale;
+  // logit soft-capping (rfa.h: rfa_ext_args.softcap; the kCap instances only): cap = softcap, 0 is off.  The two constants
+  // of the kernels, made once by the API layer: t = cap_tanh(s * cap_in) with cap_in = 2 log2(e) softmax_scale / softcap
+  // (rfa_common.hpp), and the exponent constant cap_c = softcap log2(e) that takes the place of softmax_scale log2(e)
+  float cap, cap_in, cap_c;
 };
 
 // dst[b, row, hk, :] (=|+=) sum_g src[b, row, hk*G+g, :]
@@ -198,6 +206,10 @@ int launch_bwd_dq_big(const BwdParams& p, int dtype, hipStream_t stream);
 int launch_bwd_dkdv_big(const BwdParams& p, int dtype, hipStream_t stream);
 
 int launch_preprocess(const PreParams& p, int dtype, hipStream_t stream);
+// soft cap + bounded window at head dims 65 .. 127: the zero-padded 128-wide dK/dV instance with both flags needs 40 bytes of
+// scratch / 9 spilled registers, beyond what the padded instances are allowed (32 / 4) — with the read-ahead reduced by one or
+// by two pairs alike — so it is not built and rfa_api.cpp refuses such calls (profiles/softcap.md)
+constexpr bool kCapPaddedWin = false;
 int launch_bwd_dq(const BwdParams& p, int dtype, hipStream_t stream);
 int launch_bwd_dkdv(const BwdParams& p, int dtype, hipStream_t stream);
 // dQ = scale * dS K from the dS blocks a preceding launch_bwd_dkdv (with p.ds set) stored; dense, D == 128

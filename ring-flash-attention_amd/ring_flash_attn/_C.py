@@ -107,10 +107,12 @@ class BwdArgs(C.Structure):
 
 
 class ExtArgs(C.Structure):
-    """rfa_ext_args: per-call features added after the ABI 8 structs were frozen (ALiBi); struct_bytes is filled in here"""
+    """rfa_ext_args: per-call features added after the ABI 8 structs were frozen (ALiBi, the soft cap); struct_bytes is
+    filled in here"""
     _fields_ = [
         ("struct_bytes", C.c_uint32), ("reserved", C.c_uint32),
         ("alibi_slopes", C.c_void_p), ("alibi_batch_stride", C.c_int64), ("alibi_shift", C.c_int64),
+        ("softcap", C.c_float), ("softcap_pad", C.c_uint32),
     ]
 
     def __init__(self, *args, **kw):

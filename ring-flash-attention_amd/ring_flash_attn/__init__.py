@@ -55,3 +55,6 @@ __version__ = "0.1.0"
 # resolved once) and the source of the per-forward dropout seeds
 from . import config
 from ._common import set_dropout_generator
+# flash_attn's softcap (logit soft-capping) for any of the attention functions above: with_softcap(func, softcap) — the
+# positional signatures above are the reference's and stay as they are
+from ._api import with_softcap

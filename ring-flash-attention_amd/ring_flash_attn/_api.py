@@ -16,6 +16,7 @@ inputs are the caller's LOCAL shard.
 import torch
 
 from ._common import _prep_qkv, _as_cu, check_alibi_slopes, draw_dropout_seed, require_alibi
+from .backend import softcap_scope
 from .utils import audit_verify
 
 
@@ -138,6 +139,69 @@ def checked_alibi(alibi_slopes, q, batch, what):
     return slopes
 
 
+def checked_softcap(dropout_p, alibi_slopes, q, what, window_size=None, causal=False):
+    """the soft cap bound to this public call by `with_softcap` (0.0: none) and its refusals — together with dropout or
+    alibi_slopes, head dims above 128, a window at head dims 65 .. 127 (include/rfa.h: that dK/dV instance is not built; a
+    window_size (-1, 0) with `causal` bounds nothing), a backend that does not serve a cap: NotImplementedError before anything is
+    exchanged, on every rank alike.  Read ONCE, in the autograd Function's forward, and kept on the node: the backward runs
+    under `softcap_scope(ctx.softcap)` and reads nothing ambient."""
+    from .backend import get_backend, pending_softcap, softcap_scope
+
+    cap = pending_softcap()
+    if not cap:
+        return 0.0
+    if dropout_p and dropout_p > 0:
+        raise NotImplementedError(f"ring_flash_attn: {what} with softcap together with dropout is not supported")
+    if alibi_slopes is not None:
+        raise NotImplementedError(f"ring_flash_attn: {what} with softcap together with alibi_slopes is not supported")
+    if q.shape[-1] > 128:
+        raise NotImplementedError(f"ring_flash_attn: {what} with softcap serves head dims up to 128, not {q.shape[-1]}")
+    bounded = has_window(window_size) and (window_size[0] >= 0 or not causal)
+    if bounded and 64 < q.shape[-1] < 128:
+        raise NotImplementedError(f"ring_flash_attn: {what} with softcap and a sliding window serves head dims up to 64 "
+                                  f"and 128, not {q.shape[-1]}")
+    with softcap_scope(cap):
+        get_backend()                                # (refuses a backend without `serves_softcap`)
+    return cap
+
+
+def with_softcap(func, softcap):
+    """flash_attn's logit soft-capping for one of this package's public attention functions:
+
+        capped = with_softcap(ring_flash_attn_func, 50.0)
+        out = capped(q, k, v, causal=True, window_size=(4095, 0))
+
+    returns a callable with `func`'s signature that runs `func` with scores = softcap * tanh(softmax_scale * q.k / softcap)
+    in front of the mask and the softmax (include/rfa.h: rfa_ext_args.softcap), on any group and with any window the
+    function serves.  `softcap` None or 0: `func` itself.  ValueError: a negative or non-finite value; TypeError: `func` is
+    not one of the public attention functions.  NotImplementedError at the call: together with dropout or alibi_slopes,
+    head dims above 128, and (windowed calls) head dims 65 .. 127.
+    The value is bound to the call and kept on the autograd node — activation checkpointing re-runs the wrapped call and
+    gets the same cap; there is no user-managed context.  Under torch.compile the capped call runs eagerly behind a graph
+    break (the registered operators have no capped form)."""
+    import functools
+
+    import ring_flash_attn as pkg
+    from .backend import check_softcap, softcap_scope
+
+    public = {id(getattr(pkg, n)): n for n in dir(pkg) if n.endswith("_func")}
+    if id(func) not in public:
+        raise TypeError("ring_flash_attn.with_softcap: `func` must be one of the package's public attention functions "
+                        f"(ring_flash_attn.*_func), got {func!r}")
+    cap = check_softcap(softcap)
+    if not cap:
+        return func
+
+    # (updated=(): `func`'s own attributes are not copied — a function that is already opaque to dynamo carries the marker
+    #  that makes torch.compiler.disable unwrap to ITS original, which would drop this wrapper)
+    @functools.wraps(func, updated=())
+    def capped(*args, **kwargs):
+        with softcap_scope(cap):
+            return func(*args, **kwargs)
+
+    return _opaque(capped)
+
+
 def has_window(window_size) -> bool:
     return window_size is not None and (window_size[0] >= 0 or window_size[1] >= 0)
 
@@ -224,6 +288,7 @@ def make_autograd_function(name, forward_impl, backward_impl, n_lead, window_rin
             _check_unsupported(dropout_p, window_size, alibi_slopes, windows_ok=single or window_ring, dropout_ok=single or dropout_ring,
                                alibi_ok=single or alibi_ring)
             alibi_slopes = checked_alibi(alibi_slopes, q, (len(lead[0]) - 1) if n_lead else q.shape[0], name)
+            ctx.softcap = checked_softcap(dropout_p, alibi_slopes, q, name, window_size, causal)
             q, k, v = _prep_qkv(q, k, v, group)
             tensors_lead = ()
             if n_lead:
@@ -234,10 +299,11 @@ def make_autograd_function(name, forward_impl, backward_impl, n_lead, window_rin
             ctx.dropout = (dropout_p, draw_dropout_seed()) if dropout_p and dropout_p > 0 else (0.0, None)
             if ctx.dropout[1] is not None:
                 extra["dropout_seed"] = ctx.dropout[1]
-            out, softmax_lse = forward_impl(
-                group, q, k, v, *lead, softmax_scale=softmax_scale, dropout_p=dropout_p, causal=causal,
-                window_size=window_size, alibi_slopes=alibi_slopes, deterministic=False, **extra,
-            )
+            with softcap_scope(ctx.softcap):
+                out, softmax_lse = forward_impl(
+                    group, q, k, v, *lead, softmax_scale=softmax_scale, dropout_p=dropout_p, causal=causal,
+                    window_size=window_size, alibi_slopes=alibi_slopes, deterministic=False, **extra,
+                )
             audit_verify(group, f"{name} forward")          # (config.exchange_check: a no-op otherwise)
             ctx.save_for_backward(q, k, v, out, softmax_lse, *tensors_lead, *(keep or ()))
             _hold_kept(ctx, keep)
@@ -257,11 +323,12 @@ def make_autograd_function(name, forward_impl, backward_impl, n_lead, window_rin
             tensors_lead, extra = _split_kept(ctx, more)
             if ctx.dropout[1] is not None:
                 extra["dropout_seed"] = ctx.dropout[1]
-            dq, dk, dv = backward_impl(
-                ctx.group, dout, q, k, v, out, softmax_lse, *tensors_lead, *ctx.lead_rest,
-                softmax_scale=ctx.softmax_scale, dropout_p=ctx.dropout[0], causal=ctx.causal,
-                window_size=ctx.window_size, alibi_slopes=ctx.alibi_slopes, deterministic=ctx.deterministic, **extra,
-            )
+            with softcap_scope(ctx.softcap):
+                dq, dk, dv = backward_impl(
+                    ctx.group, dout, q, k, v, out, softmax_lse, *tensors_lead, *ctx.lead_rest,
+                    softmax_scale=ctx.softmax_scale, dropout_p=ctx.dropout[0], causal=ctx.causal,
+                    window_size=ctx.window_size, alibi_slopes=ctx.alibi_slopes, deterministic=ctx.deterministic, **extra,
+                )
             _release_kept(ctx)
             audit_verify(ctx.group, f"{name} backward")
             return (dq, dk, dv) + (None,) * (n_lead + 8)
@@ -295,6 +362,7 @@ def make_packed_function(name, base_fn, forward_impl, backward_impl, n_lead, pac
             _check_unsupported(dropout_p, window_size, alibi_slopes, windows_ok=single or window_ring, dropout_ok=single or dropout_ring,
                                alibi_ok=single or alibi_ring)
             alibi_slopes = checked_alibi(alibi_slopes, q, (len(lead[0]) - 1) if n_lead else q.shape[0], name)
+            ctx.softcap = checked_softcap(dropout_p, alibi_slopes, q, name, window_size, causal)
             q, k, v = _prep_qkv(q, k, v, group, packed_travel=packed_travel and n_packed == 2)
             tensors_lead = ()
             if n_lead:
@@ -305,10 +373,11 @@ def make_packed_function(name, base_fn, forward_impl, backward_impl, n_lead, pac
             ctx.dropout = (dropout_p, draw_dropout_seed()) if dropout_p and dropout_p > 0 else (0.0, None)
             if ctx.dropout[1] is not None:
                 extra["dropout_seed"] = ctx.dropout[1]
-            out, softmax_lse = forward_impl(
-                group, q, k, v, *lead, softmax_scale=softmax_scale, dropout_p=dropout_p, causal=causal,
-                window_size=window_size, alibi_slopes=alibi_slopes, deterministic=False, **extra,
-            )
+            with softcap_scope(ctx.softcap):
+                out, softmax_lse = forward_impl(
+                    group, q, k, v, *lead, softmax_scale=softmax_scale, dropout_p=dropout_p, causal=causal,
+                    window_size=window_size, alibi_slopes=alibi_slopes, deterministic=False, **extra,
+                )
             audit_verify(group, f"{name} forward")          # (config.exchange_check: a no-op otherwise)
             ctx.save_for_backward(q, k, v, out, softmax_lse, *tensors_lead, *(keep or ()))
             _hold_kept(ctx, keep)
@@ -336,12 +405,13 @@ def make_packed_function(name, base_fn, forward_impl, backward_impl, n_lead, pac
                 out_grads = (None, views[0], views[1])
             if ctx.dropout[1] is not None:
                 extra["dropout_seed"] = ctx.dropout[1]
-            dq, dk, dv = backward_impl(
-                ctx.group, dout, q, k, v, out, softmax_lse, *tensors_lead, *ctx.lead_rest,
-                softmax_scale=ctx.softmax_scale, dropout_p=ctx.dropout[0], causal=ctx.causal,
-                window_size=ctx.window_size, alibi_slopes=ctx.alibi_slopes, deterministic=ctx.deterministic,
-                out_grads=out_grads, **extra,
-            )
+            with softcap_scope(ctx.softcap):
+                dq, dk, dv = backward_impl(
+                    ctx.group, dout, q, k, v, out, softmax_lse, *tensors_lead, *ctx.lead_rest,
+                    softmax_scale=ctx.softmax_scale, dropout_p=ctx.dropout[0], causal=ctx.causal,
+                    window_size=ctx.window_size, alibi_slopes=ctx.alibi_slopes, deterministic=ctx.deterministic,
+                    out_grads=out_grads, **extra,
+                )
             got = (dq, dk, dv)[3 - n_packed:]
             for view, g in zip(views, got):
                 if g.data_ptr() != view.data_ptr():       # schedule returned its own tensor

@@ -25,6 +25,7 @@ from typing import Optional, Tuple
 import torch
 import torch.distributed as dist
 
+from .._api import with_softcap
 from ..llama3_flash_attn_varlen import (
     llama3_flash_attn_varlen_func,
     llama3_flash_attn_prepare_cu_seqlens,
@@ -77,14 +78,16 @@ def _ring_attention(query_states, key_states, value_states, *, dropout, softmax_
     window_size = (-1, -1)
     if sliding_window is not None and key_states.shape[1] > sliding_window:
         window_size = (sliding_window, sliding_window)
-    assert softcap is None, "llama3_flash_attn_varlen_func does not support softcap yet."
     assert causal, "only causal attention is supported yet."
     assert query_states.size(0) == 1, "varlen data should be processed in advance."
     if not DATA_PARAMS:
         raise RuntimeError("call update_ring_flash_attn_params(cu_seqlens, group) before the model forward")
     if deterministic is None:
         deterministic = os.environ.get("FLASH_ATTENTION_DETERMINISTIC", "0") == "1"
-    attn_output = llama3_flash_attn_varlen_func(
+    # a configured logit soft cap (Gemma-2: 50.0, together with the sliding window on alternating layers) is applied in
+    # the kernels: with_softcap binds it to this one call (None / 0: the function itself)
+    attn_func = llama3_flash_attn_varlen_func if softcap is None else with_softcap(llama3_flash_attn_varlen_func, softcap)
+    attn_output = attn_func(
         query_states.squeeze(dim=0),
         key_states.squeeze(dim=0),
         value_states.squeeze(dim=0),

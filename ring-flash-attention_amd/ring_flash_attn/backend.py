@@ -58,6 +58,7 @@ class HipBackend:
     serves_mask_shift = True        # fwd / bwd take `mask_shift` (include/rfa.h, ABI 7): what a windowed multi-rank schedule needs
     serves_mask_shift_lens = True   # ... and `mask_shift_lens` (ABI 8), the per-sequence shift the packed (varlen) ring schedules need
     serves_alibi = True             # fwd / bwd take `alibi=(slopes, shift)` (include/rfa.h: rfa_ext_args)
+    serves_softcap = True           # ... and `softcap=` (flash_attn's logit soft-capping: rfa_ext_args.softcap)
     serves_dropout_positions = True  # `dropout=` takes the position maps (q_map, k_map): what dropout over a dense ring, zigzag or stripe schedule needs
 
     def __init__(self):
@@ -86,7 +87,7 @@ class HipBackend:
     def fwd(self, q, k, v, *, softmax_scale, causal, cu_seqlens_q=None, cu_seqlens_k=None,
             max_seqlen_q=None, max_seqlen_k=None, q_half=HALF_FULL, k_half=HALF_FULL,
             out=None, lse=None, out_acc=None, lse_acc=None, acc_init=False, window=(-1, -1), dropout=None,
-            mask_shift=0, mask_shift_lens=0, alibi=None):
+            mask_shift=0, mask_shift_lens=0, alibi=None, softcap=0.0):
         """Block attention.  Plain mode fills (out, lse); accumulate mode merges into the fp32
         (out_acc, lse_acc) pair (fused update_out_and_lse).  Dense: q (B,Sq,H,D); varlen: (T,H,D).
         dropout: (p, seed, q_pos_offset, k_pos_offset, head_offset), the same plus the position maps (q_map, k_map) —
@@ -96,7 +97,9 @@ class HipBackend:
         mask_shift_lens: the same in units of every sequence's own key length (include/rfa.h, ABI 8): the shift of packed
         (cu_seqlens) input; dense input folds it into mask_shift.
         alibi: (slopes, shift) or None — fp32 slopes (H,) or (B, H) on q's device and the block's alibi_shift
-        (include/rfa.h: rfa_ext_args; _common.alibi_arg validates and builds it)."""
+        (include/rfa.h: rfa_ext_args; _common.alibi_arg validates and builds it).
+        softcap: scores become softcap * tanh(softmax_scale * q.k / softcap) in front of the mask (include/rfa.h:
+        rfa_ext_args.softcap); 0 is off — the plain call."""
         self._check_dev(q, k, v, out, lse, out_acc, lse_acc)
         varlen = cu_seqlens_q is not None
         a = _C.FwdArgs()
@@ -134,8 +137,8 @@ class HipBackend:
         a.kv_nsplit = config.get().fwd_kv_nsplit
         # split-KV launches (few query rows against many keys on an under-filled grid: include/rfa.h) need a small
         # workspace for the partial (out, lse) pairs: a few tens of MB, only for the calls that split
-        ext = _ext_args(alibi, q)
-        if ext is not None:                       # a bias is never split: no workspace (include/rfa.h)
+        ext = _ext_args(alibi, q, softcap)
+        if ext is not None:                       # a bias or a cap is never split: no workspace (include/rfa.h)
             _C.check(self.lib.rfa_fwd_ex(C.byref(a), C.byref(ext), _stream(q)), "rfa_fwd_ex")
             return
         ws = None
@@ -169,7 +172,8 @@ class HipBackend:
             cu_seqlens_k=None, max_seqlen_q=None, max_seqlen_k=None, q_half=HALF_FULL,
             k_half=HALF_FULL, dq=None, dk=None, dv=None, dq_acc=None, dk_acc=None, dv_acc=None,
             acc_init=False, deterministic=False, phases=_C.BWD_ALL, partials=None, ds_scratch=None,
-            window=(-1, -1), prof_events=None, dropout=None, mask_shift=0, mask_shift_lens=0, alibi=None):
+            window=(-1, -1), prof_events=None, dropout=None, mask_shift=0, mask_shift_lens=0, alibi=None,
+            softcap=0.0):
         """dQ/dK/dV of one block.  Plain outputs (io dtype) or `+=` into fp32 accumulators.
         phases=BWD_COMPUTE / BWD_REDUCE splits the call so a ring step can overlap the kernels
         with the arrival of the dk/dv accumulators it adds into: the COMPUTE call RETURNS the buffer
@@ -177,7 +181,7 @@ class HipBackend:
         so interleaved backwards (other streams, re-entrant / checkpointed autograd, pipeline
         micro-batches) can never consume each other's partials.  Scratch comes from torch's caching
         allocator on the current stream, per call; the C library itself never allocates.
-        alibi: as in fwd, with the forward's values; such a call names the 128-key dK/dV form and takes no dS scratch —
+        alibi, softcap: as in fwd, with the forward's values; such a call names the 128-key dK/dV form and takes no dS scratch —
         what rfa_bwd_ex asks of the base arguments (include/rfa.h)."""
         self._check_dev(dout, q, k, v, lse, delta, dq, dk, dv, dq_acc, dk_acc, dv_acc)
         varlen = cu_seqlens_q is not None
@@ -239,7 +243,7 @@ class HipBackend:
         # large: a hand-off that does not fit runs in head-group chunks over it (include/rfa.h: ds_scratch_bytes).
         # config.bwd_ds_spill = False (RFA_BWD_DS_SPILL=0) keeps the 7-GEMM form.  Callers that split one backward over
         # several calls (measurement: BWD_SKIP_DQ / BWD_SKIP_DKDV) pass the same `ds_scratch` to both.
-        ext = _ext_args(alibi, q)
+        ext = _ext_args(alibi, q, softcap)
         if ext is not None:
             a.dkdv_form, a.dkdv_nsplit, ds_scratch = _C.DKDV_128, 0, None
         if ext is None and ds_scratch is None and not reduce_only and _spill_enabled():
@@ -467,10 +471,15 @@ def _set_dropout(a, dropout):
             tuple(int(x) for x in m) for m in dropout[5:7])
 
 
-def _ext_args(alibi, q):
-    """rfa_ext_args of a call with `alibi=(slopes, shift)`, or None: the call without the extension"""
+def _ext_args(alibi, q, softcap=0.0):
+    """rfa_ext_args of a call with `alibi=(slopes, shift)` and / or `softcap`, or None: the call without the extension"""
+    softcap = check_softcap(softcap)
     if alibi is None or alibi[0] is None:
-        return None
+        if not softcap:
+            return None
+        ext = _C.ExtArgs()
+        ext.softcap = softcap
+        return ext
     slopes, shift = alibi
     if slopes.dtype != torch.float32 or slopes.device != q.device or slopes.dim() not in (1, 2) or slopes.stride(-1) != 1:
         raise ValueError("alibi slopes must be a float32 tensor of shape (H,) or (B, H), innermost stride 1, on q's device")
@@ -478,7 +487,18 @@ def _ext_args(alibi, q):
     ext.alibi_slopes = slopes.data_ptr()
     ext.alibi_batch_stride = slopes.stride(0) if slopes.dim() == 2 else 0
     ext.alibi_shift = int(shift)
+    ext.softcap = softcap
     return ext
+
+
+def check_softcap(softcap):
+    """flash_attn's softcap as a float: None and 0 are off (0.0); a negative or non-finite value is a ValueError"""
+    import math
+
+    cap = 0.0 if softcap is None else float(softcap)
+    if not math.isfinite(cap) or cap < 0.0:
+        raise ValueError(f"ring_flash_attn: softcap must be a finite number >= 0 (0: off); got {softcap!r}")
+    return cap
 
 
 _FWD_FORMS = {"auto": _C.FWD_AUTO, "8x32": _C.FWD_8x32, "4x32": _C.FWD_4x32, "p8x32": _C.FWD_P8x32}
@@ -533,8 +553,68 @@ _backend = None
 
 def get_backend():
     """the operator backend of this process: the HIP library (raises if librfa_hip.so is missing — there is no CPU
-    path).  Tests and bench.py's in-step timer replace it through ring_flash_attn._testing.set_backend."""
+    path).  Tests and bench.py's in-step timer replace it through ring_flash_attn._testing.set_backend.
+    Inside `softcap_scope(cap)` with cap > 0 — the forward or the backward of ONE capped autograd node — the backend comes
+    wrapped so that every block call carries `softcap=cap`."""
     global _backend
     if _backend is None:
         _backend = HipBackend()
-    return _backend
+    cap = _softcap.get()
+    return _CappedBackend(_backend, cap) if cap else _backend
+
+
+# ---- logit soft-capping (ring_flash_attn.with_softcap) ------------------------------------------------------------------
+# The cap is a pointwise function of one score: unlike a window, dropout or a bias it needs nothing about where a block sits,
+# so no schedule computes anything for it — every block call of a capped forward or backward simply carries the one value.
+# That is done HERE, once, instead of at each of the schedules' call sites: a schedule asks get_backend() for its backend at
+# the start of its forward and of its backward, and gets this wrapper while its autograd node runs under softcap_scope.  The
+# scope is private and is entered by the autograd Functions only (forward: the value with_softcap bound to the call;
+# backward: the value kept on the node) — nothing ambient is read in a backward.
+import contextvars
+
+_softcap = contextvars.ContextVar("ring_flash_attn_softcap", default=0.0)
+
+
+class softcap_scope:
+    """`with softcap_scope(cap):` — block calls made inside carry softcap=cap (0: none; an enclosing scope is masked)"""
+
+    def __init__(self, cap):
+        self.cap = check_softcap(cap)
+
+    def __enter__(self):
+        self.token = _softcap.set(self.cap)
+        return self
+
+    def __exit__(self, *exc):
+        _softcap.reset(self.token)
+        return False
+
+
+def pending_softcap():
+    """the cap bound to the public call that is running (with_softcap), 0.0 without one"""
+    return _softcap.get()
+
+
+class _CappedBackend:
+    """a backend whose fwd / bwd carry `softcap=`; everything else — attributes, scratch, the other operators — is the
+    wrapped backend's own.  A backend that does not serve a cap is refused when the wrapper is made, i.e. before the
+    schedule exchanges anything, on every rank alike."""
+
+    def __init__(self, be, cap):
+        if not getattr(be, "serves_softcap", False):
+            raise NotImplementedError(f"ring_flash_attn: softcap needs a backend that serves `softcap`; "
+                                      f"{getattr(be, 'name', type(be).__name__)!r} does not (it would ignore the cap)")
+        object.__setattr__(self, "_be", be)
+        object.__setattr__(self, "_cap", cap)
+
+    def __getattr__(self, name):
+        return getattr(self._be, name)
+
+    def __setattr__(self, name, value):
+        setattr(self._be, name, value)
+
+    def fwd(self, *args, **kw):
+        return self._be.fwd(*args, softcap=self._cap, **kw)
+
+    def bwd(self, *args, **kw):
+        return self._be.bwd(*args, softcap=self._cap, **kw)

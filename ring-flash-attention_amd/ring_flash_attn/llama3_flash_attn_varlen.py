@@ -27,7 +27,7 @@ import torch
 from . import config
 from .backend import get_backend
 from .utils import AllGatherComm as Comm, group_rank_world, reduce_scatter_async, single_rank
-from ._api import _check_unsupported, _opaque, checked_alibi, window_ok_for
+from ._api import _check_unsupported, _opaque, checked_alibi, checked_softcap, softcap_scope, window_ok_for
 from ._common import alibi_kw, _as_cu, dropout_arg, draw_dropout_seed, packed_pair
 
 
@@ -320,17 +320,19 @@ def _l3_forward(ctx, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seql
     # alignment against the truncated cu_seqlens_k yields it for causal calls only (the slopes are sliced per head group)
     _check_unsupported(dropout_p, window_size, alibi_slopes, windows_ok=True, alibi_ok=window_ok_for(group) or bool(causal))
     alibi_slopes = checked_alibi(alibi_slopes, q, len(cu_seqlens_q) - 1, "llama3_flash_attn_varlen_func")
+    ctx.softcap = checked_softcap(dropout_p, alibi_slopes, q, "llama3_flash_attn_varlen_func", window_size, causal)
     # (strided views — the halves of a packed kv — are fine: the kernels take strides, and the all-gather sources are
     #  made contiguous per head group where they are posted)
     q, k, v = (t if t.stride(-1) == 1 else t.contiguous() for t in (q, k, v))
     cu_seqlens_q = _as_cu(cu_seqlens_q, q.device)
     cu_seqlens_k = _as_cu(cu_seqlens_k, q.device)
     ctx.dropout = (dropout_p, draw_dropout_seed()) if dropout_p and dropout_p > 0 else (0.0, None)
-    out, softmax_lse = llama3_flash_attn_varlen_forward(
-        group, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, heads_k_stride,
-        local_k_slice, softmax_scale=softmax_scale, dropout_p=dropout_p, causal=causal,
-        window_size=window_size, alibi_slopes=alibi_slopes, deterministic=False, dropout_seed=ctx.dropout[1],
-    )
+    with softcap_scope(ctx.softcap):
+        out, softmax_lse = llama3_flash_attn_varlen_forward(
+            group, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, heads_k_stride,
+            local_k_slice, softmax_scale=softmax_scale, dropout_p=dropout_p, causal=causal,
+            window_size=window_size, alibi_slopes=alibi_slopes, deterministic=False, dropout_seed=ctx.dropout[1],
+        )
     ctx.save_for_backward(q, k, v, out, softmax_lse, cu_seqlens_q, cu_seqlens_k)
     ctx.static = (max_seqlen_q, max_seqlen_k, heads_k_stride, local_k_slice)
     ctx.softmax_scale = softmax_scale
@@ -344,11 +346,12 @@ def _l3_forward(ctx, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seql
 
 def _l3_backward(ctx, dout, grads=None):
     q, k, v, out, softmax_lse, cu_seqlens_q, cu_seqlens_k = ctx.saved_tensors
-    return llama3_flash_attn_varlen_backward(
-        ctx.group, dout, q, k, v, out, softmax_lse, cu_seqlens_q, cu_seqlens_k, *ctx.static,
-        softmax_scale=ctx.softmax_scale, dropout_p=ctx.dropout[0], causal=ctx.causal, window_size=ctx.window_size,
-        alibi_slopes=ctx.alibi_slopes, deterministic=ctx.deterministic, dropout_seed=ctx.dropout[1], grads=grads,
-    )
+    with softcap_scope(ctx.softcap):
+        return llama3_flash_attn_varlen_backward(
+            ctx.group, dout, q, k, v, out, softmax_lse, cu_seqlens_q, cu_seqlens_k, *ctx.static,
+            softmax_scale=ctx.softmax_scale, dropout_p=ctx.dropout[0], causal=ctx.causal, window_size=ctx.window_size,
+            alibi_slopes=ctx.alibi_slopes, deterministic=ctx.deterministic, dropout_seed=ctx.dropout[1], grads=grads,
+        )
 
 
 class Llama3FlashAttnVarlenFunc(torch.autograd.Function):

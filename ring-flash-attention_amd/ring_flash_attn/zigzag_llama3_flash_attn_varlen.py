@@ -26,7 +26,7 @@ llama3_flash_attn_varlen_func; all heads are processed per call.
 """
 import torch
 
-from ._api import _check_unsupported, _opaque, checked_alibi, window_ok_for
+from ._api import _check_unsupported, _opaque, checked_alibi, checked_softcap, softcap_scope, window_ok_for
 from ._common import _as_cu, alibi_kw
 from .backend import get_backend
 from .llama3_flash_attn_varlen import llama3_flash_attn_prepare_cu_seqlens
@@ -136,6 +136,7 @@ class ZigZagLlama3FlashAttnVarlenFunc(torch.autograd.Function):
             raise NotImplementedError("zigzag_llama3_flash_attn_varlen_func: alibi_slopes per sequence, (B, H), are not "
                                       "supported (the two stream slices hold different sequences); pass (H,)")
         alibi_slopes = checked_alibi(alibi_slopes, q, 0, "zigzag_llama3_flash_attn_varlen_func")
+        ctx.softcap = checked_softcap(dropout_p, alibi_slopes, q, "zigzag_llama3_flash_attn_varlen_func", window_size, causal)
         if dropout_p and dropout_p > 0:
             raise NotImplementedError("zigzag_llama3_flash_attn_varlen_func: dropout is not supported")
         if q.shape[0] % 2 != 0 or k.shape[0] != q.shape[0] or v.shape[0] != q.shape[0]:
@@ -150,8 +151,9 @@ class ZigZagLlama3FlashAttnVarlenFunc(torch.autograd.Function):
             raise ValueError(f"zigzag_llama3: cu_seqlens ends at {int(host[-1])}, the ranks hold {q.shape[0] * world} tokens")
         params = tuple((_as_cu(cq, q.device), _as_cu(ck, q.device), mq, mk, sl)
                        for cq, ck, mq, mk, sl in zigzag_llama3_flash_attn_prepare_cu_seqlens(host, causal, rank, world))
-        out, lse = zigzag_llama3_flash_attn_varlen_forward(group, q, k, v, params, softmax_scale, causal, window_size,
-                                                           alibi_slopes)
+        with softcap_scope(ctx.softcap):
+            out, lse = zigzag_llama3_flash_attn_varlen_forward(group, q, k, v, params, softmax_scale, causal, window_size,
+                                                               alibi_slopes)
         ctx.alibi_slopes = alibi_slopes
         ctx.save_for_backward(q, k, v, out, lse)
         ctx.params = params
@@ -162,8 +164,9 @@ class ZigZagLlama3FlashAttnVarlenFunc(torch.autograd.Function):
     def backward(ctx, dout, *args):
         q, k, v, out, lse = ctx.saved_tensors
         softmax_scale, causal, window_size, deterministic, group = ctx.meta
-        dq, dk, dv = zigzag_llama3_flash_attn_varlen_backward(group, dout, q, k, v, out, lse, ctx.params, softmax_scale,
-                                                              causal, window_size, deterministic, ctx.alibi_slopes)
+        with softcap_scope(ctx.softcap):
+            dq, dk, dv = zigzag_llama3_flash_attn_varlen_backward(group, dout, q, k, v, out, lse, ctx.params, softmax_scale,
+                                                                  causal, window_size, deterministic, ctx.alibi_slopes)
         return (dq, dk, dv) + (None,) * 10
 
 
