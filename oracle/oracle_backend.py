@@ -58,16 +58,38 @@ def _drop(dropout, bq, qs, ks):
     return dict(p=float(p), seed=int(seed), batch=0, head0=h0, q_pos0=q0 + qs, k_pos0=k0 + ks)
 
 
+def _merged(out_acc, lse_acc, o, l):
+    """the reference's merge of a block result into the accumulated one: out (..., S, H, D), lse (..., H, S) -> the new pair"""
+    bl = l.transpose(-1, -2).unsqueeze(-1)                      # (..., S, H, 1)
+    cur = lse_acc.transpose(-1, -2).unsqueeze(-1)
+    new_o = out_acc - torch.sigmoid(bl - cur) * (out_acc - o.float())
+    new_l = cur - F.logsigmoid(cur - bl)
+    return new_o, new_l.squeeze(-1).transpose(-1, -2)
+
+
 class OracleBackend:
     name = "oracle"
+
+    # ------------------------------------------------------------------ one sequence's block
+    # What fwd / bwd deliver.  seq = (index of the sequence in the call, its batch index or None for packed input, its first
+    # q row, its first k row).  A subclass that serves more keywords than this class (tests/_ref_backend.py) overrides these
+    # two and takes the keywords as **ext; here an unknown keyword is a TypeError.
+    def _fwd_block(self, seq, q, k, v, scale, causal, window, dropout):
+        """(out (l,H,D), lse fp32 (H,l), +inf for a row without a key)"""
+        return R._fwd_one(q, k, v, scale, causal, window, drop=_drop(dropout, *seq[1:]))
+
+    def _bwd_block(self, seq, dout, q, k, v, lse, delta, scale, causal, window, dropout):
+        """(dq (l,H,D), dk, dv (lk,Hk,D)) from the rows' lse and delta, both (H,l)"""
+        return R._bwd_one(dout, q, k, v, None, lse, scale, causal, delta=delta, window=window, drop=_drop(dropout, *seq[1:]))
 
     # ------------------------------------------------------------------ forward
     def fwd(self, q, k, v, *, softmax_scale, causal, cu_seqlens_q=None, cu_seqlens_k=None,
             max_seqlen_q=None, max_seqlen_k=None, q_half=0, k_half=0, out=None, lse=None,
-            out_acc=None, lse_acc=None, acc_init=False, window=(-1, -1), dropout=None):
-        for (bq, qs, ql), (bk, ks, kl) in zip(_seqs(q, cu_seqlens_q, q_half), _seqs(k, cu_seqlens_k, k_half)):
-            o, l = R._fwd_one(_rows(q, bq, qs, ql), _rows(k, bk, ks, kl), _rows(v, bk, ks, kl), softmax_scale, causal,
-                              window, drop=_drop(dropout, bq, qs, ks))
+            out_acc=None, lse_acc=None, acc_init=False, window=(-1, -1), dropout=None, **ext):
+        pairs = zip(_seqs(q, cu_seqlens_q, q_half), _seqs(k, cu_seqlens_k, k_half))
+        for n, ((bq, qs, ql), (bk, ks, kl)) in enumerate(pairs):
+            o, l = self._fwd_block((n, bq, qs, ks), _rows(q, bq, qs, ql), _rows(k, bk, ks, kl), _rows(v, bk, ks, kl),
+                                   softmax_scale, causal, window, dropout, **ext)
             o = o.to(q.dtype)                       # flash_attn returns out in the io dtype
             if out_acc is None:
                 _rows(out, bq, qs, ql).copy_(o)
@@ -80,13 +102,9 @@ class OracleBackend:
                 la.copy_(torch.where(torch.isinf(l) & (l > 0), torch.full_like(l, float("-inf")), l))
                 continue
             keep = torch.isinf(l) & (l > 0)                     # rows without keys: untouched
-            bl = l.transpose(0, 1).unsqueeze(-1)                # (l,H,1)
-            cur = la.transpose(0, 1).unsqueeze(-1)
-            new_o = oa - torch.sigmoid(bl - cur) * (oa - o.float())
-            new_l = cur - F.logsigmoid(cur - bl)
-            k3 = keep.transpose(0, 1).unsqueeze(-1)
-            oa.copy_(torch.where(k3, oa, new_o))
-            la.copy_(torch.where(keep, la, new_l.squeeze(-1).transpose(0, 1)))
+            new_o, new_l = _merged(oa, la, o, l)
+            oa.copy_(torch.where(keep.transpose(0, 1).unsqueeze(-1), oa, new_o))
+            la.copy_(torch.where(keep, la, new_l))
 
     # ------------------------------------------------------------------ backward
     def bwd_preprocess(self, dout, out, delta, *, cu_seqlens_q=None, max_seqlen_q=None, q_half=0):
@@ -100,17 +118,16 @@ class OracleBackend:
             cu_seqlens_k=None, max_seqlen_q=None, max_seqlen_k=None, q_half=0, k_half=0,
             dq=None, dk=None, dv=None, dq_acc=None, dk_acc=None, dv_acc=None, acc_init=False,
             deterministic=False, phases=BWD_ALL, partials=None, ds_scratch=None, window=(-1, -1), dropout=None,
-            prof_events=None):
+            prof_events=None, **ext):
         pairs = list(zip(_seqs(q, cu_seqlens_q, q_half), _seqs(k, cu_seqlens_k, k_half)))
         kv_init = acc_init or bool(phases & 16)          # RFA_BWD_KV_OVERWRITE (include/rfa.h)
         phases &= 3
         if phases in (BWD_ALL, BWD_COMPUTE):
             pend = []
-            for (bq, qs, ql), (bk, ks, kl) in pairs:
-                gq, gk, gv = R._bwd_one(_rows(dout, bq, qs, ql), _rows(q, bq, qs, ql), _rows(k, bk, ks, kl),
-                                        _rows(v, bk, ks, kl), None, _lse_rows(lse, bq, qs, ql), softmax_scale,
-                                        causal, delta=_lse_rows(delta, bq, qs, ql), window=window,
-                                        drop=_drop(dropout, bq, qs, ks))
+            for n, ((bq, qs, ql), (bk, ks, kl)) in enumerate(pairs):
+                gq, gk, gv = self._bwd_block((n, bq, qs, ks), _rows(dout, bq, qs, ql), _rows(q, bq, qs, ql),
+                                             _rows(k, bk, ks, kl), _rows(v, bk, ks, kl), _lse_rows(lse, bq, qs, ql),
+                                             _lse_rows(delta, bq, qs, ql), softmax_scale, causal, window, dropout, **ext)
                 gq, gk, gv = gq.to(q.dtype), gk.to(q.dtype), gv.to(q.dtype)   # flash_attn rounds here
                 if dq_acc is not None:
                     t = _rows(dq_acc, bq, qs, ql)
@@ -145,12 +162,9 @@ class OracleBackend:
             out_acc.copy_(block_out.float())
             lse_acc.copy_(block_lse)
             return
-        bl = block_lse.transpose(1, 2).unsqueeze(-1)            # (B,S,H,1)
-        cur = lse_acc.transpose(1, 2).unsqueeze(-1)
-        new_o = out_acc - torch.sigmoid(bl - cur) * (out_acc - block_out.float())
-        new_l = cur - F.logsigmoid(cur - bl)
+        new_o, new_l = _merged(out_acc, lse_acc, block_out, block_lse)
         out_acc.copy_(new_o)
-        lse_acc.copy_(new_l.squeeze(-1).transpose(1, 2))
+        lse_acc.copy_(new_l)
 
     def sum_slots(self, src, dst):
         dst.copy_(src.float().sum(dim=0).to(dst.dtype))

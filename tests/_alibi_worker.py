@@ -1,7 +1,7 @@
 """Worker of the multi-rank ALiBi tests (dense ring, zigzag, llama3): one gloo rank runs the public functions with
 alibi_slopes on its shard of a seeded sequence and hands out / lse / dq / dk / dv back; the parent un-shards them by the
-schedule's own layout and compares with ONE single-device biased call (tests/_alibi_ref.py, fp64).  Backend: the CPU
-oracle with `alibi=` (tests/_alibi_backend.py) or the HIP kernels with every rank sharing cuda:0."""
+schedule's own layout and compares with ONE single-device biased call (tests/_blockref.py, fp64).  Backend: the CPU
+oracle with `alibi=` (tests/_ref_backend.py) or the HIP kernels with every rank sharing cuda:0."""
 import os
 import sys
 import traceback
@@ -73,7 +73,7 @@ def call(R, c, q, k, v, slopes, rank, dev):
 def _refusals(R, rank, W, dev):
     """what must raise on a multi-rank group — NotImplementedError before anything is exchanged, ValueError for slopes
     that are not fp32 (H,) / (B, H) on the device: list of complaints"""
-    from _band_backend import BandBackend
+    from _ref_backend import RefBackend
     from ring_flash_attn import _api, _testing, utils
 
     bad = []
@@ -122,7 +122,7 @@ def _refusals(R, rank, W, dev):
         # the torch.compile whole-schedule operators call the check without alibi_ok
         raises(NI, "the whole-schedule operator's check", _api._check_unsupported, 0.0, (-1, -1), sl, windows_ok=False)
         if dev.type == "cpu":
-            _testing.set_backend(BandBackend())                  # serves mask_shift, not alibi
+            _testing.set_backend(RefBackend(serves=("mask_shift",)))                  # serves mask_shift, not alibi
             for fn in (R.ring_flash_attn_func, R.zigzag_ring_flash_attn_func):
                 raises(NI, fn.__name__ + " on a backend without alibi", fn, q, q, q, causal=True, alibi_slopes=sl)
         if posted[0]:
@@ -146,10 +146,10 @@ def run_rank(rank, W, port, cases, use_hip, ret):
             _testing.allow_host_staging(True)                    # several gloo ranks share this one GPU
             backend = None                                       # the product's: HipBackend
         else:
-            from _alibi_backend import AlibiBackend
+            from _ref_backend import RefBackend
 
             dev = torch.device("cpu")
-            backend = AlibiBackend()
+            backend = RefBackend(serves=("mask_shift", "alibi"))
         for c in cases:
             _testing.set_backend(backend)
             if c.get("refusals"):
@@ -206,15 +206,15 @@ def run_world(W, cases, use_hip, port, limit_s=300):
 
 
 def reference(c):
-    """the ONE single-device biased call on the unsharded tensors, fp64 (tests/_alibi_ref.py): (out, lse, dq, dk, dv), and
+    """the ONE single-device biased call on the unsharded tensors, fp64 (tests/_blockref.py): (out, lse, dq, dk, dv), and
     the unbiased out (to see that the bias did something)"""
-    import _alibi_ref as AR
+    import _blockref as AR
 
     q, k, v, do = inputs(c)
-    kw = dict(causal=c["causal"], dout=do)
+    kw = dict(causal=c["causal"], dout=do, autograd=True)
     if c["kind"] == "llama3":
         cu = l3_cu(c).tolist()
         kw.update(cu_seqlens_q=cu, cu_seqlens_k=cu)
-    ref = AR.attention(q, k, v, slopes_of(c), **kw)
+    ref = AR.attention(q, k, v, slopes=slopes_of(c), **kw)
     kw.pop("dout")
-    return ref, AR.attention(q, k, v, None, **kw)[0]
+    return ref, AR.attention(q, k, v, **kw)[0]

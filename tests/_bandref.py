@@ -1,5 +1,5 @@
-"""Shifted attention bands: the fp64 reference, what a band looks like from its mask alone, and the named list of block
-geometries the band tests run (tests/test_band_cases_cpu.py checks the list, tests/test_gpu_band_forms.py runs it through
+"""Shifted attention bands: the fp64 reference (from tests/_blockref.py), what a band looks like from its mask alone, and
+the named list of block geometries the band tests run (tests/test_band_cases_cpu.py checks the list, tests/test_gpu_band_forms.py runs it through
 every kernel form).  No test in here.
 
 A block's band (include/rfa.h, `mask_shift`): query row i sees key j iff
@@ -10,51 +10,16 @@ each side only when set (>= 0); `causal` means wr = 0.  The geometries are state
 diagonal inside the block — because that is what decides which clamp, tile range and in-tile mask a kernel takes."""
 import collections
 
-import torch
+from _blockref import attention, visible as band_mask
 
 BIG = 1 << 30
 
 
-def band_mask(lq, lk, causal, window, shift=0, device=None):
-    """(lq, lk) bool: True where the key is visible"""
-    wl, wr = window
-    if causal:
-        wr = 0
-    d = torch.arange(lk, device=device).view(1, -1) - torch.arange(lq, device=device).view(-1, 1)      # j - i, int64
-    off = lk - lq + int(shift)
-    vis = torch.ones(lq, lk, dtype=torch.bool, device=device)
-    if wr >= 0:
-        vis &= d <= off + wr
-    if wl >= 0:
-        vis &= d >= off - wl
-    return vis
-
-
 def band_ref(q, k, v, do, causal, window, shift=0):
-    """fp64 attention with the mask written out (band_mask), the block taken as the WHOLE attention: returns out, lse,
-    dq, dk, dv in fp64 — lse = +inf and out = 0 for rows without a key, block-local lse and delta: what a call with plain
-    outputs computes.  q, do (B, Sq, H, D); k, v (B, Sk, Hk, D)."""
-    B, Sq, H, D = q.shape
-    Sk, Hk = k.shape[1], k.shape[2]
-    G = H // Hk
-    qd, kd, vd, dod = (t.double() for t in (q, k, v, do))
-    ke, ve = kd.repeat_interleave(G, dim=2), vd.repeat_interleave(G, dim=2)
-    vis = band_mask(Sq, Sk, causal, window, shift, device=q.device)
-    s = torch.einsum("bqhd,bkhd->bhqk", qd, ke) * (D ** -0.5)
-    s = s.masked_fill(~vis, float("-inf"))
-    lse = torch.logsumexp(s, dim=-1)                                  # (B,H,Sq); -inf for empty rows
-    empty = torch.isinf(lse)
-    p = torch.exp(s - torch.where(empty, torch.zeros_like(lse), lse).unsqueeze(-1))
-    p = torch.where(vis, p, torch.zeros_like(p))
-    out = torch.einsum("bhqk,bkhd->bqhd", p, ve)
-    dp = torch.einsum("bqhd,bkhd->bhqk", dod, ve)
-    delta = (dod * out).sum(-1).permute(0, 2, 1)                      # (B,H,Sq)
-    ds = p * (dp - delta.unsqueeze(-1)) * (D ** -0.5)
-    dq = torch.einsum("bhqk,bkhd->bqhd", ds, ke)
-    dk = torch.einsum("bhqk,bqhd->bkhd", ds, qd).view(B, Sk, Hk, G, D).sum(3)
-    dv = torch.einsum("bhqk,bqhd->bkhd", p, dod).view(B, Sk, Hk, G, D).sum(3)
-    lse = torch.where(empty, torch.full_like(lse, float("inf")), lse)
-    return out, lse, dq, dk, dv
+    """_blockref.attention with the block taken as the WHOLE attention: out, lse, dq, dk, dv in fp64 — lse = +inf and out = 0
+    for rows without a key, block-local lse and delta: what a call with plain outputs computes.  q, do (B, Sq, H, D); k, v
+    (B, Sk, Hk, D)."""
+    return attention(q, k, v, dout=do, causal=causal, window=window, shift=shift)
 
 
 def classify(lq, lk, causal, window, shift):

@@ -2,7 +2,7 @@
 dropout on its shard of a seeded sequence and hands out / lse / dq / dk / dv back; the parent un-shards them by the
 schedule's own layout and compares with ONE single-device dropout call with the same seed.  Every rank seeds torch alike
 before each call, so all ranks — and the parent — draw the same dropout seed.  Backend: the CPU oracle with dropout
-position maps (tests/_droppos_backend.py) or the HIP kernels with every rank sharing cuda:0."""
+position maps (tests/_ref_backend.py) or the HIP kernels with every rank sharing cuda:0."""
 import os
 import sys
 import traceback
@@ -140,10 +140,10 @@ def run_rank(rank, W, port, cases, use_hip, ret):
             _testing.allow_host_staging(True)                    # several gloo ranks share this one GPU
             backend = None                                       # the product's: HipBackend
         else:
-            from _droppos_backend import DropPosBackend
+            from _ref_backend import RefBackend
 
             dev = torch.device("cpu")
-            backend = DropPosBackend()
+            backend = RefBackend(serves=("dropout_positions",))
         for c in cases:
             if c.get("refusals"):
                 _testing.set_backend(backend)

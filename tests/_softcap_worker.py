@@ -1,7 +1,7 @@
 """Worker of the multi-rank soft-capping tests: one gloo rank runs `with_softcap(<public function>, cap)` on its shard of a
-seeded sequence and compares with its shard of ONE single-device capped call (tests/_softcap_ref.py, fp64) that the parent
+seeded sequence and compares with its shard of ONE single-device capped call (tests/_blockref.py, fp64) that the parent
 computed once; or, `record`, runs under a recording backend and reports the `softcap` every block call carried.  Backend:
-the CPU oracle with `softcap=` (tests/_softcap_backend.py) or the HIP kernels with every rank sharing cuda:0.  Kinds:
+the CPU oracle with `softcap=` (tests/_ref_backend.py) or the HIP kernels with every rank sharing cuda:0.  Kinds:
     ring / zigzag / stripe            dense (B, W S, H, D)
     ring_varlen / zigzag_varlen       packed, `lens` = the FULL lengths of the sequences (multiples of 2 W)
     llama3 / zigzag_llama3            packed stream of W S tokens, sequences L3_CU scaled"""
@@ -54,7 +54,7 @@ def inputs(c):
 
 def reference(c, softcap=None):
     """(out, lse, dq, dk, dv) fp64 of the ONE single-device call over the unsharded tensors"""
-    import _softcap_ref as SR
+    import _blockref as SR
 
     q, k, v, do = inputs(c)
     kw = dict(causal=c["causal"], window=c.get("window", (-1, -1)), dout=do)
@@ -64,7 +64,7 @@ def reference(c, softcap=None):
         for L in lens:
             cu.append(cu[-1] + L)
         kw.update(cu_seqlens_q=cu, cu_seqlens_k=cu)
-    return SR.attention(q, k, v, c["softcap"] if softcap is None else softcap, **kw)
+    return SR.attention(q, k, v, softcap=c["softcap"] if softcap is None else softcap, **kw)
 
 
 def shard(c, t, rank, dim):
@@ -113,7 +113,7 @@ def run_rank(rank, W, port, cases, use_hip, ret):
         dist.init_process_group("gloo", rank=rank, world_size=W)
         import ring_flash_attn as R
         from ring_flash_attn import _testing, config
-        from _softcap_backend import Recording, SoftcapBackend
+        from _ref_backend import Recording, RefBackend
 
         if use_hip:
             dev = torch.device("cuda:0")
@@ -130,12 +130,10 @@ def run_rank(rank, W, port, cases, use_hip, ret):
             q, k, v = (t.requires_grad_(True) for t in (q, k, v))
             rec = None
             if c.get("record"):
-                from _band_backend import BandBackend
-
-                rec = Recording(BandBackend())
+                rec = Recording(RefBackend(serves=("mask_shift",)))
                 _testing.set_backend(rec)
             else:
-                _testing.set_backend(None if use_hip else SoftcapBackend())
+                _testing.set_backend(None if use_hip else RefBackend(serves=("mask_shift", "mask_shift_lens", "softcap")))
             with config.override(zigzag_exchange=c.get("form") or "ring"):
                 out, lse, _ = call(R, c, q, k, v, rank, dev)
                 out.backward(do)

@@ -1,7 +1,7 @@
 """Multi-process worker of the sliding-window tests of the packed (varlen) ring and zigzag schedules and of the stripe
 schedule: one rank of a gloo world runs the public functions on its shard of seeded sequences and compares, sequence by
 sequence, with ONE windowed attention over the unsharded sequence (oracle.flash_attn_ref.full_attention_fp64).  Backend:
-the CPU oracle with `mask_shift` and `mask_shift_lens` (tests/_band_varlen_backend.py) or the HIP kernels with every rank
+the CPU oracle with `mask_shift` and `mask_shift_lens` (tests/_ref_backend.py) or the HIP kernels with every rank
 sharing cuda:0.  Case kinds:
     ring_varlen / zigzag_varlen   lens = the FULL lengths of the packed sequences, multiples of 2 W
     stripe                        dense, S rows per rank, token i of rank r = global token i W + r
@@ -153,10 +153,10 @@ def run_rank(rank, W, port, cases, use_hip, ret):
             _testing.allow_host_staging(True)
             inner, tol = get_backend(), TOL_HIP
         else:
-            from _band_varlen_backend import BandVarlenBackend
+            from _ref_backend import RefBackend
 
             dev = torch.device("cpu")
-            inner, tol = BandVarlenBackend(), TOL_ORACLE
+            inner, tol = RefBackend(serves=("mask_shift", "mask_shift_lens")), TOL_ORACLE
         errs = []
         hops = [0]
         orig_commit = utils.RingComm.commit
@@ -179,10 +179,10 @@ def run_rank(rank, W, port, cases, use_hip, ret):
                 q, k, v, do = _inputs(c)
                 tag = f"{name}[{form}][r{rank}]"
                 if c.get("refuse"):
-                    from _band_backend import BandBackend
+                    from _ref_backend import RefBackend
 
                     ql, kl, vl = (_shard(c, t, rank, 0).to(dev) for t in (q, k, v))
-                    _testing.set_backend(Counting(BandBackend()))
+                    _testing.set_backend(Counting(RefBackend(serves=("mask_shift",))))
                     hops[0] = 0
                     try:
                         _call(R, c, form, ql, kl, vl, c["window"], dev)

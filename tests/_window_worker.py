@@ -1,6 +1,6 @@
 """Multi-process worker of the sliding-window ring / zigzag tests: one rank of a gloo world runs the public functions
 on its shard of a seeded sequence and compares with ONE windowed attention over the unsharded tensors.  Backend: the
-CPU oracle with `mask_shift` (tests/_band_backend.py) or the HIP kernels with every rank sharing cuda:0."""
+CPU oracle with `mask_shift` (tests/_ref_backend.py) or the HIP kernels with every rank sharing cuda:0."""
 import os
 import sys
 import traceback
@@ -149,10 +149,10 @@ def run_rank(rank, W, port, cases, use_hip, ret):
             _testing.allow_host_staging(True)
             inner, tol = get_backend(), TOL_HIP
         else:
-            from _band_backend import BandBackend
+            from _ref_backend import RefBackend
 
             dev = torch.device("cpu")
-            inner, tol = BandBackend(), TOL_ORACLE
+            inner, tol = RefBackend(serves=("mask_shift",)), TOL_ORACLE
         errs = []
         hops = [0]
         orig_commit = utils.RingComm.commit

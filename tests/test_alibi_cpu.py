@@ -1,7 +1,7 @@
 """ALiBi (alibi_slopes), no device: the extension entry points of the C ABI (symbols, layout, the refusals that can be
 tested with NULL tensors), the shift arithmetic of the ring and zigzag schedules against positions written out by hand,
-the schedules under gloo through the public functions against ONE single-device biased call (tests/_alibi_ref.py, fp64;
-CPU oracle with `alibi=`, tests/_alibi_backend.py), and what must be refused."""
+the schedules under gloo through the public functions against ONE single-device biased call (tests/_blockref.py, fp64;
+CPU oracle with `alibi=`, tests/_ref_backend.py), and what must be refused."""
 import ctypes as C
 import os
 import subprocess
@@ -17,7 +17,7 @@ for _p in (ROOT, os.path.join(ROOT, "ring-flash-attention_amd"), os.path.join(RO
         sys.path.insert(0, _p)
 
 from conftest import free_port                   # noqa: E402
-import _alibi_ref as AR                          # noqa: E402
+import _blockref as AR                           # noqa: E402
 import _alibi_worker as AW                       # noqa: E402
 import _tol                                      # noqa: E402
 
@@ -331,9 +331,9 @@ def test_single_rank_group_serves_every_function(single_rank_group):
     """shift 0: dense, *_varlen, llama3 and zigzag_llama3 through the public functions on a single-rank group"""
     import ring_flash_attn as R
     from ring_flash_attn import _testing
-    from _alibi_backend import AlibiBackend
+    from _ref_backend import RefBackend
 
-    _testing.set_backend(AlibiBackend())
+    _testing.set_backend(RefBackend(serves=("mask_shift", "alibi")))
     g = torch.Generator().manual_seed(5)
     Bq, S, Hh, Hk, Dd = 2, 48, 4, 2, 32
     q, k, v, do = (torch.randn(Bq, S, h, Dd, generator=g).bfloat16() for h in (Hh, Hk, Hk, Hh))
@@ -344,7 +344,7 @@ def test_single_rank_group_serves_every_function(single_rank_group):
         ins = [t.clone().requires_grad_(True) for t in tensors]
         out, lse, _ = fn(*ins, *args, alibi_slopes=slopes, return_attn_probs=True)
         out.backward(dout)
-        ro, rl, rdq, rdk, rdv = AR.attention(*tensors, slopes, dout=dout, **ref_kw)
+        ro, rl, rdq, rdk, rdv = AR.attention(*tensors, slopes=slopes, dout=dout, autograd=True, **ref_kw)
         _tol.compare(f"{name} out", out, ro, "out_ring")
         _tol.compare(f"{name} lse", lse, rl, "lse_ring")
         for nm, got, ref in zip(("dq", "dk", "dv"), (t.grad for t in ins), (rdq, rdk, rdv)):
@@ -380,11 +380,11 @@ def test_require_alibi_and_the_check():
     from oracle.oracle_backend import OracleBackend
     from ring_flash_attn import _api
     from ring_flash_attn._common import check_alibi_slopes, require_alibi
-    from _alibi_backend import AlibiBackend
+    from _ref_backend import RefBackend
 
     with pytest.raises(NotImplementedError, match="alibi"):
         require_alibi(OracleBackend(), "ring_flash_attn")
-    require_alibi(AlibiBackend(), "ring_flash_attn")
+    require_alibi(RefBackend(serves=("mask_shift", "alibi")), "ring_flash_attn")
     q = torch.zeros(2, 8, 4, 16)
     assert check_alibi_slopes(None, q, 2) is None
     assert check_alibi_slopes(torch.ones(4), q, 2).shape == (4,) and check_alibi_slopes(torch.ones(2, 4), q, 2).shape == (2, 4)

@@ -1,6 +1,6 @@
 """Dropout over several ranks in the dense ring, zigzag and stripe schedules, no device: the position-map arithmetic
 against positions written out by hand, the schedules under gloo through the public functions against ONE single-device
-dropout call with the same seed (CPU oracle with position maps, tests/_droppos_backend.py), what must still be refused,
+dropout call with the same seed (CPU oracle with position maps, tests/_ref_backend.py), what must still be refused,
 and the host side of the C ABI (revision, fields, argument checks, plans)."""
 import ctypes as C
 import os
@@ -23,7 +23,7 @@ ERR_ARGS = -8
 # ---------------------------------------------------------------------------------------------- map arithmetic
 def test_position_maps_against_positions_written_out_by_hand():
     from ring_flash_attn._common import dropout_arg, map_positions, pos_map, stripe_map, zigzag_map
-    from _droppos_backend import positions
+    from _blockref import positions
 
     # zigzag, W = 2, 4 rows per rank (chunks of 2): rank 0 holds chunks 0 and 3, rank 1 chunks 1 and 2
     assert map_positions(zigzag_map(0, 2, 2), 4) == [0, 1, 6, 7]
@@ -52,12 +52,12 @@ def test_backend_flag_and_the_require_helper():
     from oracle.oracle_backend import OracleBackend
     from ring_flash_attn._common import require_dropout_positions
     from ring_flash_attn.backend import HipBackend
-    from _droppos_backend import DropPosBackend
+    from _ref_backend import RefBackend
 
     assert HipBackend.serves_dropout_positions is True
     with pytest.raises(NotImplementedError, match="position maps"):
         require_dropout_positions(OracleBackend(), "ring_flash_attn")
-    require_dropout_positions(DropPosBackend(), "ring_flash_attn")
+    require_dropout_positions(RefBackend(serves=("dropout_positions",)), "ring_flash_attn")
 
 
 def test_set_dropout_fills_the_map_fields():

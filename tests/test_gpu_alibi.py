@@ -1,4 +1,4 @@
-"""ALiBi (alibi_slopes; include/rfa.h: rfa_ext_args) in the kernels against fp64 (tests/_alibi_ref.py) through tests/_tol.py
+"""ALiBi (alibi_slopes; include/rfa.h: rfa_ext_args) in the kernels against fp64 (tests/_blockref.py) through tests/_tol.py
 (kinds out, lse, grad): the kBias instances of the forward, dQ and dK/dV kernels for head dims 128 and 64 (full) and 72 and
 40 (the zero-padded 128- / 64-wide layouts), bf16 and fp16, square / few-rows / few-keys blocks that are no multiple of a
 tile, causal and not, with the block's own distance (alibi_shift 0), a whole block in front (+Sk) or behind (-Sk) and a
@@ -19,7 +19,7 @@ for _p in (ROOT, os.path.join(ROOT, "ring-flash-attention_amd"), os.path.join(RO
         sys.path.insert(0, _p)
 
 from conftest import free_port                   # noqa: E402
-import _alibi_ref as AR                          # noqa: E402
+import _blockref as AR                           # noqa: E402
 import _tol                                      # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -87,7 +87,8 @@ class _Case:
         self.q, self.k, self.v, self.do = mk(B, sq, H, D), mk(B, sk, HK, D), mk(B, sk, HK, D), mk(B, sq, H, D)
         self.slopes = _slopes(sl)
         self.ms = shift if causal else 0
-        self.ref = AR.attention(self.q, self.k, self.v, self.slopes, causal=causal, shift=shift, mask_shift=self.ms, dout=self.do)
+        self.ref = AR.attention(self.q, self.k, self.v, slopes=self.slopes, causal=causal, alibi_shift=shift, shift=self.ms, dout=self.do,
+                                autograd=True)
         self.scale = D ** -0.5
 
     def dev(self):
@@ -198,7 +199,8 @@ def test_packed_batch_with_unequal_lengths(D, dt):
     vl = dict(cu_seqlens_q=cq, cu_seqlens_k=ck, max_seqlen_q=136, max_seqlen_k=233)
     bad = []
     for causal in (True, False):
-        ro, rl, rdq, rdk, rdv = AR.attention(q, k, v, slopes, causal=causal, dout=do, cu_seqlens_q=cu_q, cu_seqlens_k=cu_k)
+        ro, rl, rdq, rdk, rdv = AR.attention(q, k, v, slopes=slopes, causal=causal, dout=do, autograd=True, cu_seqlens_q=cu_q,
+                                             cu_seqlens_k=cu_k)
         out, lse = torch.empty_like(qd), torch.empty((H, 200), dtype=torch.float32, device=dev)
         be.fwd(qd, kd, vd, softmax_scale=D ** -0.5, causal=causal, out=out, lse=lse, alibi=(sd, 0), **vl)
         delta = torch.empty_like(lse)

@@ -5,7 +5,7 @@ run — what dropout over the dense ring, zigzag and stripe schedules is built o
   1. mask read-out, EXACT: with q = 0 every visible probability of a row is the same, so one-hot values / keys / output
      gradients make every kernel print the keep mask it applied; the boolean read-outs must EQUAL
      oracle.flash_attn_ref.dropout_keep at the mapped positions;
-  2. numeric: random inputs with GQA against the fp64 attention of tests/_droppos_backend.py, tests/_tol.py kinds
+  2. numeric: random inputs with GQA against the fp64 attention of tests/_blockref.py, tests/_tol.py kinds
      out / lse / grad unscaled, in every output mode the schedules use;
   3. identities, bit for bit: an explicit identity map is the default call, a two-piece map that describes a contiguous
      range is the one-piece call;
@@ -71,13 +71,13 @@ _KEEP = {}
 
 def _keep(geo, p, B, H, causal):
     """the reference: bool (B, H, Sq, Sk), keep mask at the mapped positions AND visible; computed once per case"""
-    from _droppos_backend import _visible, keep_mask
+    from _blockref import keep_mask, visible
 
     key = (geo, p, B, H, causal)
     if key not in _KEEP:
         Sq, Sk = GEO[geo][:2]
         d = _drop(geo, p)
-        _KEEP[key] = torch.stack([keep_mask(d, b, H, Sq, Sk) for b in range(B)]) & _visible(Sq, Sk, causal)
+        _KEEP[key] = torch.stack([keep_mask(d, b, H, Sq, Sk) for b in range(B)]) & visible(Sq, Sk, causal)
     return _KEEP[key]
 
 
@@ -143,9 +143,9 @@ def _readout(geo, D, causal, dtype=BF):
     # only; the reference says which rows they are, nothing is excluded from the comparison.
     p = 0.5
     keep = _keep(geo, p, B, H, causal)
-    from _droppos_backend import _visible
+    from _blockref import visible
 
-    nvis = _visible(Sq, Sk, causal).sum(-1)                                   # (Sq,)
+    nvis = visible(Sq, Sk, causal).sum(-1)                                   # (Sq,)
     whole = keep.sum(-1) == nvis                                              # (B, H, Sq): every visible key kept
     want = keep & ~whole.unsqueeze(-1)
     got = torch.zeros_like(want)
@@ -202,8 +202,9 @@ def _rand(B, Sq, Sk, H, Hk, D, dtype=BF):
 def test_numeric_against_fp64(geo, D, H, Hk):
     """random N(0,1) inputs with GQA; forward in plain and accumulate mode, backward in plain, two-phase fp32-accumulate
     and RFA_BWD_KV_OVERWRITE mode, against the fp64 block attention with the mapped keep mask"""
-    import _droppos_backend as DP
+    import _blockref as DP
     import _tol
+    from oracle.flash_attn_ref import drop_rescale
     from ring_flash_attn import _C
 
     be, dev = _be(), _dev()
@@ -212,12 +213,8 @@ def test_numeric_against_fp64(geo, D, H, Hk):
     q, k, v, do = _rand(B, Sq, Sk, H, Hk, D)
     drop = _drop(geo, p)
     scale = D ** -0.5
-    ref = DP.fwd64(q, k, v, scale, causal, drop)
-    ro = torch.stack([o for o, _ in ref])
-    rl = torch.stack([l for _, l in ref])
-    delta = (do.double() * ro).sum(-1).transpose(1, 2)                         # (B, H, Sq)
-    rg = DP.bwd64(do, q, k, v, rl, delta, scale, causal, drop)
-    rdq, rdk, rdv = (torch.stack([g_[i] for g_ in rg]) for i in range(3))
+    ro, rl, rdq, rdk, rdv = DP.attention(q, k, v, dout=do, causal=causal, rescale=drop_rescale(p),
+                                         keep=[DP.keep_mask(drop, b, H, Sq, Sk) for b in range(B)])
     tag = f"droppos.{geo}.D{D}.H{H}x{Hk}"
 
     qd, kd, vd, dod = (t.to(dev) for t in (q, k, v, do))

@@ -1,5 +1,5 @@
 """Logit soft-capping (flash_attn's softcap; include/rfa.h: rfa_ext_args.softcap) in the kernels against fp64
-(tests/_softcap_ref.py) through tests/_tol.py (kinds out, lse, grad; *_ring over several ranks): the kCap instances of the
+(tests/_blockref.py) through tests/_tol.py (kinds out, lse, grad; *_ring over several ranks): the kCap instances of the
 forward, dQ and dK/dV kernels for head dims 128 and 64 (full) and 72 and 40 (the zero-padded layouts), bf16 and fp16, blocks
 that are no multiple of a tile, causal and not, in two regimes — softcap = 2.0, where tanh saturates (the reference itself
 shows that a dropped cap or a dropped 1 - t^2 would be far outside the tolerance), and the realistic 50.0; with windows, a
@@ -20,7 +20,7 @@ for _p in (ROOT, os.path.join(ROOT, "ring-flash-attention_amd"), os.path.join(RO
         sys.path.insert(0, _p)
 
 from conftest import free_port                   # noqa: E402
-import _softcap_ref as SR                        # noqa: E402
+import _blockref as SR                         # noqa: E402
 import _tol                                      # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -59,10 +59,10 @@ class _Case:
         self.q, self.k, self.v, self.do = mk(B, sq, H, D), mk(B, sk, HK, D), mk(B, sk, HK, D), mk(B, sq, H, D)
         self.scale = D ** -0.5
         self.kw = dict(causal=causal, window=window, shift=shift)
-        self.ref = SR.attention(self.q, self.k, self.v, cap, dout=self.do, **self.kw)
+        self.ref = SR.attention(self.q, self.k, self.v, softcap=cap, dout=self.do, **self.kw)
 
     def uncapped(self):
-        return SR.attention(self.q, self.k, self.v, 0.0, dout=self.do, **self.kw)
+        return SR.attention(self.q, self.k, self.v, dout=self.do, **self.kw)
 
     def dev(self):
         d = _dev()
@@ -179,7 +179,7 @@ def test_packed_batch_with_unequal_lengths_and_a_window(D, dt, shift_lens):
     gen = torch.Generator().manual_seed(91 + D)
     mk = lambda t, h: torch.randn(t, h, D, generator=gen).to(dt)
     q, k, v, do = mk(200, H), mk(333, HK), mk(333, HK), mk(200, H)
-    ref = SR.attention(q, k, v, cap, causal=True, window=window, shift_lens=shift_lens, dout=do, cu_seqlens_q=cu_q,
+    ref = SR.attention(q, k, v, softcap=cap, causal=True, window=window, shift_lens=shift_lens, dout=do, cu_seqlens_q=cu_q,
                        cu_seqlens_k=cu_k)
     be, dev = _be(), _dev()
     qd, kd, vd, dod = (t.to(dev) for t in (q, k, v, do))

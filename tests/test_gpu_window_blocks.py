@@ -1,6 +1,6 @@
 """`mask_shift` of the C ABI (include/rfa.h, ABI 7) on the GPU: one dense sequence computed once unsharded with a
 sliding window and once as a grid of blocks that are told where they sit, merged through the fp32 accumulators — both
-against an fp64 attention with an explicit mask, computed on the device right here.  Plus the band normalisation of the
+against an fp64 attention with an explicit mask (tests/_blockref.py), computed on the device.  Plus the band normalisation of the
 dispatch layer (a block wholly inside the band IS the unwindowed call; an empty block touches nothing) and a block call
 under HIP graph capture."""
 import os
@@ -16,6 +16,8 @@ for _p in (ROOT, os.path.join(ROOT, "ring-flash-attention_amd"), os.path.join(RO
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
+from _bandref import band_ref                  # noqa: E402
+
 BF = torch.bfloat16
 
 
@@ -30,42 +32,6 @@ def _be():
 
     set_backend(None)
     return get_backend()
-
-
-def band_ref(q, k, v, do, causal, window):
-    """fp64 attention with the mask written out: query i (global position i + Sk - Sq) sees key j iff
-    i + Sk - Sq - wl <= j <= i + Sk - Sq + wr, each side only when >= 0, causal: wr = 0.  Returns out, lse, dq, dk, dv
-    (fp64; lse = +inf and out = 0 for rows without a key)."""
-    B, Sq, H, D = q.shape
-    Sk, Hk = k.shape[1], k.shape[2]
-    G = H // Hk
-    qd, kd, vd, dod = (t.double() for t in (q, k, v, do))
-    ke, ve = kd.repeat_interleave(G, dim=2), vd.repeat_interleave(G, dim=2)
-    i = torch.arange(Sq, device=q.device).view(-1, 1) + (Sk - Sq)
-    j = torch.arange(Sk, device=q.device).view(1, -1)
-    wl, wr = window
-    if causal:
-        wr = 0
-    vis = torch.ones(Sq, Sk, dtype=torch.bool, device=q.device)
-    if wr >= 0:
-        vis &= j <= i + wr
-    if wl >= 0:
-        vis &= j >= i - wl
-    s = torch.einsum("bqhd,bkhd->bhqk", qd, ke) * (D ** -0.5)
-    s = s.masked_fill(~vis, float("-inf"))
-    lse = torch.logsumexp(s, dim=-1)                                  # (B,H,Sq); -inf for empty rows
-    empty = torch.isinf(lse)
-    p = torch.exp(s - torch.where(empty, torch.zeros_like(lse), lse).unsqueeze(-1))
-    p = torch.where(vis, p, torch.zeros_like(p))
-    out = torch.einsum("bhqk,bkhd->bqhd", p, ve)
-    dp = torch.einsum("bqhd,bkhd->bhqk", dod, ve)
-    delta = (dod * out).sum(-1).permute(0, 2, 1)                      # (B,H,Sq)
-    ds = p * (dp - delta.unsqueeze(-1)) * (D ** -0.5)
-    dq = torch.einsum("bhqk,bkhd->bqhd", ds, ke)
-    dk = torch.einsum("bhqk,bqhd->bkhd", ds, qd).view(B, Sk, Hk, G, D).sum(3)
-    dv = torch.einsum("bhqk,bqhd->bkhd", p, dod).view(B, Sk, Hk, G, D).sum(3)
-    lse = torch.where(empty, torch.full_like(lse, float("inf")), lse)
-    return out, lse, dq, dk, dv
 
 
 def _inputs(B, Sq, Sk, H, Hk, D, dtype, seed):

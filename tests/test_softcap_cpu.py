@@ -1,8 +1,8 @@
 """Logit soft-capping (flash_attn's softcap), no device: the grown rfa_ext_args of the C ABI (layout, the size contract, every
 refusal that can be tested with NULL tensors), what HipBackend puts into the struct, `ring_flash_attn.with_softcap`, the
 Hugging Face adapter, the value on every block call of every schedule family (a recording backend under gloo), and the
-schedules' numerics against ONE single-device capped call (tests/_softcap_ref.py, fp64; CPU oracle with `softcap=`,
-tests/_softcap_backend.py)."""
+schedules' numerics against ONE single-device capped call (tests/_blockref.py, fp64; CPU oracle with `softcap=`,
+tests/_ref_backend.py)."""
 import ctypes as C
 import inspect
 import math
@@ -20,7 +20,7 @@ for _p in (ROOT, os.path.join(ROOT, "ring-flash-attention_amd"), os.path.join(RO
         sys.path.insert(0, _p)
 
 from conftest import free_port                   # noqa: E402
-import _softcap_ref as SR                        # noqa: E402
+import _blockref as SR                         # noqa: E402
 import _softcap_worker as SW                     # noqa: E402
 import _tol                                      # noqa: E402
 
@@ -191,9 +191,9 @@ def test_backend_builds_one_struct_for_bias_and_cap():
 @pytest.fixture
 def cpu_backend(single_rank_group):
     from ring_flash_attn import _testing
-    from _softcap_backend import SoftcapBackend
+    from _ref_backend import RefBackend
 
-    _testing.set_backend(SoftcapBackend())
+    _testing.set_backend(RefBackend(serves=("mask_shift", "mask_shift_lens", "softcap")))
     yield
     _testing.set_backend(None)
 
@@ -231,8 +231,8 @@ def test_with_softcap_caps_forward_and_backward_and_checkpointing_recomputes_wit
 
     q, k, v, do = _qkv()
     cap = 2.0
-    ref = SR.attention(q, k, v, cap, causal=True, dout=do)
-    plain = SR.attention(q, k, v, 0.0, causal=True, dout=do)
+    ref = SR.attention(q, k, v, softcap=cap, causal=True, dout=do)
+    plain = SR.attention(q, k, v, causal=True, dout=do)
     assert (ref[0] - plain[0]).abs().max() > 0.05                  # the cap does something at this size
     capped = R.with_softcap(R.ring_flash_attn_func, cap)
 
@@ -269,7 +269,7 @@ def test_with_softcap_caps_forward_and_backward_and_checkpointing_recomputes_wit
 def test_refusals_at_the_public_entry(cpu_backend):
     import ring_flash_attn as R
     from ring_flash_attn import _testing
-    from _band_backend import BandBackend
+    from _ref_backend import RefBackend
 
     q, k, v, _ = _qkv()
     NI = NotImplementedError
@@ -291,7 +291,7 @@ def test_refusals_at_the_public_entry(cpu_backend):
                                                               local_k_slice=slice(0, 48), causal=True, dropout_p=0.1)
     with pytest.raises(NI, match="dropout"):
         R.with_softcap(R.zigzag_llama3_flash_attn_varlen_func, 30.0)(q[0], k[0], v[0], cu, causal=True, dropout_p=0.1)
-    _testing.set_backend(BandBackend())                            # serves mask_shift, not softcap
+    _testing.set_backend(RefBackend(serves=("mask_shift",)))                            # serves mask_shift, not softcap
     with pytest.raises(NI, match="serves `softcap`"):
         R.with_softcap(R.ring_flash_attn_func, 30.0)(q, k, v, causal=True)
     R.ring_flash_attn_func(q, k, v, causal=True)                   # (the same backend serves the uncapped call)
@@ -300,10 +300,9 @@ def test_refusals_at_the_public_entry(cpu_backend):
 def test_hf_adapter_forwards_the_cap(cpu_backend):
     from ring_flash_attn import _testing
     from ring_flash_attn.adapters import hf_adapter
-    from _band_backend import BandBackend
-    from _softcap_backend import Recording
+    from _ref_backend import Recording, RefBackend
 
-    rec = Recording(BandBackend())
+    rec = Recording(RefBackend(serves=("mask_shift",)))
     _testing.set_backend(rec)
     S = 48
     hf_adapter.update_ring_flash_attn_params(torch.tensor([0, 20, S], dtype=torch.int32), None)

@@ -1,5 +1,5 @@
 """Sliding windows over multi-rank ring and zigzag schedules, on the CPU: gloo worlds of 2, 3, 4 and 8 ranks run the
-public functions through the oracle backend extended with `mask_shift` (tests/_band_backend.py) and are compared with
+public functions through the oracle backend extended with `mask_shift` (tests/_ref_backend.py) and are compared with
 ONE windowed attention over the unsharded tensors (oracle.flash_attn_ref.full_attention_fp64).  Tolerance: TOL_ORACLE of
 tests/_ring_worker.py.  Also: the number of block calls and exchanges a windowed ring makes (conditions from the step
 rule, not measurements), and that a window covering the whole sequence — and every unwindowed call — takes the
@@ -131,8 +131,8 @@ def test_still_unsupported_combinations_raise():
     # a backend that cannot be told where a block sits would band every block on its own: the schedules refuse it
     from oracle.oracle_backend import OracleBackend
     from ring_flash_attn._common import require_mask_shift
-    from _band_backend import BandBackend
+    from _ref_backend import RefBackend
 
     with pytest.raises(NotImplementedError, match="mask_shift"):
         require_mask_shift(OracleBackend(), "ring_flash_attn")
-    require_mask_shift(BandBackend(), "ring_flash_attn")
+    require_mask_shift(RefBackend(serves=("mask_shift",)), "ring_flash_attn")

@@ -1,6 +1,6 @@
 """Sliding windows over multi-rank `ring_flash_attn_varlen`, `zigzag_ring_flash_attn_varlen` and `stripe_flash_attn`
 schedules, on the CPU: gloo worlds of 2, 3 and 4 ranks run the public functions through the oracle backend extended with
-`mask_shift` and `mask_shift_lens` (tests/_band_varlen_backend.py) and are compared, sequence by sequence, with ONE
+`mask_shift` and `mask_shift_lens` (tests/_ref_backend.py) and are compared, sequence by sequence, with ONE
 windowed attention over the unsharded sequence (oracle.flash_attn_ref.full_attention_fp64).  Tolerance: TOL_ORACLE of
 tests/_ring_worker.py with _window_worker._cmp's absolute floor.  Also: the stripe blocks that are skipped (the rule, not
 a measurement), that a window covering the longest sequence takes the unwindowed path bit for bit, and that a backend
@@ -122,13 +122,12 @@ def test_covering_window_takes_the_unwindowed_path(kind):
 
 def test_backend_without_mask_shift_lens_is_refused():
     """before any exchange, on every rank alike; and the helper itself"""
-    from _band_backend import BandBackend
-    from _band_varlen_backend import BandVarlenBackend
+    from _ref_backend import RefBackend
     from ring_flash_attn._common import require_mask_shift_lens
 
     with pytest.raises(NotImplementedError, match="mask_shift_lens"):
-        require_mask_shift_lens(BandBackend(), "ring_flash_attn_varlen")
-    require_mask_shift_lens(BandVarlenBackend(), "ring_flash_attn_varlen")
+        require_mask_shift_lens(RefBackend(serves=("mask_shift",)), "ring_flash_attn_varlen")
+    require_mask_shift_lens(RefBackend(serves=("mask_shift", "mask_shift_lens")), "ring_flash_attn_varlen")
     W = 2
     cases = [dict(name=f"refuse_{kind}", kind="refuse", refuse=kind, W=W, lens=_lens(W), H=4, Hk=2, D=32, seed=90, causal=True,
                   window=(3, 0)) for kind in ("ring_varlen", "zigzag_varlen")]
@@ -141,10 +140,10 @@ def test_band_varlen_backend_serves_the_definition():
     with halves, and dense input (where the field folds into mask_shift)"""
     import torch
 
-    from _band_varlen_backend import BandVarlenBackend
+    from _ref_backend import RefBackend
     from _bandref import band_ref
 
-    be = BandVarlenBackend()
+    be = RefBackend(serves=("mask_shift", "mask_shift_lens"))
     g = torch.Generator().manual_seed(5)
     lens = [4, 10, 16]
     cu = torch.tensor([0, 4, 14, 30], dtype=torch.int32)
