@@ -465,6 +465,61 @@ int rfa_lse_unflatten(float *dst_padded, const float *src_packed, const int32_t 
                       int32_t B, int32_t H, int32_t max_seqlen, int64_t src_head_stride,
                       int64_t src_row_stride, void *stream);
 
+/* Attention sinks (GPT-OSS, the streaming-LLM family; flash_attn's / Hugging Face's `s_aux`): one logit per query head that
+ * joins the softmax as an extra column whose value vector is zero,
+ *     p_ij = exp(s_ij - lse'_i),   lse'_i = log(sum_j exp(s_ij) + exp(sink_h)),   out'_i = sum_j p_ij v_j .
+ * No attention kernel knows about it, and no existing struct changes (ABI 8 revision 1 stays; rfa_ext_args stays): the sink is
+ * applied ONCE, to the (out, lse) of the attention without it, merged over all blocks and ranks —
+ *     rfa_sink_apply:  lse' = logaddexp(lse, sink_h),  out' = out * exp(lse - lse')    (io dtype out, rounded once more)
+ * and rfa_bwd_preprocess / rfa_bwd handed (out', lse') in place of (out, lse) return the exact dq / dk / dv: the sink
+ * column's dP is 0, so delta' = rowsum(dO * out'), P' = exp(s - lse'), dS = P' (dP - delta') is the existing formula.
+ *     rfa_sink_grad:   dsink_h = - sum over the B x S rows i of exp(sink_h - lse'_i) * rowsum(dO_i * out'_i)
+ * in fp32, summed in a fixed order (no atomics): a pure function of its inputs, the same bits on every run.
+ * Layout: B x S rows of H heads — dense out (B, S, H, D) with lse (B, H, S); packed out (T, H, D) with lse (H, T) is
+ * B = 1, S = T (batch strides unused); no cu_seqlens, the operation is per row.  lse row stride is 1.  sinks, dsink: (H,)
+ * fp32, contiguous.  out_dst may be out_src and lse_dst may be lse_src (then with the same strides).
+ * Rows without a visible key (lse = +inf; -inf is read the same way) get lse' = sink_h and out' = 0.  A sink so low that
+ * exp(sink_h - lse) underflows returns the input bits: out' == out, lse' == lse.
+ * Checks, in this order and before any launch: NULL struct RFA_ERR_NULL; dtype, head_dim (a multiple of 8, <= 256), H <= 0,
+ * B < 0 as everywhere; S < 0, B or H above 65535, S * H above 16 * (2^31 - 1) RFA_ERR_SHAPE; B == 0 or S == 0: RFA_OK, nothing is launched
+ * (rfa_sink_grad then needs dsink alone and sets it to zero); NULL tensors RFA_ERR_NULL; pointers or strides off the 16-byte
+ * contract RFA_ERR_ALIGN; rfa_sink_grad: workspace_bytes below rfa_sink_grad_workspace_bytes() RFA_ERR_ARGS. */
+typedef struct {
+  const void *out_src;     /* io dtype */
+  rfa_strides out_src_st;
+  void *out_dst;
+  rfa_strides out_dst_st;
+  const float *lse_src;
+  int64_t lse_src_batch, lse_src_head; /* element strides; row stride is 1 */
+  float *lse_dst;
+  int64_t lse_dst_batch, lse_dst_head;
+  const float *sinks;      /* (H,) fp32 */
+  int32_t B, S, H, D;
+  int32_t dtype;           /* rfa_dtype */
+  int32_t reserved;        /* 0 */
+} rfa_sink_apply_args;
+int rfa_sink_apply(const rfa_sink_apply_args *args, void *stream);
+
+typedef struct {
+  const void *dout;        /* io dtype; any (batch, row, head) strides that keep rows 16-byte aligned */
+  rfa_strides dout_st;
+  const void *out;         /* out' as rfa_sink_apply wrote it */
+  rfa_strides out_st;
+  const float *lse;        /* lse' */
+  int64_t lse_batch, lse_head;
+  const float *sinks;      /* (H,) fp32 */
+  float *dsink;            /* (H,) fp32, overwritten */
+  void *workspace;         /* rfa_sink_grad_workspace_bytes() bytes, 16-byte aligned; contents do not matter */
+  int64_t workspace_bytes;
+  int32_t B, S, H, D;
+  int32_t dtype;
+  int32_t reserved;        /* 0 */
+} rfa_sink_grad_args;
+/* bytes of workspace the call needs: one fp32 partial per (batch entry, chunk of 256 rows, head); 0 for a call without rows
+ * and for arguments the call would refuse.  Pure function of B, S and H. */
+int64_t rfa_sink_grad_workspace_bytes(const rfa_sink_grad_args *args);
+int rfa_sink_grad(const rfa_sink_grad_args *args, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

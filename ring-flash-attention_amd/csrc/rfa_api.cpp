@@ -1264,5 +1264,60 @@ int rfa_lse_unflatten(float* dst, const float* src, const int32_t* cu_seqlens, i
                              false, (hipStream_t)stream) ? RFA_ERR_LAUNCH : RFA_OK;
 }
 
+// ---- attention sinks (rfa.h; csrc/rfa_sink.hip) ----------------------------------------------------------------------------
+static int sink_shape_check(int dtype, int B, int S, int H, int D, int reserved) {
+  int rc = check_common(dtype, H, H, D, B);
+  if (rc) return rc;
+  if (S < 0 || B > 65535 || H > 65535) return RFA_ERR_SHAPE;       // (B and H are grid dimensions)
+  if ((int64_t)S * H > (int64_t)16 * INT32_MAX) return RFA_ERR_SHAPE;   // (16 row-heads per workgroup of sink_apply)
+  if (reserved != 0) return RFA_ERR_ARGS;
+  return RFA_OK;
+}
+
+int rfa_sink_apply(const rfa_sink_apply_args* a, void* stream) {
+  if (!a) return RFA_ERR_NULL;
+  int rc = sink_shape_check(a->dtype, a->B, a->S, a->H, a->D, a->reserved);
+  if (rc) return rc;
+  if (a->B == 0 || a->S == 0) return RFA_OK;
+  if (!a->out_src || !a->out_dst || !a->lse_src || !a->lse_dst || !a->sinks) return RFA_ERR_NULL;
+  if (!aligned16(a->out_src) || !aligned16(a->out_dst) || !stride_ok(a->out_src_st, 2) || !stride_ok(a->out_dst_st, 2))
+    return RFA_ERR_ALIGN;
+  SinkApplyParams p{};
+  p.out_src = a->out_src; p.out_dst = a->out_dst; p.lse_src = a->lse_src; p.lse_dst = a->lse_dst; p.sinks = a->sinks;
+  p.out_src_st = cv(a->out_src_st); p.out_dst_st = cv(a->out_dst_st);
+  p.lse_src_batch = a->lse_src_batch; p.lse_src_head = a->lse_src_head;
+  p.lse_dst_batch = a->lse_dst_batch; p.lse_dst_head = a->lse_dst_head;
+  p.B = a->B; p.H = a->H; p.D = a->D; p.S = a->S;
+  return launch_sink_apply(p, a->dtype, (hipStream_t)stream) ? RFA_ERR_LAUNCH : RFA_OK;
+}
+
+int64_t rfa_sink_grad_workspace_bytes(const rfa_sink_grad_args* a) {
+  if (!a || sink_shape_check(a->dtype, a->B, a->S, a->H, a->D, a->reserved)) return 0;
+  return sink_grad_parts(a->B, a->S) * a->H * (int64_t)sizeof(float);
+}
+
+int rfa_sink_grad(const rfa_sink_grad_args* a, void* stream) {
+  if (!a) return RFA_ERR_NULL;
+  int rc = sink_shape_check(a->dtype, a->B, a->S, a->H, a->D, a->reserved);
+  if (rc) return rc;
+  if (a->B == 0 || a->S == 0) {                               // no rows: the sum is empty
+    if (!a->dsink) return RFA_ERR_NULL;
+    return hipMemsetAsync(a->dsink, 0, (size_t)a->H * sizeof(float), (hipStream_t)stream) == hipSuccess ? RFA_OK
+                                                                                                         : RFA_ERR_LAUNCH;
+  }
+  if (!a->dout || !a->out || !a->lse || !a->sinks || !a->dsink || !a->workspace) return RFA_ERR_NULL;
+  if (!aligned16(a->dout) || !aligned16(a->out) || !aligned16(a->workspace) || !stride_ok(a->dout_st, 2) ||
+      !stride_ok(a->out_st, 2))
+    return RFA_ERR_ALIGN;
+  if (a->workspace_bytes < rfa_sink_grad_workspace_bytes(a)) return RFA_ERR_ARGS;
+  SinkGradParams p{};
+  p.dout = a->dout; p.out = a->out; p.lse = a->lse; p.sinks = a->sinks; p.dsink = a->dsink;
+  p.partial = (float*)a->workspace;
+  p.dout_st = cv(a->dout_st); p.out_st = cv(a->out_st);
+  p.lse_batch = a->lse_batch; p.lse_head = a->lse_head;
+  p.B = a->B; p.H = a->H; p.D = a->D; p.S = a->S;
+  return launch_sink_grad(p, a->dtype, (hipStream_t)stream) ? RFA_ERR_LAUNCH : RFA_OK;
+}
+
 }  // extern "C"
 #pragma GCC visibility pop

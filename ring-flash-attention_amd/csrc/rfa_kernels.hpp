@@ -197,6 +197,37 @@ struct MergeParams {
   int B, H, D, S, acc_init;
 };
 
+// attention sinks (rfa_sink.hip): lse' = logaddexp(lse, sinks[h]), out' = out * exp(lse - lse'); B x S rows of H heads
+// (packed input: B = 1, S = total rows, batch strides unused); lse row stride 1
+struct SinkApplyParams {
+  const void* out_src;
+  void* out_dst;            // may be out_src
+  const float* lse_src;
+  float* lse_dst;           // may be lse_src
+  const float* sinks;       // (H,)
+  Strides out_src_st, out_dst_st;
+  int64_t lse_src_batch, lse_src_head, lse_dst_batch, lse_dst_head;
+  int B, H, D, S;
+};
+
+// dsink[h] = - sum_rows exp(sinks[h] - lse') rowsum(dout * out'): partials per (batch, chunk of kSinkGradRows rows, head),
+// then their sum in index order
+struct SinkGradParams {
+  const void* dout;
+  const void* out;
+  const float* lse;
+  const float* sinks;
+  float* dsink;             // (H,)
+  float* partial;           // sink_grad_parts(B, S) * H floats
+  Strides dout_st, out_st;
+  int64_t lse_batch, lse_head;
+  int B, H, D, S;
+};
+constexpr int kSinkGradRows = 256;
+int64_t sink_grad_parts(int B, int S);
+int launch_sink_apply(const SinkApplyParams& p, int dtype, hipStream_t stream);
+int launch_sink_grad(const SinkGradParams& p, int dtype, hipStream_t stream);
+
 int launch_fwd(const FwdParams& p, int dtype, hipStream_t stream);
 int fwd_qrows_per_block();
 // head dims 129 .. 256 (rfa_bigd.hip): same parameter blocks; the launchers set their own nqblk / nkblk

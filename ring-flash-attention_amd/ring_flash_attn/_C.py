@@ -144,6 +144,32 @@ class SumSlotsArgs(C.Structure):
     ]
 
 
+class SinkApplyArgs(C.Structure):
+    """rfa_sink_apply_args: the attention sink applied to a merged (out, lse) pair"""
+    _fields_ = [
+        ("out_src", C.c_void_p), ("out_src_st", Strides),
+        ("out_dst", C.c_void_p), ("out_dst_st", Strides),
+        ("lse_src", C.c_void_p), ("lse_src_batch", C.c_int64), ("lse_src_head", C.c_int64),
+        ("lse_dst", C.c_void_p), ("lse_dst_batch", C.c_int64), ("lse_dst_head", C.c_int64),
+        ("sinks", C.c_void_p),
+        ("B", C.c_int32), ("S", C.c_int32), ("H", C.c_int32), ("D", C.c_int32),
+        ("dtype", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
+class SinkGradArgs(C.Structure):
+    """rfa_sink_grad_args: the sinks' gradient from (dout, out', lse')"""
+    _fields_ = [
+        ("dout", C.c_void_p), ("dout_st", Strides),
+        ("out", C.c_void_p), ("out_st", Strides),
+        ("lse", C.c_void_p), ("lse_batch", C.c_int64), ("lse_head", C.c_int64),
+        ("sinks", C.c_void_p), ("dsink", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+        ("B", C.c_int32), ("S", C.c_int32), ("H", C.c_int32), ("D", C.c_int32),
+        ("dtype", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
 # every symbol include/rfa.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "rfa_abi_version": (C.c_int, []),
@@ -170,6 +196,9 @@ SYMBOLS = {
                                   C.c_int64, C.c_int64, C.c_void_p]),
     "rfa_lse_unflatten": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                     C.c_int64, C.c_int64, C.c_void_p]),
+    "rfa_sink_apply": (C.c_int, [C.POINTER(SinkApplyArgs), C.c_void_p]),
+    "rfa_sink_grad": (C.c_int, [C.POINTER(SinkGradArgs), C.c_void_p]),
+    "rfa_sink_grad_workspace_bytes": (C.c_int64, [C.POINTER(SinkGradArgs)]),
 }
 
 _lib = None
@@ -199,6 +228,10 @@ def load():
     for name in ("rfa_fwd_ex", "rfa_bwd_ex", "rfa_ext_args_bytes"):
         if not hasattr(lib, name):
             raise RuntimeError(f"ring_flash_attn: librfa_hip.so has no {name} (the extension entry points); rebuild")
+    # ... and so did the attention-sink entry points (structs of their own)
+    for name in ("rfa_sink_apply", "rfa_sink_grad", "rfa_sink_grad_workspace_bytes"):
+        if not hasattr(lib, name):
+            raise RuntimeError(f"ring_flash_attn: librfa_hip.so has no {name} (the attention-sink entry points); rebuild")
     for name, (res, args) in SYMBOLS.items():
         fn = getattr(lib, name)  # AttributeError if the .so is stale
         fn.restype = res

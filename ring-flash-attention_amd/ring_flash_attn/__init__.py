@@ -58,3 +58,6 @@ from ._common import set_dropout_generator
 # flash_attn's softcap (logit soft-capping) for any of the attention functions above: with_softcap(func, softcap) — the
 # positional signatures above are the reference's and stay as they are
 from ._api import with_softcap
+# attention sinks (GPT-OSS, streaming-LLM; Hugging Face's `s_aux`): with_sinks(func, sinks) — one learnable logit per query
+# head as an extra softmax column with a zero value vector, with its gradient, on any group
+from ._api import with_sinks

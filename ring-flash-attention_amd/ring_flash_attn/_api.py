@@ -199,7 +199,121 @@ def with_softcap(func, softcap):
         with softcap_scope(cap):
             return func(*args, **kwargs)
 
+    capped._rfa_softcap = cap                        # (with_sinks refuses to wrap a capped function)
     return _opaque(capped)
+
+
+# ---- attention sinks (ring_flash_attn.with_sinks) ------------------------------------------------------------------------
+# The sink is applied once, to the merged (out, lse) a schedule's forward returned (include/rfa.h: rfa_sink_apply), so no
+# schedule and no attention kernel computes anything for it.  The tensor has to be a real INPUT of the autograd node for
+# `sinks.grad` to be filled by ordinary autograd: with_sinks binds it to the call, the public function that runs inside hands
+# it to its autograd Function as ONE extra trailing argument of `apply` (sink_args: nothing for a call without sinks — such a
+# call builds the node it always built), and the node saves it.  The binding is read there, at the public entry of the
+# forward, and nowhere else: a backward reads its saved tensors only.
+import contextvars
+
+_sinks = contextvars.ContextVar("ring_flash_attn_sinks", default=None)
+
+
+def sink_args():
+    """() for a plain call, (sinks,) inside a call bound by `with_sinks`: the tail of the autograd Functions' `apply`"""
+    t = _sinks.get()
+    return () if t is None else (t,)
+
+
+def split_sinks(rest, n):
+    """(the n regular arguments, sinks or None) of an autograd Function's `*rest`"""
+    return rest[:n], (rest[n] if len(rest) > n else None)
+
+
+def checked_sinks(sinks, q, what):
+    """the refusals of a call with sinks that need the tensors — ValueError: not a floating (H,) tensor on q's device;
+    NotImplementedError: a backend that does not serve sinks — before anything is exchanged, on every rank alike"""
+    if sinks is None:
+        return None
+    H = q.shape[-2]
+    if (not isinstance(sinks, torch.Tensor) or not sinks.is_floating_point() or sinks.dim() != 1 or sinks.shape[0] != H
+            or sinks.device != q.device):
+        got = f"{tuple(sinks.shape)} {sinks.dtype} on {sinks.device}" if isinstance(sinks, torch.Tensor) else repr(sinks)
+        raise ValueError(f"ring_flash_attn: {what} with sinks needs a floating tensor of shape ({H},) on {q.device}, one "
+                         f"logit per query head; got {got}")
+    from .backend import get_backend
+
+    be = get_backend()
+    if not getattr(be, "serves_sinks", False):
+        raise NotImplementedError(f"ring_flash_attn: {what} with sinks needs a backend that serves `sink_apply` / `sink_grad`; "
+                                  f"{getattr(be, 'name', type(be).__name__)!r} does not")
+    return sinks
+
+
+def apply_sinks(sinks, out, lse):
+    """(out', lse') of the call with sinks from the schedule's merged (out, lse); the pair itself without sinks"""
+    if sinks is None:
+        return out, lse
+    from .backend import get_backend
+
+    return get_backend().sink_apply(out, lse, sinks, varlen=out.dim() == 3)
+
+
+def sinks_grad(ctx, sinks, dout, out, lse):
+    """the tail of a backward's gradients for the trailing `sinks` input: () without one, else (dsink,) — this rank's sum over
+    its own query rows, in sinks' dtype (None when sinks needs no gradient)"""
+    if sinks is None:
+        return ()
+    if not ctx.needs_input_grad[-1]:
+        return (None,)
+    from .backend import get_backend
+
+    return (get_backend().sink_grad(dout, out, lse, sinks, varlen=out.dim() == 3).to(sinks.dtype),)
+
+
+def with_sinks(func, sinks):
+    """Attention sinks (GPT-OSS, the streaming-LLM family; flash_attn's and Hugging Face's `s_aux`) for one of this package's
+    public attention functions:
+
+        attn = with_sinks(ring_flash_attn_func, sinks)       # sinks: (H,) floating tensor on q's device, may require grad
+        out = attn(q, k, v, causal=True, window_size=(127, 0))
+
+    returns a callable with `func`'s signature that runs `func` with one extra softmax column per query head whose logit is
+    sinks[h] and whose value vector is zero: p_ij = exp(s_ij - lse'_i), lse'_i = log(sum_j exp(s_ij) + exp(sinks[h])),
+    out'_i = sum_j p_ij v_j.  The call returns out' (and lse' with return_attn_probs=True); dq, dk, dv are exact, and
+    `sinks.grad` is filled by autograd, in sinks' dtype.  Served on any group and with everything `func` serves there —
+    windows, packed input, GQA, dropout.  `sinks` None: `func` itself.
+    Several ranks: the sink is applied on the rank that owns the query rows, after its blocks are merged; the gradient a
+    rank gets is its PARTIAL, the sum over its own query rows — as for every replicated parameter under sequence
+    parallelism, the framework's gradient all-reduce over the group completes it.  This package posts no collective for it.
+    The schedules return `out` rounded to the io dtype, so out' is rounded twice (profiles/sinks.md).
+    ValueError: sinks is not a floating tensor of shape (H,) (at the call: H is q's head count, on q's device).  TypeError:
+    `func` is not one of the public attention functions; a `with_softcap` result is refused too — the cap and the sinks
+    together are not served yet.  NotImplementedError at the call: a backend that does not serve sinks.
+    The tensor is bound to the call and saved on the autograd node — activation checkpointing re-runs the wrapped call and
+    binds it again; the backward reads nothing ambient.  Under torch.compile the call runs eagerly behind a graph break."""
+    import functools
+
+    import ring_flash_attn as pkg
+
+    if getattr(func, "_rfa_softcap", None):
+        raise TypeError("ring_flash_attn.with_sinks: `func` is a with_softcap result; soft-capping together with sinks is not "
+                        "served yet (the cap and the sinks would have to be bound to one call)")
+    public = {id(getattr(pkg, n)): n for n in dir(pkg) if n.endswith("_func")}
+    if id(func) not in public:
+        raise TypeError("ring_flash_attn.with_sinks: `func` must be one of the package's public attention functions "
+                        f"(ring_flash_attn.*_func), got {func!r}")
+    if sinks is None:
+        return func
+    if not isinstance(sinks, torch.Tensor) or not sinks.is_floating_point() or sinks.dim() != 1:
+        raise ValueError("ring_flash_attn.with_sinks: sinks must be a floating tensor of shape (H,), one logit per query "
+                         f"head; got {tuple(sinks.shape) if isinstance(sinks, torch.Tensor) else sinks!r}")
+
+    @functools.wraps(func, updated=())              # (updated=(): as in with_softcap)
+    def sunk(*args, **kwargs):
+        token = _sinks.set(sinks)
+        try:
+            return func(*args, **kwargs)
+        finally:
+            _sinks.reset(token)
+
+    return _opaque(sunk)
 
 
 def has_window(window_size) -> bool:
@@ -279,6 +393,7 @@ def make_autograd_function(name, forward_impl, backward_impl, n_lead, window_rin
     class _Fn(torch.autograd.Function):
         @staticmethod
         def forward(ctx, q, k, v, *rest):
+            rest, sinks = split_sinks(rest, n_lead + 8)
             lead = rest[:n_lead]
             (dropout_p, softmax_scale, causal, window_size, alibi_slopes, deterministic,
              return_softmax, group) = rest[n_lead:]
@@ -289,6 +404,7 @@ def make_autograd_function(name, forward_impl, backward_impl, n_lead, window_rin
                                alibi_ok=single or alibi_ring)
             alibi_slopes = checked_alibi(alibi_slopes, q, (len(lead[0]) - 1) if n_lead else q.shape[0], name)
             ctx.softcap = checked_softcap(dropout_p, alibi_slopes, q, name, window_size, causal)
+            sinks = checked_sinks(sinks, q, name)
             q, k, v = _prep_qkv(q, k, v, group)
             tensors_lead = ()
             if n_lead:
@@ -305,7 +421,10 @@ def make_autograd_function(name, forward_impl, backward_impl, n_lead, window_rin
                     window_size=window_size, alibi_slopes=alibi_slopes, deterministic=False, **extra,
                 )
             audit_verify(group, f"{name} forward")          # (config.exchange_check: a no-op otherwise)
-            ctx.save_for_backward(q, k, v, out, softmax_lse, *tensors_lead, *(keep or ()))
+            # (with sinks: out', lse' are what the backward is handed and what the call returns)
+            out, softmax_lse = apply_sinks(sinks, out, softmax_lse)
+            ctx.save_for_backward(q, k, v, out, softmax_lse, *tensors_lead, *(keep or ()), *(() if sinks is None else (sinks,)))
+            ctx.has_sinks = sinks is not None
             _hold_kept(ctx, keep)
             ctx.n_lead_t, ctx.n_keep = len(tensors_lead), len(keep or ())
             ctx.lead_rest = tuple(lead[1:]) if n_lead else ()
@@ -320,6 +439,7 @@ def make_autograd_function(name, forward_impl, backward_impl, n_lead, window_rin
         @staticmethod
         def backward(ctx, dout, *args):
             q, k, v, out, softmax_lse, *more = ctx.saved_tensors
+            sinks = more.pop() if ctx.has_sinks else None
             tensors_lead, extra = _split_kept(ctx, more)
             if ctx.dropout[1] is not None:
                 extra["dropout_seed"] = ctx.dropout[1]
@@ -331,7 +451,7 @@ def make_autograd_function(name, forward_impl, backward_impl, n_lead, window_rin
                 )
             _release_kept(ctx)
             audit_verify(ctx.group, f"{name} backward")
-            return (dq, dk, dv) + (None,) * (n_lead + 8)
+            return (dq, dk, dv) + (None,) * (n_lead + 8) + sinks_grad(ctx, sinks, dout, out, softmax_lse)
 
     _Fn.__name__ = _Fn.__qualname__ = name
     return _Fn
@@ -353,6 +473,7 @@ def make_packed_function(name, base_fn, forward_impl, backward_impl, n_lead, pac
             packed = tensors[-1]
             parts = [packed.select(pack_dim, i) for i in range(n_packed)]
             q, k, v = (parts if n_packed == 3 else [tensors[0]] + parts)
+            rest, sinks = split_sinks(rest, n_lead + 8)
             lead = rest[:n_lead]
             (dropout_p, softmax_scale, causal, window_size, alibi_slopes, deterministic,
              return_softmax, group) = rest[n_lead:]
@@ -363,6 +484,7 @@ def make_packed_function(name, base_fn, forward_impl, backward_impl, n_lead, pac
                                alibi_ok=single or alibi_ring)
             alibi_slopes = checked_alibi(alibi_slopes, q, (len(lead[0]) - 1) if n_lead else q.shape[0], name)
             ctx.softcap = checked_softcap(dropout_p, alibi_slopes, q, name, window_size, causal)
+            sinks = checked_sinks(sinks, q, name)
             q, k, v = _prep_qkv(q, k, v, group, packed_travel=packed_travel and n_packed == 2)
             tensors_lead = ()
             if n_lead:
@@ -379,7 +501,10 @@ def make_packed_function(name, base_fn, forward_impl, backward_impl, n_lead, pac
                     window_size=window_size, alibi_slopes=alibi_slopes, deterministic=False, **extra,
                 )
             audit_verify(group, f"{name} forward")          # (config.exchange_check: a no-op otherwise)
-            ctx.save_for_backward(q, k, v, out, softmax_lse, *tensors_lead, *(keep or ()))
+            # (with sinks: out', lse' are what the backward is handed and what the call returns)
+            out, softmax_lse = apply_sinks(sinks, out, softmax_lse)
+            ctx.save_for_backward(q, k, v, out, softmax_lse, *tensors_lead, *(keep or ()), *(() if sinks is None else (sinks,)))
+            ctx.has_sinks = sinks is not None
             _hold_kept(ctx, keep)
             ctx.n_lead_t, ctx.n_keep = len(tensors_lead), len(keep or ())
             ctx.lead_rest = tuple(lead[1:]) if n_lead else ()
@@ -395,6 +520,7 @@ def make_packed_function(name, base_fn, forward_impl, backward_impl, n_lead, pac
         @staticmethod
         def backward(ctx, dout, *args):
             q, k, v, out, softmax_lse, *more = ctx.saved_tensors
+            sinks = more.pop() if ctx.has_sinks else None
             tensors_lead, extra = _split_kept(ctx, more)
             shape, dtype, device = ctx.packed_meta
             dpacked = torch.empty(shape, dtype=dtype, device=device)
@@ -419,7 +545,7 @@ def make_packed_function(name, base_fn, forward_impl, backward_impl, n_lead, pac
             grads = (dpacked,) if n_packed == 3 else (dq, dpacked)
             _release_kept(ctx)
             audit_verify(ctx.group, f"{name} backward")
-            return grads + (None,) * (n_lead + 8)
+            return grads + (None,) * (n_lead + 8) + sinks_grad(ctx, sinks, dout, out, softmax_lse)
 
     _PFn.__name__ = _PFn.__qualname__ = name
     return _PFn
@@ -449,23 +575,23 @@ def make_dense_api(fn, prefix, forward_impl=None, backward_impl=None, packed_tra
     def func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
              alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None):
         return fn.apply(q, k, v, dropout_p, softmax_scale, causal, window_size, alibi_slopes,
-                        deterministic, return_attn_probs, group)
+                        deterministic, return_attn_probs, group, *sink_args())
 
     def kvpacked_func(q, kv, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
                       alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None):
         if kv_fn is not None:
             return kv_fn.apply(q, kv, dropout_p, softmax_scale, causal, window_size, alibi_slopes,
-                               deterministic, return_attn_probs, group)
+                               deterministic, return_attn_probs, group, *sink_args())
         return fn.apply(q, kv[:, :, 0], kv[:, :, 1], dropout_p, softmax_scale, causal, window_size,
-                        alibi_slopes, deterministic, return_attn_probs, group)
+                        alibi_slopes, deterministic, return_attn_probs, group, *sink_args())
 
     def qkvpacked_func(qkv, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
                        alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None):
         if qkv_fn is not None:
             return qkv_fn.apply(qkv, dropout_p, softmax_scale, causal, window_size, alibi_slopes,
-                                deterministic, return_attn_probs, group)
+                                deterministic, return_attn_probs, group, *sink_args())
         return fn.apply(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], dropout_p, softmax_scale, causal,
-                        window_size, alibi_slopes, deterministic, return_attn_probs, group)
+                        window_size, alibi_slopes, deterministic, return_attn_probs, group, *sink_args())
 
     must_be_causal = prefix in ("zigzag_ring_flash_attn", "stripe_flash_attn")
 
@@ -522,25 +648,25 @@ def make_varlen_api(fn, prefix, forward_impl=None, backward_impl=None, window_ri
              window_size=(-1, -1), alibi_slopes=None, deterministic=False, return_attn_probs=False,
              group=None):
         return fn.apply(q, k, v, cu_seqlens, max_seqlen, dropout_p, softmax_scale, causal, window_size,
-                        alibi_slopes, deterministic, return_attn_probs, group)
+                        alibi_slopes, deterministic, return_attn_probs, group, *sink_args())
 
     def kvpacked_func(q, kv, cu_seqlens, max_seqlen, dropout_p=0.0, softmax_scale=None, causal=False,
                       window_size=(-1, -1), alibi_slopes=None, deterministic=False,
                       return_attn_probs=False, group=None):
         if kv_fn is not None:
             return kv_fn.apply(q, kv, cu_seqlens, max_seqlen, dropout_p, softmax_scale, causal, window_size,
-                               alibi_slopes, deterministic, return_attn_probs, group)
+                               alibi_slopes, deterministic, return_attn_probs, group, *sink_args())
         return fn.apply(q, kv[:, 0], kv[:, 1], cu_seqlens, max_seqlen, dropout_p, softmax_scale, causal,
-                        window_size, alibi_slopes, deterministic, return_attn_probs, group)
+                        window_size, alibi_slopes, deterministic, return_attn_probs, group, *sink_args())
 
     def qkvpacked_func(qkv, cu_seqlens, max_seqlen, dropout_p=0.0, softmax_scale=None, causal=False,
                        window_size=(-1, -1), alibi_slopes=None, deterministic=False,
                        return_attn_probs=False, group=None):
         if qkv_fn is not None:
             return qkv_fn.apply(qkv, cu_seqlens, max_seqlen, dropout_p, softmax_scale, causal, window_size,
-                                alibi_slopes, deterministic, return_attn_probs, group)
+                                alibi_slopes, deterministic, return_attn_probs, group, *sink_args())
         return fn.apply(qkv[:, 0], qkv[:, 1], qkv[:, 2], cu_seqlens, max_seqlen, dropout_p, softmax_scale,
-                        causal, window_size, alibi_slopes, deterministic, return_attn_probs, group)
+                        causal, window_size, alibi_slopes, deterministic, return_attn_probs, group, *sink_args())
 
     must_be_causal = prefix.startswith("zigzag")
 

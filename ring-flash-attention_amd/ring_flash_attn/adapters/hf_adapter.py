@@ -25,7 +25,7 @@ from typing import Optional, Tuple
 import torch
 import torch.distributed as dist
 
-from .._api import with_softcap
+from .._api import with_sinks, with_softcap
 from ..llama3_flash_attn_varlen import (
     llama3_flash_attn_varlen_func,
     llama3_flash_attn_prepare_cu_seqlens,
@@ -69,7 +69,7 @@ def use_ring_attn(flag):
 
 
 def _ring_attention(query_states, key_states, value_states, *, dropout, softmax_scale, causal,
-                    softcap=None, deterministic=None, sliding_window=None):
+                    softcap=None, deterministic=None, sliding_window=None, s_aux=None):
     """(1,S,H,D) local q/k/v -> (1,S,H,D).  Same guards as reference hf_adapter.py:137-147."""
     # reference hf_adapter.py:121-128: a configured sliding window that is shorter than the (local) key length
     # is forwarded as window_size=(w, w); llama3_flash_attn_varlen_func applies it in the kernels (flash_attn
@@ -87,6 +87,10 @@ def _ring_attention(query_states, key_states, value_states, *, dropout, softmax_
     # a configured logit soft cap (Gemma-2: 50.0, together with the sliding window on alternating layers) is applied in
     # the kernels: with_softcap binds it to this one call (None / 0: the function itself)
     attn_func = llama3_flash_attn_varlen_func if softcap is None else with_softcap(llama3_flash_attn_varlen_func, softcap)
+    # attention sinks (GPT-OSS: one learnable logit per query head, which transformers passes as `s_aux`): with_sinks binds the
+    # parameter to this one call and autograd fills its .grad with this rank's partial (a capped function is refused there)
+    if s_aux is not None:
+        attn_func = with_sinks(attn_func, s_aux)
     attn_output = attn_func(
         query_states.squeeze(dim=0),
         key_states.squeeze(dim=0),
@@ -127,13 +131,15 @@ def ring_flash_attention_forward(
     scaling: Optional[float] = None,
     sliding_window: Optional[int] = None,
     softcap: Optional[float] = None,
+    s_aux: Optional[torch.Tensor] = None,
     **kwargs,
 ) -> Tuple[torch.Tensor, None]:
     """AttentionInterface entry (query (B,H,S,D), key/value (B,Hk,S,D)) — the counterpart of
     reference hf_adapter.py:293-358."""
     if not RING_ATTN_SWITCH and _STATE["fallback"] is not None:
         return _STATE["fallback"](module, query, key, value, attention_mask, dropout=dropout, scaling=scaling,
-                                  sliding_window=sliding_window, softcap=softcap, **kwargs)
+                                  sliding_window=sliding_window, softcap=softcap,
+                                  **({} if s_aux is None else {"s_aux": s_aux}), **kwargs)
     original_dtype = query.dtype
     target_dtype = _target_dtype(query, module)
     # FA layout is (B,S,H,D)
@@ -147,7 +153,7 @@ def ring_flash_attention_forward(
         is_causal = getattr(module, "is_causal", True)
     attn_output = _ring_attention(query, key, value, dropout=dropout, softmax_scale=scaling, causal=is_causal,
                                   softcap=softcap, deterministic=kwargs.get("deterministic", None),
-                                  sliding_window=sliding_window)
+                                  sliding_window=sliding_window, s_aux=s_aux)
     return attn_output.to(original_dtype), None
 
 

@@ -59,6 +59,7 @@ class HipBackend:
     serves_mask_shift_lens = True   # ... and `mask_shift_lens` (ABI 8), the per-sequence shift the packed (varlen) ring schedules need
     serves_alibi = True             # fwd / bwd take `alibi=(slopes, shift)` (include/rfa.h: rfa_ext_args)
     serves_softcap = True           # ... and `softcap=` (flash_attn's logit soft-capping: rfa_ext_args.softcap)
+    serves_sinks = True             # sink_apply / sink_grad (include/rfa.h: rfa_sink_apply, rfa_sink_grad): ring_flash_attn.with_sinks
     serves_dropout_positions = True  # `dropout=` takes the position maps (q_map, k_map): what dropout over a dense ring, zigzag or stripe schedule needs
 
     def __init__(self):
@@ -405,6 +406,68 @@ class HipBackend:
         a.dtype = self._dtype(block_out)
         _C.check(self.lib.rfa_merge(C.byref(a), _stream(block_out)), "rfa_merge")
 
+    # ------------------------------------------------------------------ attention sinks
+    def sink_apply(self, out, lse, sinks, *, varlen, inplace=False):
+        """(out', lse') of the attention with one sink logit per query head, from the merged (out, lse) of the attention
+        without it: lse' = logaddexp(lse, sinks[h]), out' = out * exp(lse - lse') (include/rfa.h: rfa_sink_apply).
+        out (B,S,H,D) with lse (B,H,S), or varlen: (T,H,D) with (H,T); sinks (H,), any floating dtype.  New tensors unless
+        `inplace` (then `out` and `lse` are overwritten and returned)."""
+        self._check_dev(out, lse, sinks)
+        if lse.stride(-1) != 1 and lse.shape[-1] != 1:
+            lse, inplace_lse = lse.contiguous(), True
+        else:
+            inplace_lse = inplace
+        out_dst = out if inplace else torch.empty_like(out)
+        lse_dst = lse if inplace_lse else torch.empty_like(lse)
+        s32 = _sinks_f32(sinks, out)
+        a = _C.SinkApplyArgs()
+        a.out_src, a.out_src_st = _ptr(out), _st3(out, varlen)
+        a.out_dst, a.out_dst_st = _ptr(out_dst), _st3(out_dst, varlen)
+        a.lse_src, a.lse_dst = _ptr(lse), _ptr(lse_dst)
+        a.lse_src_batch, a.lse_src_head = _lse_st(lse, varlen)
+        a.lse_dst_batch, a.lse_dst_head = _lse_st(lse_dst, varlen)
+        a.sinks = _ptr(s32)
+        a.B, (a.S, a.H, a.D) = (1, out.shape) if varlen else (out.shape[0], out.shape[1:])
+        a.dtype = self._dtype(out)
+        _C.check(self.lib.rfa_sink_apply(C.byref(a), _stream(out)), "rfa_sink_apply")
+        return out_dst, lse_dst
+
+    def sink_grad(self, dout, out, lse, sinks, *, varlen):
+        """(H,) fp32: dsink[h] = - sum over rows of exp(sinks[h] - lse') * rowsum(dout * out'), with the (out', lse') that
+        sink_apply returned (include/rfa.h: rfa_sink_grad) — summed in a fixed order, the same bits on every run.  dout may
+        be any strided view whose rows stay 16-byte aligned (anything else is copied)."""
+        self._check_dev(dout, out, lse, sinks)
+        if dout.stride(-1) != 1 or any(st % 8 for st in dout.stride()[:-1]) or dout.data_ptr() % 16:
+            dout = dout.contiguous()
+        if lse.stride(-1) != 1 and lse.shape[-1] != 1:
+            lse = lse.contiguous()
+        s32 = _sinks_f32(sinks, out)
+        dsink = torch.empty(s32.shape, dtype=torch.float32, device=out.device)
+        a = _C.SinkGradArgs()
+        a.dout, a.dout_st = _ptr(dout), _st3(dout, varlen)
+        a.out, a.out_st = _ptr(out), _st3(out, varlen)
+        a.lse = _ptr(lse)
+        a.lse_batch, a.lse_head = _lse_st(lse, varlen)
+        a.sinks, a.dsink = _ptr(s32), _ptr(dsink)
+        a.B, (a.S, a.H, a.D) = (1, out.shape) if varlen else (out.shape[0], out.shape[1:])
+        a.dtype = self._dtype(out)
+        nbytes = self.lib.rfa_sink_grad_workspace_bytes(C.byref(a))
+        if nbytes:
+            ws = self._sink_scratch(nbytes, out.device)
+            a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+        _C.check(self.lib.rfa_sink_grad(C.byref(a), _stream(out)), "rfa_sink_grad")
+        return dsink
+
+    def _sink_scratch(self, nbytes, device):
+        """the partial sums of sink_grad: ONE reusable buffer per (device, stream) in the scratch pool (kernels of one stream
+        run in order, so the next call cannot overwrite partials that are still to be read); release_scratch() drops it"""
+        key = ("sink", device.index if device.index is not None else torch.cuda.current_device(),
+               torch.cuda.current_stream(device).cuda_stream)
+        buf = self._ds_pool.get(key)
+        if buf is None or buf.numel() < nbytes:
+            buf = self._ds_pool[key] = torch.empty(max(nbytes, 1 << 16), dtype=torch.uint8, device=device)
+        return buf
+
     def sum_slots(self, src: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
         """dst[...] = sum over dim 0 of src (io dtype, summed in fp32).  src: (W, B, S, H, D) or (W, T, H, D), each slot
         laid out like dst up to strides; dst may be a strided view (a slice of a packed gradient)."""
@@ -469,6 +532,14 @@ def _set_dropout(a, dropout):
     if len(dropout) > 5:
         (a.q_pos_stride, a.q_pos_split, a.q_pos_offset2), (a.k_pos_stride, a.k_pos_split, a.k_pos_offset2) = (
             tuple(int(x) for x in m) for m in dropout[5:7])
+
+
+def _sinks_f32(sinks, like):
+    """the sinks as the kernels read them: (H,) fp32, contiguous, on `like`'s device (a copy only when they are not)"""
+    if sinks.dim() != 1 or sinks.shape[0] != like.shape[-2] or sinks.device != like.device or not sinks.is_floating_point():
+        raise ValueError(f"ring_flash_attn: sinks must be a floating tensor of shape ({like.shape[-2]},) on {like.device}; "
+                         f"got {tuple(sinks.shape)} {sinks.dtype} on {sinks.device}")
+    return sinks.detach().to(torch.float32).contiguous()
 
 
 def _ext_args(alibi, q, softcap=0.0):

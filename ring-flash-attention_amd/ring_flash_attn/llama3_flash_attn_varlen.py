@@ -27,7 +27,8 @@ import torch
 from . import config
 from .backend import get_backend
 from .utils import AllGatherComm as Comm, group_rank_world, reduce_scatter_async, single_rank
-from ._api import _check_unsupported, _opaque, checked_alibi, checked_softcap, softcap_scope, window_ok_for
+from ._api import (_check_unsupported, _opaque, apply_sinks, checked_alibi, checked_sinks, checked_softcap, sink_args, sinks_grad,
+                   softcap_scope, window_ok_for)
 from ._common import alibi_kw, _as_cu, dropout_arg, draw_dropout_seed, packed_pair
 
 
@@ -313,7 +314,7 @@ def llama3_flash_attn_varlen_backward(
 
 
 def _l3_forward(ctx, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, heads_k_stride, local_k_slice,
-                dropout_p, softmax_scale, causal, window_size, alibi_slopes, deterministic, return_softmax, group):
+                dropout_p, softmax_scale, causal, window_size, alibi_slopes, deterministic, return_softmax, group, sinks=None):
     if softmax_scale is None:
         softmax_scale = q.shape[-1] ** (-0.5)
     # K/V are gathered: one kernel sees them all.  A bias needs the global distance i - j: on several ranks the bottom-right
@@ -321,6 +322,7 @@ def _l3_forward(ctx, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seql
     _check_unsupported(dropout_p, window_size, alibi_slopes, windows_ok=True, alibi_ok=window_ok_for(group) or bool(causal))
     alibi_slopes = checked_alibi(alibi_slopes, q, len(cu_seqlens_q) - 1, "llama3_flash_attn_varlen_func")
     ctx.softcap = checked_softcap(dropout_p, alibi_slopes, q, "llama3_flash_attn_varlen_func", window_size, causal)
+    sinks = checked_sinks(sinks, q, "llama3_flash_attn_varlen_func")
     # (strided views — the halves of a packed kv — are fine: the kernels take strides, and the all-gather sources are
     #  made contiguous per head group where they are posted)
     q, k, v = (t if t.stride(-1) == 1 else t.contiguous() for t in (q, k, v))
@@ -333,7 +335,10 @@ def _l3_forward(ctx, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seql
             local_k_slice, softmax_scale=softmax_scale, dropout_p=dropout_p, causal=causal,
             window_size=window_size, alibi_slopes=alibi_slopes, deterministic=False, dropout_seed=ctx.dropout[1],
         )
-    ctx.save_for_backward(q, k, v, out, softmax_lse, cu_seqlens_q, cu_seqlens_k)
+    # (with_sinks: the sink joins the merged result of this rank's query rows; out', lse' are saved and returned)
+    out, softmax_lse = apply_sinks(sinks, out, softmax_lse)
+    ctx.save_for_backward(q, k, v, out, softmax_lse, cu_seqlens_q, cu_seqlens_k, *(() if sinks is None else (sinks,)))
+    ctx.has_sinks = sinks is not None
     ctx.static = (max_seqlen_q, max_seqlen_k, heads_k_stride, local_k_slice)
     ctx.softmax_scale = softmax_scale
     ctx.causal = causal
@@ -345,13 +350,22 @@ def _l3_forward(ctx, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seql
 
 
 def _l3_backward(ctx, dout, grads=None):
-    q, k, v, out, softmax_lse, cu_seqlens_q, cu_seqlens_k = ctx.saved_tensors
+    q, k, v, out, softmax_lse, cu_seqlens_q, cu_seqlens_k = ctx.saved_tensors[:7]
     with softcap_scope(ctx.softcap):
         return llama3_flash_attn_varlen_backward(
             ctx.group, dout, q, k, v, out, softmax_lse, cu_seqlens_q, cu_seqlens_k, *ctx.static,
             softmax_scale=ctx.softmax_scale, dropout_p=ctx.dropout[0], causal=ctx.causal, window_size=ctx.window_size,
             alibi_slopes=ctx.alibi_slopes, deterministic=ctx.deterministic, dropout_seed=ctx.dropout[1], grads=grads,
         )
+
+
+def _l3_tail(ctx, dout):
+    """the gradients of everything behind the tensors: None for the 14 plain arguments — and for the slot of a `sinks` that is
+    not there — or the sinks' gradient in the 15th (with_sinks)"""
+    if not ctx.has_sinks:
+        return (None,) * 15
+    out, softmax_lse, sinks = ctx.saved_tensors[3], ctx.saved_tensors[4], ctx.saved_tensors[7]
+    return (None,) * 14 + sinks_grad(ctx, sinks, dout, out, softmax_lse)
 
 
 class Llama3FlashAttnVarlenFunc(torch.autograd.Function):
@@ -363,7 +377,7 @@ class Llama3FlashAttnVarlenFunc(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout, *args):
-        return _l3_backward(ctx, dout) + (None,) * 15
+        return _l3_backward(ctx, dout) + _l3_tail(ctx, dout)
 
 
 class Llama3FlashAttnVarlenKVPackedFunc(torch.autograd.Function):
@@ -380,7 +394,7 @@ class Llama3FlashAttnVarlenKVPackedFunc(torch.autograd.Function):
         k = ctx.saved_tensors[1]
         dkv = torch.empty((k.shape[0], 2) + tuple(k.shape[1:]), dtype=k.dtype, device=k.device)
         dq, _, _ = _l3_backward(ctx, dout, (torch.empty_like(ctx.saved_tensors[0]), dkv[:, 0], dkv[:, 1]))
-        return (dq, dkv) + (None,) * 15
+        return (dq, dkv) + _l3_tail(ctx, dout)
 
 
 class Llama3FlashAttnVarlenQKVPackedFunc(torch.autograd.Function):
@@ -395,7 +409,7 @@ class Llama3FlashAttnVarlenQKVPackedFunc(torch.autograd.Function):
         q = ctx.saved_tensors[0]
         dqkv = torch.empty((q.shape[0], 3) + tuple(q.shape[1:]), dtype=q.dtype, device=q.device)
         _l3_backward(ctx, dout, (dqkv[:, 0], dqkv[:, 1], dqkv[:, 2]))
-        return (dqkv,) + (None,) * 15
+        return (dqkv,) + _l3_tail(ctx, dout)
 
 
 def _make_llama3_api():
@@ -404,7 +418,7 @@ def _make_llama3_api():
              deterministic=False, return_attn_probs=False, group=None):
         return Llama3FlashAttnVarlenFunc.apply(
             q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, heads_k_stride, local_k_slice,
-            dropout_p, softmax_scale, causal, window_size, alibi_slopes, deterministic, return_attn_probs, group)
+            dropout_p, softmax_scale, causal, window_size, alibi_slopes, deterministic, return_attn_probs, group, *sink_args())
 
     # (same positional tails as the reference wrappers, llama3_flash_attn_varlen.py:390-445)
     def kvpacked_func(q, kv, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, heads_k_stride, local_k_slice,
@@ -413,7 +427,7 @@ def _make_llama3_api():
         return Llama3FlashAttnVarlenKVPackedFunc.apply(
             q, kv, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, heads_k_stride,
             local_k_slice, dropout_p, softmax_scale, causal, window_size, alibi_slopes, deterministic,
-            return_attn_probs, group)
+            return_attn_probs, group, *sink_args())
 
     def qkvpacked_func(qkv, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, heads_k_stride, local_k_slice,
                        dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1), alibi_slopes=None,
@@ -421,7 +435,7 @@ def _make_llama3_api():
         return Llama3FlashAttnVarlenQKVPackedFunc.apply(
             qkv, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, heads_k_stride,
             local_k_slice, dropout_p, softmax_scale, causal, window_size, alibi_slopes, deterministic,
-            return_attn_probs, group)
+            return_attn_probs, group, *sink_args())
 
     func.__name__ = func.__qualname__ = "llama3_flash_attn_varlen_func"
     kvpacked_func.__name__ = kvpacked_func.__qualname__ = "llama3_flash_attn_varlen_kvpacked_func"

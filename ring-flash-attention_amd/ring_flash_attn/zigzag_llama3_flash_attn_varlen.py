@@ -26,7 +26,8 @@ llama3_flash_attn_varlen_func; all heads are processed per call.
 """
 import torch
 
-from ._api import _check_unsupported, _opaque, checked_alibi, checked_softcap, softcap_scope, window_ok_for
+from ._api import (_check_unsupported, _opaque, apply_sinks, checked_alibi, checked_sinks, checked_softcap, sink_args, sinks_grad,
+                   softcap_scope, window_ok_for)
 from ._common import _as_cu, alibi_kw
 from .backend import get_backend
 from .llama3_flash_attn_varlen import llama3_flash_attn_prepare_cu_seqlens
@@ -127,7 +128,7 @@ def zigzag_llama3_flash_attn_varlen_backward(process_group, dout, q, k, v, out, 
 class ZigZagLlama3FlashAttnVarlenFunc(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, cu_seqlens, heads_k_stride, dropout_p, softmax_scale, causal, window_size, alibi_slopes,
-                deterministic, return_softmax, group):
+                deterministic, return_softmax, group, sinks=None):
         if softmax_scale is None:
             softmax_scale = q.shape[-1] ** (-0.5)
         _check_unsupported(dropout_p, window_size, alibi_slopes, windows_ok=True,   # K/V are gathered
@@ -137,6 +138,7 @@ class ZigZagLlama3FlashAttnVarlenFunc(torch.autograd.Function):
                                       "supported (the two stream slices hold different sequences); pass (H,)")
         alibi_slopes = checked_alibi(alibi_slopes, q, 0, "zigzag_llama3_flash_attn_varlen_func")
         ctx.softcap = checked_softcap(dropout_p, alibi_slopes, q, "zigzag_llama3_flash_attn_varlen_func", window_size, causal)
+        sinks = checked_sinks(sinks, q, "zigzag_llama3_flash_attn_varlen_func")
         if dropout_p and dropout_p > 0:
             raise NotImplementedError("zigzag_llama3_flash_attn_varlen_func: dropout is not supported")
         if q.shape[0] % 2 != 0 or k.shape[0] != q.shape[0] or v.shape[0] != q.shape[0]:
@@ -155,19 +157,20 @@ class ZigZagLlama3FlashAttnVarlenFunc(torch.autograd.Function):
             out, lse = zigzag_llama3_flash_attn_varlen_forward(group, q, k, v, params, softmax_scale, causal, window_size,
                                                                alibi_slopes)
         ctx.alibi_slopes = alibi_slopes
-        ctx.save_for_backward(q, k, v, out, lse)
+        out, lse = apply_sinks(sinks, out, lse)             # (with_sinks: out', lse' are saved and returned)
+        ctx.save_for_backward(q, k, v, out, lse, *(() if sinks is None else (sinks,)))
         ctx.params = params
         ctx.meta = (softmax_scale, causal, tuple(window_size), deterministic, group)
         return out if not return_softmax else (out, lse, None)
 
     @staticmethod
     def backward(ctx, dout, *args):
-        q, k, v, out, lse = ctx.saved_tensors
+        q, k, v, out, lse, *sinks = ctx.saved_tensors
         softmax_scale, causal, window_size, deterministic, group = ctx.meta
         with softcap_scope(ctx.softcap):
             dq, dk, dv = zigzag_llama3_flash_attn_varlen_backward(group, dout, q, k, v, out, lse, ctx.params, softmax_scale,
                                                                   causal, window_size, deterministic, ctx.alibi_slopes)
-        return (dq, dk, dv) + (None,) * 10
+        return (dq, dk, dv) + (None,) * 10 + sinks_grad(ctx, sinks[0] if sinks else None, dout, out, lse)
 
 
 def _make_api():
@@ -175,7 +178,7 @@ def _make_api():
              window_size=(-1, -1), alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None):
         return ZigZagLlama3FlashAttnVarlenFunc.apply(q, k, v, cu_seqlens, heads_k_stride, dropout_p, softmax_scale,
                                                      causal, window_size, alibi_slopes, deterministic,
-                                                     return_attn_probs, group)
+                                                     return_attn_probs, group, *sink_args())
 
     def kvpacked_func(q, kv, cu_seqlens, heads_k_stride=1, **kw):
         return func(q, kv[:, 0], kv[:, 1], cu_seqlens, heads_k_stride, **kw)
