@@ -520,6 +520,55 @@ typedef struct {
 int64_t rfa_sink_grad_workspace_bytes(const rfa_sink_grad_args *args);
 int rfa_sink_grad(const rfa_sink_grad_args *args, void *stream);
 
+/* Sequence/head exchange copies (DeepSpeed-Ulysses in front of a ring: ring_flash_attn.with_ulysses).  Inside a group of U
+ * ranks every rank trades heads for rows with ONE all-to-all per direction; this entry point is the layout change on either
+ * side of it, for up to three tensors of one call in one launch.  No attention kernel knows about it and no existing struct
+ * changes (ABI 8 revision 1 stays).  Three views of a tensor, rank at index p of the group, Hs = H / U:
+ *     local    (B, S, P, H, D)        this rank's rows, all heads; P parts (1: q, k, v, out; 2: packed kv; 3: qkv)
+ *     merged   (B, U*S, P, Hs, D)     the U ranks' rows, head slice p
+ *     slots    U x { for each tensor of the call: [B][S][P][Hs][D] }    the all-to-all buffer, contiguous; slot j is what is
+ *                                     sent to rank j, or what arrived from rank j
+ * local and merged take any (batch, row, part, head) element strides with last stride 1 and 16-byte aligned rows.  Slot j pairs
+ * with head slice j of the local view and, row i of it, with row m(j, i) of the merged view:
+ *     RFA_SEQHEAD_CONTIGUOUS  m = j S + i                                                     (the ring schedule's rows)
+ *     RFA_SEQHEAD_ZIGZAG      m = i < S/2 ? j S/2 + i : U S/2 + (U-1-j) S/2 + (i - S/2)       (S even)
+ *     RFA_SEQHEAD_STRIPE      m = i U + j
+ * so that the merged tensor is the schedule's own layout at 1/U of the ranks.  Ops (t[k].ptr is the local or the merged view, whichever the op names;
+ * the slot buffer is the other side):
+ *     RFA_SEQHEAD_PACK             local  -> slots      (before the all-to-all, towards the attention)
+ *     RFA_SEQHEAD_UNPACK           slots  -> merged     (after it)
+ *     RFA_SEQHEAD_MERGED_TO_SLOTS  merged -> slots      (inverse of UNPACK: out and the gradients on the way back)
+ *     RFA_SEQHEAD_SLOTS_TO_HEADS   slots  -> local      (inverse of PACK)
+ * Pure data movement: bytes are copied, never converted.  Every element of the destination inside the map is written exactly
+ * once, nothing outside it is touched.  t[k].H is the head count of the LOCAL view (the merged one has H / U).
+ * Checks, in this order and before any pointer is read: NULL struct RFA_ERR_NULL; struct_bytes != sizeof, reserved != 0, op or
+ * layout unknown, ntensors outside 1..3, a P outside 1..3 RFA_ERR_ARGS; elem_bytes != 2 RFA_ERR_DTYPE; D not a multiple of 8 in
+ * 8..256 RFA_ERR_HEAD_DIM; U <= 0, B < 0, S < 0, odd S with ZIGZAG, U*S or U*S*B above 2^31 - 1 RFA_ERR_SHAPE; an H <= 0 or not
+ * divisible by U, of any tensor, RFA_ERR_HEADS; then a tensor's 16-byte chunk count (U B S P (H/U) D/8, which needs its H) above
+ * 2^31 - 1 RFA_ERR_SHAPE; B == 0 or S == 0: RFA_OK, nothing is launched; NULL tensors or
+ * slots RFA_ERR_NULL; pointers or strides off the 16-byte contract RFA_ERR_ALIGN; slots_elems below U times the slot size
+ * RFA_ERR_ARGS. */
+enum { RFA_SEQHEAD_PACK = 0, RFA_SEQHEAD_UNPACK = 1, RFA_SEQHEAD_MERGED_TO_SLOTS = 2, RFA_SEQHEAD_SLOTS_TO_HEADS = 3 };
+enum { RFA_SEQHEAD_CONTIGUOUS = 0, RFA_SEQHEAD_ZIGZAG = 1, RFA_SEQHEAD_STRIPE = 2 };
+typedef struct {
+  void *ptr;               /* local or merged view (by op); read or written (by op) */
+  int64_t batch, row, part, head; /* element strides; `part` unused when P == 1 */
+  int32_t P;               /* 1, 2 or 3 */
+  int32_t H;               /* heads per part of the LOCAL view */
+} rfa_seq_head_tensor;
+typedef struct {
+  uint32_t struct_bytes;   /* sizeof(rfa_seq_head_args) */
+  uint32_t reserved;       /* 0 */
+  int32_t op, layout;
+  int32_t U, B, S, D;      /* S: rows of the LOCAL view */
+  int32_t elem_bytes;      /* 2 */
+  int32_t ntensors;        /* 1..3 */
+  rfa_seq_head_tensor t[3];
+  void *slots;             /* 16-byte aligned */
+  int64_t slots_elems;     /* its size in elements: at least U * sum_k B S P_k (H_k / U) D */
+} rfa_seq_head_args;
+int rfa_seq_head_copy(const rfa_seq_head_args *args, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

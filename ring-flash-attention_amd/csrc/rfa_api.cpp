@@ -1319,5 +1319,56 @@ int rfa_sink_grad(const rfa_sink_grad_args* a, void* stream) {
   return launch_sink_grad(p, a->dtype, (hipStream_t)stream) ? RFA_ERR_LAUNCH : RFA_OK;
 }
 
+// ---- sequence/head exchange copies (rfa.h; csrc/rfa_seqhead.hip) -----------------------------------------------------------
+int rfa_seq_head_copy(const rfa_seq_head_args* a, void* stream) {
+  if (!a) return RFA_ERR_NULL;
+  if (a->struct_bytes != sizeof(rfa_seq_head_args) || a->reserved != 0) return RFA_ERR_ARGS;
+  if (a->op < RFA_SEQHEAD_PACK || a->op > RFA_SEQHEAD_SLOTS_TO_HEADS) return RFA_ERR_ARGS;
+  if (a->layout < RFA_SEQHEAD_CONTIGUOUS || a->layout > RFA_SEQHEAD_STRIPE) return RFA_ERR_ARGS;
+  if (a->ntensors < 1 || a->ntensors > 3) return RFA_ERR_ARGS;
+  for (int k = 0; k < a->ntensors; ++k)
+    if (a->t[k].P < 1 || a->t[k].P > 3) return RFA_ERR_ARGS;
+  if (a->elem_bytes != 2) return RFA_ERR_DTYPE;
+  if (a->D <= 0 || a->D > kMaxHeadDim || (a->D % 8) != 0) return RFA_ERR_HEAD_DIM;
+  if (a->U <= 0 || a->B < 0 || a->S < 0) return RFA_ERR_SHAPE;
+  if (a->layout == RFA_SEQHEAD_ZIGZAG && (a->S & 1)) return RFA_ERR_SHAPE;
+  if ((int64_t)a->U * a->S > INT32_MAX) return RFA_ERR_SHAPE;
+  const int64_t rows = (int64_t)a->U * a->S * a->B;            // (U * S fits 31 bits: the product fits 62)
+  if (rows > INT32_MAX) return RFA_ERR_SHAPE;
+  for (int k = 0; k < a->ntensors; ++k)                        // every tensor's heads before any tensor's chunk count
+    if (a->t[k].H <= 0 || (a->t[k].H % a->U) != 0) return RFA_ERR_HEADS;
+  SeqHeadParams p{};
+  p.g.op = a->op; p.g.layout = a->layout;
+  p.g.U = (uint32_t)a->U; p.g.B = (uint32_t)a->B; p.g.S = (uint32_t)a->S; p.g.D8 = (uint32_t)a->D / 8;
+  int64_t slot = 0;
+  for (int k = 0; k < a->ntensors; ++k) {
+    const rfa_seq_head_tensor& s = a->t[k];
+    const int64_t rowchunks = (int64_t)s.P * (s.H / a->U) * (a->D / 8);
+    // (both factors are checked to fit 31 bits before they are multiplied: the product fits 62)
+    if (rowchunks > INT32_MAX || rows * rowchunks > INT32_MAX) return RFA_ERR_SHAPE;
+    const int64_t nchunks = rows * rowchunks;
+    SeqHeadTensor& t = p.t[k];
+    t.batch = s.batch; t.row = s.row; t.part = s.P > 1 ? s.part : 0; t.head = s.head;
+    t.slot_base = slot;
+    t.P = (uint32_t)s.P; t.Hs = (uint32_t)(s.H / a->U); t.rowchunks = (uint32_t)rowchunks; t.nchunks = (uint32_t)nchunks;
+    slot += (int64_t)a->B * a->S * rowchunks * 8;
+    p.strided[k] = s.ptr;
+  }
+  if (a->B == 0 || a->S == 0) return RFA_OK;
+  if (!a->slots) return RFA_ERR_NULL;
+  for (int k = 0; k < a->ntensors; ++k)
+    if (!a->t[k].ptr) return RFA_ERR_NULL;
+  if (!aligned16(a->slots)) return RFA_ERR_ALIGN;
+  for (int k = 0; k < a->ntensors; ++k) {
+    const rfa_seq_head_tensor& s = a->t[k];
+    if (!aligned16(s.ptr) || (s.batch % 8) || (s.row % 8) || (s.head % 8) || (s.P > 1 && (s.part % 8))) return RFA_ERR_ALIGN;
+  }
+  if (a->slots_elems < (int64_t)a->U * slot) return RFA_ERR_ARGS;
+  p.g.slot_stride = slot;
+  p.slots = a->slots;
+  p.ntensors = a->ntensors;
+  return launch_seq_head_copy(p, (hipStream_t)stream) ? RFA_ERR_LAUNCH : RFA_OK;
+}
+
 }  // extern "C"
 #pragma GCC visibility pop

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "rfa_common.hpp"
+#include "rfa_seqhead_index.h"
 
 #include <atomic>
 
@@ -227,6 +228,17 @@ constexpr int kSinkGradRows = 256;
 int64_t sink_grad_parts(int B, int S);
 int launch_sink_apply(const SinkApplyParams& p, int dtype, hipStream_t stream);
 int launch_sink_grad(const SinkGradParams& p, int dtype, hipStream_t stream);
+
+// sequence/head exchange copies (rfa_seqhead.hip; index arithmetic: rfa_seqhead_index.h): up to three tensors per launch
+// between their strided side and the all-to-all slot buffer, 16 bytes per thread
+struct SeqHeadParams {
+  SeqHeadGeom g;
+  SeqHeadTensor t[3];
+  void* strided[3];         // read by PACK / MERGED_TO_SLOTS, written by UNPACK / SLOTS_TO_HEADS
+  void* slots;              // the other side
+  int ntensors;
+};
+int launch_seq_head_copy(const SeqHeadParams& p, hipStream_t stream);
 
 int launch_fwd(const FwdParams& p, int dtype, hipStream_t stream);
 int fwd_qrows_per_block();

@@ -170,6 +170,36 @@ class SinkGradArgs(C.Structure):
     ]
 
 
+SEQHEAD_PACK, SEQHEAD_UNPACK, SEQHEAD_MERGED_TO_SLOTS, SEQHEAD_SLOTS_TO_HEADS = 0, 1, 2, 3
+SEQHEAD_CONTIGUOUS, SEQHEAD_ZIGZAG, SEQHEAD_STRIPE = 0, 1, 2
+
+
+class SeqHeadTensor(C.Structure):
+    """rfa_seq_head_tensor: one tensor of a sequence/head exchange copy — its local or merged view"""
+    _fields_ = [
+        ("ptr", C.c_void_p),
+        ("batch", C.c_int64), ("row", C.c_int64), ("part", C.c_int64), ("head", C.c_int64),
+        ("P", C.c_int32), ("H", C.c_int32),
+    ]
+
+
+class SeqHeadArgs(C.Structure):
+    """rfa_seq_head_args: the layout change on either side of the Ulysses all-to-all; struct_bytes is filled in here"""
+    _fields_ = [
+        ("struct_bytes", C.c_uint32), ("reserved", C.c_uint32),
+        ("op", C.c_int32), ("layout", C.c_int32),
+        ("U", C.c_int32), ("B", C.c_int32), ("S", C.c_int32), ("D", C.c_int32),
+        ("elem_bytes", C.c_int32), ("ntensors", C.c_int32),
+        ("t", SeqHeadTensor * 3),
+        ("slots", C.c_void_p), ("slots_elems", C.c_int64),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if not self.struct_bytes:
+            self.struct_bytes = C.sizeof(SeqHeadArgs)
+
+
 # every symbol include/rfa.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "rfa_abi_version": (C.c_int, []),
@@ -199,6 +229,7 @@ SYMBOLS = {
     "rfa_sink_apply": (C.c_int, [C.POINTER(SinkApplyArgs), C.c_void_p]),
     "rfa_sink_grad": (C.c_int, [C.POINTER(SinkGradArgs), C.c_void_p]),
     "rfa_sink_grad_workspace_bytes": (C.c_int64, [C.POINTER(SinkGradArgs)]),
+    "rfa_seq_head_copy": (C.c_int, [C.POINTER(SeqHeadArgs), C.c_void_p]),
 }
 
 _lib = None
@@ -232,6 +263,9 @@ def load():
     for name in ("rfa_sink_apply", "rfa_sink_grad", "rfa_sink_grad_workspace_bytes"):
         if not hasattr(lib, name):
             raise RuntimeError(f"ring_flash_attn: librfa_hip.so has no {name} (the attention-sink entry points); rebuild")
+    # ... and the sequence/head exchange copy (a struct of its own)
+    if not hasattr(lib, "rfa_seq_head_copy"):
+        raise RuntimeError("ring_flash_attn: librfa_hip.so has no rfa_seq_head_copy (the sequence/head exchange copies); rebuild")
     for name, (res, args) in SYMBOLS.items():
         fn = getattr(lib, name)  # AttributeError if the .so is stale
         fn.restype = res

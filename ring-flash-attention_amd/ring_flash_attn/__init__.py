@@ -61,3 +61,6 @@ from ._api import with_softcap
 # attention sinks (GPT-OSS, streaming-LLM; Hugging Face's `s_aux`): with_sinks(func, sinks) — one learnable logit per query
 # head as an extra softmax column with a zero value vector, with its gradient, on any group
 from ._api import with_sinks
+# DeepSpeed-Ulysses head parallelism in front of the dense schedules ("USP"): with_ulysses(func, ulysses_group) exchanges heads
+# for rows around `func`; make_usp_groups(func, ulysses_size) makes the (Ulysses, ring) groups of func's family
+from .ulysses import make_usp_groups, with_ulysses

@@ -313,6 +313,7 @@ def with_sinks(func, sinks):
         finally:
             _sinks.reset(token)
 
+    sunk._rfa_sinks = True                           # (with_ulysses refuses to wrap a function with sinks)
     return _opaque(sunk)
 
 

@@ -60,6 +60,7 @@ class HipBackend:
     serves_alibi = True             # fwd / bwd take `alibi=(slopes, shift)` (include/rfa.h: rfa_ext_args)
     serves_softcap = True           # ... and `softcap=` (flash_attn's logit soft-capping: rfa_ext_args.softcap)
     serves_sinks = True             # sink_apply / sink_grad (include/rfa.h: rfa_sink_apply, rfa_sink_grad): ring_flash_attn.with_sinks
+    serves_seq_head_exchange = True  # seq_head_copy (include/rfa.h: rfa_seq_head_copy): ring_flash_attn.with_ulysses
     serves_dropout_positions = True  # `dropout=` takes the position maps (q_map, k_map): what dropout over a dense ring, zigzag or stripe schedule needs
 
     def __init__(self):
@@ -467,6 +468,34 @@ class HipBackend:
         if buf is None or buf.numel() < nbytes:
             buf = self._ds_pool[key] = torch.empty(max(nbytes, 1 << 16), dtype=torch.uint8, device=device)
         return buf
+
+    # ------------------------------------------------------------------ sequence/head exchange (with_ulysses)
+    def seq_head_copy(self, op, layout, U, tensors, slots):
+        """one launch of the layout change on either side of the Ulysses all-to-all (include/rfa.h: rfa_seq_head_copy) for
+        up to three tensors.  op / layout: _C.SEQHEAD_*.  tensors: the LOCAL views (B,S,[P,]H,D) for PACK (read) and
+        SLOTS_TO_HEADS (written), the MERGED views (B,U*S,[P,]H/U,D) for UNPACK (written) and MERGED_TO_SLOTS (read); any
+        strides with last stride 1 and 16-byte aligned rows.  slots: the contiguous all-to-all buffer, U slots of
+        [tensor 0 | tensor 1 | ...], same dtype."""
+        self._check_dev(slots, *tensors)
+        local = op in (_C.SEQHEAD_PACK, _C.SEQHEAD_SLOTS_TO_HEADS)
+        a = _C.SeqHeadArgs()
+        a.op, a.layout, a.U = op, layout, U
+        t0 = tensors[0]
+        a.B, a.S, a.D = t0.shape[0], t0.shape[1] if local else t0.shape[1] // U, t0.shape[-1]
+        a.elem_bytes, a.ntensors = t0.element_size(), len(tensors)
+        for d, t in zip(a.t, tensors):
+            if t.dtype != slots.dtype or t.stride(-1) != 1:
+                raise ValueError("seq_head_copy: tensors and slots share one dtype; last (head_dim) stride must be 1")
+            d.ptr = t.data_ptr()
+            # (the stride of a dimension of length 1 is never used: 0, whatever torch reports for it)
+            st = [s_ if n > 1 else 0 for n, s_ in zip(t.shape, t.stride())]
+            d.batch, d.row, d.head = st[0], st[1], st[-2]
+            d.P, d.part = (t.shape[2], st[2]) if t.dim() == 5 else (1, 0)
+            d.H = t.shape[-2] if local else t.shape[-2] * U
+        a.slots, a.slots_elems = slots.data_ptr(), slots.numel()
+        if not slots.is_contiguous():
+            raise ValueError("seq_head_copy: the slot buffer must be contiguous")
+        _C.check(self.lib.rfa_seq_head_copy(C.byref(a), _stream(slots)), "rfa_seq_head_copy")
 
     def sum_slots(self, src: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
         """dst[...] = sum over dim 0 of src (io dtype, summed in fp32).  src: (W, B, S, H, D) or (W, T, H, D), each slot
