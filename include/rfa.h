@@ -569,6 +569,52 @@ typedef struct {
 } rfa_seq_head_args;
 int rfa_seq_head_copy(const rfa_seq_head_args *args, void *stream);
 
+/* Per-head max attention logit (QK-Clip / MuonClip; Transformer Engine's and Megatron's `max_logit`): for every query head h
+ *     max_logit[h] = max over batch b, query row i and the keys j that row i SEES of  softmax_scale * q[b,i,h,:] . k[b,j,h/G,:]
+ * for one block call — the raw scaled dot product (no soft cap, bias, dropout or sink enters it), -inf for a head that sees no
+ * pair.  "Sees" is the band of rfa_fwd_args with the same fields and the same meaning: causal, window, mask_shift,
+ * mask_shift_lens, q_half / k_half, dense or packed (cu_seqlens) input; dense calls go through the forward's normalisation
+ * (mask_shift_lens folded into mask_shift, unreachable bounds dropped, an empty band recognised on the host: it contributes
+ * -inf and launches no attention kernel).  No attention kernel and no existing struct changes (ABI 8 revision 1 stays;
+ * rfa_ext_args stays): the kernel is the forward's S phase alone (csrc/rfa_maxlogit.hip) — no V, no softmax, no output.
+ *   max_logit: (H,) fp32, DEVICE.  accumulate != 0: max_logit[h] = max(max_logit[h], new) — blocks of a ring and calls of a
+ *   step fold into one tensor the caller pre-fills with -inf; accumulate == 0: overwritten.
+ *   workspace: rfa_max_logit_workspace_bytes() bytes, one fp32 partial per (head, batch entry, block of 256 query rows); may be
+ *   NULL when that is 0.  Contents do not matter.  Partials are folded in a fixed order without atomics: the same bits on every
+ *   run, and a block cut into block calls accumulates to the bits of the uncut call.
+ *   NaN scores are ignored (the hardware max returns its other operand).
+ * Checks, in this order and before any tensor pointer is read: NULL struct RFA_ERR_NULL; struct_bytes != sizeof, reserved != 0,
+ * a half selector outside 0..2 RFA_ERR_ARGS; dtype RFA_ERR_DTYPE; D not a multiple of 8 in 8..256 RFA_ERR_HEAD_DIM; B, Sq, Sk
+ * or total_q negative, or more than 2^31 - 1 workgroups (H * B * ceil(Sq / 256)) RFA_ERR_SHAPE; H or Hk not positive, H not a
+ * multiple of Hk RFA_ERR_HEADS; softmax_scale not finite or not positive, only one of cu_seqlens_q / cu_seqlens_k, a non-zero
+ * mask_shift with cu_seqlens, |mask_shift_lens| * Sk >= 2^30, workspace_bytes below rfa_max_logit_workspace_bytes()
+ * RFA_ERR_ARGS; then NULL max_logit, and — unless the call has nothing to look at — NULL q, k or (where bytes are needed)
+ * workspace RFA_ERR_NULL; pointers or strides off the 16-byte contract RFA_ERR_ALIGN. */
+typedef struct {
+  uint32_t struct_bytes;   /* sizeof(rfa_max_logit_args) */
+  uint32_t reserved;       /* 0 */
+  const void *q, *k;       /* io dtype: (B,Sq,H,D) / (B,Sk,Hk,D), or packed (Tq,H,D) / (Tk,Hk,D) */
+  rfa_strides q_st, k_st;
+  const int32_t *cu_seqlens_q, *cu_seqlens_k; /* (B+1,) int32 device, or NULL */
+  int32_t B, Sq, Sk, H, Hk, D;                /* packed: Sq / Sk = the longest sequence */
+  int64_t total_q;         /* packed: rows of q addressed (kept for symmetry with rfa_fwd_args; not read) */
+  int32_t q_half, k_half;
+  float softmax_scale;
+  int32_t causal;
+  int32_t window, window_left, window_right;
+  int32_t mask_shift_lens;
+  int64_t mask_shift;
+  int32_t dtype;           /* rfa_dtype */
+  int32_t accumulate;
+  float *max_logit;        /* (H,) fp32 */
+  void *workspace;
+  int64_t workspace_bytes;
+} rfa_max_logit_args;
+/* bytes of workspace the call needs; 0 for a call without rows or keys and for arguments the call would refuse.  Pure function
+ * of H, B, Sq and q_half. */
+int64_t rfa_max_logit_workspace_bytes(const rfa_max_logit_args *args);
+int rfa_max_logit(const rfa_max_logit_args *args, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

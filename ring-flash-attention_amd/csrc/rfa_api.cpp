@@ -1370,5 +1370,66 @@ int rfa_seq_head_copy(const rfa_seq_head_args* a, void* stream) {
   return launch_seq_head_copy(p, (hipStream_t)stream) ? RFA_ERR_LAUNCH : RFA_OK;
 }
 
+// ---- per-head max attention logit (rfa.h; csrc/rfa_maxlogit.hip) ------------------------------------------------------------
+// everything that needs no tensor pointer, in the header's order; *nqblk = blocks of 256 query rows per batch entry
+static int max_logit_check(const rfa_max_logit_args* a, int* nqblk) {
+  if (!a) return RFA_ERR_NULL;
+  if (a->struct_bytes != sizeof(rfa_max_logit_args) || a->reserved != 0) return RFA_ERR_ARGS;
+  if (a->q_half < RFA_HALF_FULL || a->q_half > RFA_HALF_BACK || a->k_half < RFA_HALF_FULL || a->k_half > RFA_HALF_BACK)
+    return RFA_ERR_ARGS;
+  if (a->dtype != RFA_BF16 && a->dtype != RFA_F16) return RFA_ERR_DTYPE;
+  if (a->D <= 0 || a->D > kMaxHeadDim || (a->D % 8) != 0) return RFA_ERR_HEAD_DIM;
+  if (a->B < 0 || a->Sq < 0 || a->Sk < 0 || a->total_q < 0) return RFA_ERR_SHAPE;
+  *nqblk = (eff_len(a->Sq, a->q_half) + kMlQRows - 1) / kMlQRows;
+  if ((int64_t)(a->H > 0 ? a->H : 0) * a->B * *nqblk > INT32_MAX) return RFA_ERR_SHAPE;
+  if (a->H <= 0 || a->Hk <= 0 || (a->H % a->Hk) != 0) return RFA_ERR_HEADS;
+  if (!(a->softmax_scale > 0.f) || !(a->softmax_scale <= FLT_MAX)) return RFA_ERR_ARGS;       // NaN, infinite, zero, negative
+  if ((a->cu_seqlens_q == nullptr) != (a->cu_seqlens_k == nullptr)) return RFA_ERR_ARGS;
+  if (a->mask_shift != 0 && a->cu_seqlens_q != nullptr) return RFA_ERR_ARGS;
+  const int64_t n = a->mask_shift_lens < 0 ? -(int64_t)a->mask_shift_lens : (int64_t)a->mask_shift_lens;
+  if (n * (int64_t)a->Sk >= ((int64_t)1 << 30)) return RFA_ERR_ARGS;
+  return RFA_OK;
+}
+
+int64_t rfa_max_logit_workspace_bytes(const rfa_max_logit_args* a) {
+  int nqblk = 0;
+  if (max_logit_check(a, &nqblk) || a->Sk == 0) return 0;
+  return (int64_t)a->H * a->B * nqblk * (int64_t)sizeof(float);
+}
+
+int rfa_max_logit(const rfa_max_logit_args* a0, void* stream) {
+  int nqblk = 0;
+  if (int rc = max_logit_check(a0, &nqblk)) return rc;
+  const int64_t need = rfa_max_logit_workspace_bytes(a0);
+  if (a0->workspace_bytes < need) return RFA_ERR_ARGS;
+  if (!a0->max_logit) return RFA_ERR_NULL;
+  const rfa_max_logit_args a = fold_lens(*a0);
+  MaxLogitParams p{};
+  p.dst = a.max_logit; p.H = a.H; p.scale = a.softmax_scale; p.accumulate = a.accumulate ? 1 : 0;
+  // nothing to look at — no rows, no keys, or a dense band no element of the block lies in: -inf, no attention launch
+  bool attention = need > 0;
+  Band band{a.causal ? 1 : 0, a.window ? 1 : 0, a.window_left, a.window_right, 0, false};
+  if (attention && a.cu_seqlens_q == nullptr) {
+    band = norm_band(a.Sq, a.q_half, a.Sk, a.k_half, a.causal, a.window, a.window_left, a.window_right, a.mask_shift);
+    if (band.empty || dense_len(a.Sq, a.q_half) <= 0 || dense_len(a.Sk, a.k_half) <= 0) attention = false;
+  }
+  if (!attention) return launch_status(launch_max_logit(p, a.dtype, false, (hipStream_t)stream));
+  if (!a.q || !a.k || !a.workspace) return RFA_ERR_NULL;
+  if (!aligned16(a.q) || !aligned16(a.k) || !aligned16(a.workspace) || !stride_ok(a.q_st, 2) || !stride_ok(a.k_st, 2))
+    return RFA_ERR_ALIGN;
+  p.q = a.q; p.k = a.k; p.cu_q = a.cu_seqlens_q; p.cu_k = a.cu_seqlens_k;
+  p.q_st = cv(a.q_st); p.k_st = cv(a.k_st);
+  p.B = a.B; p.Hk = a.Hk; p.D = a.D; p.Sq = a.Sq; p.Sk = a.Sk;
+  p.q_half = a.q_half; p.k_half = a.k_half;
+  p.wl = (band.window && band.wl >= 0) ? band.wl : -1;
+  p.wr = band.causal ? 0 : ((band.window && band.wr >= 0) ? band.wr : -1);
+  const bool banded = p.wl >= 0 || p.wr >= 0;
+  p.shift = banded ? band.shift : 0;                             // (packed input: 0 — an absolute shift is refused above)
+  p.shift_lens = banded ? a.mask_shift_lens : 0;                 // (dense input: folded into the shift)
+  p.nqblk = nqblk;
+  p.partial = (float*)a.workspace;
+  return launch_status(launch_max_logit(p, a.dtype, true, (hipStream_t)stream));
+}
+
 }  // extern "C"
 #pragma GCC visibility pop

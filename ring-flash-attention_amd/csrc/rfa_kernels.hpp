@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include "rfa_common.hpp"
 #include "rfa_seqhead_index.h"
+#include "rfa_maxlogit_band.h"
 
 #include <atomic>
 
@@ -239,6 +240,28 @@ struct SeqHeadParams {
   int ntensors;
 };
 int launch_seq_head_copy(const SeqHeadParams& p, hipStream_t stream);
+
+// per-head max attention logit (rfa_maxlogit.hip; tile arithmetic: rfa_maxlogit_band.h): the forward's S phase alone.
+// Workgroup (batch b, query block qb, head h) stores the max of its UNSCALED visible scores to
+// partial[h * nparts + b * nqblk + qb] (-inf: it saw nothing), nparts = B * nqblk; maxlogit_finish_kernel folds a head's
+// partials in index order, multiplies by `scale` once and writes or max-accumulates dst[h].  nparts == 0 (an empty band): only
+// the finish kernel runs, with -inf.
+struct MaxLogitParams {
+  const void *q, *k;
+  const int32_t *cu_q, *cu_k;
+  Strides q_st, k_st;
+  int B, H, Hk, D, Sq, Sk;
+  int q_half, k_half;
+  int wl, wr;          // as in FwdParams (causal: wr = 0)
+  int64_t shift;       // dense: after the band normalisation; packed: 0
+  int shift_lens;      // packed input only
+  int nqblk;
+  float* partial;
+  float* dst;          // (H,)
+  float scale;
+  int accumulate;
+};
+int launch_max_logit(const MaxLogitParams& p, int dtype, bool attention, hipStream_t stream);
 
 int launch_fwd(const FwdParams& p, int dtype, hipStream_t stream);
 int fwd_qrows_per_block();

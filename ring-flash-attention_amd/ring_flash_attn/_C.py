@@ -200,6 +200,33 @@ class SeqHeadArgs(C.Structure):
             self.struct_bytes = C.sizeof(SeqHeadArgs)
 
 
+class MaxLogitArgs(C.Structure):
+    """rfa_max_logit_args: the per-head max attention logit of one block call; struct_bytes is filled in here"""
+    _fields_ = [
+        ("struct_bytes", C.c_uint32), ("reserved", C.c_uint32),
+        ("q", C.c_void_p), ("k", C.c_void_p),
+        ("q_st", Strides), ("k_st", Strides),
+        ("cu_seqlens_q", C.c_void_p), ("cu_seqlens_k", C.c_void_p),
+        ("B", C.c_int32), ("Sq", C.c_int32), ("Sk", C.c_int32), ("H", C.c_int32), ("Hk", C.c_int32), ("D", C.c_int32),
+        ("total_q", C.c_int64),
+        ("q_half", C.c_int32), ("k_half", C.c_int32),
+        ("softmax_scale", C.c_float),
+        ("causal", C.c_int32),
+        ("window", C.c_int32), ("window_left", C.c_int32), ("window_right", C.c_int32),
+        ("mask_shift_lens", C.c_int32),
+        ("mask_shift", C.c_int64),
+        ("dtype", C.c_int32),
+        ("accumulate", C.c_int32),
+        ("max_logit", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if not self.struct_bytes:
+            self.struct_bytes = C.sizeof(MaxLogitArgs)
+
+
 # every symbol include/rfa.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "rfa_abi_version": (C.c_int, []),
@@ -230,6 +257,8 @@ SYMBOLS = {
     "rfa_sink_grad": (C.c_int, [C.POINTER(SinkGradArgs), C.c_void_p]),
     "rfa_sink_grad_workspace_bytes": (C.c_int64, [C.POINTER(SinkGradArgs)]),
     "rfa_seq_head_copy": (C.c_int, [C.POINTER(SeqHeadArgs), C.c_void_p]),
+    "rfa_max_logit": (C.c_int, [C.POINTER(MaxLogitArgs), C.c_void_p]),
+    "rfa_max_logit_workspace_bytes": (C.c_int64, [C.POINTER(MaxLogitArgs)]),
 }
 
 _lib = None
@@ -266,6 +295,10 @@ def load():
     # ... and the sequence/head exchange copy (a struct of its own)
     if not hasattr(lib, "rfa_seq_head_copy"):
         raise RuntimeError("ring_flash_attn: librfa_hip.so has no rfa_seq_head_copy (the sequence/head exchange copies); rebuild")
+    # ... and the per-head max attention logit (a struct of its own)
+    for name in ("rfa_max_logit", "rfa_max_logit_workspace_bytes"):
+        if not hasattr(lib, name):
+            raise RuntimeError(f"ring_flash_attn: librfa_hip.so has no {name} (the max-logit entry points); rebuild")
     for name, (res, args) in SYMBOLS.items():
         fn = getattr(lib, name)  # AttributeError if the .so is stale
         fn.restype = res

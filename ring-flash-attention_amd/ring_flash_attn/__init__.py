@@ -61,6 +61,10 @@ from ._api import with_softcap
 # attention sinks (GPT-OSS, streaming-LLM; Hugging Face's `s_aux`): with_sinks(func, sinks) — one learnable logit per query
 # head as an extra softmax column with a zero value vector, with its gradient, on any group
 from ._api import with_sinks
+# QK-Clip / MuonClip (Transformer Engine's and Megatron's `max_logit`): with_max_logit(func, max_logit) max-accumulates the
+# largest pre-softmax logit softmax_scale * q.k of every query head, over the pairs the attention looks at, into an fp32 (H,)
+# tensor — this rank's partial; the caller's all_reduce(MAX) over the group completes it
+from ._api import with_max_logit
 # DeepSpeed-Ulysses head parallelism in front of the dense schedules ("USP"): with_ulysses(func, ulysses_group) exchanges heads
 # for rows around `func`; make_usp_groups(func, ulysses_size) makes the (Ulysses, ring) groups of func's family
 from .ulysses import make_usp_groups, with_ulysses

@@ -317,6 +317,82 @@ def with_sinks(func, sinks):
     return _opaque(sunk)
 
 
+# ---- per-head max attention logit (ring_flash_attn.with_max_logit) ---------------------------------------------------------
+def _check_max_logit_tensor(t, q=None):
+    """ValueError unless t is a contiguous float32 1-d tensor that does not require grad — and, given the call's first tensor
+    argument (q, or a packed qkv: heads are its second-to-last dimension), has one entry per query head on its device"""
+    ok = (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.dim() == 1 and t.is_contiguous()
+          and not t.requires_grad)
+    if ok and q is not None:
+        ok = t.shape[0] == q.shape[-2] and t.device == q.device
+    if not ok:
+        want = f"({q.shape[-2]},) on {q.device}" if q is not None else "(H,)"
+        got = f"{tuple(t.shape)} {t.dtype} on {t.device}, requires_grad={t.requires_grad}" if isinstance(t, torch.Tensor) else repr(t)
+        raise ValueError(f"ring_flash_attn.with_max_logit: max_logit must be a contiguous float32 tensor of shape {want}, one "
+                         f"entry per query head, that does not require grad; got {got}")
+
+
+def with_max_logit(func, max_logit):
+    """The per-head max attention logit (QK-Clip / MuonClip; Transformer Engine's and Megatron's `max_logit`) of one of this
+    package's public attention functions:
+
+        m = torch.full((H,), float("-inf"), device=q.device)        # fp32; -inf starts a new measurement
+        attn = with_max_logit(ring_flash_attn_func, m)
+        out = attn(q, k, v, causal=True)
+        dist.all_reduce(m, op=dist.ReduceOp.MAX, group=group)       # several ranks: the caller completes it
+
+    returns a callable with `func`'s signature and return value; every forward it runs max-accumulates, for every query head h,
+
+        max over batch b, this rank's query rows i and ALL keys j of the full sequence that row i sees
+        of softmax_scale * q[b,i,h,:] . k[b,j,h // G,:]
+
+    into max_logit[h] — "sees" is exactly the visibility of the attention that ran (causal, window_size, packed sequences, the
+    schedule's own layout); the value is the raw scaled dot product, whatever softcap, alibi_slopes, dropout or sinks the call
+    carries; a head without a visible pair contributes -inf; NaN logits are ignored.  There is no gradient and the backward
+    never touches the tensor; a re-run under activation checkpointing accumulates the same values again.
+    Several ranks: a rank gets its PARTIAL — its own query rows against all keys, the convention of `sinks.grad`; this package
+    posts no collective for it.
+    `max_logit` None: `func` itself.  Served: the 21 `*_func` of the package and `with_softcap` / `with_sinks` results of them, on
+    any group, head dims 8 .. 256.  TypeError: any other callable — a `with_ulysses` result (heads are renumbered) and a
+    `with_max_logit` result included.  ValueError, here or at the call: a tensor that is not float32, (H,), contiguous, on q's
+    device, or that requires grad; at the call: softmax_scale <= 0.  NotImplementedError at the call, before anything is
+    exchanged: a backend that does not serve `max_logit`.  Under torch.compile the call runs eagerly behind a graph break.
+    The separate pass over q and k costs about a forward's S GEMM (profiles/max_logit.md)."""
+    import functools
+    import inspect
+
+    import ring_flash_attn as pkg
+    from .backend import max_logit_scope, require_max_logit
+
+    if getattr(func, "_rfa_ulysses", False):
+        raise TypeError("ring_flash_attn.with_max_logit: `func` is a with_ulysses result; the exchange renumbers the heads a "
+                        "rank computes — not served yet (bind with_max_logit to the function and read the head slices)")
+    if getattr(func, "_rfa_max_logit", False):
+        raise TypeError("ring_flash_attn.with_max_logit: `func` is a with_max_logit result already")
+    public = {id(getattr(pkg, n)): n for n in dir(pkg) if n.endswith("_func")}
+    if id(func) not in public and not getattr(func, "_rfa_softcap", None) and not getattr(func, "_rfa_sinks", False):
+        raise TypeError("ring_flash_attn.with_max_logit: `func` must be one of the package's public attention functions "
+                        f"(ring_flash_attn.*_func) or a with_softcap / with_sinks result of one, got {func!r}")
+    if max_logit is None:
+        return func
+    _check_max_logit_tensor(max_logit)
+    sig = inspect.signature(func)
+
+    @functools.wraps(func, updated=())               # (updated=(): as in with_softcap)
+    def measured(*args, **kwargs):
+        bound = sig.bind(*args, **kwargs).arguments
+        _check_max_logit_tensor(max_logit, next(iter(bound.values())))
+        scale = bound.get("softmax_scale", None)
+        if scale is not None and not scale > 0:
+            raise ValueError(f"ring_flash_attn.with_max_logit: softmax_scale must be positive, got {scale!r}")
+        require_max_logit(public.get(id(func), getattr(func, "__name__", "the call")) + " with max_logit")
+        with max_logit_scope(max_logit):
+            return func(*args, **kwargs)
+
+    measured._rfa_max_logit = True
+    return _opaque(measured)
+
+
 def has_window(window_size) -> bool:
     return window_size is not None and (window_size[0] >= 0 or window_size[1] >= 0)
 

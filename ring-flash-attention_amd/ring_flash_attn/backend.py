@@ -61,6 +61,7 @@ class HipBackend:
     serves_softcap = True           # ... and `softcap=` (flash_attn's logit soft-capping: rfa_ext_args.softcap)
     serves_sinks = True             # sink_apply / sink_grad (include/rfa.h: rfa_sink_apply, rfa_sink_grad): ring_flash_attn.with_sinks
     serves_seq_head_exchange = True  # seq_head_copy (include/rfa.h: rfa_seq_head_copy): ring_flash_attn.with_ulysses
+    serves_max_logit = True          # max_logit (include/rfa.h: rfa_max_logit): ring_flash_attn.with_max_logit
     serves_dropout_positions = True  # `dropout=` takes the position maps (q_map, k_map): what dropout over a dense ring, zigzag or stripe schedule needs
 
     def __init__(self):
@@ -469,6 +470,60 @@ class HipBackend:
             buf = self._ds_pool[key] = torch.empty(max(nbytes, 1 << 16), dtype=torch.uint8, device=device)
         return buf
 
+    # ------------------------------------------------------------------ per-head max attention logit (with_max_logit)
+    def max_logit(self, q, k, dst, *, softmax_scale, causal, cu_seqlens_q=None, cu_seqlens_k=None, max_seqlen_q=None,
+                  max_seqlen_k=None, q_half=HALF_FULL, k_half=HALF_FULL, window=(-1, -1), mask_shift=0, mask_shift_lens=0,
+                  accumulate=True, head0=0):
+        """dst[head0 + h] = max(dst[head0 + h], m_h) (accumulate) or m_h, for the H query heads of q: m_h = the largest
+        softmax_scale * q.k over the (query row, key) pairs the block call `fwd(q, k, ...)` with the same geometry keywords
+        looks at, -inf when it looks at none (include/rfa.h: rfa_max_logit).  dst: fp32, contiguous, 1-d, on q's device.  The
+        raw scaled dot product: a soft cap, a bias, dropout and sinks do not enter it.  Same bits on every run."""
+        self._check_dev(q, k, dst)
+        varlen = cu_seqlens_q is not None
+        a = _C.MaxLogitArgs()
+        a.q, a.k = _ptr(q), _ptr(k)
+        a.q_st, a.k_st = _st3(q, varlen), _st3(k, varlen)
+        if varlen:
+            a.cu_seqlens_q, a.cu_seqlens_k = _ptr(cu_seqlens_q), _ptr(cu_seqlens_k)
+            a.B = cu_seqlens_q.numel() - 1
+            a.H, a.D = q.shape[1], q.shape[2]
+            a.Hk = k.shape[1]
+            a.Sq, a.Sk = int(max_seqlen_q), int(max_seqlen_k)
+            a.total_q = q.shape[0]
+        else:
+            a.B, a.Sq, a.H, a.D = q.shape
+            a.Sk, a.Hk = k.shape[1], k.shape[2]
+        head0 = int(head0)
+        if (dst.dtype != torch.float32 or dst.dim() != 1 or not dst.is_contiguous() or dst.device != q.device
+                or head0 < 0 or head0 + a.H > dst.numel()):
+            raise ValueError(f"ring_flash_attn: max_logit needs a contiguous float32 (H,) tensor on {q.device} with room for "
+                             f"heads [{head0}, {head0 + a.H}); got {tuple(dst.shape)} {dst.dtype} on {dst.device}")
+        a.q_half, a.k_half = q_half, k_half
+        a.softmax_scale = float(softmax_scale)
+        a.causal = 1 if causal else 0
+        if window is not None and (window[0] >= 0 or window[1] >= 0):
+            a.window, a.window_left, a.window_right = 1, int(window[0]), int(window[1])
+        a.mask_shift = int(mask_shift)
+        a.mask_shift_lens = int(mask_shift_lens)
+        a.dtype = self._dtype(q)
+        a.accumulate = 1 if accumulate else 0
+        a.max_logit = dst.data_ptr() + 4 * head0
+        nbytes = self.lib.rfa_max_logit_workspace_bytes(C.byref(a))
+        if nbytes:
+            ws = self._max_logit_scratch(nbytes, q.device)
+            a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+        _C.check(self.lib.rfa_max_logit(C.byref(a), _stream(q)), "rfa_max_logit")
+
+    def _max_logit_scratch(self, nbytes, device):
+        """the per-workgroup partials of max_logit: ONE reusable buffer per (device, stream) in the scratch pool, kept like
+        _sink_scratch (kernels of one stream run in order); release_scratch() drops it"""
+        key = ("maxlogit", device.index if device.index is not None else torch.cuda.current_device(),
+               torch.cuda.current_stream(device).cuda_stream)
+        buf = self._ds_pool.get(key)
+        if buf is None or buf.numel() < nbytes:
+            buf = self._ds_pool[key] = torch.empty(max(nbytes, 1 << 16), dtype=torch.uint8, device=device)
+        return buf
+
     # ------------------------------------------------------------------ sequence/head exchange (with_ulysses)
     def seq_head_copy(self, op, layout, U, tensors, slots):
         """one launch of the layout change on either side of the Ulysses all-to-all (include/rfa.h: rfa_seq_head_copy) for
@@ -655,12 +710,15 @@ def get_backend():
     """the operator backend of this process: the HIP library (raises if librfa_hip.so is missing — there is no CPU
     path).  Tests and bench.py's in-step timer replace it through ring_flash_attn._testing.set_backend.
     Inside `softcap_scope(cap)` with cap > 0 — the forward or the backward of ONE capped autograd node — the backend comes
-    wrapped so that every block call carries `softcap=cap`."""
+    wrapped so that every block call carries `softcap=cap`.  Inside a call bound by `with_max_logit` it comes wrapped — outside
+    a cap wrapper — so that every forward block call is followed by the backend's `max_logit` of the same block."""
     global _backend
     if _backend is None:
         _backend = HipBackend()
     cap = _softcap.get()
-    return _CappedBackend(_backend, cap) if cap else _backend
+    be = _CappedBackend(_backend, cap) if cap else _backend
+    dst = _max_logit.get()
+    return be if dst is None else _MaxLogitBackend(be, dst)
 
 
 # ---- logit soft-capping (ring_flash_attn.with_softcap) ------------------------------------------------------------------
@@ -718,3 +776,73 @@ class _CappedBackend:
 
     def bwd(self, *args, **kw):
         return self._be.bwd(*args, softcap=self._cap, **kw)
+
+
+# ---- per-head max attention logit (ring_flash_attn.with_max_logit) --------------------------------------------------------
+# The largest softmax_scale * q.k over the pairs an attention looks at is the max over the block calls its schedule makes: every
+# block call already names its q, its k and its visibility (causal, window, halves, packed lengths, where the block sits).  So
+# no schedule computes anything for it either: inside a call bound by with_max_logit, get_backend() hands out this wrapper,
+# which follows every `fwd` with the backend's `max_logit` of the same q, k and geometry keywords, max-accumulated into the
+# caller's tensor.  No new keyword reaches a backend's fwd.  The scope is entered by with_max_logit's callable only, around the
+# public call: a backward (which runs outside it) never touches the tensor, a checkpointed re-run accumulates the same values.
+_max_logit = contextvars.ContextVar("ring_flash_attn_max_logit", default=None)
+
+_MAX_LOGIT_GEOMETRY = ("softmax_scale", "causal", "cu_seqlens_q", "cu_seqlens_k", "max_seqlen_q", "max_seqlen_k", "q_half",
+                       "k_half", "window", "mask_shift", "mask_shift_lens")
+
+
+class max_logit_scope:
+    """`with max_logit_scope(t):` — forward block calls made inside max-accumulate their per-head max logit into t (None: none)"""
+
+    def __init__(self, dst):
+        self.dst = dst
+
+    def __enter__(self):
+        self.token = _max_logit.set(self.dst)
+        return self
+
+    def __exit__(self, *exc):
+        _max_logit.reset(self.token)
+        return False
+
+
+def require_max_logit(what):
+    """NotImplementedError unless the process's backend serves `max_logit` — asked at the public entry, before anything is
+    exchanged, on every rank alike"""
+    global _backend
+    if _backend is None:
+        _backend = HipBackend()
+    if not getattr(_backend, "serves_max_logit", False):
+        raise NotImplementedError(f"ring_flash_attn: {what} needs a backend that serves `max_logit`; "
+                                  f"{getattr(_backend, 'name', type(_backend).__name__)!r} does not")
+
+
+class _MaxLogitBackend:
+    """a backend whose every `fwd` is followed by `max_logit` of the same block into dst[head0 : head0 + q's heads]; everything
+    else is the wrapped backend's own (which may be a cap wrapper: the max is of the RAW logit and carries no cap)"""
+
+    def __init__(self, be, dst, head0=0):
+        object.__setattr__(self, "_be", be)
+        object.__setattr__(self, "_dst", dst)
+        object.__setattr__(self, "_head0", head0)
+
+    def __getattr__(self, name):
+        return getattr(self._be, name)
+
+    def __setattr__(self, name, value):
+        setattr(self._be, name, value)
+
+    def fwd(self, q, k, v, **kw):
+        res = self._be.fwd(q, k, v, **kw)
+        self._be.max_logit(q, k, self._dst, accumulate=True, head0=self._head0,
+                           **{n: kw[n] for n in _MAX_LOGIT_GEOMETRY if n in kw})
+        return res
+
+    def heads_from(self, head0):
+        return _MaxLogitBackend(self._be, self._dst, head0)
+
+
+def heads_from(be, head0):
+    """the backend for block calls whose q is the slice of query heads that starts at `head0` (llama3's head groups): the
+    max-logit wrapper then writes that slice of the caller's tensor; any other backend is returned as it is"""
+    return be.heads_from(head0) if isinstance(be, _MaxLogitBackend) else be

@@ -25,7 +25,7 @@ MI355X-first changes:
 import torch
 
 from . import config
-from .backend import get_backend
+from .backend import get_backend, heads_from
 from .utils import AllGatherComm as Comm, group_rank_world, reduce_scatter_async, single_rank
 from ._api import (_check_unsupported, _opaque, apply_sinks, checked_alibi, checked_sinks, checked_softcap, sink_args, sinks_grad,
                    softcap_scope, window_ok_for)
@@ -167,7 +167,8 @@ def llama3_flash_attn_varlen_forward(
         if gi + 1 < len(groups):
             pending = post_gather(gi + 1)          # next super-group's K/V arrive beside this one's attention
         q_slice = slice(g0 * nheads // nheads_k, (g0 + hs) * nheads // nheads_k)
-        be.fwd(q[:, q_slice], buf[0][local_k_slice], buf[1][local_k_slice],
+        # (heads_from: inside a with_max_logit call the slice's first head tells the wrapper where its heads go)
+        heads_from(be, q_slice.start).fwd(q[:, q_slice], buf[0][local_k_slice], buf[1][local_k_slice],
                softmax_scale=softmax_scale, causal=causal, out=out[:, q_slice], lse=lse[q_slice], window=window_size,
                dropout=drop(q_slice.start), **alibi_kw(alibi_slopes, heads=q_slice), **vl)
 
