@@ -615,6 +615,86 @@ typedef struct {
 int64_t rfa_max_logit_workspace_bytes(const rfa_max_logit_args *args);
 int rfa_max_logit(const rfa_max_logit_args *args, void *stream);
 
+/* A gradient of lse (ring_flash_attn.with_lse_grad).  lse_i = log sum_j exp(s_ij), so d lse_i / d s_ij = P_ij: a loss that
+ * also touches lse, with g_i = dLoss / dlse_i, adds g_i P_ij to dS.  Every backward kernel forms dS = P (dP - delta) — times
+ * (1 - t^2) under a soft cap, which multiplies (dP - delta) as a whole; P undropped under dropout, as lse is the undropped
+ * softmax's — so handing the UNCHANGED kernels
+ *     delta'_i = rowsum(dout_i * out_i) - g_i
+ * in place of delta serves it exactly, in every form (7-GEMM dQ, the dS hand-off, the 128-key / 256-key / balanced dK/dV
+ * kernels, head dims above 128), with a bias, windows, mask_shift, packed input and GQA.  No attention kernel and no existing
+ * struct changes (ABI 8 revision 1 stays; rfa_ext_args stays).
+ *   rfa_bwd_preprocess_lse: rfa_bwd_preprocess with `dlse` — fp32, laid out like lse / delta (dense (B, H, Sq), packed (H, Tq),
+ *   row stride 1) with batch / head strides of its own, addressed through the same cu_seqlens_q / q_half.  The accumulator is
+ *   rfa_bwd_preprocess's; the stored value is ONE fp32 subtraction further: bit for bit delta - dlse.  dlse == NULL: the call IS
+ *   rfa_bwd_preprocess (same kernel instance, same bits).  Rows without a visible key (lse = +inf) have P = 0: their dlse is
+ *   read and has no effect.
+ * Checks, in this order and before any launch: NULL struct RFA_ERR_NULL; dtype, head_dim, H <= 0, B < 0 as rfa_bwd_preprocess;
+ * Sq < 0 RFA_ERR_SHAPE; a non-zero `reserved`, a q_half outside 0..2 RFA_ERR_ARGS; B == 0 or Sq == 0: RFA_OK, nothing is
+ * launched; NULL dout, out or delta RFA_ERR_NULL; pointers or strides off the 16-byte contract RFA_ERR_ALIGN. */
+typedef struct {
+  const void *dout, *out;  /* io dtype */
+  rfa_strides dout_st, out_st;
+  float *delta;            /* same layout contract as lse */
+  int64_t delta_batch, delta_head;
+  const float *dlse;       /* NULL: rfa_bwd_preprocess */
+  int64_t dlse_batch, dlse_head;
+  const int32_t *cu_seqlens_q;
+  int32_t q_half;
+  int32_t B, H, D, Sq;
+  int32_t dtype;
+  int32_t reserved;        /* 0 */
+} rfa_bwd_preprocess_lse_args;
+int rfa_bwd_preprocess_lse(const rfa_bwd_preprocess_lse_args *args, void *stream);
+
+/* Pairwise merge of two FINISHED attention results (ring_flash_attn.merge_attn): attention over the union of two key sets is
+ *     lse = logaddexp(lse_a, lse_b),   w_x = exp(lse_x - lse),   out = w_a out_a + w_b out_b
+ * in fp32, out rounded to the io dtype once.  rfa_merge (the ring's running fp32 accumulator, with the reference's +inf rule)
+ * stays as it is.  Backward, from the four forward inputs alone, with x = sum_d dout_d (out_a - out_b)_d:
+ *     dout_a = w_a dout,   dout_b = w_b dout,   dlse_a = w_a dlse + w_a w_b x,   dlse_b = w_b dlse - w_a w_b x .
+ * x is summed in a fixed order without atomics: the same bits on every run.
+ * Empty rows: an infinite lse_x of EITHER sign (+inf: a direct forward; -inf: an accumulate-mode forward) means side x saw no
+ * key: its weight is 0, its out is never multiplied and all its gradients are 0.  Both sides empty: out = 0, lse = -inf.
+ * Layout: B x S rows of H heads, as rfa_sink_apply — dense out (B, S, H, D) with lse (B, H, S); packed out (T, H, D) with lse
+ * (H, T) is B = 1, S = T (batch strides unused).  Every tensor has strides of its own; lse-like tensors have row stride 1.
+ * The outputs must not alias the inputs.  rfa_merge_pair_bwd: dlse == NULL reads as zero.
+ * Checks, in this order and before any launch: NULL struct RFA_ERR_NULL; dtype, head_dim (a multiple of 8, <= 256), H <= 0,
+ * B < 0 as everywhere; S < 0, B or H above 65535, S * H above 16 * (2^31 - 1) RFA_ERR_SHAPE; a non-zero `reserved` RFA_ERR_ARGS;
+ * B == 0 or S == 0: RFA_OK, nothing is launched; NULL tensors (all but dlse) RFA_ERR_NULL; pointers or strides of the io-dtype
+ * tensors off the 16-byte contract RFA_ERR_ALIGN. */
+typedef struct {
+  const void *out_a, *out_b;   /* io dtype */
+  rfa_strides out_a_st, out_b_st;
+  const float *lse_a, *lse_b;
+  int64_t lse_a_batch, lse_a_head, lse_b_batch, lse_b_head; /* element strides; row stride is 1 */
+  void *out;
+  rfa_strides out_st;
+  float *lse;
+  int64_t lse_batch, lse_head;
+  int32_t B, S, H, D;
+  int32_t dtype;               /* rfa_dtype */
+  int32_t reserved;            /* 0 */
+} rfa_merge_pair_args;
+int rfa_merge_pair(const rfa_merge_pair_args *args, void *stream);
+
+typedef struct {
+  const void *dout;            /* io dtype */
+  rfa_strides dout_st;
+  const float *dlse;           /* NULL: zero */
+  int64_t dlse_batch, dlse_head;
+  const void *out_a, *out_b;   /* the forward's inputs */
+  rfa_strides out_a_st, out_b_st;
+  const float *lse_a, *lse_b;
+  int64_t lse_a_batch, lse_a_head, lse_b_batch, lse_b_head;
+  void *dout_a, *dout_b;       /* io dtype, overwritten */
+  rfa_strides dout_a_st, dout_b_st;
+  float *dlse_a, *dlse_b;      /* fp32, overwritten */
+  int64_t dlse_a_batch, dlse_a_head, dlse_b_batch, dlse_b_head;
+  int32_t B, S, H, D;
+  int32_t dtype;
+  int32_t reserved;            /* 0 */
+} rfa_merge_pair_bwd_args;
+int rfa_merge_pair_bwd(const rfa_merge_pair_bwd_args *args, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

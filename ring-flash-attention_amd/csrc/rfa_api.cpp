@@ -660,6 +660,27 @@ int rfa_bwd_preprocess(const rfa_bwd_preprocess_args* a, void* stream) {
   return launch_preprocess(p, a->dtype, (hipStream_t)stream) ? RFA_ERR_LAUNCH : RFA_OK;
 }
 
+// delta' = rowsum(dout * out) - dlse (rfa.h): the gradient of lse rides on delta into every backward kernel.  A NULL dlse
+// launches the plain instance — the call is rfa_bwd_preprocess.
+int rfa_bwd_preprocess_lse(const rfa_bwd_preprocess_lse_args* a, void* stream) {
+  if (!a) return RFA_ERR_NULL;
+  int rc = check_common(a->dtype, a->H, a->H, a->D, a->B);
+  if (rc) return rc;
+  if (a->Sq < 0) return RFA_ERR_SHAPE;
+  if (a->reserved != 0 || a->q_half < RFA_HALF_FULL || a->q_half > RFA_HALF_BACK) return RFA_ERR_ARGS;
+  if (a->B == 0 || a->Sq == 0) return RFA_OK;
+  if (!a->dout || !a->out || !a->delta) return RFA_ERR_NULL;
+  if (!aligned16(a->dout) || !aligned16(a->out) || !stride_ok(a->dout_st, 2) || !stride_ok(a->out_st, 2))
+    return RFA_ERR_ALIGN;
+  PreParams p{};
+  p.dout = a->dout; p.out = a->out; p.delta = a->delta; p.cu_q = a->cu_seqlens_q;
+  p.dout_st = cv(a->dout_st); p.out_st = cv(a->out_st);
+  p.delta_batch = a->delta_batch; p.delta_head = a->delta_head;
+  p.B = a->B; p.H = a->H; p.D = a->D; p.Sq = a->Sq; p.q_half = a->q_half;
+  p.dlse = a->dlse; p.dlse_batch = a->dlse_batch; p.dlse_head = a->dlse_head;
+  return launch_preprocess(p, a->dtype, (hipStream_t)stream) ? RFA_ERR_LAUNCH : RFA_OK;
+}
+
 // The dK/dV kernel sums the query heads of a K/V group itself, so GQA needs no scratch.  A workspace
 // (bf16/fp16 partials, (rows, Hk, D) x 2) is only used when the result is ADDED to fp32 accumulators or
 // when compute and reduction are issued as two phases (ring steps: compute overlaps the arrival of the
@@ -1317,6 +1338,48 @@ int rfa_sink_grad(const rfa_sink_grad_args* a, void* stream) {
   p.lse_batch = a->lse_batch; p.lse_head = a->lse_head;
   p.B = a->B; p.H = a->H; p.D = a->D; p.S = a->S;
   return launch_sink_grad(p, a->dtype, (hipStream_t)stream) ? RFA_ERR_LAUNCH : RFA_OK;
+}
+
+// ---- pairwise merge of two finished (out, lse) pairs and its backward (rfa.h; csrc/rfa_mergepair.hip) ---------------------
+int rfa_merge_pair(const rfa_merge_pair_args* a, void* stream) {
+  if (!a) return RFA_ERR_NULL;
+  int rc = sink_shape_check(a->dtype, a->B, a->S, a->H, a->D, a->reserved);
+  if (rc) return rc;
+  if (a->B == 0 || a->S == 0) return RFA_OK;
+  if (!a->out_a || !a->out_b || !a->lse_a || !a->lse_b || !a->out || !a->lse) return RFA_ERR_NULL;
+  if (!aligned16(a->out_a) || !aligned16(a->out_b) || !aligned16(a->out) || !stride_ok(a->out_a_st, 2) ||
+      !stride_ok(a->out_b_st, 2) || !stride_ok(a->out_st, 2))
+    return RFA_ERR_ALIGN;
+  MergePairParams p{};
+  p.out_a = a->out_a; p.out_b = a->out_b; p.out = a->out; p.lse_a = a->lse_a; p.lse_b = a->lse_b; p.lse = a->lse;
+  p.out_a_st = cv(a->out_a_st); p.out_b_st = cv(a->out_b_st); p.out_st = cv(a->out_st);
+  p.lse_a_st = LseSt{a->lse_a_batch, a->lse_a_head}; p.lse_b_st = LseSt{a->lse_b_batch, a->lse_b_head};
+  p.lse_st = LseSt{a->lse_batch, a->lse_head};
+  p.B = a->B; p.H = a->H; p.D = a->D; p.S = a->S;
+  return launch_merge_pair(p, a->dtype, (hipStream_t)stream) ? RFA_ERR_LAUNCH : RFA_OK;
+}
+
+int rfa_merge_pair_bwd(const rfa_merge_pair_bwd_args* a, void* stream) {
+  if (!a) return RFA_ERR_NULL;
+  int rc = sink_shape_check(a->dtype, a->B, a->S, a->H, a->D, a->reserved);
+  if (rc) return rc;
+  if (a->B == 0 || a->S == 0) return RFA_OK;
+  if (!a->dout || !a->out_a || !a->out_b || !a->lse_a || !a->lse_b || !a->dout_a || !a->dout_b || !a->dlse_a || !a->dlse_b)
+    return RFA_ERR_NULL;
+  if (!aligned16(a->dout) || !aligned16(a->out_a) || !aligned16(a->out_b) || !aligned16(a->dout_a) || !aligned16(a->dout_b) ||
+      !stride_ok(a->dout_st, 2) || !stride_ok(a->out_a_st, 2) || !stride_ok(a->out_b_st, 2) || !stride_ok(a->dout_a_st, 2) ||
+      !stride_ok(a->dout_b_st, 2))
+    return RFA_ERR_ALIGN;
+  MergePairBwdParams p{};
+  p.dout = a->dout; p.out_a = a->out_a; p.out_b = a->out_b; p.dlse = a->dlse; p.lse_a = a->lse_a; p.lse_b = a->lse_b;
+  p.dout_a = a->dout_a; p.dout_b = a->dout_b; p.dlse_a = a->dlse_a; p.dlse_b = a->dlse_b;
+  p.dout_st = cv(a->dout_st); p.out_a_st = cv(a->out_a_st); p.out_b_st = cv(a->out_b_st);
+  p.dout_a_st = cv(a->dout_a_st); p.dout_b_st = cv(a->dout_b_st);
+  p.dlse_st = LseSt{a->dlse_batch, a->dlse_head};
+  p.lse_a_st = LseSt{a->lse_a_batch, a->lse_a_head}; p.lse_b_st = LseSt{a->lse_b_batch, a->lse_b_head};
+  p.dlse_a_st = LseSt{a->dlse_a_batch, a->dlse_a_head}; p.dlse_b_st = LseSt{a->dlse_b_batch, a->dlse_b_head};
+  p.B = a->B; p.H = a->H; p.D = a->D; p.S = a->S;
+  return launch_merge_pair_bwd(p, a->dtype, (hipStream_t)stream) ? RFA_ERR_LAUNCH : RFA_OK;
 }
 
 // ---- sequence/head exchange copies (rfa.h; csrc/rfa_seqhead.hip) -----------------------------------------------------------

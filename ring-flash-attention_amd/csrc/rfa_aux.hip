@@ -1,6 +1,7 @@
 // rfa_aux.hip — the HBM-bound side kernels of the ring attention path (gfx950).
 //
-//   preprocess_kernel : Δ = rowsum(dO ∘ O)            (prologue of flash_attn's backward)
+//   preprocess_kernel : Δ = rowsum(dO ∘ O)            (prologue of flash_attn's backward); kDlse: Δ' = Δ − dlse, the form
+//                       that carries a gradient of lse into every backward kernel (∂lse_i/∂s_ij = P_ij, dS = P ∘ (dP − Δ'))
 //   reduce_kernel     : dK/dV partial sums (io dtype or fp32 partials) + fp32 accumulate / cast
 //                       (flash_attn's dk_expanded.sum + the reference's `dk += dk_buffer`,
 //                       /root/reference/ring_flash_attn/zigzag_ring_flash_attn.py:182-187)
@@ -17,8 +18,10 @@ namespace rfa {
 // ------------------------------------------------------------------------------------
 // Δ[b,h,row] = Σ_d dO·O.   16 lanes per (row, head): 16 x 8 = 128 elements.
 // grid: x = ceil(rows*H / 16) blocks of 256 threads (16 row-heads per block), y = B
+// kDlse: the one lane that stores writes acc - dlse[b,h,row] (dlse: fp32, addressed like delta with strides of its own) — the
+// same accumulator, then ONE correctly rounded fp32 subtraction
 // ------------------------------------------------------------------------------------
-template <typename T>
+template <typename T, bool kDlse = false>
 __global__ __launch_bounds__(256) void preprocess_kernel(const PreParams p) {
   const int b = blockIdx.y;
   const SeqSpan qs = resolve_span(p.cu_q, b, p.Sq, p.q_half);
@@ -29,6 +32,8 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const PreParams p) {
   if (row >= qs.len) return;
   const int64_t qbatch = p.cu_q ? 0 : (int64_t)b;
   const int64_t arow = qs.row0 + row;
+  float g = 0.f;                                             // (kDlse: read in front of the rows, its latency under theirs)
+  if constexpr (kDlse) g = p.dlse[qbatch * p.dlse_batch + (int64_t)h * p.dlse_head + arow];
   float acc = 0.f;
   for (int d = sub * 8; d < p.D; d += 128) {                 // (one pass for head dims <= 128)
     const vec8<T> a = *(const vec8<T>*)((const T*)p.dout + qbatch * p.dout_st.batch +
@@ -40,7 +45,11 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const PreParams p) {
   }
 #pragma unroll
   for (int s = 8; s >= 1; s >>= 1) acc += __shfl_xor(acc, s, 64);
-  if (sub == 0) p.delta[qbatch * p.delta_batch + (int64_t)h * p.delta_head + arow] = acc;
+  if constexpr (kDlse) {
+    if (sub == 0) p.delta[qbatch * p.delta_batch + (int64_t)h * p.delta_head + arow] = acc - g;
+  } else {
+    if (sub == 0) p.delta[qbatch * p.delta_batch + (int64_t)h * p.delta_head + arow] = acc;
+  }
 }
 
 // ------------------------------------------------------------------------------------
@@ -203,6 +212,11 @@ int launch_preprocess(const PreParams& p, int dtype, hipStream_t stream) {
   const int64_t items = (int64_t)p.Sq * p.H;
   if (items <= 0 || p.B <= 0) return 0;
   dim3 grid((unsigned)((items + 15) / 16), (unsigned)p.B);
+  if (p.dlse != nullptr) {
+    if (dtype == 0) hipLaunchKernelGGL((preprocess_kernel<bf16_t, true>), grid, dim3(256), 0, stream, p);
+    else hipLaunchKernelGGL((preprocess_kernel<f16_t, true>), grid, dim3(256), 0, stream, p);
+    return ok();
+  }
   if (dtype == 0) hipLaunchKernelGGL(preprocess_kernel<bf16_t>, grid, dim3(256), 0, stream, p);
   else hipLaunchKernelGGL(preprocess_kernel<f16_t>, grid, dim3(256), 0, stream, p);
   return ok();

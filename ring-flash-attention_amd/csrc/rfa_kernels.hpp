@@ -94,6 +94,10 @@ struct PreParams {
   Strides dout_st, out_st;
   int64_t delta_batch, delta_head;
   int B, H, D, Sq, q_half;
+  // the gradient of lse (fp32, laid out like delta with strides of its own): the kDlse instance stores delta - dlse, the plain
+  // instance never reads these fields
+  const float* dlse;
+  int64_t dlse_batch, dlse_head;
 };
 
 struct BwdParams {
@@ -324,6 +328,31 @@ int bwd_dq_rows_per_block();
 int bwd_dkdv_keys_per_block(bool wide);
 int launch_reduce(const ReduceParams& p, int dtype, hipStream_t stream);
 int launch_merge(const MergeParams& p, int dtype, hipStream_t stream);
+
+// pairwise merge of two finished (out, lse) pairs and its backward (rfa_mergepair.hip): B x S rows of H heads (packed input:
+// B = 1, S = total rows, batch strides unused); every lse-like tensor has row stride 1 and (batch, head) strides of its own
+struct LseSt { int64_t batch, head; };
+struct MergePairParams {
+  const void *out_a, *out_b;
+  void* out;
+  const float *lse_a, *lse_b;
+  float* lse;
+  Strides out_a_st, out_b_st, out_st;
+  LseSt lse_a_st, lse_b_st, lse_st;
+  int B, H, D, S;
+};
+struct MergePairBwdParams {
+  const void *dout, *out_a, *out_b;
+  const float *dlse;        // may be nullptr: zero
+  const float *lse_a, *lse_b;
+  void *dout_a, *dout_b;
+  float *dlse_a, *dlse_b;
+  Strides dout_st, out_a_st, out_b_st, dout_a_st, dout_b_st;
+  LseSt dlse_st, lse_a_st, lse_b_st, dlse_a_st, dlse_b_st;
+  int B, H, D, S;
+};
+int launch_merge_pair(const MergePairParams& p, int dtype, hipStream_t stream);
+int launch_merge_pair_bwd(const MergePairBwdParams& p, int dtype, hipStream_t stream);
 int launch_combine(const CombineParams& p, int dtype, hipStream_t stream);
 int launch_cast(void* dst, const float* src, int64_t n, int dtype, hipStream_t stream);
 int launch_lse_relayout(float* dst, const float* src, const int32_t* cu, int B, int H,

@@ -227,6 +227,52 @@ class MaxLogitArgs(C.Structure):
             self.struct_bytes = C.sizeof(MaxLogitArgs)
 
 
+class BwdPreLseArgs(C.Structure):
+    """rfa_bwd_preprocess_lse_args: rfa_bwd_preprocess with the gradient of lse (delta' = delta - dlse)"""
+    _fields_ = [
+        ("dout", C.c_void_p), ("out", C.c_void_p),
+        ("dout_st", Strides), ("out_st", Strides),
+        ("delta", C.c_void_p), ("delta_batch", C.c_int64), ("delta_head", C.c_int64),
+        ("dlse", C.c_void_p), ("dlse_batch", C.c_int64), ("dlse_head", C.c_int64),
+        ("cu_seqlens_q", C.c_void_p),
+        ("q_half", C.c_int32),
+        ("B", C.c_int32), ("H", C.c_int32), ("D", C.c_int32), ("Sq", C.c_int32),
+        ("dtype", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
+class MergePairArgs(C.Structure):
+    """rfa_merge_pair_args: the merge of two finished (out, lse) pairs"""
+    _fields_ = [
+        ("out_a", C.c_void_p), ("out_b", C.c_void_p),
+        ("out_a_st", Strides), ("out_b_st", Strides),
+        ("lse_a", C.c_void_p), ("lse_b", C.c_void_p),
+        ("lse_a_batch", C.c_int64), ("lse_a_head", C.c_int64), ("lse_b_batch", C.c_int64), ("lse_b_head", C.c_int64),
+        ("out", C.c_void_p), ("out_st", Strides),
+        ("lse", C.c_void_p), ("lse_batch", C.c_int64), ("lse_head", C.c_int64),
+        ("B", C.c_int32), ("S", C.c_int32), ("H", C.c_int32), ("D", C.c_int32),
+        ("dtype", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
+class MergePairBwdArgs(C.Structure):
+    """rfa_merge_pair_bwd_args: its backward, from the forward's four inputs"""
+    _fields_ = [
+        ("dout", C.c_void_p), ("dout_st", Strides),
+        ("dlse", C.c_void_p), ("dlse_batch", C.c_int64), ("dlse_head", C.c_int64),
+        ("out_a", C.c_void_p), ("out_b", C.c_void_p),
+        ("out_a_st", Strides), ("out_b_st", Strides),
+        ("lse_a", C.c_void_p), ("lse_b", C.c_void_p),
+        ("lse_a_batch", C.c_int64), ("lse_a_head", C.c_int64), ("lse_b_batch", C.c_int64), ("lse_b_head", C.c_int64),
+        ("dout_a", C.c_void_p), ("dout_b", C.c_void_p),
+        ("dout_a_st", Strides), ("dout_b_st", Strides),
+        ("dlse_a", C.c_void_p), ("dlse_b", C.c_void_p),
+        ("dlse_a_batch", C.c_int64), ("dlse_a_head", C.c_int64), ("dlse_b_batch", C.c_int64), ("dlse_b_head", C.c_int64),
+        ("B", C.c_int32), ("S", C.c_int32), ("H", C.c_int32), ("D", C.c_int32),
+        ("dtype", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
 # every symbol include/rfa.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "rfa_abi_version": (C.c_int, []),
@@ -259,6 +305,9 @@ SYMBOLS = {
     "rfa_seq_head_copy": (C.c_int, [C.POINTER(SeqHeadArgs), C.c_void_p]),
     "rfa_max_logit": (C.c_int, [C.POINTER(MaxLogitArgs), C.c_void_p]),
     "rfa_max_logit_workspace_bytes": (C.c_int64, [C.POINTER(MaxLogitArgs)]),
+    "rfa_bwd_preprocess_lse": (C.c_int, [C.POINTER(BwdPreLseArgs), C.c_void_p]),
+    "rfa_merge_pair": (C.c_int, [C.POINTER(MergePairArgs), C.c_void_p]),
+    "rfa_merge_pair_bwd": (C.c_int, [C.POINTER(MergePairBwdArgs), C.c_void_p]),
 }
 
 _lib = None
@@ -299,6 +348,10 @@ def load():
     for name in ("rfa_max_logit", "rfa_max_logit_workspace_bytes"):
         if not hasattr(lib, name):
             raise RuntimeError(f"ring_flash_attn: librfa_hip.so has no {name} (the max-logit entry points); rebuild")
+    # ... and the gradient of lse and the pairwise merge (structs of their own)
+    for name in ("rfa_bwd_preprocess_lse", "rfa_merge_pair", "rfa_merge_pair_bwd"):
+        if not hasattr(lib, name):
+            raise RuntimeError(f"ring_flash_attn: librfa_hip.so has no {name} (the lse-gradient / merge entry points); rebuild")
     for name, (res, args) in SYMBOLS.items():
         fn = getattr(lib, name)  # AttributeError if the .so is stale
         fn.restype = res

@@ -65,6 +65,10 @@ from ._api import with_sinks
 # largest pre-softmax logit softmax_scale * q.k of every query head, over the pairs the attention looks at, into an fp32 (H,)
 # tensor — this rank's partial; the caller's all_reduce(MAX) over the group completes it
 from ._api import with_max_logit
+# a differentiable lse: with_lse_grad(func) returns func with an lse whose gradient reaches dq / dk — what makes (out, lse) the
+# handle by which attention over two key sets composes, backward included; merge_attn(out_a, lse_a, out_b, lse_b) is that
+# composition as one fused, differentiable kernel each way (replicated prefix / global tokens next to a sharded sequence)
+from ._api import merge_attn, with_lse_grad
 # DeepSpeed-Ulysses head parallelism in front of the dense schedules ("USP"): with_ulysses(func, ulysses_group) exchanges heads
 # for rows around `func`; make_usp_groups(func, ulysses_size) makes the (Ulysses, ring) groups of func's family
 from .ulysses import make_usp_groups, with_ulysses

@@ -203,6 +203,170 @@ def with_softcap(func, softcap):
     return _opaque(capped)
 
 
+# ---- a gradient for the returned lse (ring_flash_attn.with_lse_grad) ------------------------------------------------------
+# lse_i = log sum_j exp(s_ij), so d lse_i / d s_ij = P_ij: a gradient g_i on lse_i adds g_i P_ij to dS = P (dP - delta).  Every
+# backward kernel is therefore served, unchanged, by delta' = delta - g (include/rfa.h: rfa_bwd_preprocess_lse): the ONE place a
+# schedule's backward computes delta takes `dlse=`.  The binding is read once, at the public entry of the forward, and kept on
+# the node (ctx.lse_grad); a backward reads ctx and the gradients autograd hands it, nothing ambient.  An unbound node is the
+# node it always was: it never looks at the gradient of lse.
+import contextvars
+
+_lse_grad = contextvars.ContextVar("ring_flash_attn_lse_grad", default=False)
+
+
+def checked_lse_grad(ctx, what):
+    """True inside a call bound by `with_lse_grad` — the node then takes undefined output gradients as None (an unused lse costs
+    nothing and leaves the plain backward, bit for bit).  NotImplementedError: a backend whose bwd_preprocess does not take
+    `dlse=` — before anything is exchanged, on every rank alike."""
+    if not _lse_grad.get():
+        return False
+    from .backend import get_backend
+
+    be = get_backend()
+    if not getattr(be, "serves_lse_grad", False):
+        raise NotImplementedError(f"ring_flash_attn: {what} with a gradient for lse needs a backend that serves `lse_grad` "
+                                  f"(bwd_preprocess(dlse=)); {getattr(be, 'name', type(be).__name__)!r} does not")
+    ctx.set_materialize_grads(False)
+    return True
+
+
+def lse_grad_kw(ctx, dout, args, out, lse):
+    """(dout, the `dlse=` keyword of the schedule's backward) from what autograd handed a node's backward: an unbound node
+    passes dout through and no keyword; a bound one replaces an undefined dout (a loss that uses lse alone) by zeros in out's
+    dtype and passes the gradient of lse — fp32, in lse's layout, contiguous — when there is one"""
+    if not getattr(ctx, "lse_grad", False):
+        return dout, {}
+    if dout is None:
+        dout = torch.zeros_like(out)
+    dlse = args[0] if args else None
+    if dlse is None:
+        return dout, {}
+    if tuple(dlse.shape) != tuple(lse.shape):
+        raise ValueError(f"ring_flash_attn: the gradient of lse has shape {tuple(dlse.shape)}, lse has {tuple(lse.shape)}")
+    return dout, {"dlse": dlse.to(torch.float32).contiguous()}
+
+
+def with_lse_grad(func):
+    """A differentiable `lse` for one of this package's public attention functions:
+
+        attn = with_lse_grad(zigzag_ring_flash_attn_func)
+        out, lse, _ = attn(q, k, v, causal=True, return_attn_probs=True)
+        loss = f(out) + 1e-4 * lse.square().mean()               # e.g. a z-loss on the attention normaliser
+
+    returns a callable with `func`'s signature whose returned lse carries its gradient into dq and dk (dv does not depend on
+    lse) — exactly: the backward kernels get delta' = rowsum(dout * out) - dlse in place of delta, at the cost of 4 more bytes
+    read per row and head.  That makes (out, lse) the handle by which attention over two key sets composes, backward included:
+    `merge_attn` of two such calls is attention over the union of their keys.  A plain call's lse also leaves the autograd node,
+    but its gradient is dropped.
+    Served: the 21 `*_func` of the package and `with_softcap` results of them, on any group and with everything `func` serves
+    there — windows, packed input, GQA, alibi_slopes, dropout (lse is the undropped softmax's).  `dlse` belongs to the rank
+    that owns the query rows; no collective is added.  TypeError: any other callable — `with_sinks` results (the sinks'
+    gradient needs the same term: follow-up), `with_max_logit`, `with_ulysses` and `with_lse_grad` results (bind with_lse_grad
+    first: the other binders refuse its result as well).  NotImplementedError at the call, before anything is exchanged: a
+    backend that does not serve it.  An lse that the loss does not use costs nothing: the backward is the plain one, bit for
+    bit; a loss that uses lse alone is served too.  Double backward is not.  Under torch.compile the call runs eagerly behind a
+    graph break."""
+    import functools
+
+    import ring_flash_attn as pkg
+
+    for marker, what in (("_rfa_lse_grad", "with_lse_grad"), ("_rfa_sinks", "with_sinks"), ("_rfa_max_logit", "with_max_logit"),
+                         ("_rfa_ulysses", "with_ulysses")):
+        if getattr(func, marker, False):
+            raise TypeError(f"ring_flash_attn.with_lse_grad: `func` is a {what} result; not served")
+    public = {id(getattr(pkg, n)): n for n in dir(pkg) if n.endswith("_func")}
+    f = func
+    while id(f) not in public and getattr(f, "_rfa_softcap", None) and hasattr(f, "__wrapped__"):
+        f = f.__wrapped__                            # (a with_softcap result leads to the public function it wraps)
+    if id(f) not in public:
+        raise TypeError("ring_flash_attn.with_lse_grad: `func` must be one of the package's public attention functions "
+                        f"(ring_flash_attn.*_func) or a with_softcap result of one, got {func!r}")
+
+    @functools.wraps(func, updated=())              # (updated=(): as in with_softcap; the cap's marker is NOT carried over)
+    def bound(*args, **kwargs):
+        token = _lse_grad.set(True)
+        try:
+            return func(*args, **kwargs)
+        finally:
+            _lse_grad.reset(token)
+
+    bound._rfa_lse_grad = True
+    return _opaque(bound)
+
+
+# ---- attention over the union of two key sets (ring_flash_attn.merge_attn) ------------------------------------------------
+def _check_merge_args(out_a, lse_a, out_b, lse_b):
+    ts = (out_a, lse_a, out_b, lse_b)
+    if not all(isinstance(t, torch.Tensor) for t in ts):
+        raise ValueError("ring_flash_attn.merge_attn: out_a, lse_a, out_b, lse_b must be tensors")
+    if out_a.dim() not in (3, 4) or out_a.shape != out_b.shape or out_a.dtype != out_b.dtype:
+        raise ValueError(f"ring_flash_attn.merge_attn: out_a {tuple(out_a.shape)} {out_a.dtype} and out_b {tuple(out_b.shape)} "
+                         f"{out_b.dtype} must be (B, S, H, D) or (T, H, D) tensors of one shape and dtype")
+    want = (out_a.shape[1], out_a.shape[0]) if out_a.dim() == 3 else (out_a.shape[0], out_a.shape[2], out_a.shape[1])
+    for nm, l in (("lse_a", lse_a), ("lse_b", lse_b)):
+        if l.dtype != torch.float32 or tuple(l.shape) != want:
+            raise ValueError(f"ring_flash_attn.merge_attn: {nm} must be float32 of shape {want} — (B, H, S) for a (B, S, H, D) "
+                             f"out, (H, T) for a (T, H, D) out; got {l.dtype} {tuple(l.shape)}")
+    if any(t.device != out_a.device for t in ts):
+        raise ValueError("ring_flash_attn.merge_attn: out_a, lse_a, out_b, lse_b must be on one device; got "
+                         + ", ".join(str(t.device) for t in ts))
+
+
+class _MergeAttn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, out_a, lse_a, out_b, lse_b):
+        from .backend import get_backend
+
+        out, lse = get_backend().merge_pair(out_a, lse_a, out_b, lse_b)
+        ctx.save_for_backward(out_a, lse_a, out_b, lse_b)
+        ctx.set_materialize_grads(False)
+        return out, lse
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout, dlse):
+        from .backend import get_backend
+
+        out_a, lse_a, out_b, lse_b = ctx.saved_tensors
+        if dout is None:
+            dout = torch.zeros_like(out_a)
+        if dlse is not None:
+            dlse = dlse.to(torch.float32)
+        da, dla, db, dlb = get_backend().merge_pair_bwd(dout, dlse, out_a, lse_a, out_b, lse_b)
+        need = ctx.needs_input_grad
+        return (da if need[0] else None, dla if need[1] else None, db if need[2] else None, dlb if need[3] else None)
+
+
+def merge_attn(out_a, lse_a, out_b, lse_b):
+    """(out, lse) of attention over the UNION of two key sets, from the finished results of attention over each:
+
+        attn = with_lse_grad(zigzag_ring_flash_attn_func)
+        out_s, lse_s, _ = attn(q, k, v, causal=True, return_attn_probs=True)                # the sharded sequence
+        out_p, lse_p, _ = with_lse_grad(ring_flash_attn_func)(q, kp, vp, return_attn_probs=True, group=self_group)   # replicated prefix keys
+        out, lse = merge_attn(out_p, lse_p, out_s, lse_s)
+
+    lse = logaddexp(lse_a, lse_b), out = exp(lse_a - lse) out_a + exp(lse_b - lse) out_b — one fused kernel each way, fp32
+    arithmetic, out rounded once; differentiable in all four inputs (once).  The forward is exact; the backward is exact only
+    if the gradients of lse_a / lse_b reach the scores, which is what `with_lse_grad` is for.  out_x: (B, S, H, D) with lse_x
+    (B, H, S) float32, or packed (T, H, D) with (H, T) — the layouts the attention functions return; bf16 / fp16.
+    Empty rows: an infinite lse_x of either sign (+inf: a row without a visible key) marks side x as empty — weight 0, zero
+    gradients; both empty: out = 0, lse = -inf.  No NaN comes out of such rows.  The result merges again (an N-way merge is a
+    chain of these).
+    ValueError: mismatched shapes or dtypes, an lse that is not float32 in the layout belonging to out, tensors on different
+    devices.  NotImplementedError: a backend that does not serve it."""
+    _check_merge_args(out_a, lse_a, out_b, lse_b)
+    from .backend import get_backend
+
+    be = get_backend()
+    if not getattr(be, "serves_merge_pair", False):
+        raise NotImplementedError("ring_flash_attn.merge_attn needs a backend that serves `merge_pair` / `merge_pair_bwd`; "
+                                  f"{getattr(be, 'name', type(be).__name__)!r} does not")
+    return _MergeAttn.apply(out_a, lse_a, out_b, lse_b)
+
+
+merge_attn = _opaque(merge_attn)
+
+
 # ---- attention sinks (ring_flash_attn.with_sinks) ------------------------------------------------------------------------
 # The sink is applied once, to the merged (out, lse) a schedule's forward returned (include/rfa.h: rfa_sink_apply), so no
 # schedule and no attention kernel computes anything for it.  The tensor has to be a real INPUT of the autograd node for
@@ -481,6 +645,7 @@ def make_autograd_function(name, forward_impl, backward_impl, n_lead, window_rin
                                alibi_ok=single or alibi_ring)
             alibi_slopes = checked_alibi(alibi_slopes, q, (len(lead[0]) - 1) if n_lead else q.shape[0], name)
             ctx.softcap = checked_softcap(dropout_p, alibi_slopes, q, name, window_size, causal)
+            ctx.lse_grad = checked_lse_grad(ctx, name)
             sinks = checked_sinks(sinks, q, name)
             q, k, v = _prep_qkv(q, k, v, group)
             tensors_lead = ()
@@ -518,6 +683,8 @@ def make_autograd_function(name, forward_impl, backward_impl, n_lead, window_rin
             q, k, v, out, softmax_lse, *more = ctx.saved_tensors
             sinks = more.pop() if ctx.has_sinks else None
             tensors_lead, extra = _split_kept(ctx, more)
+            dout, lse_kw = lse_grad_kw(ctx, dout, args, out, softmax_lse)
+            extra.update(lse_kw)
             if ctx.dropout[1] is not None:
                 extra["dropout_seed"] = ctx.dropout[1]
             with softcap_scope(ctx.softcap):
@@ -561,6 +728,7 @@ def make_packed_function(name, base_fn, forward_impl, backward_impl, n_lead, pac
                                alibi_ok=single or alibi_ring)
             alibi_slopes = checked_alibi(alibi_slopes, q, (len(lead[0]) - 1) if n_lead else q.shape[0], name)
             ctx.softcap = checked_softcap(dropout_p, alibi_slopes, q, name, window_size, causal)
+            ctx.lse_grad = checked_lse_grad(ctx, name)
             sinks = checked_sinks(sinks, q, name)
             q, k, v = _prep_qkv(q, k, v, group, packed_travel=packed_travel and n_packed == 2)
             tensors_lead = ()
@@ -599,6 +767,8 @@ def make_packed_function(name, base_fn, forward_impl, backward_impl, n_lead, pac
             q, k, v, out, softmax_lse, *more = ctx.saved_tensors
             sinks = more.pop() if ctx.has_sinks else None
             tensors_lead, extra = _split_kept(ctx, more)
+            dout, lse_kw = lse_grad_kw(ctx, dout, args, out, softmax_lse)
+            extra.update(lse_kw)
             shape, dtype, device = ctx.packed_meta
             dpacked = torch.empty(shape, dtype=dtype, device=device)
             views = [dpacked.select(pack_dim, i) for i in range(n_packed)]

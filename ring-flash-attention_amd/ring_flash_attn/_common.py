@@ -108,6 +108,12 @@ def alibi_kw(alibi_slopes, shift=0, heads=None):
     return {"alibi": (alibi_slopes, int(shift))}
 
 
+def dlse_kw(dlse):
+    """the `dlse=` keyword of a backward's bwd_preprocess (the gradient of lse, ring_flash_attn.with_lse_grad); nothing
+    without one, so that backends that predate the keyword keep serving plain calls"""
+    return {} if dlse is None else {"dlse": dlse}
+
+
 def _as_cu(cu_seqlens, device):
     """cu_seqlens as an int32 tensor on the compute device (the kernels read it on device)."""
     import torch

@@ -42,6 +42,18 @@ def _lse_st(t: torch.Tensor, varlen: bool):
     return t.stride(0), t.stride(1)
 
 
+def _rows16(t: torch.Tensor) -> torch.Tensor:
+    """t, or a contiguous copy when a view's rows are off the library's 16-byte contract (last stride 1, 2-byte elements)"""
+    if t.stride(-1) != 1 or any(st % 8 for st in t.stride()[:-1]) or t.data_ptr() % 16:
+        return t.contiguous()
+    return t
+
+
+def _unit_rows(t: torch.Tensor) -> torch.Tensor:
+    """an lse-like tensor with row stride 1 (a copy when it has another)"""
+    return t.contiguous() if t.stride(-1) != 1 and t.shape[-1] != 1 else t
+
+
 def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else t.data_ptr()
 
@@ -62,6 +74,8 @@ class HipBackend:
     serves_sinks = True             # sink_apply / sink_grad (include/rfa.h: rfa_sink_apply, rfa_sink_grad): ring_flash_attn.with_sinks
     serves_seq_head_exchange = True  # seq_head_copy (include/rfa.h: rfa_seq_head_copy): ring_flash_attn.with_ulysses
     serves_max_logit = True          # max_logit (include/rfa.h: rfa_max_logit): ring_flash_attn.with_max_logit
+    serves_lse_grad = True           # bwd_preprocess takes `dlse=` (include/rfa.h: rfa_bwd_preprocess_lse): ring_flash_attn.with_lse_grad
+    serves_merge_pair = True         # merge_pair / merge_pair_bwd (include/rfa.h: rfa_merge_pair, rfa_merge_pair_bwd): ring_flash_attn.merge_attn
     serves_dropout_positions = True  # `dropout=` takes the position maps (q_map, k_map): what dropout over a dense ring, zigzag or stripe schedule needs
 
     def __init__(self):
@@ -152,14 +166,22 @@ class HipBackend:
         _C.check(self.lib.rfa_fwd(C.byref(a), _stream(q)), "rfa_fwd")
 
     # ------------------------------------------------------------------ backward
-    def bwd_preprocess(self, dout, out, delta, *, cu_seqlens_q=None, max_seqlen_q=None, q_half=HALF_FULL):
-        """delta[b,h,i] = sum_d dout*out, fp32, laid out like lse."""
-        self._check_dev(dout, out, delta)
+    def bwd_preprocess(self, dout, out, delta, *, cu_seqlens_q=None, max_seqlen_q=None, q_half=HALF_FULL, dlse=None):
+        """delta[b,h,i] = sum_d dout*out, fp32, laid out like lse.
+        dlse: the gradient of lse (ring_flash_attn.with_lse_grad) — fp32, laid out like lse / delta, row stride 1: delta
+        becomes sum_d dout*out - dlse, which carries it through every backward kernel (include/rfa.h:
+        rfa_bwd_preprocess_lse).  None: the existing call, bit for bit."""
+        self._check_dev(dout, out, delta, dlse)
         varlen = cu_seqlens_q is not None
-        a = _C.BwdPreArgs()
+        a = _C.BwdPreArgs() if dlse is None else _C.BwdPreLseArgs()
         a.dout, a.out, a.delta = _ptr(dout), _ptr(out), _ptr(delta)
         a.dout_st, a.out_st = _st3(dout, varlen), _st3(out, varlen)
         a.delta_batch, a.delta_head = _lse_st(delta, varlen)
+        if dlse is not None:
+            if tuple(dlse.shape) != tuple(delta.shape):
+                raise ValueError(f"dlse {tuple(dlse.shape)} must have delta's shape {tuple(delta.shape)}")
+            a.dlse = _ptr(dlse)
+            a.dlse_batch, a.dlse_head = _lse_st(dlse, varlen)
         if varlen:
             a.cu_seqlens_q = _ptr(cu_seqlens_q)
             a.B = cu_seqlens_q.numel() - 1
@@ -169,6 +191,9 @@ class HipBackend:
             a.B, a.Sq, a.H, a.D = dout.shape
         a.q_half = q_half
         a.dtype = self._dtype(dout)
+        if dlse is not None:
+            _C.check(self.lib.rfa_bwd_preprocess_lse(C.byref(a), _stream(dout)), "rfa_bwd_preprocess_lse")
+            return
         _C.check(self.lib.rfa_bwd_preprocess(C.byref(a), _stream(dout)), "rfa_bwd_preprocess")
 
     def bwd(self, dout, q, k, v, lse, delta, *, softmax_scale, causal, cu_seqlens_q=None,
@@ -407,6 +432,61 @@ class HipBackend:
         a.acc_init = 1 if acc_init else 0
         a.dtype = self._dtype(block_out)
         _C.check(self.lib.rfa_merge(C.byref(a), _stream(block_out)), "rfa_merge")
+
+    # ------------------------------------------------------------------ pairwise merge (ring_flash_attn.merge_attn)
+    def merge_pair(self, out_a, lse_a, out_b, lse_b):
+        """(out, lse) of attention over the union of two key sets from the two parts' finished results: lse =
+        logaddexp(lse_a, lse_b), out = exp(lse_a - lse) out_a + exp(lse_b - lse) out_b in fp32, rounded once (include/rfa.h:
+        rfa_merge_pair).  out_x (B,S,H,D) with lse_x (B,H,S), or packed (T,H,D) with (H,T); an infinite lse_x of either sign
+        marks an empty side.  New tensors."""
+        self._check_dev(out_a, lse_a, out_b, lse_b)
+        varlen = out_a.dim() == 3
+        out_a, out_b = (_rows16(t) for t in (out_a, out_b))
+        lse_a, lse_b = (_unit_rows(t) for t in (lse_a, lse_b))
+        out = torch.empty(out_a.shape, dtype=out_a.dtype, device=out_a.device)
+        lse = torch.empty(lse_a.shape, dtype=torch.float32, device=out_a.device)
+        a = _C.MergePairArgs()
+        a.out_a, a.out_b, a.out = _ptr(out_a), _ptr(out_b), _ptr(out)
+        a.out_a_st, a.out_b_st, a.out_st = _st3(out_a, varlen), _st3(out_b, varlen), _st3(out, varlen)
+        a.lse_a, a.lse_b, a.lse = _ptr(lse_a), _ptr(lse_b), _ptr(lse)
+        a.lse_a_batch, a.lse_a_head = _lse_st(lse_a, varlen)
+        a.lse_b_batch, a.lse_b_head = _lse_st(lse_b, varlen)
+        a.lse_batch, a.lse_head = _lse_st(lse, varlen)
+        a.B, (a.S, a.H, a.D) = (1, out.shape) if varlen else (out.shape[0], out.shape[1:])
+        a.dtype = self._dtype(out)
+        _C.check(self.lib.rfa_merge_pair(C.byref(a), _stream(out)), "rfa_merge_pair")
+        return out, lse
+
+    def merge_pair_bwd(self, dout, dlse, out_a, lse_a, out_b, lse_b):
+        """(dout_a, dlse_a, dout_b, dlse_b) of merge_pair from the gradients of its outputs and its four inputs (include/rfa.h:
+        rfa_merge_pair_bwd); dlse None: zero.  Summed in a fixed order: the same bits on every run."""
+        self._check_dev(dout, dlse, out_a, lse_a, out_b, lse_b)
+        varlen = out_a.dim() == 3
+        dout, out_a, out_b = (_rows16(t) for t in (dout, out_a, out_b))
+        lse_a, lse_b = (_unit_rows(t) for t in (lse_a, lse_b))
+        dlse = None if dlse is None else _unit_rows(dlse)
+        dout_a, dout_b = torch.empty_like(dout, memory_format=torch.contiguous_format), torch.empty_like(dout, memory_format=torch.contiguous_format)
+        dlse_a = torch.empty(lse_a.shape, dtype=torch.float32, device=dout.device)
+        dlse_b = torch.empty(lse_a.shape, dtype=torch.float32, device=dout.device)
+        a = _C.MergePairBwdArgs()
+        a.dout, a.dout_st = _ptr(dout), _st3(dout, varlen)
+        if dlse is not None:
+            a.dlse = _ptr(dlse)
+            a.dlse_batch, a.dlse_head = _lse_st(dlse, varlen)
+        a.out_a, a.out_b = _ptr(out_a), _ptr(out_b)
+        a.out_a_st, a.out_b_st = _st3(out_a, varlen), _st3(out_b, varlen)
+        a.lse_a, a.lse_b = _ptr(lse_a), _ptr(lse_b)
+        a.lse_a_batch, a.lse_a_head = _lse_st(lse_a, varlen)
+        a.lse_b_batch, a.lse_b_head = _lse_st(lse_b, varlen)
+        a.dout_a, a.dout_b = _ptr(dout_a), _ptr(dout_b)
+        a.dout_a_st, a.dout_b_st = _st3(dout_a, varlen), _st3(dout_b, varlen)
+        a.dlse_a, a.dlse_b = _ptr(dlse_a), _ptr(dlse_b)
+        a.dlse_a_batch, a.dlse_a_head = _lse_st(dlse_a, varlen)
+        a.dlse_b_batch, a.dlse_b_head = _lse_st(dlse_b, varlen)
+        a.B, (a.S, a.H, a.D) = (1, dout.shape) if varlen else (dout.shape[0], dout.shape[1:])
+        a.dtype = self._dtype(dout)
+        _C.check(self.lib.rfa_merge_pair_bwd(C.byref(a), _stream(dout)), "rfa_merge_pair_bwd")
+        return dout_a, dlse_a, dout_b, dlse_b
 
     # ------------------------------------------------------------------ attention sinks
     def sink_apply(self, out, lse, sinks, *, varlen, inplace=False):

@@ -28,8 +28,8 @@ from . import config
 from .backend import get_backend, heads_from
 from .utils import AllGatherComm as Comm, group_rank_world, reduce_scatter_async, single_rank
 from ._api import (_check_unsupported, _opaque, apply_sinks, checked_alibi, checked_sinks, checked_softcap, sink_args, sinks_grad,
-                   softcap_scope, window_ok_for)
-from ._common import alibi_kw, _as_cu, dropout_arg, draw_dropout_seed, packed_pair
+                   softcap_scope, window_ok_for, checked_lse_grad, lse_grad_kw)
+from ._common import alibi_kw, dlse_kw, _as_cu, dropout_arg, draw_dropout_seed, packed_pair
 
 
 def fused_heads_k_stride(nheads_k: int, heads_k_stride: int, total_k: int, world: int, head_dim: int,
@@ -197,8 +197,10 @@ def llama3_flash_attn_varlen_backward(
     deterministic=False,
     dropout_seed=None,
     grads=None,
+    dlse=None,
 ):
-    """grads: optional (dq, dk, dv) buffers the gradients are written into — views of one packed gradient for the
+    """dlse: the gradient of lse, (nheads, T) fp32 (with_lse_grad), or None.
+    grads: optional (dq, dk, dv) buffers the gradients are written into — views of one packed gradient for the
     kv / qkv packed entry points (last stride 1), so that no per-tensor gradient is copied into it afterwards"""
     be = get_backend()
     T, nheads, head_dim = q.shape
@@ -212,7 +214,7 @@ def llama3_flash_attn_varlen_backward(
         dout = dout.contiguous()
 
     delta = torch.empty((nheads, T), dtype=torch.float32, device=q.device)
-    be.bwd_preprocess(dout, out, delta, cu_seqlens_q=cu_seqlens_q, max_seqlen_q=max_seqlen_q)
+    be.bwd_preprocess(dout, out, delta, cu_seqlens_q=cu_seqlens_q, max_seqlen_q=max_seqlen_q, **dlse_kw(dlse))
 
     if grads is not None:
         dq, dk, dv = grads
@@ -323,6 +325,7 @@ def _l3_forward(ctx, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seql
     _check_unsupported(dropout_p, window_size, alibi_slopes, windows_ok=True, alibi_ok=window_ok_for(group) or bool(causal))
     alibi_slopes = checked_alibi(alibi_slopes, q, len(cu_seqlens_q) - 1, "llama3_flash_attn_varlen_func")
     ctx.softcap = checked_softcap(dropout_p, alibi_slopes, q, "llama3_flash_attn_varlen_func", window_size, causal)
+    ctx.lse_grad = checked_lse_grad(ctx, "llama3_flash_attn_varlen_func")
     sinks = checked_sinks(sinks, q, "llama3_flash_attn_varlen_func")
     # (strided views — the halves of a packed kv — are fine: the kernels take strides, and the all-gather sources are
     #  made contiguous per head group where they are posted)
@@ -350,13 +353,15 @@ def _l3_forward(ctx, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seql
     return out if not return_softmax else (out, softmax_lse, None)
 
 
-def _l3_backward(ctx, dout, grads=None):
+def _l3_backward(ctx, dout, grads=None, args=()):
+    """args: the gradients of the node's outputs behind out — that of lse first (read by a node bound by with_lse_grad only)"""
     q, k, v, out, softmax_lse, cu_seqlens_q, cu_seqlens_k = ctx.saved_tensors[:7]
+    dout, lse_kw = lse_grad_kw(ctx, dout, args, out, softmax_lse)
     with softcap_scope(ctx.softcap):
         return llama3_flash_attn_varlen_backward(
             ctx.group, dout, q, k, v, out, softmax_lse, cu_seqlens_q, cu_seqlens_k, *ctx.static,
             softmax_scale=ctx.softmax_scale, dropout_p=ctx.dropout[0], causal=ctx.causal, window_size=ctx.window_size,
-            alibi_slopes=ctx.alibi_slopes, deterministic=ctx.deterministic, dropout_seed=ctx.dropout[1], grads=grads,
+            alibi_slopes=ctx.alibi_slopes, deterministic=ctx.deterministic, dropout_seed=ctx.dropout[1], grads=grads, **lse_kw,
         )
 
 
@@ -378,7 +383,7 @@ class Llama3FlashAttnVarlenFunc(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout, *args):
-        return _l3_backward(ctx, dout) + _l3_tail(ctx, dout)
+        return _l3_backward(ctx, dout, args=args) + _l3_tail(ctx, dout)
 
 
 class Llama3FlashAttnVarlenKVPackedFunc(torch.autograd.Function):
@@ -394,7 +399,7 @@ class Llama3FlashAttnVarlenKVPackedFunc(torch.autograd.Function):
     def backward(ctx, dout, *args):
         k = ctx.saved_tensors[1]
         dkv = torch.empty((k.shape[0], 2) + tuple(k.shape[1:]), dtype=k.dtype, device=k.device)
-        dq, _, _ = _l3_backward(ctx, dout, (torch.empty_like(ctx.saved_tensors[0]), dkv[:, 0], dkv[:, 1]))
+        dq, _, _ = _l3_backward(ctx, dout, (torch.empty_like(ctx.saved_tensors[0]), dkv[:, 0], dkv[:, 1]), args)
         return (dq, dkv) + _l3_tail(ctx, dout)
 
 
@@ -409,7 +414,7 @@ class Llama3FlashAttnVarlenQKVPackedFunc(torch.autograd.Function):
     def backward(ctx, dout, *args):
         q = ctx.saved_tensors[0]
         dqkv = torch.empty((q.shape[0], 3) + tuple(q.shape[1:]), dtype=q.dtype, device=q.device)
-        _l3_backward(ctx, dout, (dqkv[:, 0], dqkv[:, 1], dqkv[:, 2]))
+        _l3_backward(ctx, dout, (dqkv[:, 0], dqkv[:, 1], dqkv[:, 2]), args)
         return (dqkv,) + _l3_tail(ctx, dout)
 
 

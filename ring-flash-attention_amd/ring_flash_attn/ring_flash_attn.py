@@ -23,7 +23,7 @@ import torch
 from . import _C
 from .backend import get_backend
 from .utils import RingComm, single_rank
-from ._common import alibi_kw, dropout_arg, global_window, pos_map, require_dropout_positions, require_mask_shift
+from ._common import alibi_kw, dlse_kw, dropout_arg, global_window, pos_map, require_dropout_positions, require_mask_shift
 from ._api import make_autograd_function, make_dense_api, _grad_buffers
 
 
@@ -211,6 +211,7 @@ def ring_flash_attn_backward(
     deterministic=False,
     dropout_seed=None,
     out_grads=None,
+    dlse=None,
 ):
     be = get_backend()
     kv_comm = RingComm(process_group)
@@ -222,7 +223,7 @@ def ring_flash_attn_backward(
         dout = dout.contiguous()
 
     delta = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
-    be.bwd_preprocess(dout, out, delta)
+    be.bwd_preprocess(dout, out, delta, **dlse_kw(dlse))
 
     if single_rank(kv_comm.world_size):
         dq, dk, dv = _grad_buffers(out_grads, q, k, v)

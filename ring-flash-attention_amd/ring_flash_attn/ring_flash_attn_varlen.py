@@ -21,7 +21,7 @@ import torch
 from . import _C
 from .backend import get_backend
 from .utils import RingComm, single_rank
-from ._common import alibi_kw, dropout_arg, global_window, require_mask_shift_lens
+from ._common import alibi_kw, dlse_kw, dropout_arg, global_window, require_mask_shift_lens
 from ._api import make_autograd_function, make_varlen_api, _grad_buffers
 
 
@@ -103,6 +103,7 @@ def ring_flash_attn_varlen_backward(
     deterministic=False,
     dropout_seed=None,
     out_grads=None,
+    dlse=None,
 ):
     be = get_backend()
     kv_comm = RingComm(process_group)
@@ -115,7 +116,7 @@ def ring_flash_attn_varlen_backward(
         dout = dout.contiguous()
 
     delta = torch.empty((H, T), dtype=torch.float32, device=q.device)
-    be.bwd_preprocess(dout, out, delta, cu_seqlens_q=cu_seqlens, max_seqlen_q=max_seqlen)
+    be.bwd_preprocess(dout, out, delta, cu_seqlens_q=cu_seqlens, max_seqlen_q=max_seqlen, **dlse_kw(dlse))
 
     if single_rank(kv_comm.world_size):
         dq, dk, dv = _grad_buffers(out_grads, q, k, v)

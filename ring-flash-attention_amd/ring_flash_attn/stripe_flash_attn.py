@@ -21,7 +21,7 @@ import torch
 from . import _C
 from .backend import get_backend
 from .utils import RingComm, single_rank
-from ._common import alibi_kw, dropout_arg, global_window, require_dropout_positions, require_mask_shift, stripe_map
+from ._common import alibi_kw, dlse_kw, dropout_arg, global_window, require_dropout_positions, require_mask_shift, stripe_map
 from ._api import make_autograd_function, make_dense_api, _grad_buffers
 
 
@@ -173,6 +173,7 @@ def stripe_flash_attn_backward(
     deterministic=False,
     dropout_seed=None,
     out_grads=None,
+    dlse=None,
 ):
     assert (
         causal
@@ -187,7 +188,7 @@ def stripe_flash_attn_backward(
         dout = dout.contiguous()
 
     delta = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
-    be.bwd_preprocess(dout, out, delta)
+    be.bwd_preprocess(dout, out, delta, **dlse_kw(dlse))
 
     if single_rank(kv_comm.world_size):
         dq, dk, dv = _grad_buffers(out_grads, q, k, v)

@@ -27,8 +27,8 @@ llama3_flash_attn_varlen_func; all heads are processed per call.
 import torch
 
 from ._api import (_check_unsupported, _opaque, apply_sinks, checked_alibi, checked_sinks, checked_softcap, sink_args, sinks_grad,
-                   softcap_scope, window_ok_for)
-from ._common import _as_cu, alibi_kw
+                   softcap_scope, window_ok_for, checked_lse_grad, lse_grad_kw)
+from ._common import _as_cu, alibi_kw, dlse_kw
 from .backend import get_backend
 from .llama3_flash_attn_varlen import llama3_flash_attn_prepare_cu_seqlens
 from .utils import AllGatherComm, group_rank_world, reduce_scatter_async, single_rank
@@ -94,7 +94,8 @@ def zigzag_llama3_flash_attn_varlen_forward(process_group, q, k, v, params, soft
 
 
 def zigzag_llama3_flash_attn_varlen_backward(process_group, dout, q, k, v, out, softmax_lse, params, softmax_scale,
-                                             causal=True, window_size=(-1, -1), deterministic=False, alibi_slopes=None):
+                                             causal=True, window_size=(-1, -1), deterministic=False, alibi_slopes=None,
+                                             dlse=None):
     be = get_backend()
     T, H, _ = q.shape
     L = T // 2
@@ -109,7 +110,8 @@ def zigzag_llama3_flash_attn_varlen_backward(process_group, dout, q, k, v, out, 
     dvg = torch.zeros(vg.shape, dtype=torch.float32, device=q.device)
     for i, (cu_q, cu_k, mq, mk, ksl) in enumerate(params):
         rows = slice(i * L, (i + 1) * L)
-        be.bwd_preprocess(dout[rows], out[rows], delta[:, rows], cu_seqlens_q=cu_q, max_seqlen_q=mq)
+        be.bwd_preprocess(dout[rows], out[rows], delta[:, rows], cu_seqlens_q=cu_q, max_seqlen_q=mq,
+                          **dlse_kw(None if dlse is None else dlse[:, rows]))
         be.bwd(dout[rows], q[rows], kg[ksl], vg[ksl], softmax_lse[:, rows], delta[:, rows],
                softmax_scale=softmax_scale, causal=causal, dq=dq[rows], dk_acc=dkg[ksl], dv_acc=dvg[ksl],
                acc_init=False, deterministic=deterministic, window=window_size, cu_seqlens_q=cu_q,
@@ -138,6 +140,7 @@ class ZigZagLlama3FlashAttnVarlenFunc(torch.autograd.Function):
                                       "supported (the two stream slices hold different sequences); pass (H,)")
         alibi_slopes = checked_alibi(alibi_slopes, q, 0, "zigzag_llama3_flash_attn_varlen_func")
         ctx.softcap = checked_softcap(dropout_p, alibi_slopes, q, "zigzag_llama3_flash_attn_varlen_func", window_size, causal)
+        ctx.lse_grad = checked_lse_grad(ctx, "zigzag_llama3_flash_attn_varlen_func")
         sinks = checked_sinks(sinks, q, "zigzag_llama3_flash_attn_varlen_func")
         if dropout_p and dropout_p > 0:
             raise NotImplementedError("zigzag_llama3_flash_attn_varlen_func: dropout is not supported")
@@ -167,9 +170,10 @@ class ZigZagLlama3FlashAttnVarlenFunc(torch.autograd.Function):
     def backward(ctx, dout, *args):
         q, k, v, out, lse, *sinks = ctx.saved_tensors
         softmax_scale, causal, window_size, deterministic, group = ctx.meta
+        dout, lse_kw = lse_grad_kw(ctx, dout, args, out, lse)
         with softcap_scope(ctx.softcap):
             dq, dk, dv = zigzag_llama3_flash_attn_varlen_backward(group, dout, q, k, v, out, lse, ctx.params, softmax_scale,
-                                                                  causal, window_size, deterministic, ctx.alibi_slopes)
+                                                                  causal, window_size, deterministic, ctx.alibi_slopes, **lse_kw)
         return (dq, dk, dv) + (None,) * 10 + sinks_grad(ctx, sinks[0] if sinks else None, dout, out, lse)
 
 

@@ -52,7 +52,7 @@ from . import _C, config
 from .backend import get_backend
 from .utils import Agreement, AllGatherComm, RingComm, SourceArrivals, all_to_all_async, reduce_scatter_async, single_rank
 from ._api import make_autograd_function, make_dense_api, _grad_buffers
-from ._common import alibi_kw, packed_pair, dropout_arg, global_window, require_dropout_positions, require_mask_shift, zigzag_map
+from ._common import alibi_kw, dlse_kw, packed_pair, dropout_arg, global_window, require_dropout_positions, require_mask_shift, zigzag_map
 
 
 def gather_scratch_bytes(k: torch.Tensor, world: int, wire_fp32: bool) -> int:
@@ -416,6 +416,7 @@ def zigzag_ring_flash_attn_backward(
     deterministic=False,
     dropout_seed=None,
     out_grads=None,
+    dlse=None,
     kept=None,
 ):
     """kept: the gathered K/V buffers the forward handed over (`keep=`), or None"""
@@ -431,7 +432,7 @@ def zigzag_ring_flash_attn_backward(
         dout = dout.contiguous()
 
     delta = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
-    be.bwd_preprocess(dout, out, delta)
+    be.bwd_preprocess(dout, out, delta, **dlse_kw(dlse))
 
     if single_rank(kv_comm.world_size):
         dq, dk, dv = _grad_buffers(out_grads, q, k, v)

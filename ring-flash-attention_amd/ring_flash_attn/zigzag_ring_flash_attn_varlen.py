@@ -33,7 +33,7 @@ import torch
 from . import _C, config
 from .backend import get_backend, HALF_FRONT, HALF_BACK
 from .utils import AllGatherComm, RingComm, all_to_all_async, reduce_scatter_async, single_rank
-from ._common import alibi_kw, dropout_arg, global_window, require_mask_shift_lens
+from ._common import alibi_kw, dlse_kw, dropout_arg, global_window, require_mask_shift_lens
 from ._api import make_autograd_function, make_varlen_api, _grad_buffers
 
 
@@ -273,6 +273,7 @@ def zigzag_ring_flash_attn_varlen_backward(
     deterministic=False,
     dropout_seed=None,
     out_grads=None,
+    dlse=None,
 ):
     assert causal == True, "zigzag ring is meaningless for causal=False"
     be = get_backend()
@@ -286,7 +287,7 @@ def zigzag_ring_flash_attn_varlen_backward(
         dout = dout.contiguous()
 
     delta = torch.empty((H, T), dtype=torch.float32, device=q.device)
-    be.bwd_preprocess(dout, out, delta, cu_seqlens_q=cu_seqlens, max_seqlen_q=max_seqlen)
+    be.bwd_preprocess(dout, out, delta, cu_seqlens_q=cu_seqlens, max_seqlen_q=max_seqlen, **dlse_kw(dlse))
 
     if single_rank(kv_comm.world_size):
         dq, dk, dv = _grad_buffers(out_grads, q, k, v)
