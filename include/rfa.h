@@ -695,6 +695,32 @@ typedef struct {
 } rfa_merge_pair_bwd_args;
 int rfa_merge_pair_bwd(const rfa_merge_pair_bwd_args *args, void *stream);
 
+/* A value head dim of its own (multi-head latent attention as DeepSeek-V2/V3 and Kimi K2 train it: QK head dim 192, V head
+ * dim 128).  Two entry points with a struct of their own; no existing struct changes (ABI 8 revision 1 stays; rfa_ext_args
+ * stays).  The base structs are the existing ones with
+ *     D                                                        the QK head dim: q, k, dq, dk (and their accumulators),
+ *     v_st, out_st, out_acc_st, dout_st, dv_st, dv_acc_st      rows of head_dim_v elements: v, out, dout, dv,
+ * everything else as rfa_fwd / rfa_bwd say.  Served: D a multiple of 8 in 136..192, head_dim_v a multiple of 8 in 8..128,
+ * bf16 / fp16, dense and packed input, causal / window / mask_shift / mask_shift_lens, q_half / k_half, plain and accumulate
+ * outputs (csrc/rfa_vdim.hip).  No dropout.
+ * rfa_bwd_vd runs the BASE arguments' own plan: dkdv_nsplit, phases, RFA_BWD_KV_OVERWRITE, workspace, ds_scratch /
+ * ds_scratch_bytes mean what they mean to rfa_bwd, and rfa_bwd_plan, rfa_bwd_workspace_bytes, rfa_bwd_ds_scratch_bytes and
+ * rfa_bwd_ds_chunks of the base arguments describe it (the workspace holds D-wide slots for dV too, head_dim_v <= D of them
+ * used; the dS scratch does not depend on V: dQ = scale dS K is finished by the same kernel as for rfa_bwd).
+ * rfa_bwd_preprocess and rfa_merge serve a head_dim_v-wide out through their own D.
+ * Checks, before any pointer of the base struct is looked at: NULL args RFA_ERR_NULL; a NULL vd, struct_bytes below
+ * sizeof(rfa_vdim_args) (or above it with a non-zero tail), a non-zero reserved or pad, dropout_p > 0 RFA_ERR_ARGS; head_dim_v
+ * not a multiple of 8 in 8..128, D not a multiple of 8 in 136..192 RFA_ERR_HEAD_DIM.  Then the checks of rfa_fwd / rfa_bwd in
+ * their order. */
+typedef struct {
+  uint32_t struct_bytes;       /* sizeof(rfa_vdim_args) as the caller compiled it */
+  uint32_t reserved;           /* 0 */
+  int32_t head_dim_v;
+  int32_t pad;                 /* 0 */
+} rfa_vdim_args;
+int rfa_fwd_vd(const rfa_fwd_args *args, const rfa_vdim_args *vd, void *stream);
+int rfa_bwd_vd(const rfa_bwd_args *args, const rfa_vdim_args *vd, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -531,7 +531,31 @@ int64_t rfa_ext_args_bytes(void) { return (int64_t)sizeof(rfa_ext_args); }
 
 int rfa_fwd(const rfa_fwd_args* a, void* stream) { return rfa_fwd_ex(a, nullptr, stream); }
 
-int rfa_fwd_ex(const rfa_fwd_args* a, const rfa_ext_args* ext, void* stream) {
+// ---- a value head dim of its own (rfa.h: rfa_vdim_args; csrc/rfa_vdim.hip) ---------------------------------------------------
+// Parsed before any pointer of the base struct is looked at; a longer struct is accepted while its unknown tail is zero.
+inline int parse_vdim(const rfa_vdim_args* v, float dropout_p, int D, int* Dv) {
+  if (v == nullptr || v->struct_bytes < sizeof(rfa_vdim_args) || v->reserved != 0 || v->pad != 0) return RFA_ERR_ARGS;
+  const unsigned char* src = reinterpret_cast<const unsigned char*>(v);
+  for (uint32_t i = sizeof(rfa_vdim_args); i < v->struct_bytes; ++i)
+    if (src[i] != 0) return RFA_ERR_ARGS;
+  if (dropout_p > 0.f) return RFA_ERR_ARGS;
+  if (v->head_dim_v < 8 || v->head_dim_v > kVdMaxHeadDimV || (v->head_dim_v & 7)) return RFA_ERR_HEAD_DIM;
+  if (D < kVdMinHeadDim || D > kVdMaxHeadDim || (D & 7)) return RFA_ERR_HEAD_DIM;
+  *Dv = v->head_dim_v;
+  return RFA_OK;
+}
+
+// Dv = 0: one head dim (rfa_fwd, rfa_fwd_ex); else the V head dim of rfa_fwd_vd
+static int fwd_impl(const rfa_fwd_args* a, const rfa_ext_args* ext, int Dv, void* stream);
+int rfa_fwd_ex(const rfa_fwd_args* a, const rfa_ext_args* ext, void* stream) { return fwd_impl(a, ext, 0, stream); }
+int rfa_fwd_vd(const rfa_fwd_args* a, const rfa_vdim_args* vd, void* stream) {
+  if (!a) return RFA_ERR_NULL;
+  int Dv = 0;
+  if (int rc = parse_vdim(vd, a->dropout_p, a->D, &Dv)) return rc;
+  return fwd_impl(a, nullptr, Dv, stream);
+}
+
+static int fwd_impl(const rfa_fwd_args* a, const rfa_ext_args* ext, int Dv, void* stream) {
   if (!a) return RFA_ERR_NULL;
   Ext e;
   if (int rce = parse_ext(ext, &e)) return rce;
@@ -637,6 +661,7 @@ int rfa_fwd_ex(const rfa_fwd_args* a, const rfa_ext_args* ext, void* stream) {
   p.nqblk = (eff_len(a->Sq, a->q_half) + rows - 1) / rows;
   p.persist_grid = (plan.persist && rows == 256 && ns <= 1 && plan.ns <= 1) ? device_cus() : 0;
   if (a->fwd_form < RFA_FWD_AUTO || a->fwd_form > RFA_FWD_P8x32 || a->fwd_form == RFA_FWD_RETIRED_2) return RFA_ERR_ARGS;
+  if (Dv) return launch_status(launch_fwd_vd(p, Dv, a->dtype, (hipStream_t)stream));
   if (a->D > kHeadDim) return launch_status(launch_fwd_big(p, a->dtype, (hipStream_t)stream));
   if (int rc2 = launch_fwd(p, a->dtype, (hipStream_t)stream)) return launch_status(rc2);
   if (ns > 1 && launch_combine(cb, a->dtype, (hipStream_t)stream)) return RFA_ERR_LAUNCH;
@@ -1008,7 +1033,18 @@ int64_t rfa_bwd_workspace_bytes(const rfa_bwd_args* a) {
 
 int rfa_bwd(const rfa_bwd_args* a, void* stream) { return rfa_bwd_ex(a, nullptr, stream); }
 
-int rfa_bwd_ex(const rfa_bwd_args* a, const rfa_ext_args* ext, void* stream) {
+// Dv = 0: one head dim (rfa_bwd, rfa_bwd_ex); else the V head dim of rfa_bwd_vd — the same plan, workspace layout (dV in D-wide
+// slots, Dv of them used) and dS hand-off, with the dK + dV and 7-GEMM dQ kernels of rfa_vdim.hip
+static int bwd_impl(const rfa_bwd_args* a, const rfa_ext_args* ext, int Dv, void* stream);
+int rfa_bwd_ex(const rfa_bwd_args* a, const rfa_ext_args* ext, void* stream) { return bwd_impl(a, ext, 0, stream); }
+int rfa_bwd_vd(const rfa_bwd_args* a, const rfa_vdim_args* vd, void* stream) {
+  if (!a) return RFA_ERR_NULL;
+  int Dv = 0;
+  if (int rc = parse_vdim(vd, a->dropout_p, a->D, &Dv)) return rc;
+  return bwd_impl(a, nullptr, Dv, stream);
+}
+
+static int bwd_impl(const rfa_bwd_args* a, const rfa_ext_args* ext, int Dv, void* stream) {
   if (!a) return RFA_ERR_NULL;
   Ext e;
   if (int rce = parse_ext(ext, &e)) return rce;
@@ -1177,7 +1213,7 @@ int rfa_bwd_ex(const rfa_bwd_args* a, const rfa_ext_args* ext, void* stream) {
           pc.kv_accum = f > 0 ? 1 : 0;
         }
         if (!(a->phases & RFA_BWD_SKIP_DKDV))
-          if (int rc2 = launch_bwd_dkdv(pc, a->dtype, st)) return launch_status(rc2);
+          if (int rc2 = Dv ? launch_bwd_dkdv_vd(pc, Dv, a->dtype, st) : launch_bwd_dkdv(pc, a->dtype, st)) return launch_status(rc2);
         if (c == 0) mark(1);
         if (!(a->phases & RFA_BWD_SKIP_DQ))
           if (int rc2 = launch_bwd_dq_from_ds(pc, a->dtype, st)) return launch_status(rc2);
@@ -1185,10 +1221,10 @@ int rfa_bwd_ex(const rfa_bwd_args* a, const rfa_ext_args* ext, void* stream) {
       mark(2);
     } else {
       if (!(a->phases & RFA_BWD_SKIP_DQ))
-        if (int rc2 = launch_bwd_dq(p, a->dtype, st)) return launch_status(rc2);
+        if (int rc2 = Dv ? launch_bwd_dq_vd(p, Dv, a->dtype, st) : launch_bwd_dq(p, a->dtype, st)) return launch_status(rc2);
       mark(1);
       if (!(a->phases & RFA_BWD_SKIP_DKDV))
-        if (int rc2 = launch_bwd_dkdv(p, a->dtype, st)) return launch_status(rc2);
+        if (int rc2 = Dv ? launch_bwd_dkdv_vd(p, Dv, a->dtype, st) : launch_bwd_dkdv(p, a->dtype, st)) return launch_status(rc2);
       mark(2);
     }
   } else {
@@ -1210,6 +1246,15 @@ int rfa_bwd_ex(const rfa_bwd_args* a, const rfa_ext_args* ext, void* stream) {
     } else {
       r.dst = a->dk; r.dst2 = a->dv;
       r.dst_st = cv(a->dk_st); r.dst2_st = cv(a->dv_st);
+    }
+    if (Dv) {
+      // dK (D wide) and dV (Dv wide) differ in width: the same kernel once per tensor
+      ReduceParams rv = r;
+      rv.src = r.src2; rv.dst = r.dst2; rv.dst_acc = r.dst_acc2; rv.dst_st = r.dst2_st; rv.dst_acc_st = r.dst_acc2_st;
+      rv.src2 = nullptr; rv.dst2 = nullptr; rv.dst_acc2 = nullptr;
+      rv.D = Dv;
+      r.src2 = nullptr; r.dst2 = nullptr; r.dst_acc2 = nullptr;
+      if (launch_reduce(rv, a->dtype, st)) return RFA_ERR_LAUNCH;
     }
     if (launch_reduce(r, a->dtype, st)) return RFA_ERR_LAUNCH;
   }

@@ -274,6 +274,21 @@ constexpr int kMaxHeadDim = 256;
 int launch_fwd_big(const FwdParams& p, int dtype, hipStream_t stream);
 int launch_bwd_dq_big(const BwdParams& p, int dtype, hipStream_t stream);
 int launch_bwd_dkdv_big(const BwdParams& p, int dtype, hipStream_t stream);
+// a value head dim of its own (rfa_vdim.hip): QK head dims 136 .. 192 (D of the block), V head dims 8 .. 128 (Dv).  The blocks
+// above stay as they are — and with them the kernarg of every other kernel; v_st / out_st / out_acc_st / dout_st / dv_st
+// describe Dv-wide rows
+constexpr int kVdMinHeadDim = 136, kVdMaxHeadDim = 192, kVdMaxHeadDimV = 128;
+struct FwdParamsVd {
+  FwdParams base;
+  int Dv;
+};
+struct BwdParamsVd {
+  BwdParams base;
+  int Dv;
+};
+int launch_fwd_vd(const FwdParams& p, int Dv, int dtype, hipStream_t stream);
+int launch_bwd_dq_vd(const BwdParams& p, int Dv, int dtype, hipStream_t stream);
+int launch_bwd_dkdv_vd(const BwdParams& p, int Dv, int dtype, hipStream_t stream);
 
 int launch_preprocess(const PreParams& p, int dtype, hipStream_t stream);
 // soft cap + bounded window at head dims 65 .. 127: the zero-padded 128-wide dK/dV instance with both flags needs 40 bytes of

@@ -273,6 +273,19 @@ class MergePairBwdArgs(C.Structure):
     ]
 
 
+class VdimArgs(C.Structure):
+    """rfa_vdim_args: the V head dim of a call whose QK head dim (the base struct's D) differs; struct_bytes is filled in here"""
+    _fields_ = [
+        ("struct_bytes", C.c_uint32), ("reserved", C.c_uint32),
+        ("head_dim_v", C.c_int32), ("pad", C.c_int32),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if not self.struct_bytes:
+            self.struct_bytes = C.sizeof(VdimArgs)
+
+
 # every symbol include/rfa.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "rfa_abi_version": (C.c_int, []),
@@ -308,6 +321,8 @@ SYMBOLS = {
     "rfa_bwd_preprocess_lse": (C.c_int, [C.POINTER(BwdPreLseArgs), C.c_void_p]),
     "rfa_merge_pair": (C.c_int, [C.POINTER(MergePairArgs), C.c_void_p]),
     "rfa_merge_pair_bwd": (C.c_int, [C.POINTER(MergePairBwdArgs), C.c_void_p]),
+    "rfa_fwd_vd": (C.c_int, [C.POINTER(FwdArgs), C.POINTER(VdimArgs), C.c_void_p]),
+    "rfa_bwd_vd": (C.c_int, [C.POINTER(BwdArgs), C.POINTER(VdimArgs), C.c_void_p]),
 }
 
 _lib = None
@@ -352,6 +367,10 @@ def load():
     for name in ("rfa_bwd_preprocess_lse", "rfa_merge_pair", "rfa_merge_pair_bwd"):
         if not hasattr(lib, name):
             raise RuntimeError(f"ring_flash_attn: librfa_hip.so has no {name} (the lse-gradient / merge entry points); rebuild")
+    # ... and the pair with a value head dim of its own (a struct of its own)
+    for name in ("rfa_fwd_vd", "rfa_bwd_vd"):
+        if not hasattr(lib, name):
+            raise RuntimeError(f"ring_flash_attn: librfa_hip.so has no {name} (the value-head-dim entry points); rebuild")
     for name, (res, args) in SYMBOLS.items():
         fn = getattr(lib, name)  # AttributeError if the .so is stale
         fn.restype = res

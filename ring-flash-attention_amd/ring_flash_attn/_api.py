@@ -60,6 +60,9 @@ def _compilable(fn, lower, multi=None):
         if torch.compiler.is_compiling():
             # `group` may be passed positionally: resolve it the way the call itself would
             bound = sig.bind(*args, **kwargs).arguments
+            # (a value head dim of its own runs eagerly too: the registered operators' fake kernels assume out like q)
+            if "v" in bound and "q" in bound and bound["v"].shape[-1] != bound["q"].shape[-1]:
+                return eager(*args, **kwargs)
             # (dropout draws a host-side seed per call: such calls run eagerly behind a graph break)
             # (a bias runs the eager autograd path too: the registered operators have no biased form)
             if not bound.get("dropout_p", 0.0) and bound.get("alibi_slopes", None) is None:
@@ -163,6 +166,43 @@ def checked_softcap(dropout_p, alibi_slopes, q, what, window_size=None, causal=F
     with softcap_scope(cap):
         get_backend()                                # (refuses a backend without `serves_softcap`)
     return cap
+
+
+VDIM_QK = (136, 192)      # QK head dims served next to a value head dim of its own (csrc/rfa_vdim.hip) ...
+VDIM_V = (8, 128)         # ... and the value head dims
+
+
+def checked_vdim(q, k, v, dropout_p, alibi_slopes, what, served=True):
+    """A `v` whose head dim differs from q's (multi-head latent attention: 192 / 128), decided once per public call, on every
+    rank alike, before anything is exchanged.  Equal widths: nothing to check.  ValueError: v's leading dims differ from k's,
+    a value head dim that is no multiple of 8.  NotImplementedError: a (D, Dv) pair outside QK head dims 136 .. 192 and value
+    head dims 8 .. 128, dropout, alibi_slopes, a function that does not serve it (`served` False: the llama3 families and
+    with_ulysses move K and V in one buffer of one width), a backend without `serves_vdim`."""
+    D, Dv = q.shape[-1], v.shape[-1]
+    if Dv == D:
+        return False
+    if tuple(v.shape[:-1]) != tuple(k.shape[:-1]):
+        raise ValueError(f"ring_flash_attn: {what}: v {tuple(v.shape)} must have k's leading dims {tuple(k.shape[:-1])}")
+    if Dv % 8:
+        raise ValueError(f"ring_flash_attn: {what}: the value head dim must be a multiple of 8, got {Dv}")
+    if not served:
+        raise NotImplementedError(f"ring_flash_attn: {what} does not serve a value head dim ({Dv}) that differs from q's ({D}): "
+                                  "K and V travel in one buffer of one width there; the ring, zigzag and stripe functions "
+                                  "and their *_varlen forms do")
+    if not (VDIM_QK[0] <= D <= VDIM_QK[1] and VDIM_V[0] <= Dv <= VDIM_V[1]):
+        raise NotImplementedError(f"ring_flash_attn: {what} serves a value head dim of its own for QK head dims {VDIM_QK[0]} .. "
+                                  f"{VDIM_QK[1]} and value head dims {VDIM_V[0]} .. {VDIM_V[1]}, not ({D}, {Dv})")
+    if dropout_p and dropout_p > 0:
+        raise NotImplementedError(f"ring_flash_attn: {what} with dropout and a value head dim that differs from q's is not supported")
+    if alibi_slopes is not None:
+        raise NotImplementedError(f"ring_flash_attn: {what} with alibi_slopes and a value head dim that differs from q's is not supported")
+    from .backend import get_backend
+
+    be = get_backend()
+    if not getattr(be, "serves_vdim", False):
+        raise NotImplementedError(f"ring_flash_attn: {what} with a value head dim that differs from q's needs a backend that "
+                                  f"serves it (serves_vdim); {getattr(be, 'name', type(be).__name__)!r} does not")
+    return True
 
 
 def with_softcap(func, softcap):
@@ -624,12 +664,13 @@ def _split_kept(ctx, more):
 
 
 def make_autograd_function(name, forward_impl, backward_impl, n_lead, window_ring=False, dropout_ring=False,
-                           alibi_ring=False):
+                           alibi_ring=False, vdim=False):
     """n_lead: number of non-tensor positional arguments between (q,k,v) and the common tail
     (0 for the batch API, 2 = (cu_seqlens, max_seqlen) for varlen).  window_ring: the schedule serves a sliding window
     on a multi-rank group (every ring family does: dense and varlen ring and zigzag, stripe).  dropout_ring: it serves
     dropout there (the dense ring, zigzag and stripe schedules: every block call is told the global positions of its
-    rows, _common.dropout_arg).  alibi_ring: it serves alibi_slopes there (the dense ring and zigzag schedules)."""
+    rows, _common.dropout_arg).  alibi_ring: it serves alibi_slopes there (the dense ring and zigzag schedules).
+    vdim: it serves a `v` whose head dim differs from q's (the five ring-type families, on any group: checked_vdim)."""
 
     class _Fn(torch.autograd.Function):
         @staticmethod
@@ -640,6 +681,7 @@ def make_autograd_function(name, forward_impl, backward_impl, n_lead, window_rin
              return_softmax, group) = rest[n_lead:]
             if softmax_scale is None:
                 softmax_scale = q.shape[-1] ** (-0.5)
+            checked_vdim(q, k, v, dropout_p, alibi_slopes, name, served=vdim)
             single = window_ok_for(group)
             _check_unsupported(dropout_p, window_size, alibi_slopes, windows_ok=single or window_ring, dropout_ok=single or dropout_ring,
                                alibi_ok=single or alibi_ring)

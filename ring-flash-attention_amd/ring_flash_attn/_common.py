@@ -20,6 +20,11 @@ def packed_pair(k, v):
     return torch.as_strided(k, lead + (2, hk, d), strides, k.storage_offset())
 
 
+def out_shape(q, v):
+    """the shape of attention's output: q's rows and heads, v's head dim (they differ for MLA: 192 / 128)"""
+    return tuple(q.shape[:-1]) + (v.shape[-1],)
+
+
 def _prep_qkv(q, k, v, group, packed_travel=False):
     """Kernels take strided views (last stride 1, 16-byte aligned rows).  K/V only have to be
     contiguous when they travel (world_size > 1: they are RCCL send buffers), so the packed

@@ -76,6 +76,7 @@ class HipBackend:
     serves_max_logit = True          # max_logit (include/rfa.h: rfa_max_logit): ring_flash_attn.with_max_logit
     serves_lse_grad = True           # bwd_preprocess takes `dlse=` (include/rfa.h: rfa_bwd_preprocess_lse): ring_flash_attn.with_lse_grad
     serves_merge_pair = True         # merge_pair / merge_pair_bwd (include/rfa.h: rfa_merge_pair, rfa_merge_pair_bwd): ring_flash_attn.merge_attn
+    serves_vdim = True               # fwd / bwd take a `v` whose head dim differs from q's (include/rfa.h: rfa_fwd_vd, rfa_bwd_vd): MLA 192 / 128
     serves_dropout_positions = True  # `dropout=` takes the position maps (q_map, k_map): what dropout over a dense ring, zigzag or stripe schedule needs
 
     def __init__(self):
@@ -154,6 +155,10 @@ class HipBackend:
         a.kv_nsplit = config.get().fwd_kv_nsplit
         # split-KV launches (few query rows against many keys on an under-filled grid: include/rfa.h) need a small
         # workspace for the partial (out, lse) pairs: a few tens of MB, only for the calls that split
+        vd = _vdim_args(q, v, alibi, softcap, dropout)
+        if vd is not None:                        # a value head dim of its own (csrc/rfa_vdim.hip): never split either
+            _C.check(self.lib.rfa_fwd_vd(C.byref(a), C.byref(vd), _stream(q)), "rfa_fwd_vd")
+            return
         ext = _ext_args(alibi, q, softcap)
         if ext is not None:                       # a bias or a cap is never split: no workspace (include/rfa.h)
             _C.check(self.lib.rfa_fwd_ex(C.byref(a), C.byref(ext), _stream(q)), "rfa_fwd_ex")
@@ -271,6 +276,7 @@ class HipBackend:
         # large: a hand-off that does not fit runs in head-group chunks over it (include/rfa.h: ds_scratch_bytes).
         # config.bwd_ds_spill = False (RFA_BWD_DS_SPILL=0) keeps the 7-GEMM form.  Callers that split one backward over
         # several calls (measurement: BWD_SKIP_DQ / BWD_SKIP_DKDV) pass the same `ds_scratch` to both.
+        vd = _vdim_args(q, v, alibi, softcap, dropout)    # (rfa_bwd_vd runs the base arguments' own plan and scratch)
         ext = _ext_args(alibi, q, softcap)
         if ext is not None:
             a.dkdv_form, a.dkdv_nsplit, ds_scratch = _C.DKDV_128, 0, None
@@ -293,7 +299,9 @@ class HipBackend:
             ws._rfa_plan = (form, ns if form == _C.DKDV_256 or a.D > 128 else 0)
         if ws is not None:
             a.workspace = ws.data_ptr()
-        if ext is not None:
+        if vd is not None:
+            _C.check(self.lib.rfa_bwd_vd(C.byref(a), C.byref(vd), _stream(q)), "rfa_bwd_vd")
+        elif ext is not None:
             _C.check(self.lib.rfa_bwd_ex(C.byref(a), C.byref(ext), _stream(q)), "rfa_bwd_ex")
         else:
             _C.check(self.lib.rfa_bwd(C.byref(a), _stream(q)), "rfa_bwd")
@@ -724,6 +732,21 @@ def _ext_args(alibi, q, softcap=0.0):
     ext.alibi_shift = int(shift)
     ext.softcap = softcap
     return ext
+
+
+def _vdim_args(q, v, alibi, softcap, dropout):
+    """rfa_vdim_args of a call whose `v` has a head dim of its own, or None: equal widths — the call as it always was.
+    What the kernels of such a call do not have (a bias, a soft cap, dropout) is refused here, before the library is called."""
+    if v.shape[-1] == q.shape[-1]:
+        return None
+    if (alibi is not None and alibi[0] is not None) or check_softcap(softcap):
+        raise NotImplementedError("ring_flash_attn: alibi / softcap with a value head dim that differs from q's is not served "
+                                  "(both stop at head dim 128)")
+    if dropout is not None and dropout[0] > 0:
+        raise NotImplementedError("ring_flash_attn: dropout with a value head dim that differs from q's is not served")
+    vd = _C.VdimArgs()
+    vd.head_dim_v = v.shape[-1]
+    return vd
 
 
 def check_softcap(softcap):

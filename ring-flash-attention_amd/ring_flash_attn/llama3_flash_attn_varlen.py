@@ -27,7 +27,7 @@ import torch
 from . import config
 from .backend import get_backend, heads_from
 from .utils import AllGatherComm as Comm, group_rank_world, reduce_scatter_async, single_rank
-from ._api import (_check_unsupported, _opaque, apply_sinks, checked_alibi, checked_sinks, checked_softcap, sink_args, sinks_grad,
+from ._api import (_check_unsupported, _opaque, apply_sinks, checked_alibi, checked_sinks, checked_softcap, checked_vdim, sink_args, sinks_grad,
                    softcap_scope, window_ok_for, checked_lse_grad, lse_grad_kw)
 from ._common import alibi_kw, dlse_kw, _as_cu, dropout_arg, draw_dropout_seed, packed_pair
 
@@ -320,6 +320,7 @@ def _l3_forward(ctx, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seql
                 dropout_p, softmax_scale, causal, window_size, alibi_slopes, deterministic, return_softmax, group, sinks=None):
     if softmax_scale is None:
         softmax_scale = q.shape[-1] ** (-0.5)
+    checked_vdim(q, k, v, dropout_p, alibi_slopes, "llama3_flash_attn_varlen_func", served=False)   # (the gathers stack K and V)
     # K/V are gathered: one kernel sees them all.  A bias needs the global distance i - j: on several ranks the bottom-right
     # alignment against the truncated cu_seqlens_k yields it for causal calls only (the slopes are sliced per head group)
     _check_unsupported(dropout_p, window_size, alibi_slopes, windows_ok=True, alibi_ok=window_ok_for(group) or bool(causal))

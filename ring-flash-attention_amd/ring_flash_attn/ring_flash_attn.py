@@ -23,7 +23,7 @@ import torch
 from . import _C
 from .backend import get_backend
 from .utils import RingComm, single_rank
-from ._common import alibi_kw, dlse_kw, dropout_arg, global_window, pos_map, require_dropout_positions, require_mask_shift
+from ._common import alibi_kw, dlse_kw, out_shape, dropout_arg, global_window, pos_map, require_dropout_positions, require_mask_shift
 from ._api import make_autograd_function, make_dense_api, _grad_buffers
 
 
@@ -66,7 +66,7 @@ def _band(causal, window, t, S, alibi_slopes=None):
 def _ring_window_forward(be, comm, q, k, v, softmax_scale, causal, window, alibi_slopes=None):
     B, S, H, D = q.shape
     n_steps, dists = ring_window_plan(comm.rank, comm.world_size, S, causal, window)
-    out_acc = torch.empty((B, S, H, D), dtype=torch.float32, device=q.device)
+    out_acc = torch.empty(out_shape(q, v), dtype=torch.float32, device=q.device)
     lse_acc = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
     first = True
     next_k, next_v = None, None
@@ -159,7 +159,7 @@ def ring_flash_attn_forward(
     B, S, H, D = q.shape
 
     if single_rank(comm.world_size):
-        out = torch.empty_like(q)
+        out = torch.empty(out_shape(q, v), dtype=q.dtype, device=q.device)
         lse = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
         be.fwd(q, k, v, softmax_scale=softmax_scale, causal=causal, out=out, lse=lse, window=window_size, dropout=dropout_arg(dropout_p, dropout_seed),
                **alibi_kw(alibi_slopes))
@@ -173,7 +173,7 @@ def ring_flash_attn_forward(
         require_mask_shift(be, "ring_flash_attn")
         return _ring_window_forward(be, comm, q, k, v, softmax_scale, causal, win, alibi_slopes)
 
-    out_acc = torch.empty((B, S, H, D), dtype=torch.float32, device=q.device)
+    out_acc = torch.empty(out_shape(q, v), dtype=torch.float32, device=q.device)
     lse_acc = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
     first = True
     next_k, next_v = None, None
@@ -281,7 +281,7 @@ def ring_flash_attn_backward(
 
 
 RingFlashAttnFunc = make_autograd_function(
-    "RingFlashAttnFunc", ring_flash_attn_forward, ring_flash_attn_backward, 0, window_ring=True, dropout_ring=True,
+    "RingFlashAttnFunc", ring_flash_attn_forward, ring_flash_attn_backward, 0, vdim=True, window_ring=True, dropout_ring=True,
     alibi_ring=True)
 (
     ring_flash_attn_func,

@@ -21,7 +21,7 @@ import torch
 from . import _C
 from .backend import get_backend
 from .utils import RingComm, single_rank
-from ._common import alibi_kw, dlse_kw, dropout_arg, global_window, require_mask_shift_lens
+from ._common import alibi_kw, dlse_kw, out_shape, dropout_arg, global_window, require_mask_shift_lens
 from ._api import make_autograd_function, make_varlen_api, _grad_buffers
 
 
@@ -58,7 +58,7 @@ def ring_flash_attn_varlen_forward(
     vl = dict(cu_seqlens_q=cu_seqlens, cu_seqlens_k=cu_seqlens, max_seqlen_q=max_seqlen, max_seqlen_k=max_seqlen)
 
     if single_rank(comm.world_size):
-        out = torch.empty_like(q)
+        out = torch.empty(out_shape(q, v), dtype=q.dtype, device=q.device)
         lse = torch.empty((H, T), dtype=torch.float32, device=q.device)
         be.fwd(q, k, v, softmax_scale=softmax_scale, causal=causal, out=out, lse=lse, window=window_size, dropout=dropout_arg(dropout_p, dropout_seed), **alibi_kw(alibi_slopes), **vl)
         return out, lse
@@ -67,7 +67,7 @@ def ring_flash_attn_varlen_forward(
     if win is not None:
         require_mask_shift_lens(be, "ring_flash_attn_varlen")
 
-    out_acc = torch.empty((T, H, D), dtype=torch.float32, device=q.device)
+    out_acc = torch.empty(out_shape(q, v), dtype=torch.float32, device=q.device)
     lse_acc = torch.empty((H, T), dtype=torch.float32, device=q.device)
     first = True
     next_k, next_v = None, None
@@ -166,7 +166,7 @@ def ring_flash_attn_varlen_backward(
 
 
 RingFlashAttnVarlenFunc = make_autograd_function(
-    "RingFlashAttnVarlenFunc", ring_flash_attn_varlen_forward, ring_flash_attn_varlen_backward, 2, window_ring=True)
+    "RingFlashAttnVarlenFunc", ring_flash_attn_varlen_forward, ring_flash_attn_varlen_backward, 2, window_ring=True, vdim=True)
 (
     ring_flash_attn_varlen_func,
     ring_flash_attn_varlen_kvpacked_func,

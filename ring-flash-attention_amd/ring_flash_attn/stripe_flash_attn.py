@@ -21,7 +21,7 @@ import torch
 from . import _C
 from .backend import get_backend
 from .utils import RingComm, single_rank
-from ._common import alibi_kw, dlse_kw, dropout_arg, global_window, require_dropout_positions, require_mask_shift, stripe_map
+from ._common import alibi_kw, dlse_kw, out_shape, dropout_arg, global_window, require_dropout_positions, require_mask_shift, stripe_map
 from ._api import make_autograd_function, make_dense_api, _grad_buffers
 
 
@@ -37,7 +37,7 @@ def stripe_window_band(rank, src, world, window_left):
 def _stripe_window_forward(be, comm, q, k, v, softmax_scale, wl):
     B, S, H, D = q.shape
     W, rank = comm.world_size, comm.rank
-    out_acc = torch.empty((B, S, H, D), dtype=torch.float32, device=q.device)
+    out_acc = torch.empty(out_shape(q, v), dtype=torch.float32, device=q.device)
     lse_acc = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
     next_k, next_v = None, None
     for step in range(W):
@@ -125,7 +125,7 @@ def stripe_flash_attn_forward(
     B, S, H, D = q.shape
 
     if single_rank(comm.world_size):
-        out = torch.empty_like(q)
+        out = torch.empty(out_shape(q, v), dtype=q.dtype, device=q.device)
         lse = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
         be.fwd(q, k, v, softmax_scale=softmax_scale, causal=True, out=out, lse=lse, window=window_size, dropout=dropout_arg(dropout_p, dropout_seed), **alibi_kw(alibi_slopes))
         return out, lse
@@ -135,7 +135,7 @@ def stripe_flash_attn_forward(
         require_mask_shift(be, "stripe_flash_attn")
         return _stripe_window_forward(be, comm, q, k, v, softmax_scale, win[0])
 
-    out_acc = torch.empty((B, S, H, D), dtype=torch.float32, device=q.device)
+    out_acc = torch.empty(out_shape(q, v), dtype=torch.float32, device=q.device)
     lse_acc = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
     next_k, next_v = None, None
     for step in range(comm.world_size):
@@ -249,7 +249,7 @@ def stripe_flash_attn_backward(
 
 
 StripeFlashAttnFunc = make_autograd_function(
-    "StripeFlashAttnFunc", stripe_flash_attn_forward, stripe_flash_attn_backward, 0, window_ring=True, dropout_ring=True)
+    "StripeFlashAttnFunc", stripe_flash_attn_forward, stripe_flash_attn_backward, 0, vdim=True, window_ring=True, dropout_ring=True)
 (
     stripe_flash_attn_func,
     stripe_flash_attn_kvpacked_func,

@@ -268,6 +268,10 @@ def _check_call(func, tensors, names, layout, U, a):
         want = 4 if n in ("q", "k", "v") else 5
         if not isinstance(t, torch.Tensor) or t.dim() != want:
             raise ValueError(f"ring_flash_attn: with_ulysses({what}): {n} must be a {want}-dimensional tensor")
+    if names == ("q", "k", "v"):                     # (q, k, v travel in one buffer of one width)
+        from ._api import checked_vdim
+
+        checked_vdim(*tensors, a.get("dropout_p"), a.get("alibi_slopes"), f"with_ulysses({what})", served=False)
     S = tensors[0].shape[1]
     if any(t.shape[1] != S or t.shape[0] != tensors[0].shape[0] for t in tensors):
         raise ValueError(f"ring_flash_attn: with_ulysses({what}): q, k and v must have the same batch and row counts, got "

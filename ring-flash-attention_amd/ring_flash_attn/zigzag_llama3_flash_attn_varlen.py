@@ -26,7 +26,7 @@ llama3_flash_attn_varlen_func; all heads are processed per call.
 """
 import torch
 
-from ._api import (_check_unsupported, _opaque, apply_sinks, checked_alibi, checked_sinks, checked_softcap, sink_args, sinks_grad,
+from ._api import (_check_unsupported, _opaque, apply_sinks, checked_alibi, checked_sinks, checked_softcap, checked_vdim, sink_args, sinks_grad,
                    softcap_scope, window_ok_for, checked_lse_grad, lse_grad_kw)
 from ._common import _as_cu, alibi_kw, dlse_kw
 from .backend import get_backend
@@ -133,6 +133,7 @@ class ZigZagLlama3FlashAttnVarlenFunc(torch.autograd.Function):
                 deterministic, return_softmax, group, sinks=None):
         if softmax_scale is None:
             softmax_scale = q.shape[-1] ** (-0.5)
+        checked_vdim(q, k, v, dropout_p, alibi_slopes, "zigzag_llama3_flash_attn_varlen_func", served=False)   # (the gathers stack K and V)
         _check_unsupported(dropout_p, window_size, alibi_slopes, windows_ok=True,   # K/V are gathered
                            alibi_ok=window_ok_for(group) and bool(causal))
         if alibi_slopes is not None and alibi_slopes.dim() != 1:

@@ -52,7 +52,7 @@ from . import _C, config
 from .backend import get_backend
 from .utils import Agreement, AllGatherComm, RingComm, SourceArrivals, all_to_all_async, reduce_scatter_async, single_rank
 from ._api import make_autograd_function, make_dense_api, _grad_buffers
-from ._common import alibi_kw, dlse_kw, packed_pair, dropout_arg, global_window, require_dropout_positions, require_mask_shift, zigzag_map
+from ._common import alibi_kw, dlse_kw, out_shape, packed_pair, dropout_arg, global_window, require_dropout_positions, require_mask_shift, zigzag_map
 
 
 def gather_scratch_bytes(k: torch.Tensor, world: int, wire_fp32: bool) -> int:
@@ -127,12 +127,12 @@ def _try_keep(keep, bufs, process_group):
     keep.agreed = Agreement(process_group, token is not None, bufs[0].device)
 
 
-def _kv_views(bufs, k, world):
+def _kv_views(bufs, k, v, world):
     """(k_all, v_all) views — indexed by source rank — of the gathered base buffers `bufs`"""
     if len(bufs) == 1:                                   # packed kv travelled as one buffer
         kv_all = bufs[0].view((world, k.shape[0], k.shape[1], 2) + tuple(k.shape[2:]))
         return kv_all.select(-3, 0), kv_all.select(-3, 1)
-    return bufs[0].view((world,) + tuple(k.shape)), bufs[1].view((world,) + tuple(k.shape))
+    return bufs[0].view((world,) + tuple(k.shape)), bufs[1].view((world,) + tuple(v.shape))
 
 
 def _gather_kv(comm_group, k, v, world, per_source=False):
@@ -158,7 +158,7 @@ def _gather_kv(comm_group, k, v, world, per_source=False):
         gather = AllGatherComm(comm_group)
         for b_, t_ in zip(bufs, locals_):
             gather.all_gather(b_, t_)
-    return (gather, bufs) + _kv_views(bufs, k, world)
+    return (gather, bufs) + _kv_views(bufs, k, v, world)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -196,7 +196,7 @@ def _zigzag_window_forward(be, process_group, comm, q, k, v, softmax_scale, wind
     B, S, H, D = q.shape
     W, rank = comm.world_size, comm.rank
     hs = _halves(S)
-    out_acc = torch.empty((B, S, H, D), dtype=torch.float32, device=q.device)
+    out_acc = torch.empty(out_shape(q, v), dtype=torch.float32, device=q.device)
     lse_acc = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
     started = [False, False]
 
@@ -252,7 +252,7 @@ def _zigzag_window_backward(be, process_group, kv_comm, d_kv_comm, dout, q, k, v
     if mode in ("gather", "gather_ps"):
         per_source = mode == "gather_ps"
         if kept:
-            gather, (k_all, v_all) = None, _kv_views(kept, k, W)
+            gather, (k_all, v_all) = None, _kv_views(kept, k, v, W)
         else:
             gather, _, k_all, v_all = _gather_kv(process_group, k, v, W, per_source=per_source)
         # slot c: this rank's dK/dV for the chunks owned by rank c, fp32, summed over the ranks by a reduce-scatter
@@ -337,7 +337,7 @@ def zigzag_ring_flash_attn_forward(
     half = S // 2
 
     if single_rank(comm.world_size):
-        out = torch.empty_like(q)
+        out = torch.empty(out_shape(q, v), dtype=q.dtype, device=q.device)
         lse = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
         be.fwd(q, k, v, softmax_scale=softmax_scale, causal=True, out=out, lse=lse, window=window_size, dropout=dropout_arg(dropout_p, dropout_seed),
                **alibi_kw(alibi_slopes))
@@ -351,7 +351,7 @@ def zigzag_ring_flash_attn_forward(
         require_mask_shift(be, "zigzag_ring_flash_attn")
         return _zigzag_window_forward(be, process_group, comm, q, k, v, softmax_scale, win, alibi_slopes)
 
-    out_acc = torch.empty((B, S, H, D), dtype=torch.float32, device=q.device)
+    out_acc = torch.empty(out_shape(q, v), dtype=torch.float32, device=q.device)
     lse_acc = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
 
     mode = exchange_mode(k, comm.world_size, q, process_group, v)
@@ -457,7 +457,7 @@ def zigzag_ring_flash_attn_backward(
         wire32 = _wire_fp32()
         per_source = mode == "gather_ps"
         if kept:
-            gather, (k_all, v_all) = None, _kv_views(kept, k, W)
+            gather, (k_all, v_all) = None, _kv_views(kept, k, v, W)
         else:
             gather, _, k_all, v_all = _gather_kv(process_group, k, v, W, per_source=per_source)
         # K/V of every rank are here already: remote steps first, local block beside the all-to-all (the fp32
@@ -614,7 +614,7 @@ zigzag_ring_flash_attn_forward.keeps_for_backward = True
 
 ZigZagRingFlashAttnFunc = make_autograd_function(
     "ZigZagRingFlashAttnFunc", zigzag_ring_flash_attn_forward, zigzag_ring_flash_attn_backward, 0, window_ring=True,
-    dropout_ring=True, alibi_ring=True)
+    dropout_ring=True, alibi_ring=True, vdim=True)
 (
     zigzag_ring_flash_attn_func,
     zigzag_ring_flash_attn_kvpacked_func,

@@ -33,7 +33,7 @@ import torch
 from . import _C, config
 from .backend import get_backend, HALF_FRONT, HALF_BACK
 from .utils import AllGatherComm, RingComm, all_to_all_async, reduce_scatter_async, single_rank
-from ._common import alibi_kw, dlse_kw, dropout_arg, global_window, require_mask_shift_lens
+from ._common import alibi_kw, dlse_kw, out_shape, dropout_arg, global_window, require_mask_shift_lens
 from ._api import make_autograd_function, make_varlen_api, _grad_buffers
 
 
@@ -45,7 +45,7 @@ def varlen_exchange_mode() -> str:
 def _gather_kv(process_group, k, v, world):
     comm = AllGatherComm(process_group)
     k_cat = torch.empty((world * k.shape[0],) + tuple(k.shape[1:]), dtype=k.dtype, device=k.device)
-    v_cat = torch.empty_like(k_cat)
+    v_cat = torch.empty((world * v.shape[0],) + tuple(v.shape[1:]), dtype=v.dtype, device=v.device)
     comm.all_gather(k_cat, k.contiguous())
     comm.all_gather(v_cat, v.contiguous())
     return comm, k_cat.view((world,) + tuple(k.shape)), v_cat.view((world,) + tuple(v.shape))
@@ -107,7 +107,7 @@ def _band_lens(d):
 def _zigzag_varlen_window_forward(be, process_group, comm, q, k, v, vl, softmax_scale, window):
     T, H, D = q.shape
     W, rank = comm.world_size, comm.rank
-    out_acc = torch.empty((T, H, D), dtype=torch.float32, device=q.device)
+    out_acc = torch.empty(out_shape(q, v), dtype=torch.float32, device=q.device)
     lse_acc = torch.empty((H, T), dtype=torch.float32, device=q.device)
     started = [False, False]
 
@@ -207,7 +207,7 @@ def zigzag_ring_flash_attn_varlen_forward(
     vl = dict(cu_seqlens_q=cu_seqlens, cu_seqlens_k=cu_seqlens, max_seqlen_q=max_seqlen, max_seqlen_k=max_seqlen)
 
     if single_rank(comm.world_size):
-        out = torch.empty_like(q)
+        out = torch.empty(out_shape(q, v), dtype=q.dtype, device=q.device)
         lse = torch.empty((H, T), dtype=torch.float32, device=q.device)
         be.fwd(q, k, v, softmax_scale=softmax_scale, causal=True, out=out, lse=lse, window=window_size, dropout=dropout_arg(dropout_p, dropout_seed), **alibi_kw(alibi_slopes), **vl)
         return out, lse
@@ -217,7 +217,7 @@ def zigzag_ring_flash_attn_varlen_forward(
         require_mask_shift_lens(be, "zigzag_ring_flash_attn_varlen")
         return _zigzag_varlen_window_forward(be, process_group, comm, q, k, v, vl, softmax_scale, win)
 
-    out_acc = torch.empty((T, H, D), dtype=torch.float32, device=q.device)
+    out_acc = torch.empty(out_shape(q, v), dtype=torch.float32, device=q.device)
     lse_acc = torch.empty((H, T), dtype=torch.float32, device=q.device)
 
     if varlen_exchange_mode() == "gather":
@@ -310,7 +310,7 @@ def zigzag_ring_flash_attn_varlen_backward(
         gather, k_all, v_all = _gather_kv(process_group, k, v, W)
         # slot c: this rank's dK/dV contribution (io dtype) for the rows of rank c
         dk_all = torch.empty((W,) + tuple(k.shape), dtype=q.dtype, device=q.device)
-        dv_all = torch.empty_like(dk_all)
+        dv_all = torch.empty((W,) + tuple(v.shape), dtype=q.dtype, device=q.device)
         be.bwd(dout, q, k, v, softmax_lse, delta, softmax_scale=softmax_scale, causal=True,       # beside the all-gather
                dq_acc=dq, acc_init=True, dk=dk_all[rank], dv=dv_all[rank], deterministic=deterministic, **vl)
         gather.wait()
@@ -378,7 +378,7 @@ def zigzag_ring_flash_attn_varlen_backward(
 
 ZigZagRingFlashAttnVarlenFunc = make_autograd_function(
     "ZigZagRingFlashAttnVarlenFunc", zigzag_ring_flash_attn_varlen_forward,
-    zigzag_ring_flash_attn_varlen_backward, 2, window_ring=True)
+    zigzag_ring_flash_attn_varlen_backward, 2, window_ring=True, vdim=True)
 (
     zigzag_ring_flash_attn_varlen_func,
     zigzag_ring_flash_attn_varlen_kvpacked_func,
