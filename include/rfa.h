@@ -721,6 +721,40 @@ typedef struct {
 int rfa_fwd_vd(const rfa_fwd_args *args, const rfa_vdim_args *vd, void *stream);
 int rfa_bwd_vd(const rfa_bwd_args *args, const rfa_vdim_args *vd, void *stream);
 
+/* Per-row key ranges (interval masks: documents on dense input, prefix-LM, shared prefixes, a window plus global tokens).
+ * Two entry points with a struct of their own; no existing struct changes (ABI 8 revision 1 stays).  Query row i of batch
+ * entry b sees key row j of the block iff
+ *     start[b * batch_stride + i] <= k_pos0 + j < end[b * batch_stride + i]
+ * AND the base arguments' own mask (causal, window, mask_shift) allows the pair.  start / end: int32, one entry per query
+ * row of the call (row stride 1), GLOBAL key positions; k_pos0: the global position of key row 0 of the block.  Values are
+ * clamped to the block, so anything outside it is allowed; start >= end is an empty row (out = 0, lse = +inf; -inf into
+ * lse_acc by acc_init; an accumulate call leaves such a row as it was).  All query heads share the ranges; they get no gradient.
+ * The kernels are the 8 x 32 forward, the 7-GEMM dQ kernel and the 128-key dK/dV kernel (csrc: the kRng instances), whose
+ * tile walks skip the key tiles / query tiles outside every row's range; a call whose rows all miss the block runs as a dark
+ * block does.  The backward needs `tile_bounds`: rfa_rowrange_workspace_bytes(args) bytes of device memory, 16-byte aligned,
+ * filled and read by rfa_bwd_rr itself (nothing to keep between calls; the forward ignores the field).
+ * Served: dense input, head dims 8 .. 128 (multiples of 8), bf16 / fp16, GQA, causal / window / mask_shift, plain and
+ * accumulate outputs, the two-phase backward.  rfa_bwd_rr runs the base arguments' plan, which must say what the kernels are:
+ * dkdv_form = RFA_DKDV_128 and no ds_scratch — rfa_bwd_plan / rfa_bwd_workspace_bytes of the base arguments then describe it.
+ * Checks, in this order, before any tensor pointer of the base struct is looked at: NULL args RFA_ERR_NULL; a NULL rr,
+ * struct_bytes below sizeof(rfa_rowrange_args) (or above it with a non-zero tail), a non-zero reserved RFA_ERR_ARGS;
+ * dropout_p > 0, cu_seqlens_q / cu_seqlens_k, q_half / k_half, a ds_scratch, (rfa_bwd_rr) dkdv_form other than RFA_DKDV_128
+ * RFA_ERR_ARGS; D above 128 RFA_ERR_HEAD_DIM; a negative batch_stride RFA_ERR_ARGS; then the checks of rfa_fwd / rfa_bwd in
+ * their order; then, where the call has work to do, a NULL start / end (rfa_bwd_rr: or tile_bounds) RFA_ERR_NULL and a
+ * tile_bounds off 16 bytes RFA_ERR_ALIGN. */
+typedef struct {
+  uint32_t struct_bytes;       /* sizeof(rfa_rowrange_args) as the caller compiled it */
+  uint32_t reserved;           /* 0 */
+  const int32_t *start;        /* (B, Sq) */
+  const int32_t *end;
+  int64_t batch_stride;        /* elements between two batch entries of start / end (>= 0) */
+  int64_t k_pos0;
+  void *tile_bounds;           /* backward only */
+} rfa_rowrange_args;
+int64_t rfa_rowrange_workspace_bytes(const rfa_bwd_args *args);
+int rfa_fwd_rr(const rfa_fwd_args *args, const rfa_rowrange_args *rr, void *stream);
+int rfa_bwd_rr(const rfa_bwd_args *args, const rfa_rowrange_args *rr, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

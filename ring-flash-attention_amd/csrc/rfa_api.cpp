@@ -545,8 +545,34 @@ inline int parse_vdim(const rfa_vdim_args* v, float dropout_p, int D, int* Dv) {
   return RFA_OK;
 }
 
-// Dv = 0: one head dim (rfa_fwd, rfa_fwd_ex); else the V head dim of rfa_fwd_vd
-static int fwd_impl(const rfa_fwd_args* a, const rfa_ext_args* ext, int Dv, void* stream);
+// ---- per-row key ranges (rfa.h: rfa_rowrange_args; the kRng kernel instances) ----------------------------------------------
+// Parsed, and the base arguments' combination checked, before any tensor pointer of the base struct is looked at; a longer
+// struct is accepted while its unknown tail is zero.
+inline int parse_rr(const rfa_rowrange_args* r, RowRangeParams* out) {
+  if (r == nullptr || r->struct_bytes < sizeof(rfa_rowrange_args) || r->reserved != 0) return RFA_ERR_ARGS;
+  const unsigned char* src = reinterpret_cast<const unsigned char*>(r);
+  for (uint32_t i = sizeof(rfa_rowrange_args); i < r->struct_bytes; ++i)
+    if (src[i] != 0) return RFA_ERR_ARGS;
+  *out = RowRangeParams{};
+  out->start = r->start;
+  out->end = r->end;
+  out->bstride = r->batch_stride;
+  out->k_pos0 = r->k_pos0;
+  out->tile_bounds = (int2*)r->tile_bounds;
+  return RFA_OK;
+}
+inline int rr_base_check(float dropout_p, const void* cu_q, const void* cu_k, int q_half, int k_half) {
+  if (dropout_p > 0.f || cu_q != nullptr || cu_k != nullptr || q_half != 0 || k_half != 0) return RFA_ERR_ARGS;
+  return RFA_OK;
+}
+inline int rr_dim_check(int D, const RowRangeParams& r) {
+  if (D > kHeadDim || (!kRngPadded128 && D > 64 && D < kHeadDim)) return RFA_ERR_HEAD_DIM;
+  if (r.bstride < 0) return RFA_ERR_ARGS;
+  return RFA_OK;
+}
+
+// Dv = 0: one head dim (rfa_fwd, rfa_fwd_ex); else the V head dim of rfa_fwd_vd; rr: the row ranges of rfa_fwd_rr
+static int fwd_impl(const rfa_fwd_args* a, const rfa_ext_args* ext, int Dv, void* stream, const RowRangeParams* rr = nullptr);
 int rfa_fwd_ex(const rfa_fwd_args* a, const rfa_ext_args* ext, void* stream) { return fwd_impl(a, ext, 0, stream); }
 int rfa_fwd_vd(const rfa_fwd_args* a, const rfa_vdim_args* vd, void* stream) {
   if (!a) return RFA_ERR_NULL;
@@ -554,8 +580,16 @@ int rfa_fwd_vd(const rfa_fwd_args* a, const rfa_vdim_args* vd, void* stream) {
   if (int rc = parse_vdim(vd, a->dropout_p, a->D, &Dv)) return rc;
   return fwd_impl(a, nullptr, Dv, stream);
 }
+int rfa_fwd_rr(const rfa_fwd_args* a, const rfa_rowrange_args* rr, void* stream) {
+  if (!a) return RFA_ERR_NULL;
+  RowRangeParams r;
+  if (int rc = parse_rr(rr, &r)) return rc;
+  if (int rc = rr_base_check(a->dropout_p, a->cu_seqlens_q, a->cu_seqlens_k, a->q_half, a->k_half)) return rc;
+  if (int rc = rr_dim_check(a->D, r)) return rc;
+  return fwd_impl(a, nullptr, 0, stream, &r);
+}
 
-static int fwd_impl(const rfa_fwd_args* a, const rfa_ext_args* ext, int Dv, void* stream) {
+static int fwd_impl(const rfa_fwd_args* a, const rfa_ext_args* ext, int Dv, void* stream, const RowRangeParams* rr) {
   if (!a) return RFA_ERR_NULL;
   Ext e;
   if (int rce = parse_ext(ext, &e)) return rce;
@@ -619,7 +653,9 @@ static int fwd_impl(const rfa_fwd_args* a, const rfa_ext_args* ext, int Dv, void
   // a bias runs the 256-row form: the persistent form, the 4-wave form and split-KV shares do not exist for it and read as
   // RFA_FWD_AUTO / "never split" (`workspace` is ignored), as they do for dropout
   // (a soft cap likewise: the 256-row instances with or without a window)
-  const bool bias = e.slopes != nullptr || e.cap > 0.f;
+  // (row ranges likewise: the windowed 256-row instances with kRng, never split)
+  const bool bias = e.slopes != nullptr || e.cap > 0.f || rr != nullptr;
+  if (rr != nullptr && (!rr->start || !rr->end)) return RFA_ERR_NULL;
   if (e.slopes != nullptr) set_bias(p, e, a->softmax_scale);
   if (e.cap > 0.f) set_cap(p, e, a->softmax_scale);
   const FwdPlan plan = bias ? FwdPlan{fwd_qrows_per_block(), 1, 0} : fwd_plan(a);
@@ -662,6 +698,7 @@ static int fwd_impl(const rfa_fwd_args* a, const rfa_ext_args* ext, int Dv, void
   p.persist_grid = (plan.persist && rows == 256 && ns <= 1 && plan.ns <= 1) ? device_cus() : 0;
   if (a->fwd_form < RFA_FWD_AUTO || a->fwd_form > RFA_FWD_P8x32 || a->fwd_form == RFA_FWD_RETIRED_2) return RFA_ERR_ARGS;
   if (Dv) return launch_status(launch_fwd_vd(p, Dv, a->dtype, (hipStream_t)stream));
+  if (rr != nullptr) return launch_status(launch_fwd_rr(p, *rr, a->dtype, (hipStream_t)stream));
   if (a->D > kHeadDim) return launch_status(launch_fwd_big(p, a->dtype, (hipStream_t)stream));
   if (int rc2 = launch_fwd(p, a->dtype, (hipStream_t)stream)) return launch_status(rc2);
   if (ns > 1 && launch_combine(cb, a->dtype, (hipStream_t)stream)) return RFA_ERR_LAUNCH;
@@ -1035,7 +1072,22 @@ int rfa_bwd(const rfa_bwd_args* a, void* stream) { return rfa_bwd_ex(a, nullptr,
 
 // Dv = 0: one head dim (rfa_bwd, rfa_bwd_ex); else the V head dim of rfa_bwd_vd — the same plan, workspace layout (dV in D-wide
 // slots, Dv of them used) and dS hand-off, with the dK + dV and 7-GEMM dQ kernels of rfa_vdim.hip
-static int bwd_impl(const rfa_bwd_args* a, const rfa_ext_args* ext, int Dv, void* stream);
+static int bwd_impl(const rfa_bwd_args* a, const rfa_ext_args* ext, int Dv, void* stream, const RowRangeParams* rr = nullptr);
+int64_t rfa_rowrange_workspace_bytes(const rfa_bwd_args* a) {
+  if (!a || a->B <= 0 || a->Sq <= 0) return 0;
+  return (int64_t)a->B * ((a->Sq + kRrTileRows - 1) / kRrTileRows) * (int64_t)sizeof(int2);
+}
+int rfa_bwd_rr(const rfa_bwd_args* a, const rfa_rowrange_args* rr, void* stream) {
+  if (!a) return RFA_ERR_NULL;
+  RowRangeParams r;
+  if (int rc = parse_rr(rr, &r)) return rc;
+  if (int rc = rr_base_check(a->dropout_p, a->cu_seqlens_q, a->cu_seqlens_k, a->q_half, a->k_half)) return rc;
+  // the ranged kernels are the 128-key dK/dV and the 7-GEMM dQ, and the base arguments must say so (as for rfa_bwd_ex)
+  if (a->ds_scratch != nullptr || a->dkdv_form != RFA_DKDV_128) return RFA_ERR_ARGS;
+  if (int rc = rr_dim_check(a->D, r)) return rc;
+  r.ntile_q = a->Sq > 0 ? (a->Sq + kRrTileRows - 1) / kRrTileRows : 0;
+  return bwd_impl(a, nullptr, 0, stream, &r);
+}
 int rfa_bwd_ex(const rfa_bwd_args* a, const rfa_ext_args* ext, void* stream) { return bwd_impl(a, ext, 0, stream); }
 int rfa_bwd_vd(const rfa_bwd_args* a, const rfa_vdim_args* vd, void* stream) {
   if (!a) return RFA_ERR_NULL;
@@ -1044,7 +1096,7 @@ int rfa_bwd_vd(const rfa_bwd_args* a, const rfa_vdim_args* vd, void* stream) {
   return bwd_impl(a, nullptr, Dv, stream);
 }
 
-static int bwd_impl(const rfa_bwd_args* a, const rfa_ext_args* ext, int Dv, void* stream) {
+static int bwd_impl(const rfa_bwd_args* a, const rfa_ext_args* ext, int Dv, void* stream, const RowRangeParams* rr) {
   if (!a) return RFA_ERR_NULL;
   Ext e;
   if (int rce = parse_ext(ext, &e)) return rce;
@@ -1099,6 +1151,10 @@ static int bwd_impl(const rfa_bwd_args* a, const rfa_ext_args* ext, int Dv, void
   if (!a->dk_acc && (!aligned16(a->dk) || !aligned16(a->dv) || !stride_ok(a->dk_st, 2) || !stride_ok(a->dv_st, 2)))
     return RFA_ERR_ALIGN;
 
+  if (rr != nullptr) {
+    if (!rr->start || !rr->end || !rr->tile_bounds) return RFA_ERR_NULL;
+    if (!aligned16(rr->tile_bounds)) return RFA_ERR_ALIGN;
+  }
   hipStream_t st = (hipStream_t)stream;
   BwdParams p{};
   p.dout = a->dout; p.q = a->q; p.k = a->k; p.v = a->v; p.lse = a->lse; p.delta = a->delta;
@@ -1221,10 +1277,10 @@ static int bwd_impl(const rfa_bwd_args* a, const rfa_ext_args* ext, int Dv, void
       mark(2);
     } else {
       if (!(a->phases & RFA_BWD_SKIP_DQ))
-        if (int rc2 = Dv ? launch_bwd_dq_vd(p, Dv, a->dtype, st) : launch_bwd_dq(p, a->dtype, st)) return launch_status(rc2);
+        if (int rc2 = Dv ? launch_bwd_dq_vd(p, Dv, a->dtype, st) : rr ? launch_bwd_dq_rr(p, *rr, a->dtype, st) : launch_bwd_dq(p, a->dtype, st)) return launch_status(rc2);
       mark(1);
       if (!(a->phases & RFA_BWD_SKIP_DKDV))
-        if (int rc2 = Dv ? launch_bwd_dkdv_vd(p, Dv, a->dtype, st) : launch_bwd_dkdv(p, a->dtype, st)) return launch_status(rc2);
+        if (int rc2 = Dv ? launch_bwd_dkdv_vd(p, Dv, a->dtype, st) : rr ? launch_bwd_dkdv_rr(p, *rr, a->dtype, st) : launch_bwd_dkdv(p, a->dtype, st)) return launch_status(rc2);
       mark(2);
     }
   } else {

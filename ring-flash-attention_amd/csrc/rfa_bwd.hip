@@ -96,8 +96,11 @@ template <int kD> constexpr int dq_smem() { return 4 * kDqKV * HeadGeo<kD>::kRow
 // kCap: logit soft-capping (rfa.h: rfa_ext_args.softcap) — t = tanh(softmax_scale s / softcap) by the forward's expression
 // (rfa_common.hpp: cap_tanh), dP - delta takes the factor 1 - t^2 BEFORE the exponential overwrites s, then P = exp2(t c - lse
 // log2 e) with softcap's exponent constant: no register lives across the GEMMs.  With or without a window; no dropout, no bias.
-template <typename T, int kD, bool kFullD, bool kWin, bool kDrop = false, bool kBias = false, bool kCap = false>
-__global__ __launch_bounds__(kDqThreads, 2) void dq_kernel(const BwdParams p) {
+// kRng: per-row key ranges (rfa.h: rfa_rowrange_args; rfa_rowrange.h), as in the forward — the lane's two bounds intersect the
+// band's in the mask, the workgroup's tile range is cut to the (min lo, max hi) of its rows.  The windowed instances only.
+template <typename T, int kD, bool kFullD, bool kWin, bool kDrop = false, bool kBias = false, bool kCap = false, bool kRng = false>
+__global__ __launch_bounds__(kDqThreads, 2) void dq_kernel(const std::conditional_t<kRng, BwdParamsRr, BwdParams> p) {
+  static_assert(!kRng || (kWin && !kDrop && !kBias && !kCap), "row ranges: the windowed instances");
   static_assert(!kBias || (!kWin && !kDrop), "ALiBi: the instances without a window or dropout");
   static_assert(!kCap || (!kDrop && !kBias), "soft-capping: the instances without dropout or bias");
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -163,10 +166,30 @@ __global__ __launch_bounds__(kDqThreads, 2) void dq_kernel(const BwdParams p) {
   const bool hi = kWin ? p.wr >= 0 : p.causal != 0;
   const bool lo = kWin && p.wl >= 0;
   const int wr = kWin ? p.wr : 0, wl = kWin ? p.wl : 0;
+  // kRng: this lane's row bounds, the wave's and the workgroup's (min lo, max hi) — ahead of the tile range below, which
+  // they cut: tiles outside every row's range are neither loaded nor computed; nothing visible at all (rr_tiles): the
+  // existing empty path.  (The exchange uses the tail of V stage 1, which nothing fills before the prologue's barrier.)
+  int rr_lo = 0, rr_hi = 0, rr_wg_lo = 0, rr_wg_hi = 0;
+  RrWave rr_w{};
+  if constexpr (kRng) {
+    const int64_t ri = (int64_t)b * p.rr.bstride + arow;
+    const RrRow rw = rr_row(p.rr.start[ri], p.rr.end[ri], p.rr.k_pos0, lk);
+    rr_lo = rw.lo;
+    rr_hi = rw.hi;
+    rr_w = rr_wave(rr_lo, rr_hi);
+    rr_workgroup(rr_w, wave, lane, kDqWaves, (volatile int*)(smem_raw + dq_smem<kD>() - 64), rr_wg_lo, rr_wg_hi);
+    const int bmax = (hi && qend + off + wr < lk) ? qend + off + wr : lk;
+    if (rr_tiles(lo ? qwg0 + off - wl : 0, bmax, rr_wg_lo, rr_wg_hi, kDqKV, 2).ntiles == 0) {
+      rr_wg_lo = kRrNoLo;
+      rr_wg_hi = 0;
+    }
+  }
   int kmax = lk;
   if (hi && qend + off + wr < kmax) kmax = qend + off + wr;
+  if (kRng && rr_wg_hi < kmax) kmax = rr_wg_hi;          // (the rows' ranges cut the band's key range on both sides)
   const int ntiles = kmax > 0 ? (kmax + kDqKV - 1) / kDqKV : 0;
   int kmin = lo ? qwg0 + off - wl : 0;
+  if (kRng && rr_wg_lo > kmin) kmin = rr_wg_lo;
   kmin = kmin > 0 ? (kmin < lk ? kmin : lk) : 0;          // (a shifted band may start behind the last key)
   const int jt0 = (kmin / kDqKV) & ~1;                  // first tile (even: LDS stage = j & 1)
   // rows wholly outside the band (a block of a longer sequence: p.shift) add nothing to dq_acc: no tile, no store
@@ -277,12 +300,17 @@ __global__ __launch_bounds__(kDqThreads, 2) void dq_kernel(const BwdParams p) {
     if (j + 1 < ntiles) load_tile(j + 1, next_t{});
     const int kt0 = j * kDqKV;
     const bool active = (qw0 < lq) && !(hi && kt0 > qw0 + 31 + off + wr) &&
-                        !(lo && kt0 + kDqKV - 1 < qw0 + off - wl);
+                        !(lo && kt0 + kDqKV - 1 < qw0 + off - wl) && (!kRng || (kt0 < rr_w.hi && kt0 + kDqKV > rr_w.lo));
     if (active) {
       const bool need_mask = (kt0 + kDqKV > lk) || (hi && kt0 + kDqKV - 1 > qw0 + off + wr) ||
                              (lo && kt0 < qw0 + 31 + off - wl);
-      const int lim = hi ? ((qrow + off + wr < lk - 1) ? qrow + off + wr : lk - 1) : lk - 1;
-      const int lim_lo = lo ? qrow + off - wl : -0x40000000;
+      // (kRng: a tile inside every row's range needs no predicate either; a ternary on the flag, so that the other
+      //  instances' code is the code of before)
+      const bool need_mask_r = kRng ? (need_mask || kt0 < rr_w.mlo || kt0 + kDqKV > rr_w.mhi) : need_mask;
+      const int lim_b = hi ? ((qrow + off + wr < lk - 1) ? qrow + off + wr : lk - 1) : lk - 1;
+      const int lim_lo_b = lo ? qrow + off - wl : -0x40000000;
+      const int lim = (kRng && rr_hi - 1 < lim_b) ? rr_hi - 1 : lim_b;
+      const int lim_lo = (kRng && rr_lo > lim_lo_b) ? rr_lo : lim_lo_b;
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         f32x16 s, dp;
@@ -327,7 +355,7 @@ __global__ __launch_bounds__(kDqThreads, 2) void dq_kernel(const BwdParams p) {
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) s[r] = fast_exp2(__builtin_fmaf(s[r], c, -L2));
-        if (need_mask) {
+        if (need_mask_r) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             const int key = kt0 + 32 * t + crow(r, g);
@@ -431,8 +459,8 @@ constexpr int kKvThreads = kKvWaves * 64;
 constexpr int kKvKeys = 128;                       // keys / workgroup
 constexpr int kKvQ = 64;                           // query rows per tile (2 sub-tiles of 32)
 constexpr int kKvStatBytes = 2 * kKvQ * 4;         // lse[64] + delta[64] per stage
-template <int kD> constexpr int kv_smem() {        // 129 KiB (65 KiB at kD = 64)
-  return 2 * kKvKeys * HeadGeo<kD>::kRowBytes + 4 * kKvQ * HeadGeo<kD>::kRowBytes + 2 * kKvStatBytes;
+template <int kD, bool kRng = false> constexpr int kv_smem() {        // 129 KiB (65 KiB at kD = 64); kRng: + the rows' bounds
+  return 2 * kKvKeys * HeadGeo<kD>::kRowBytes + 4 * kKvQ * HeadGeo<kD>::kRowBytes + (kRng ? 4 : 2) * kKvStatBytes;
 }
 
 // kD: compiled head dim (128 / 64); kFullD: D == kD (LDS-DMA staging) else zero padded (register staging);
@@ -454,8 +482,14 @@ template <int kD> constexpr int kv_smem() {        // 129 KiB (65 KiB at kD = 64
 // kCap: logit soft-capping, as in dq_kernel (the 128-key instances with or without a window; dp is dO V^T - delta when the
 // factor 1 - t^2 is applied)
 template <typename T, int kD, bool kFullD, bool kSpill, bool kWin, bool kWide, bool kDrop = false, bool kBal = false, bool kMap = false,
-          bool kBias = false, bool kCap = false>
-__global__ __launch_bounds__(kKvThreads, 2) void dkdv_kernel(const BwdParams p) {
+          bool kBias = false, bool kCap = false, bool kRng = false>
+__global__ __launch_bounds__(kKvThreads, 2) void dkdv_kernel(const std::conditional_t<kRng, BwdParamsRr, BwdParams> p) {
+  // kRng: per-row key ranges (rfa.h: rfa_rowrange_args; rfa_rowrange.h).  This kernel owns keys: the rows' bounds of a Q/dO
+  // tile travel like lse and delta (waves 2 and 3 stage them, rebased and clamped, behind the two statistics) and enter the
+  // mask; the tile walk visits only the tiles whose (min lo, max hi) pair — p.rr.tile_bounds, made by rowrange_bounds_kernel —
+  // touches the workgroup's key block.  The windowed 128-key instances only.
+  static_assert(!kRng || (kWin && !kSpill && !kWide && !kDrop && !kBias && !kCap), "row ranges: the windowed 128-key instances");
+  constexpr int kStatBytes = kRng ? 2 * kKvStatBytes : kKvStatBytes;     // per stage: lse[64] delta[64] (kRng: + lo[64] hi[64])
   static_assert(!kBias || (!kSpill && !kWin && !kWide && !kDrop), "ALiBi: the plain 128-key instances");
   static_assert(!kCap || (!kSpill && !kWide && !kDrop && !kBias), "soft-capping: the 128-key instances without dS spill, dropout or bias");
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -579,6 +613,44 @@ __global__ __launch_bounds__(kKvThreads, 2) void dkdv_kernel(const BwdParams p) 
   // time and the L2 serves a Q/dO tile to all of them (contiguous halves: 2.4x the HBM fetch, measured).
   int jtop = jt1 - 1 - qsplit;
   int ntile_q = jtop >= jt0 ? (jtop - jt0) / nsplit + 1 : 0;
+  // kRng: of the band's tiles jt0 .. jt1 - 1 only those whose rows' (min lo, max hi) touches this key block are visited —
+  // counted here (64 tiles per ballot), walked from the highest down with rr_prev()
+  const int2* rr_tb = nullptr;
+  int rr_bot = jt0;                                    // the lowest visited tile: rr_prev() never scans below it
+  if constexpr (kRng) {
+    rr_tb = p.rr.tile_bounds + (int64_t)b * p.rr.ntile_q;
+    int cnt = 0, top = -1, bot = jt1;
+    for (int j0 = jt0; j0 < jt1; j0 += 64) {
+      const int jj = j0 + lane;
+      bool t = false;
+      if (jj < jt1) {
+        const int2 pr = rr_tb[jj];
+        t = rr_touches(pr.x, pr.y, kwg0, kKeys);
+      }
+      const unsigned long long m = __ballot(t);
+      if (m) {
+        cnt += __popcll(m);
+        top = j0 + 63 - __clzll(m);
+        if (bot == jt1) bot = j0 + __ffsll((long long)m) - 1;
+      }
+    }
+    jtop = __builtin_amdgcn_readfirstlane(top);
+    ntile_q = __builtin_amdgcn_readfirstlane(cnt);
+    rr_bot = __builtin_amdgcn_readfirstlane(bot);
+  }
+  auto rr_prev = [&](int jj) {                         // the next visited tile below jj (below rr_bot: none left)
+    if constexpr (kRng) {
+      int2 pr;
+      do {
+        --jj;
+        if (jj < rr_bot) break;
+        pr = rr_tb[jj];
+      } while (!rr_touches(pr.x, pr.y, kwg0, kKeys));
+      return jj;
+    } else {
+      return jj - nsplit;
+    }
+  };
   // kBal: w_n1 tiles from jtop downward, then (type A) upward from w_j2
   int w_n1 = 0x7fffffff, w_j2 = 0;
   if (kBal) {
@@ -663,7 +735,13 @@ __global__ __launch_bounds__(kKvThreads, 2) void dkdv_kernel(const BwdParams p) 
   // below), all in front of the tile's first fragment read, in BOTH waves of a SIMD at once behind the barrier.
   const int64_t q_tile_e = (int64_t)kKvQ * p.q_st.row, do_tile_e = (int64_t)kKvQ * p.dout_st.row;
   const float* st_base0 = wave ? dltbase0 : lsebase0;  // (wave 0 stages lse, wave 1 delta)
-  const int64_t st_head_e = wave ? p.delta_head : p.lse_head;
+  int64_t st_head_e = wave ? p.delta_head : p.lse_head;
+  if constexpr (kRng) {                                // (waves 2 / 3: the rows' start / end — per batch entry, the same for every head)
+    if (wave >= 2) {
+      st_base0 = (const float*)((wave == 2 ? p.rr.start : p.rr.end) + (int64_t)b * p.rr.bstride + qs.row0);
+      st_head_e = 0;
+    }
+  }
   const T* ld_q = qbase0 + ld_j * q_tile_e;
   const T* ld_do = dobase0 + ld_j * do_tile_e;
   const float* ld_st = st_base0 + ld_j * kKvQ;
@@ -678,7 +756,7 @@ __global__ __launch_bounds__(kKvThreads, 2) void dkdv_kernel(const BwdParams p) 
         ++ld_c;
         ld_j = ld_c == w_n1 ? w_j2 : (ld_c < w_n1 ? ld_j - 1 : ld_j + 1);
       } else {
-        ld_j -= nsplit;
+        ld_j = rr_prev(ld_j);
       }
       ld_q = qbase0 + ld_j * q_tile_e;
       ld_do = dobase0 + ld_j * do_tile_e;
@@ -711,7 +789,7 @@ __global__ __launch_bounds__(kKvThreads, 2) void dkdv_kernel(const BwdParams p) 
         }
       }
     }
-    if (wave < 2) {                            // wave 0 stages lse, wave 1 delta (wave-uniform descriptor)
+    if (wave < (kRng ? 4 : 2)) {               // wave 0 stages lse, wave 1 delta (wave-uniform descriptor); kRng: 2 / 3 the bounds
       // asynchronous like the tile DMA (counted by the wait in front of write_tile): a compiler-tracked load
       // would be protected with vmcnt(0) at its use and drain the dS spill stores issued after it every tile
       const dma_rsrc_t rs = make_dma_rsrc(sttile, rows > 0 ? rows * 4 : 0);
@@ -730,6 +808,10 @@ __global__ __launch_bounds__(kKvThreads, 2) void dkdv_kernel(const BwdParams p) 
       }
     }
     if (tid < 2 * kKvQ) *(__attribute__((address_space(3))) float*)lds_ptr(ws) = statreg * stat_scale;
+    if constexpr (kRng) {                      // the bounds as integers, block-relative and clamped (rows past the end: 0, 0)
+      if (tid >= 2 * kKvQ && tid < 4 * kKvQ)
+        *(__attribute__((address_space(3))) int*)lds_ptr(ws) = rr_rel(__builtin_bit_cast(int, statreg), p.rr.k_pos0, lk);
+    }
   };
 
   // Fragment addresses: the swizzle makes chunk selection an XOR on address bits 4..7, so a fragment's
@@ -788,7 +870,7 @@ __global__ __launch_bounds__(kKvThreads, 2) void dkdv_kernel(const BwdParams p) 
   load_landed(statreg);
   write_tile();
   wq ^= kKvTileBytes;
-  ws ^= kKvStatBytes;
+  ws ^= kStatBytes;
   __syncthreads();
 
 #if RFA_KV_PRIO == 1
@@ -836,8 +918,8 @@ __global__ __launch_bounds__(kKvThreads, 2) void dkdv_kernel(const BwdParams p) 
       {
         // dP - delta = dO V_w^T (+ init; V_w fragments from LDS) then S = Q K_w^T (K_w in registers):
         // 2 kNK MFMAs, LDS operands read kAhead steps ahead
-        // (the zero-padded 128-wide ALiBi and soft-capping instances read one pair less ahead: they hold their staging registers on top of a full file)
-        constexpr int kAhead = ((kBias || kCap) && !kFullD && kD == 128) ? RFA_KV_AHEAD - 1 : RFA_KV_AHEAD;
+        // (the zero-padded 128-wide ALiBi, soft-capping and row-range instances read one pair less ahead: they hold their staging registers on top of a full file)
+        constexpr int kAhead = ((kBias || kCap || kRng) && !kFullD && kD == 128) ? RFA_KV_AHEAD - 1 : RFA_KV_AHEAD;
         constexpr int kN = 2 * kNK;
         vec8<T> a[kN], w[kNK];
         auto fa = [&](int i) {
@@ -913,6 +995,17 @@ __global__ __launch_bounds__(kKvThreads, 2) void dkdv_kernel(const BwdParams p) 
           s[r] = ok ? s[r] : 0.f;
         }
       }
+      if constexpr (kRng) {
+        // this lane's key against the bounds of the sub-tile's rows 8 jj + 4 g + e (read like lse above: 4 rows per access)
+        const int krow_m = mask_kg + mask_g4;
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) {
+          const i32x4 lo4 = *(__attribute__((address_space(3))) i32x4*)(lds_ptr(sa) + (2 * kKvQ + 8 * jj) * 4 + soff_t);
+          const i32x4 hi4 = *(__attribute__((address_space(3))) i32x4*)(lds_ptr(sa) + (3 * kKvQ + 8 * jj) * 4 + soff_t);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) s[4 * jj + e] = (krow_m >= lo4[e] && krow_m < hi4[e]) ? s[4 * jj + e] : 0.f;
+        }
+      }
       if (kDrop) {
         // dp holds dO V^T - delta (it was initialised with -delta).  With dropout
         //     dP = keep ? (dO V^T) / (1 - p) : 0,   dS = P (dP - delta),   dV takes keep ? P / (1 - p) : 0
@@ -966,7 +1059,7 @@ __global__ __launch_bounds__(kKvThreads, 2) void dkdv_kernel(const BwdParams p) 
         };
         if (RFA_SPILL_PROBE != 2) spill();
         if (RFA_KV_PRIO == 4 || RFA_KV_PRIO == 5) __builtin_amdgcn_s_setprio(1);
-        constexpr int kAhead = ((kBias || kCap) && !kFullD && kD == 128) ? RFA_KV_AHEAD2 - 1 : RFA_KV_AHEAD2;
+        constexpr int kAhead = ((kBias || kCap || kRng) && !kFullD && kD == 128) ? RFA_KV_AHEAD2 - 1 : RFA_KV_AHEAD2;
         constexpr int kN2 = 4 * kNB;                   // [ks2][which: 0 = dO^T (dV), 1 = Q^T (dK)][dblk]
         vec8<T> a[kN2];
         auto frag = [&](int i) {
@@ -1029,7 +1122,7 @@ __global__ __launch_bounds__(kKvThreads, 2) void dkdv_kernel(const BwdParams p) 
         ++jc;
         j = jc == w_n1 ? w_j2 : (jc < w_n1 ? j - 1 : j + 1);
       } else {
-        j -= nsplit;
+        j = rr_prev(j);
       }
       if (kSpill) {
         ds_roff0 = (int)ds_rowpart(p, 2 * j, ds_g0, ds_nkb);
@@ -1045,9 +1138,9 @@ __global__ __launch_bounds__(kKvThreads, 2) void dkdv_kernel(const BwdParams p) 
       tq[kv][0] ^= kKvTileBytes;
       tq[kv][1] ^= kKvTileBytes;
     }
-    sa ^= kKvStatBytes;
+    sa ^= kStatBytes;
     wq ^= kKvTileBytes;
-    ws ^= kKvStatBytes;
+    ws ^= kStatBytes;
     if (RFA_KV_X_SYNC) __syncthreads();
   }
 
@@ -1207,13 +1300,13 @@ __global__ __launch_bounds__(kKvThreads, 2) void dkdv_kernel(const BwdParams p) 
   }   // segment loop
 }
 
-template <typename T, int kD, bool kFullD, bool kWin, bool kDrop = false, bool kBias = false, bool kCap = false>
-static int launch_dq_t(const BwdParams& p, hipStream_t stream) {
+template <typename T, int kD, bool kFullD, bool kWin, bool kDrop = false, bool kBias = false, bool kCap = false, bool kRng = false>
+static int launch_dq_t(const std::conditional_t<kRng, BwdParamsRr, BwdParams>& p, hipStream_t stream) {
   static std::atomic<unsigned long long> attr_done{0};
-  if (int rc = opt_in_dynamic_lds((const void*)dq_kernel<T, kD, kFullD, kWin, kDrop, kBias, kCap>, dq_smem<kD>(), attr_done)) return rc;
+  if (int rc = opt_in_dynamic_lds((const void*)dq_kernel<T, kD, kFullD, kWin, kDrop, kBias, kCap, kRng>, dq_smem<kD>(), attr_done)) return rc;
   const int64_t nblocks = (int64_t)p.nqblk * p.H * p.B;
   if (nblocks <= 0) return 0;
-  hipLaunchKernelGGL((dq_kernel<T, kD, kFullD, kWin, kDrop, kBias, kCap>), dim3((unsigned)nblocks), dim3(kDqThreads), dq_smem<kD>(), stream, p);
+  hipLaunchKernelGGL((dq_kernel<T, kD, kFullD, kWin, kDrop, kBias, kCap, kRng>), dim3((unsigned)nblocks), dim3(kDqThreads), dq_smem<kD>(), stream, p);
   return hipGetLastError() == hipSuccess ? kLaunchOk : kLaunchFailed;
 }
 
@@ -1223,10 +1316,10 @@ __global__ void zero_words_kernel(unsigned* w, int n) {
 }
 
 template <typename T, int kD, bool kFullD, bool kSpill, bool kWin, bool kWide = false, bool kDrop = false, bool kBal = false, bool kMap = false,
-          bool kBias = false, bool kCap = false>
-static int launch_dkdv_t(const BwdParams& p, hipStream_t stream) {
+          bool kBias = false, bool kCap = false, bool kRng = false>
+static int launch_dkdv_t(const std::conditional_t<kRng, BwdParamsRr, BwdParams>& p, hipStream_t stream) {
   static std::atomic<unsigned long long> attr_done{0};
-  if (int rc = opt_in_dynamic_lds((const void*)dkdv_kernel<T, kD, kFullD, kSpill, kWin, kWide, kDrop, kBal, kMap, kBias, kCap>, kv_smem<kD>(), attr_done)) return rc;
+  if (int rc = opt_in_dynamic_lds((const void*)dkdv_kernel<T, kD, kFullD, kSpill, kWin, kWide, kDrop, kBal, kMap, kBias, kCap, kRng>, kv_smem<kD, kRng>(), attr_done)) return rc;
   // one workgroup per (key block, K/V head) [x tile-range split of the 256-key form]
   const int64_t nblocks = (int64_t)p.nkblk * p.Hk * p.B * ((kWide && !kBal) ? p.nsplit : 1);
   if (nblocks <= 0) return 0;
@@ -1238,8 +1331,54 @@ static int launch_dkdv_t(const BwdParams& p, hipStream_t stream) {
     hipLaunchKernelGGL(zero_words_kernel, dim3((unsigned)((nflags + 255) / 256)), dim3(256), 0, stream, p.pair_flags, nflags);
     if (hipGetLastError() != hipSuccess) return kLaunchFailed;
   }
-  hipLaunchKernelGGL((dkdv_kernel<T, kD, kFullD, kSpill, kWin, kWide, kDrop, kBal, kMap, kBias, kCap>), dim3((unsigned)nblocks), dim3(kKvThreads), kv_smem<kD>(), stream, p);
+  hipLaunchKernelGGL((dkdv_kernel<T, kD, kFullD, kSpill, kWin, kWide, kDrop, kBal, kMap, kBias, kCap, kRng>), dim3((unsigned)nblocks), dim3(kKvThreads), (kv_smem<kD, kRng>()), stream, p);
   return hipGetLastError() == hipSuccess ? kLaunchOk : kLaunchFailed;
+}
+
+// ---- per-row key ranges: the tile bounds of the dK/dV kernel and the launchers of the kRng instances --------------------------
+// tile_bounds[b * ntile_q + t] = (min lo, max hi) over the rows 64 t .. 64 t + 63 of batch entry b (rows past the end: none),
+// block-relative (rfa_rowrange.h): what the dK/dV tile walk skips by.  One wave per tile.
+__global__ __launch_bounds__(64) void rowrange_bounds_kernel(const RowRangeParams r, int Sq, int lk) {
+  const int t = blockIdx.x, b = blockIdx.y, lane = threadIdx.x;
+  const int row = t * kRrTileRows + lane;
+  RrRow rw{kRrNoLo, 0};
+  if (row < Sq) rw = rr_row(r.start[(int64_t)b * r.bstride + row], r.end[(int64_t)b * r.bstride + row], r.k_pos0, lk);
+  const RrWave w = rr_wave(rw.lo, rw.hi);
+  if (lane == 0) r.tile_bounds[(int64_t)b * r.ntile_q + t] = make_int2(w.lo, w.hi);
+}
+template <typename T>
+static int launch_dq_rng(const BwdParamsRr& p, hipStream_t stream) {
+  if (p.D == 128) return launch_dq_t<T, 128, true, true, false, false, false, true>(p, stream);
+  if (p.D > 64) return launch_dq_t<T, 128, false, true, false, false, false, true>(p, stream);
+  if (p.D == 64) return launch_dq_t<T, 64, true, true, false, false, false, true>(p, stream);
+  return launch_dq_t<T, 64, false, true, false, false, false, true>(p, stream);
+}
+template <typename T>
+static int launch_dkdv_rng(const BwdParamsRr& p, hipStream_t stream) {
+  if (p.D == 128) return launch_dkdv_t<T, 128, true, false, true, false, false, false, false, false, false, true>(p, stream);
+  if constexpr (kRngPadded128) {
+    if (p.D > 64) return launch_dkdv_t<T, 128, false, false, true, false, false, false, false, false, false, true>(p, stream);
+  } else {
+    if (p.D > 64) return kLaunchFailed;          // (not built: rfa_kernels.hpp; rfa_api.cpp refuses such calls)
+  }
+  if (p.D == 64) return launch_dkdv_t<T, 64, true, false, true, false, false, false, false, false, false, true>(p, stream);
+  return launch_dkdv_t<T, 64, false, false, true, false, false, false, false, false, false, true>(p, stream);
+}
+int launch_bwd_dq_rr(const BwdParams& p, const RowRangeParams& r, int dtype, hipStream_t stream) {
+  BwdParamsRr pr;
+  static_cast<BwdParams&>(pr) = p;
+  pr.rr = r;
+  return dtype == 0 ? launch_dq_rng<bf16_t>(pr, stream) : launch_dq_rng<f16_t>(pr, stream);
+}
+int launch_bwd_dkdv_rr(const BwdParams& p, const RowRangeParams& r, int dtype, hipStream_t stream) {
+  BwdParamsRr pr;
+  static_cast<BwdParams&>(pr) = p;
+  pr.rr = r;
+  if (r.ntile_q > 0 && p.B > 0) {
+    hipLaunchKernelGGL(rowrange_bounds_kernel, dim3((unsigned)r.ntile_q, (unsigned)p.B), dim3(64), 0, stream, r, p.Sq, p.Sk);
+    if (hipGetLastError() != hipSuccess) return kLaunchFailed;
+  }
+  return dtype == 0 ? launch_dkdv_rng<bf16_t>(pr, stream) : launch_dkdv_rng<f16_t>(pr, stream);
 }
 
 template <typename T, bool kWin, bool kDrop>

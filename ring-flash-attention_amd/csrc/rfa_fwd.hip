@@ -95,8 +95,13 @@ template <int kD> constexpr int fwd_smem() { return 2 * kFwdStages * kFwdKV * He
 // of the mask; from there on the scores are in units of softcap (the exponent constant and the lse factor are softcap's
 // instead of softmax_scale's), the row max, the deferred rescale and the merge epilogue are unchanged.  With or without a
 // window; no dropout, no bias.
-template <typename T, int kD, bool kFullD, bool kWin, bool kDrop = false, int kW = kFwdWavesMax, bool kBias = false, bool kCap = false>
-__global__ __launch_bounds__(kW * 64, 2) void fwd_kernel(const FwdParams p) {
+// kRng: per-row key ranges (rfa.h: rfa_rowrange_args; rfa_rowrange.h) — each lane holds its row's two bounds, rebased by k_pos0
+// and clamped to the block; they intersect the band's bounds in the mask, and the workgroup's tile range is cut to the
+// (min lo, max hi) of its rows.  Built on the windowed 256-row instances; no dropout, bias or cap.
+template <typename T, int kD, bool kFullD, bool kWin, bool kDrop = false, int kW = kFwdWavesMax, bool kBias = false, bool kCap = false,
+          bool kRng = false>
+__global__ __launch_bounds__(kW * 64, 2) void fwd_kernel(const std::conditional_t<kRng, FwdParamsRr, FwdParams> p) {
+  static_assert(!kRng || (kWin && !kDrop && !kBias && !kCap && kW == kFwdWavesMax), "row ranges: the windowed 256-row instances");
   static_assert(!kBias || (!kWin && !kDrop), "ALiBi: the instances without a window or dropout");
   static_assert(!kCap || (!kDrop && !kBias && kW == kFwdWavesMax), "soft-capping: the 256-row instances without dropout or bias");
   constexpr int kFwdWaves = kW, kFwdThreads = kW * 64, kFwdQRows = kW * 32;   // (query rows per workgroup)
@@ -173,6 +178,22 @@ __global__ __launch_bounds__(kW * 64, 2) void fwd_kernel(const FwdParams p) {
   int kmin = lo ? qwg0 + off - wl : 0;
   kmin = kmin > 0 ? (kmin < lk ? kmin : lk) : 0;          // (a shifted band may start behind the last key)
   int jt0 = (kmin / kFwdKV) / kFwdStages * kFwdStages;   // first tile (aligned to the LDS ring: stage = j % stages)
+  // kRng: this lane's row bounds, the wave's and the workgroup's; tiles outside every row's range are neither loaded nor
+  // computed (the exchange uses the tail of the last V stage, which nothing fills before the prologue's barrier)
+  int rr_lo = 0, rr_hi = 0;
+  RrWave rr_w{};
+  if constexpr (kRng) {
+    const int64_t ri = (int64_t)b * p.rr.bstride + qs.row0 + qrow_c;
+    const RrRow rw = rr_row(p.rr.start[ri], p.rr.end[ri], p.rr.k_pos0, lk);
+    rr_lo = rw.lo;
+    rr_hi = rw.hi;
+    rr_w = rr_wave(rr_lo, rr_hi);
+    int wg_lo, wg_hi;
+    rr_workgroup(rr_w, wave, lane, kFwdWaves, (volatile int*)(smem_raw + fwd_smem<kD>() - 64), wg_lo, wg_hi);
+    const RrTiles rt = rr_tiles(kmin, kmax, wg_lo, wg_hi, kFwdKV, kFwdStages);
+    jt0 = rt.jt0;
+    ntiles = rt.ntiles;
+  }
   if (nsplit > 1) {
     // this workgroup's contiguous share of the tiles [jt0, ntiles), a multiple of the ring depth long (stage = j % stages)
     int chunk = (ntiles - jt0 + nsplit - 1) / nsplit;
@@ -323,7 +344,7 @@ __global__ __launch_bounds__(kW * 64, 2) void fwd_kernel(const FwdParams p) {
 
     const int kt0 = j * kFwdKV;
     const bool active = (qw0 < lq) && !(hi && kt0 > qw0 + 31 + off + wr) &&
-                        !(lo && kt0 + kFwdKV - 1 < qw0 + off - wl);
+                        !(lo && kt0 + kFwdKV - 1 < qw0 + off - wl) && (!kRng || (kt0 < rr_w.hi && kt0 + kFwdKV > rr_w.lo));
     if (active) {
       // ---------------- S^T = K Q^T ----------------
       f32x16 s[kFwdSub];
@@ -371,10 +392,14 @@ __global__ __launch_bounds__(kW * 64, 2) void fwd_kernel(const FwdParams p) {
       }
       // ---------------- mask ----------------
       const bool need_mask = (kt0 + kFwdKV > lk) || (hi && kt0 + kFwdKV - 1 > qw0 + off + wr) ||
-                             (lo && kt0 < qw0 + 31 + off - wl);
+                             (lo && kt0 < qw0 + 31 + off - wl) || (kRng && (kt0 < rr_w.mlo || kt0 + kFwdKV > rr_w.mhi));
       if (need_mask) {
-        const int lim = hi ? ((qrow + off + wr < lk - 1) ? qrow + off + wr : lk - 1) : lk - 1;
-        const int lim_lo = lo ? qrow + off - wl : -0x40000000;
+        int lim = hi ? ((qrow + off + wr < lk - 1) ? qrow + off + wr : lk - 1) : lk - 1;
+        int lim_lo = lo ? qrow + off - wl : -0x40000000;
+        if (kRng) {
+          lim = lim < rr_hi - 1 ? lim : rr_hi - 1;
+          lim_lo = lim_lo > rr_lo ? lim_lo : rr_lo;
+        }
 #pragma unroll
         for (int t = 0; t < kFwdSub; ++t)
 #pragma unroll
@@ -932,13 +957,14 @@ static int launch_fwd_persist(const FwdParams& p, hipStream_t stream) {
   return hipGetLastError() == hipSuccess ? kLaunchOk : kLaunchFailed;
 }
 
-template <typename T, int kD, bool kFullD, bool kWin, bool kDrop = false, int kW = kFwdWavesMax, bool kBias = false, bool kCap = false>
-static int launch_fwd_w(const FwdParams& p, hipStream_t stream) {
+template <typename T, int kD, bool kFullD, bool kWin, bool kDrop = false, int kW = kFwdWavesMax, bool kBias = false, bool kCap = false,
+          bool kRng = false>
+static int launch_fwd_w(const std::conditional_t<kRng, FwdParamsRr, FwdParams>& p, hipStream_t stream) {
   static std::atomic<unsigned long long> attr_done{0};
-  if (int rc = opt_in_dynamic_lds((const void*)fwd_kernel<T, kD, kFullD, kWin, kDrop, kW, kBias, kCap>, fwd_smem<kD>(), attr_done)) return rc;
+  if (int rc = opt_in_dynamic_lds((const void*)fwd_kernel<T, kD, kFullD, kWin, kDrop, kW, kBias, kCap, kRng>, fwd_smem<kD>(), attr_done)) return rc;
   const int64_t nblocks = (int64_t)p.nqblk * p.H * p.B * (p.kv_nsplit > 1 ? p.kv_nsplit : 1);
   if (nblocks <= 0) return 0;
-  hipLaunchKernelGGL((fwd_kernel<T, kD, kFullD, kWin, kDrop, kW, kBias, kCap>), dim3((unsigned)nblocks), dim3(kW * 64), fwd_smem<kD>(), stream, p);
+  hipLaunchKernelGGL((fwd_kernel<T, kD, kFullD, kWin, kDrop, kW, kBias, kCap, kRng>), dim3((unsigned)nblocks), dim3(kW * 64), fwd_smem<kD>(), stream, p);
   return hipGetLastError() == hipSuccess ? kLaunchOk : kLaunchFailed;
 }
 template <typename T, int kD, bool kFullD, bool kWin, bool kDrop = false>
@@ -980,6 +1006,22 @@ static int launch_fwd_cap(const FwdParams& p, hipStream_t stream) {
   if (p.D > 64) return launch_fwd_w<T, 128, false, kWin, false, kFwdWavesMax, false, true>(p, stream);
   if (p.D == 64) return launch_fwd_w<T, 64, true, kWin, false, kFwdWavesMax, false, true>(p, stream);
   return launch_fwd_w<T, 64, false, kWin, false, kFwdWavesMax, false, true>(p, stream);
+}
+
+// per-row key ranges (rfa_api.cpp: dense input, head dim <= 128, no dropout, the 256-row form): the windowed instances with
+// kRng — 128 and 64 full, every other head dim through the zero-padded 128- / 64-wide layouts
+template <typename T>
+static int launch_fwd_rng(const FwdParamsRr& p, hipStream_t stream) {
+  if (p.D == 128) return launch_fwd_w<T, 128, true, true, false, kFwdWavesMax, false, false, true>(p, stream);
+  if (p.D > 64) return launch_fwd_w<T, 128, false, true, false, kFwdWavesMax, false, false, true>(p, stream);
+  if (p.D == 64) return launch_fwd_w<T, 64, true, true, false, kFwdWavesMax, false, false, true>(p, stream);
+  return launch_fwd_w<T, 64, false, true, false, kFwdWavesMax, false, false, true>(p, stream);
+}
+int launch_fwd_rr(const FwdParams& p, const RowRangeParams& r, int dtype, hipStream_t stream) {
+  FwdParamsRr pr;
+  static_cast<FwdParams&>(pr) = p;
+  pr.rr = r;
+  return dtype == 0 ? launch_fwd_rng<bf16_t>(pr, stream) : launch_fwd_rng<f16_t>(pr, stream);
 }
 
 int launch_fwd(const FwdParams& p, int dtype, hipStream_t stream) {

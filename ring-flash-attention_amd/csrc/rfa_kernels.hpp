@@ -5,6 +5,7 @@
 #include "rfa_common.hpp"
 #include "rfa_seqhead_index.h"
 #include "rfa_maxlogit_band.h"
+#include "rfa_rowrange.h"
 
 #include <atomic>
 
@@ -289,6 +290,28 @@ struct BwdParamsVd {
 int launch_fwd_vd(const FwdParams& p, int Dv, int dtype, hipStream_t stream);
 int launch_bwd_dq_vd(const BwdParams& p, int Dv, int dtype, hipStream_t stream);
 int launch_bwd_dkdv_vd(const BwdParams& p, int Dv, int dtype, hipStream_t stream);
+
+// per-row key ranges (rfa.h: rfa_rowrange_args; arithmetic: rfa_rowrange.h): the kRng instances of the 8 x 32 forward, the
+// 7-GEMM dQ kernel and the 128-key dK/dV kernel take the block above with this one behind it — the blocks above stay as they
+// are, and with them the kernarg of every other kernel.  Dense input, head dims <= 128, built on the windowed instances.
+struct RowRangeParams {
+  const int32_t *start, *end;   // (B, Sq) global key positions, row stride 1
+  int64_t bstride;              // batch stride of both, in elements
+  int64_t k_pos0;               // global position of the block's key row 0
+  int2* tile_bounds;            // dK/dV only: (min lo, max hi), block-relative, per (batch, 64-row query tile)
+  int ntile_q;                  // query tiles per batch entry in tile_bounds
+};
+struct FwdParamsRr : FwdParams {
+  RowRangeParams rr;
+};
+struct BwdParamsRr : BwdParams {
+  RowRangeParams rr;
+};
+constexpr int kRrTileRows = 64;                // query rows per entry of tile_bounds: the dK/dV kernel's Q/dO tile
+constexpr bool kRngPadded128 = true;           // the zero-padded 128-wide dK/dV instance (head dims 65 .. 127) is built
+int launch_fwd_rr(const FwdParams& p, const RowRangeParams& r, int dtype, hipStream_t stream);
+int launch_bwd_dq_rr(const BwdParams& p, const RowRangeParams& r, int dtype, hipStream_t stream);
+int launch_bwd_dkdv_rr(const BwdParams& p, const RowRangeParams& r, int dtype, hipStream_t stream);   // (fills tile_bounds first)
 
 int launch_preprocess(const PreParams& p, int dtype, hipStream_t stream);
 // soft cap + bounded window at head dims 65 .. 127: the zero-padded 128-wide dK/dV instance with both flags needs 40 bytes of

@@ -286,6 +286,22 @@ class VdimArgs(C.Structure):
             self.struct_bytes = C.sizeof(VdimArgs)
 
 
+class RowRangeArgs(C.Structure):
+    """rfa_rowrange_args: per-row key ranges of a block call (start / end: int32 (B, Sq) global key positions, k_pos0: the
+    global position of the block's key row 0, tile_bounds: the backward's workspace); struct_bytes is filled in here"""
+    _fields_ = [
+        ("struct_bytes", C.c_uint32), ("reserved", C.c_uint32),
+        ("start", C.c_void_p), ("end", C.c_void_p),
+        ("batch_stride", C.c_int64), ("k_pos0", C.c_int64),
+        ("tile_bounds", C.c_void_p),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if not self.struct_bytes:
+            self.struct_bytes = C.sizeof(RowRangeArgs)
+
+
 # every symbol include/rfa.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "rfa_abi_version": (C.c_int, []),
@@ -323,6 +339,9 @@ SYMBOLS = {
     "rfa_merge_pair_bwd": (C.c_int, [C.POINTER(MergePairBwdArgs), C.c_void_p]),
     "rfa_fwd_vd": (C.c_int, [C.POINTER(FwdArgs), C.POINTER(VdimArgs), C.c_void_p]),
     "rfa_bwd_vd": (C.c_int, [C.POINTER(BwdArgs), C.POINTER(VdimArgs), C.c_void_p]),
+    "rfa_fwd_rr": (C.c_int, [C.POINTER(FwdArgs), C.POINTER(RowRangeArgs), C.c_void_p]),
+    "rfa_bwd_rr": (C.c_int, [C.POINTER(BwdArgs), C.POINTER(RowRangeArgs), C.c_void_p]),
+    "rfa_rowrange_workspace_bytes": (C.c_int64, [C.POINTER(BwdArgs)]),
 }
 
 _lib = None
@@ -371,6 +390,10 @@ def load():
     for name in ("rfa_fwd_vd", "rfa_bwd_vd"):
         if not hasattr(lib, name):
             raise RuntimeError(f"ring_flash_attn: librfa_hip.so has no {name} (the value-head-dim entry points); rebuild")
+    # ... and the pair with per-row key ranges (a struct of its own)
+    for name in ("rfa_fwd_rr", "rfa_bwd_rr", "rfa_rowrange_workspace_bytes"):
+        if not hasattr(lib, name):
+            raise RuntimeError(f"ring_flash_attn: librfa_hip.so has no {name} (the row-range entry points); rebuild")
     for name, (res, args) in SYMBOLS.items():
         fn = getattr(lib, name)  # AttributeError if the .so is stale
         fn.restype = res

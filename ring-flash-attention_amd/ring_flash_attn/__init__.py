@@ -69,6 +69,9 @@ from ._api import with_max_logit
 # handle by which attention over two key sets composes, backward included; merge_attn(out_a, lse_a, out_b, lse_b) is that
 # composition as one fused, differentiable kernel each way (replicated prefix / global tokens next to a sharded sequence)
 from ._api import merge_attn, with_lse_grad
+# per-row key ranges (interval masks: documents on dense input, prefix-LM, shared prefixes): with_row_ranges(func, start, end)
+# lets query row i see the keys start[i] <= j < end[i] (global positions) in the dense ring and zigzag functions
+from ._api import with_row_ranges
 # DeepSpeed-Ulysses head parallelism in front of the dense schedules ("USP"): with_ulysses(func, ulysses_group) exchanges heads
 # for rows around `func`; make_usp_groups(func, ulysses_size) makes the (Ulysses, ring) groups of func's family
 from .ulysses import make_usp_groups, with_ulysses

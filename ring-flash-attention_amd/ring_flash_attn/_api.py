@@ -334,6 +334,120 @@ def with_lse_grad(func):
     return _opaque(bound)
 
 
+# ---- per-row key ranges (ring_flash_attn.with_row_ranges) -----------------------------------------------------------------
+# Row i sees key j iff start[i] <= pos(j) < end[i] and the call's own mask allows the pair: one interval of GLOBAL key positions
+# per query row (FlashMask's O(S) description of document, prefix-LM, shared-prefix masks ...).  The two tensors are bound to
+# the call like the gradient of lse above: read ONCE, in the autograd Function's forward, kept on the node (ctx.row_ranges) and
+# handed to the schedule's forward and backward as `row_ranges=` — a backward reads nothing ambient.  The schedules give every
+# block call the slice that belongs to its query rows and the global position of its key row 0 (include/rfa.h: rfa_rowrange_args).
+_row_ranges = contextvars.ContextVar("ring_flash_attn_row_ranges", default=None)
+
+ROW_RANGE_FUNCS = tuple(f"{p}_{s}" for p in ("ring_flash_attn", "zigzag_ring_flash_attn") for s in ("func", "kvpacked_func", "qkvpacked_func"))
+
+
+def _check_row_range_tensors(start, end, q=None):
+    """ValueError unless start and end are contiguous int32 2-d tensors of one shape on one device — and, given the call's q,
+    (B, S_local) on q's device"""
+    for nm, t in (("start", start), ("end", end)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 2 or not t.is_contiguous():
+            got = f"{tuple(t.shape)} {t.dtype}, contiguous={t.is_contiguous()}" if isinstance(t, torch.Tensor) else repr(t)
+            raise ValueError(f"ring_flash_attn.with_row_ranges: {nm} must be a contiguous int32 tensor of shape (B, S_local); got {got}")
+    if start.shape != end.shape or start.device != end.device:
+        raise ValueError(f"ring_flash_attn.with_row_ranges: start {tuple(start.shape)} on {start.device} and end "
+                         f"{tuple(end.shape)} on {end.device} must have one shape and device")
+    if q is not None and (tuple(start.shape) != tuple(q.shape[:2]) or start.device != q.device):
+        raise ValueError(f"ring_flash_attn.with_row_ranges: start / end must be {tuple(q.shape[:2])} on {q.device} — one entry "
+                         f"per local query row; got {tuple(start.shape)} on {start.device}")
+
+
+def checked_row_ranges(q, k, v, dropout_p, alibi_slopes, what):
+    """(start, end) bound to this public call by `with_row_ranges`, or None.  ValueError: tensors that do not fit q.
+    NotImplementedError — before anything is exchanged, on every rank alike: dropout, alibi_slopes, head dims above 128, a value
+    head dim of its own, a backend without `serves_row_ranges`."""
+    rr = _row_ranges.get()
+    if rr is None:
+        return None
+    _check_row_range_tensors(rr[0], rr[1], q)
+    if dropout_p and dropout_p > 0:
+        raise NotImplementedError(f"ring_flash_attn: {what} with row ranges together with dropout is not supported")
+    if alibi_slopes is not None:
+        raise NotImplementedError(f"ring_flash_attn: {what} with row ranges together with alibi_slopes is not supported")
+    if q.shape[-1] > 128:
+        raise NotImplementedError(f"ring_flash_attn: {what} with row ranges serves head dims up to 128, not {q.shape[-1]}")
+    if v.shape[-1] != q.shape[-1]:
+        raise NotImplementedError(f"ring_flash_attn: {what} with row ranges does not serve a value head dim ({v.shape[-1]}) "
+                                  f"that differs from q's ({q.shape[-1]})")
+    from .backend import get_backend
+
+    be = get_backend()
+    if not getattr(be, "serves_row_ranges", False):
+        raise NotImplementedError(f"ring_flash_attn: {what} with row ranges needs a backend that serves `row_ranges` "
+                                  f"(serves_row_ranges); {getattr(be, 'name', type(be).__name__)!r} does not")
+    return rr
+
+
+def row_ranges_extra(ctx):
+    """the `row_ranges=` keyword of the schedule's forward / backward of a bound node; nothing for an unbound one"""
+    rr = getattr(ctx, "row_ranges", None)
+    return {} if rr is None else {"row_ranges": rr}
+
+
+def with_row_ranges(func, start, end):
+    """One interval of keys per query row — document masks on dense (zigzag-balanced) input, prefix-LM and image-bidirectional
+    masks, shared prefixes — for the dense ring and zigzag functions:
+
+        attn = with_row_ranges(zigzag_ring_flash_attn_func, start, end)     # int32 (B, S_local), contiguous, on q's device
+        out = attn(q, k, v, causal=False)
+
+    returns a callable with `func`'s signature and return value in which query row i sees key j iff
+    start[b, i] <= pos(j) < end[b, i] AND the call's own mask (`causal`, `window_size`) allows the pair.  start / end hold THIS
+    rank's query rows in the order of q's rows; their values are GLOBAL key positions in the natural order of the unsharded
+    sequence (0 .. W * S_local), not layout indices.  Values outside [0, total] are clamped; start >= end is an empty row
+    (out = 0, lse = +inf, zero gradients); all query heads share the ranges; the ranges get no gradient, dq, dk, dv are exact.
+    The kernels skip every key tile (forward, dQ) and every query tile (dK/dV) that no row's range reaches.  A zigzag call may
+    be non-causal.  Unions of disjoint intervals compose through `with_lse_grad` and `merge_attn` (README).
+    `start=None, end=None`: `func` itself.  Served: ring_flash_attn_{,kvpacked_,qkvpacked_}func and
+    zigzag_ring_flash_attn_{,kvpacked_,qkvpacked_}func or a `with_lse_grad` result of one (with_row_ranges goes on the outside),
+    on any group, with windows, GQA, return_attn_probs, bf16 / fp16.  TypeError: any other callable — the *_varlen, stripe_,
+    llama3_ and zigzag_llama3_ families and with_softcap / with_sinks / with_max_logit / with_ulysses / with_row_ranges results.
+    ValueError: only one of start / end; tensors that are not contiguous int32 (B, S_local) on q's device.  NotImplementedError at
+    the call, before anything is exchanged: dropout_p > 0, alibi_slopes, head dims above 128, a value head dim of its own, a
+    backend that does not serve it.  The tensors are bound to the call and kept on the autograd node — activation
+    checkpointing re-runs the wrapped call and binds them again.  Under torch.compile the call runs eagerly behind a graph break."""
+    import functools
+
+    import ring_flash_attn as pkg
+
+    for marker, what in (("_rfa_row_ranges", "with_row_ranges"), ("_rfa_softcap", "with_softcap"), ("_rfa_sinks", "with_sinks"),
+                         ("_rfa_max_logit", "with_max_logit"), ("_rfa_ulysses", "with_ulysses")):
+        if getattr(func, marker, False):
+            raise TypeError(f"ring_flash_attn.with_row_ranges: `func` is a {what} result; not served")
+    served = {id(getattr(pkg, n)) for n in ROW_RANGE_FUNCS}
+    f = func
+    # (a with_lse_grad result carries the marker on both of its layers and leads to the public function it wraps)
+    while id(f) not in served and getattr(f, "_rfa_lse_grad", False) and hasattr(f, "__wrapped__"):
+        f = f.__wrapped__
+    if id(f) not in served:
+        raise TypeError("ring_flash_attn.with_row_ranges: `func` must be one of ring_flash_attn_{,kvpacked_,qkvpacked_}func and "
+                        f"zigzag_ring_flash_attn_{{,kvpacked_,qkvpacked_}}func or a with_lse_grad result of one, got {func!r}")
+    if (start is None) != (end is None):
+        raise ValueError("ring_flash_attn.with_row_ranges: start and end come together (both tensors, or both None)")
+    if start is None:
+        return func
+    _check_row_range_tensors(start, end)
+
+    @functools.wraps(func, updated=())              # (updated=(): as in with_softcap)
+    def ranged(*args, **kwargs):
+        token = _row_ranges.set((start, end))
+        try:
+            return func(*args, **kwargs)
+        finally:
+            _row_ranges.reset(token)
+
+    ranged._rfa_row_ranges = True                    # (the other binders refuse a ranged function)
+    return _opaque(ranged)
+
+
 # ---- attention over the union of two key sets (ring_flash_attn.merge_attn) ------------------------------------------------
 def _check_merge_args(out_a, lse_a, out_b, lse_b):
     ts = (out_a, lse_a, out_b, lse_b)
@@ -688,6 +802,7 @@ def make_autograd_function(name, forward_impl, backward_impl, n_lead, window_rin
             alibi_slopes = checked_alibi(alibi_slopes, q, (len(lead[0]) - 1) if n_lead else q.shape[0], name)
             ctx.softcap = checked_softcap(dropout_p, alibi_slopes, q, name, window_size, causal)
             ctx.lse_grad = checked_lse_grad(ctx, name)
+            ctx.row_ranges = checked_row_ranges(q, k, v, dropout_p, alibi_slopes, name)
             sinks = checked_sinks(sinks, q, name)
             q, k, v = _prep_qkv(q, k, v, group)
             tensors_lead = ()
@@ -696,6 +811,7 @@ def make_autograd_function(name, forward_impl, backward_impl, n_lead, window_rin
                 lead = (cu,) + tuple(lead[1:])
                 tensors_lead = (cu,)
             keep, extra = _keep_list(ctx, forward_impl)
+            extra.update(row_ranges_extra(ctx))
             ctx.dropout = (dropout_p, draw_dropout_seed()) if dropout_p and dropout_p > 0 else (0.0, None)
             if ctx.dropout[1] is not None:
                 extra["dropout_seed"] = ctx.dropout[1]
@@ -727,6 +843,7 @@ def make_autograd_function(name, forward_impl, backward_impl, n_lead, window_rin
             tensors_lead, extra = _split_kept(ctx, more)
             dout, lse_kw = lse_grad_kw(ctx, dout, args, out, softmax_lse)
             extra.update(lse_kw)
+            extra.update(row_ranges_extra(ctx))
             if ctx.dropout[1] is not None:
                 extra["dropout_seed"] = ctx.dropout[1]
             with softcap_scope(ctx.softcap):
@@ -771,6 +888,7 @@ def make_packed_function(name, base_fn, forward_impl, backward_impl, n_lead, pac
             alibi_slopes = checked_alibi(alibi_slopes, q, (len(lead[0]) - 1) if n_lead else q.shape[0], name)
             ctx.softcap = checked_softcap(dropout_p, alibi_slopes, q, name, window_size, causal)
             ctx.lse_grad = checked_lse_grad(ctx, name)
+            ctx.row_ranges = checked_row_ranges(q, k, v, dropout_p, alibi_slopes, name)
             sinks = checked_sinks(sinks, q, name)
             q, k, v = _prep_qkv(q, k, v, group, packed_travel=packed_travel and n_packed == 2)
             tensors_lead = ()
@@ -779,6 +897,7 @@ def make_packed_function(name, base_fn, forward_impl, backward_impl, n_lead, pac
                 lead = (cu,) + tuple(lead[1:])
                 tensors_lead = (cu,)
             keep, extra = _keep_list(ctx, forward_impl)
+            extra.update(row_ranges_extra(ctx))
             ctx.dropout = (dropout_p, draw_dropout_seed()) if dropout_p and dropout_p > 0 else (0.0, None)
             if ctx.dropout[1] is not None:
                 extra["dropout_seed"] = ctx.dropout[1]
@@ -811,6 +930,7 @@ def make_packed_function(name, base_fn, forward_impl, backward_impl, n_lead, pac
             tensors_lead, extra = _split_kept(ctx, more)
             dout, lse_kw = lse_grad_kw(ctx, dout, args, out, softmax_lse)
             extra.update(lse_kw)
+            extra.update(row_ranges_extra(ctx))
             shape, dtype, device = ctx.packed_meta
             dpacked = torch.empty(shape, dtype=dtype, device=device)
             views = [dpacked.select(pack_dim, i) for i in range(n_packed)]

@@ -113,6 +113,18 @@ def alibi_kw(alibi_slopes, shift=0, heads=None):
     return {"alibi": (alibi_slopes, int(shift))}
 
 
+def row_ranges_kw(row_ranges, k_pos0, rows=None):
+    """the `row_ranges=` keyword of a block call whose key row 0 sits at global position `k_pos0`, for the query rows `rows`
+    (a slice of this rank's rows: the ranges are views) — ring_flash_attn.with_row_ranges; nothing without ranges, so that
+    backends that predate the keyword keep serving plain calls"""
+    if row_ranges is None:
+        return {}
+    start, end = row_ranges[:2]
+    if rows is not None:
+        start, end = start[:, rows], end[:, rows]
+    return {"row_ranges": (start, end, int(k_pos0))}
+
+
 def dlse_kw(dlse):
     """the `dlse=` keyword of a backward's bwd_preprocess (the gradient of lse, ring_flash_attn.with_lse_grad); nothing
     without one, so that backends that predate the keyword keep serving plain calls"""

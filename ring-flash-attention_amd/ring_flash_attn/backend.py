@@ -77,6 +77,7 @@ class HipBackend:
     serves_lse_grad = True           # bwd_preprocess takes `dlse=` (include/rfa.h: rfa_bwd_preprocess_lse): ring_flash_attn.with_lse_grad
     serves_merge_pair = True         # merge_pair / merge_pair_bwd (include/rfa.h: rfa_merge_pair, rfa_merge_pair_bwd): ring_flash_attn.merge_attn
     serves_vdim = True               # fwd / bwd take a `v` whose head dim differs from q's (include/rfa.h: rfa_fwd_vd, rfa_bwd_vd): MLA 192 / 128
+    serves_row_ranges = True         # fwd / bwd take `row_ranges=(start, end, k_pos0)` (include/rfa.h: rfa_fwd_rr, rfa_bwd_rr): ring_flash_attn.with_row_ranges
     serves_dropout_positions = True  # `dropout=` takes the position maps (q_map, k_map): what dropout over a dense ring, zigzag or stripe schedule needs
 
     def __init__(self):
@@ -105,7 +106,7 @@ class HipBackend:
     def fwd(self, q, k, v, *, softmax_scale, causal, cu_seqlens_q=None, cu_seqlens_k=None,
             max_seqlen_q=None, max_seqlen_k=None, q_half=HALF_FULL, k_half=HALF_FULL,
             out=None, lse=None, out_acc=None, lse_acc=None, acc_init=False, window=(-1, -1), dropout=None,
-            mask_shift=0, mask_shift_lens=0, alibi=None, softcap=0.0):
+            mask_shift=0, mask_shift_lens=0, alibi=None, softcap=0.0, row_ranges=None):
         """Block attention.  Plain mode fills (out, lse); accumulate mode merges into the fp32
         (out_acc, lse_acc) pair (fused update_out_and_lse).  Dense: q (B,Sq,H,D); varlen: (T,H,D).
         dropout: (p, seed, q_pos_offset, k_pos_offset, head_offset), the same plus the position maps (q_map, k_map) —
@@ -117,7 +118,11 @@ class HipBackend:
         alibi: (slopes, shift) or None — fp32 slopes (H,) or (B, H) on q's device and the block's alibi_shift
         (include/rfa.h: rfa_ext_args; _common.alibi_arg validates and builds it).
         softcap: scores become softcap * tanh(softmax_scale * q.k / softcap) in front of the mask (include/rfa.h:
-        rfa_ext_args.softcap); 0 is off — the plain call."""
+        rfa_ext_args.softcap); 0 is off — the plain call.
+        row_ranges: (start, end, k_pos0) or None — int32 (B, Sq) tensors on q's device (row stride 1; the batch stride is
+        free, so a schedule passes slices) holding GLOBAL key positions, and the global position of k's row 0: row i sees key
+        row j iff start[b, i] <= k_pos0 + j < end[b, i] and the call's own mask allows it (include/rfa.h: rfa_rowrange_args).
+        Dense input, head dims <= 128, no dropout, bias or cap."""
         self._check_dev(q, k, v, out, lse, out_acc, lse_acc)
         varlen = cu_seqlens_q is not None
         a = _C.FwdArgs()
@@ -156,6 +161,10 @@ class HipBackend:
         # split-KV launches (few query rows against many keys on an under-filled grid: include/rfa.h) need a small
         # workspace for the partial (out, lse) pairs: a few tens of MB, only for the calls that split
         vd = _vdim_args(q, v, alibi, softcap, dropout)
+        rr = _rowrange_args(row_ranges, q, alibi, softcap, dropout, vd, varlen)
+        if rr is not None:                        # per-row key ranges: the kRng instances of the 8 x 32 form, never split
+            _C.check(self.lib.rfa_fwd_rr(C.byref(a), C.byref(rr), _stream(q)), "rfa_fwd_rr")
+            return
         if vd is not None:                        # a value head dim of its own (csrc/rfa_vdim.hip): never split either
             _C.check(self.lib.rfa_fwd_vd(C.byref(a), C.byref(vd), _stream(q)), "rfa_fwd_vd")
             return
@@ -206,7 +215,7 @@ class HipBackend:
             k_half=HALF_FULL, dq=None, dk=None, dv=None, dq_acc=None, dk_acc=None, dv_acc=None,
             acc_init=False, deterministic=False, phases=_C.BWD_ALL, partials=None, ds_scratch=None,
             window=(-1, -1), prof_events=None, dropout=None, mask_shift=0, mask_shift_lens=0, alibi=None,
-            softcap=0.0):
+            softcap=0.0, row_ranges=None):
         """dQ/dK/dV of one block.  Plain outputs (io dtype) or `+=` into fp32 accumulators.
         phases=BWD_COMPUTE / BWD_REDUCE splits the call so a ring step can overlap the kernels
         with the arrival of the dk/dv accumulators it adds into: the COMPUTE call RETURNS the buffer
@@ -215,7 +224,9 @@ class HipBackend:
         micro-batches) can never consume each other's partials.  Scratch comes from torch's caching
         allocator on the current stream, per call; the C library itself never allocates.
         alibi, softcap: as in fwd, with the forward's values; such a call names the 128-key dK/dV form and takes no dS scratch —
-        what rfa_bwd_ex asks of the base arguments (include/rfa.h)."""
+        what rfa_bwd_ex asks of the base arguments (include/rfa.h).
+        row_ranges: as in fwd, with the forward's values; the same two conditions (rfa_bwd_rr), plus a small tile-bounds
+        workspace from torch's caching allocator, per call."""
         self._check_dev(dout, q, k, v, lse, delta, dq, dk, dv, dq_acc, dk_acc, dv_acc)
         varlen = cu_seqlens_q is not None
         a = _C.BwdArgs()
@@ -278,9 +289,10 @@ class HipBackend:
         # several calls (measurement: BWD_SKIP_DQ / BWD_SKIP_DKDV) pass the same `ds_scratch` to both.
         vd = _vdim_args(q, v, alibi, softcap, dropout)    # (rfa_bwd_vd runs the base arguments' own plan and scratch)
         ext = _ext_args(alibi, q, softcap)
-        if ext is not None:
+        rr = _rowrange_args(row_ranges, q, alibi, softcap, dropout, vd, varlen)
+        if ext is not None or rr is not None:
             a.dkdv_form, a.dkdv_nsplit, ds_scratch = _C.DKDV_128, 0, None
-        if ext is None and ds_scratch is None and not reduce_only and _spill_enabled():
+        if ext is None and rr is None and ds_scratch is None and not reduce_only and _spill_enabled():
             ds_scratch = self.bwd_ds_scratch(a, q.device)
         if ds_scratch is not None and not reduce_only:
             a.ds_scratch = ds_scratch.data_ptr()
@@ -299,7 +311,12 @@ class HipBackend:
             ws._rfa_plan = (form, ns if form == _C.DKDV_256 or a.D > 128 else 0)
         if ws is not None:
             a.workspace = ws.data_ptr()
-        if vd is not None:
+        if rr is not None:
+            nb = self.lib.rfa_rowrange_workspace_bytes(C.byref(a))
+            tb = torch.empty(max(nb, 16), dtype=torch.uint8, device=q.device)
+            rr.tile_bounds = tb.data_ptr()
+            _C.check(self.lib.rfa_bwd_rr(C.byref(a), C.byref(rr), _stream(q)), "rfa_bwd_rr")
+        elif vd is not None:
             _C.check(self.lib.rfa_bwd_vd(C.byref(a), C.byref(vd), _stream(q)), "rfa_bwd_vd")
         elif ext is not None:
             _C.check(self.lib.rfa_bwd_ex(C.byref(a), C.byref(ext), _stream(q)), "rfa_bwd_ex")
@@ -732,6 +749,32 @@ def _ext_args(alibi, q, softcap=0.0):
     ext.alibi_shift = int(shift)
     ext.softcap = softcap
     return ext
+
+
+def _rowrange_args(row_ranges, q, alibi, softcap, dropout, vd, varlen):
+    """rfa_rowrange_args of a call with `row_ranges=(start, end, k_pos0)`, or None: the call without them.  What the ranged
+    kernels do not have is refused here, before the library is called."""
+    if row_ranges is None:
+        return None
+    start, end, k_pos0 = row_ranges
+    if (alibi is not None and alibi[0] is not None) or check_softcap(softcap) or (dropout is not None and dropout[0] > 0):
+        raise NotImplementedError("ring_flash_attn: row ranges together with alibi, softcap or dropout are not served")
+    if vd is not None or varlen or q.shape[-1] > 128:
+        raise NotImplementedError("ring_flash_attn: row ranges are served for dense input with one head dim up to 128")
+    want = tuple(q.shape[:2])
+    for nm, t in (("start", start), ("end", end)):
+        if (not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or tuple(t.shape) != want or t.device != q.device
+                or (t.stride(1) != 1 and t.shape[1] != 1)):
+            raise ValueError(f"row_ranges: {nm} must be an int32 tensor of shape {want} on {q.device} with row stride 1")
+    if start.stride(0) != end.stride(0) and start.shape[0] > 1:
+        end = end.contiguous()
+        start = start.contiguous()
+    rr = _C.RowRangeArgs()
+    rr.start, rr.end = start.data_ptr(), end.data_ptr()
+    rr.batch_stride = start.stride(0) if start.shape[0] > 1 else 0
+    rr.k_pos0 = int(k_pos0)
+    rr._keep = (start, end)                       # (the tensors live as long as the struct does)
+    return rr
 
 
 def _vdim_args(q, v, alibi, softcap, dropout):

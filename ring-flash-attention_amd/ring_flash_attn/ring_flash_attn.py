@@ -17,13 +17,17 @@ transfer (`ring_window_plan`).  Calls without a window that cuts the global sequ
 ALiBi over several ranks rides on the same bookkeeping: the bias is a function of the global distance i - j, so the block
 at signed rank distance t is told alibi_shift = t * S (include/rfa.h: rfa_ext_args) — `ring_window_plan` with both sides
 unbounded walks all W steps, and the causal diagonal moves with the same t * S as a windowed call's.
+
+Per-row key ranges (ring_flash_attn.with_row_ranges) take that route as well: the block at signed rank distance t holds the
+keys of rank r - t, so its key row 0 sits at global position k_pos0 = (r - t) S; every block call gets this rank's
+(start, end) and that one number (`row_ranges=`, include/rfa.h: rfa_rowrange_args), and the kernels skip what no row sees.
 """
 import torch
 
 from . import _C
 from .backend import get_backend
 from .utils import RingComm, single_rank
-from ._common import alibi_kw, dlse_kw, out_shape, dropout_arg, global_window, pos_map, require_dropout_positions, require_mask_shift
+from ._common import alibi_kw, dlse_kw, out_shape, row_ranges_kw, dropout_arg, global_window, pos_map, require_dropout_positions, require_mask_shift
 from ._api import make_autograd_function, make_dense_api, _grad_buffers
 
 
@@ -53,17 +57,20 @@ def ring_window_plan(rank, world_size, S, causal, window):
     return n_steps, dists
 
 
-def _band(causal, window, t, S, alibi_slopes=None):
+def _band(causal, window, t, S, alibi_slopes=None, row_ranges=None, rank=0):
     """keywords of a block call t ranks off the diagonal (the shift only where it is not zero: backends that predate
-    it serve the diagonal block unchanged; the bias only where there is one)"""
+    it serve the diagonal block unchanged; the bias only where there is one; the ranges only where there are some, with the
+    global position of the block's key row 0)"""
     kw = {"causal": causal, "window": window}
     if t:
         kw["mask_shift"] = t * S
     kw.update(alibi_kw(alibi_slopes, t * S))
+    if row_ranges is not None:
+        kw["row_ranges"] = (row_ranges[0], row_ranges[1], (rank - t) * S)
     return kw
 
 
-def _ring_window_forward(be, comm, q, k, v, softmax_scale, causal, window, alibi_slopes=None):
+def _ring_window_forward(be, comm, q, k, v, softmax_scale, causal, window, alibi_slopes=None, row_ranges=None):
     B, S, H, D = q.shape
     n_steps, dists = ring_window_plan(comm.rank, comm.world_size, S, causal, window)
     out_acc = torch.empty(out_shape(q, v), dtype=torch.float32, device=q.device)
@@ -75,7 +82,7 @@ def _ring_window_forward(be, comm, q, k, v, softmax_scale, causal, window, alibi
             next_k, next_v = comm.send_recv_kv(k, v)
         if dists[step] is not None:
             be.fwd(q, k, v, softmax_scale=softmax_scale, out_acc=out_acc, lse_acc=lse_acc, acc_init=first,
-                   **_band(causal, window, dists[step], S, alibi_slopes))
+                   **_band(causal, window, dists[step], S, alibi_slopes, row_ranges, comm.rank))
             first = False
         if step + 1 != n_steps:
             comm.wait()
@@ -84,7 +91,7 @@ def _ring_window_forward(be, comm, q, k, v, softmax_scale, causal, window, alibi
 
 
 def _ring_window_backward(be, process_group, kv_comm, d_kv_comm, dout, q, k, v, softmax_lse, delta, softmax_scale,
-                          causal, window, deterministic, alibi_slopes=None):
+                          causal, window, deterministic, alibi_slopes=None, row_ranges=None):
     B, S, H, D = q.shape
     world = kv_comm.world_size
     n_steps, dists = ring_window_plan(kv_comm.rank, world, S, causal, window)
@@ -97,7 +104,7 @@ def _ring_window_backward(be, process_group, kv_comm, d_kv_comm, dout, q, k, v, 
         if step + 1 != n_steps:
             next_k, next_v = kv_comm.send_recv_kv(k, v)
         if dists[step] is not None:
-            band = _band(causal, window, dists[step], S, alibi_slopes)
+            band = _band(causal, window, dists[step], S, alibi_slopes, row_ranges, kv_comm.rank)
             if dq is None:                       # step 0: the diagonal block always computes
                 dq = torch.empty((B, S, H, D), dtype=torch.float32, device=q.device)
                 be.bwd(dout, q, k, v, softmax_lse, delta, softmax_scale=softmax_scale,
@@ -153,7 +160,9 @@ def ring_flash_attn_forward(
     alibi_slopes=None,
     deterministic=False,
     dropout_seed=None,
+    row_ranges=None,
 ):
+    """row_ranges: (start, end) of a call bound by with_row_ranges — this rank's rows, global key positions — or None"""
     be = get_backend()
     comm = RingComm(process_group)
     B, S, H, D = q.shape
@@ -162,16 +171,18 @@ def ring_flash_attn_forward(
         out = torch.empty(out_shape(q, v), dtype=q.dtype, device=q.device)
         lse = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
         be.fwd(q, k, v, softmax_scale=softmax_scale, causal=causal, out=out, lse=lse, window=window_size, dropout=dropout_arg(dropout_p, dropout_seed),
-               **alibi_kw(alibi_slopes))
+               **alibi_kw(alibi_slopes), **row_ranges_kw(row_ranges, 0))
         return out, lse
     drop = _ring_dropout(be, comm, S, dropout_p, dropout_seed)
 
     win = global_window(window_size, causal, comm.world_size * S)
     if alibi_slopes is not None:                 # (never together with a window: _api._check_unsupported)
         win = (-1, -1)
+    if row_ranges is not None and win is None:   # (the ranges ride on the windowed route's bookkeeping, with or without a window)
+        win = (-1, -1)
     if win is not None:
         require_mask_shift(be, "ring_flash_attn")
-        return _ring_window_forward(be, comm, q, k, v, softmax_scale, causal, win, alibi_slopes)
+        return _ring_window_forward(be, comm, q, k, v, softmax_scale, causal, win, alibi_slopes, row_ranges)
 
     out_acc = torch.empty(out_shape(q, v), dtype=torch.float32, device=q.device)
     lse_acc = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
@@ -212,6 +223,7 @@ def ring_flash_attn_backward(
     dropout_seed=None,
     out_grads=None,
     dlse=None,
+    row_ranges=None,
 ):
     be = get_backend()
     kv_comm = RingComm(process_group)
@@ -229,16 +241,18 @@ def ring_flash_attn_backward(
         dq, dk, dv = _grad_buffers(out_grads, q, k, v)
         be.bwd(dout, q, k, v, softmax_lse, delta, softmax_scale=softmax_scale, causal=causal,
                dq=dq, dk=dk, dv=dv, deterministic=deterministic, window=window_size, dropout=dropout_arg(dropout_p, dropout_seed),
-               **alibi_kw(alibi_slopes))
+               **alibi_kw(alibi_slopes), **row_ranges_kw(row_ranges, 0))
         return dq, dk, dv
     drop = _ring_dropout(be, kv_comm, S, dropout_p, dropout_seed)
 
     win = global_window(window_size, causal, kv_comm.world_size * S)
     if alibi_slopes is not None:
         win = (-1, -1)
+    if row_ranges is not None and win is None:
+        win = (-1, -1)
     if win is not None:
         return _ring_window_backward(be, process_group, kv_comm, d_kv_comm, dout, q, k, v, softmax_lse, delta,
-                                     softmax_scale, causal, win, deterministic, alibi_slopes)
+                                     softmax_scale, causal, win, deterministic, alibi_slopes, row_ranges)
 
     dq = None
     dk = torch.empty(k.shape, dtype=torch.float32, device=q.device)

@@ -52,7 +52,7 @@ from . import _C, config
 from .backend import get_backend
 from .utils import Agreement, AllGatherComm, RingComm, SourceArrivals, all_to_all_async, reduce_scatter_async, single_rank
 from ._api import make_autograd_function, make_dense_api, _grad_buffers
-from ._common import alibi_kw, dlse_kw, out_shape, packed_pair, dropout_arg, global_window, require_dropout_positions, require_mask_shift, zigzag_map
+from ._common import alibi_kw, dlse_kw, out_shape, row_ranges_kw, packed_pair, dropout_arg, global_window, require_dropout_positions, require_mask_shift, zigzag_map
 
 
 def gather_scratch_bytes(k: torch.Tensor, world: int, wire_fp32: bool) -> int:
@@ -172,16 +172,21 @@ def _gather_kv(comm_group, k, v, world, per_source=False):
 # gradient accumulators, single-phase block calls, fp32 reduce-scatter of the dK/dV slots in the gather forms.
 # ALiBi over several ranks takes the same decomposition with an unbounded left window: the bias is a function of the global
 # distance i - j, which for the pair (cq, ck) is the block's own plus (cq - ck) C — its alibi_shift (include/rfa.h).
-def zigzag_window_pairs(rank, src, world, C, window_left):
+# Per-row key ranges (ring_flash_attn.with_row_ranges) take it too: each key side of a pair is ONE contiguous run of the
+# sequence, chunk ck, so its key row 0 sits at global position k_pos0 = ck C and no position map is needed; the query side
+# gets the slice of (start, end) that belongs to its half.  Such a call may be non-causal (a prefix-LM mask on zigzag-balanced
+# input): the pairs with ck > cq are then issued as well.
+def zigzag_window_pairs(rank, src, world, C, window_left, causal=True):
     """the (query half, key half, mask_shift) block calls of rank `rank` against the K/V of rank `src`, diagonal
-    blocks first (they initialise the accumulators of their half)"""
+    blocks first (they initialise the accumulators of their half); causal False (ranged calls only): the pairs above the
+    diagonal too"""
     qc = (rank, 2 * world - 1 - rank)
     kc = (src, 2 * world - 1 - src)
     pairs = []
     for hq in (0, 1):
         for hk in (0, 1):
             d = qc[hq] - kc[hk]
-            if d < 0 or (window_left >= 0 and d * C - window_left > C - 1):
+            if (d < 0 and causal) or (window_left >= 0 and d * C - window_left > C - 1):
                 continue
             pairs.append((hq, hk, d * C))
     return sorted(pairs, key=lambda p: p[2] != 0)
@@ -192,7 +197,8 @@ def _halves(S):
     return (slice(0, C), slice(C, S))
 
 
-def _zigzag_window_forward(be, process_group, comm, q, k, v, softmax_scale, window, alibi_slopes=None):
+def _zigzag_window_forward(be, process_group, comm, q, k, v, softmax_scale, window, alibi_slopes=None, row_ranges=None,
+                           causal=True):
     B, S, H, D = q.shape
     W, rank = comm.world_size, comm.rank
     hs = _halves(S)
@@ -201,11 +207,11 @@ def _zigzag_window_forward(be, process_group, comm, q, k, v, softmax_scale, wind
     started = [False, False]
 
     def blocks(src, ks, vs):
-        for hq, hk, shift in zigzag_window_pairs(rank, src, W, S // 2, window[0]):
+        for hq, hk, shift in zigzag_window_pairs(rank, src, W, S // 2, window[0], causal):
             band = {"mask_shift": shift} if shift else {}
-            be.fwd(q[:, hs[hq]], ks[:, hs[hk]], vs[:, hs[hk]], softmax_scale=softmax_scale, causal=True, window=window,
+            be.fwd(q[:, hs[hq]], ks[:, hs[hk]], vs[:, hs[hk]], softmax_scale=softmax_scale, causal=causal, window=window,
                    out_acc=out_acc[:, hs[hq]], lse_acc=lse_acc[:, :, hs[hq]], acc_init=not started[hq], **band,
-                   **alibi_kw(alibi_slopes, shift))
+                   **alibi_kw(alibi_slopes, shift), **row_ranges_kw(row_ranges, (src, 2 * W - 1 - src)[hk] * (S // 2), hs[hq]))
             started[hq] = True
 
     mode = exchange_mode(k, W, q, process_group, v)
@@ -232,7 +238,7 @@ def _zigzag_window_forward(be, process_group, comm, q, k, v, softmax_scale, wind
 
 
 def _zigzag_window_backward(be, process_group, kv_comm, d_kv_comm, dout, q, k, v, softmax_lse, delta, softmax_scale,
-                            window, deterministic, kept, alibi_slopes=None):
+                            window, deterministic, kept, alibi_slopes=None, row_ranges=None, causal=True):
     B, S, H, D = q.shape
     W, rank = kv_comm.world_size, kv_comm.rank
     hs = _halves(S)
@@ -241,12 +247,12 @@ def _zigzag_window_backward(be, process_group, kv_comm, d_kv_comm, dout, q, k, v
     delta_h = [delta[:, :, h].contiguous() for h in hs]
 
     def blocks(src, ks, vs, dk, dv):
-        for hq, hk, shift in zigzag_window_pairs(rank, src, W, S // 2, window[0]):
+        for hq, hk, shift in zigzag_window_pairs(rank, src, W, S // 2, window[0], causal):
             band = {"mask_shift": shift} if shift else {}
             be.bwd(dout[:, hs[hq]], q[:, hs[hq]], ks[:, hs[hk]], vs[:, hs[hk]], lse_h[hq], delta_h[hq],
-                   softmax_scale=softmax_scale, causal=True, window=window, dq_acc=dq[:, hs[hq]],
+                   softmax_scale=softmax_scale, causal=causal, window=window, dq_acc=dq[:, hs[hq]],
                    dk_acc=dk[:, hs[hk]], dv_acc=dv[:, hs[hk]], deterministic=deterministic, **band,
-                   **alibi_kw(alibi_slopes, shift))
+                   **alibi_kw(alibi_slopes, shift), **row_ranges_kw(row_ranges, (src, 2 * W - 1 - src)[hk] * (S // 2), hs[hq]))
 
     mode = exchange_mode(k, W, q, process_group, v)
     if mode in ("gather", "gather_ps"):
@@ -327,10 +333,12 @@ def zigzag_ring_flash_attn_forward(
     deterministic=False,
     dropout_seed=None,
     keep=None,
+    row_ranges=None,
 ):
     """keep: a list (or None) the gather form appends its gathered K/V buffers to — the autograd Function saves them
-    for the backward (`kept=`)"""
-    assert causal == True, "zigzag ring is meaningless for causal=False"
+    for the backward (`kept=`).  row_ranges: (start, end) of a call bound by with_row_ranges — this rank's rows in q's
+    order, global key positions — or None; such a call may be non-causal"""
+    assert causal == True or row_ranges is not None, "zigzag ring is meaningless for causal=False"
     be = get_backend()
     comm = RingComm(process_group)
     B, S, H, D = q.shape
@@ -339,17 +347,19 @@ def zigzag_ring_flash_attn_forward(
     if single_rank(comm.world_size):
         out = torch.empty(out_shape(q, v), dtype=q.dtype, device=q.device)
         lse = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
-        be.fwd(q, k, v, softmax_scale=softmax_scale, causal=True, out=out, lse=lse, window=window_size, dropout=dropout_arg(dropout_p, dropout_seed),
-               **alibi_kw(alibi_slopes))
+        be.fwd(q, k, v, softmax_scale=softmax_scale, causal=bool(causal), out=out, lse=lse, window=window_size, dropout=dropout_arg(dropout_p, dropout_seed),
+               **alibi_kw(alibi_slopes), **row_ranges_kw(row_ranges, 0))
         return out, lse
     drop = _zigzag_dropout(be, comm.rank, comm.world_size, half, dropout_p, dropout_seed)
 
-    win = global_window(window_size, True, comm.world_size * S)
+    win = global_window(window_size, bool(causal), comm.world_size * S)
     if alibi_slopes is not None:                 # (never together with a window: _api._check_unsupported)
+        win = (-1, -1)
+    if row_ranges is not None and win is None:   # (the ranges take the per-pair route, with or without a window)
         win = (-1, -1)
     if win is not None:
         require_mask_shift(be, "zigzag_ring_flash_attn")
-        return _zigzag_window_forward(be, process_group, comm, q, k, v, softmax_scale, win, alibi_slopes)
+        return _zigzag_window_forward(be, process_group, comm, q, k, v, softmax_scale, win, alibi_slopes, row_ranges, bool(causal))
 
     out_acc = torch.empty(out_shape(q, v), dtype=torch.float32, device=q.device)
     lse_acc = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
@@ -418,9 +428,10 @@ def zigzag_ring_flash_attn_backward(
     out_grads=None,
     dlse=None,
     kept=None,
+    row_ranges=None,
 ):
     """kept: the gathered K/V buffers the forward handed over (`keep=`), or None"""
-    assert causal == True, "zigzag ring is meaningless for causal=False"
+    assert causal == True or row_ranges is not None, "zigzag ring is meaningless for causal=False"
     be = get_backend()
     kv_comm = RingComm(process_group)
     d_kv_comm = RingComm(process_group)
@@ -436,18 +447,20 @@ def zigzag_ring_flash_attn_backward(
 
     if single_rank(kv_comm.world_size):
         dq, dk, dv = _grad_buffers(out_grads, q, k, v)
-        be.bwd(dout, q, k, v, softmax_lse, delta, softmax_scale=softmax_scale, causal=True,
+        be.bwd(dout, q, k, v, softmax_lse, delta, softmax_scale=softmax_scale, causal=bool(causal),
                dq=dq, dk=dk, dv=dv, deterministic=deterministic, window=window_size, dropout=dropout_arg(dropout_p, dropout_seed),
-               **alibi_kw(alibi_slopes))
+               **alibi_kw(alibi_slopes), **row_ranges_kw(row_ranges, 0))
         return dq, dk, dv
     drop = _zigzag_dropout(be, kv_comm.rank, kv_comm.world_size, half, dropout_p, dropout_seed)
 
-    win = global_window(window_size, True, kv_comm.world_size * S)
+    win = global_window(window_size, bool(causal), kv_comm.world_size * S)
     if alibi_slopes is not None:
+        win = (-1, -1)
+    if row_ranges is not None and win is None:
         win = (-1, -1)
     if win is not None:
         return _zigzag_window_backward(be, process_group, kv_comm, d_kv_comm, dout, q, k, v, softmax_lse, delta,
-                                       softmax_scale, win, deterministic, kept, alibi_slopes)
+                                       softmax_scale, win, deterministic, kept, alibi_slopes, row_ranges, bool(causal))
 
     dq = torch.empty((B, S, H, D), dtype=torch.float32, device=q.device)
 
