@@ -314,14 +314,15 @@ def test_live_band_beside_large_numbers_is_its_small_twin(name, D):
 
 def test_shift_together_with_dense_halves():
     """rfa_fwd / rfa_bwd take dense q_half / k_half together with a shift: the band sits on the HALF lengths.  The off = 65
-    block as the back halves of twice-as-long tensors (front halves: other data, never read, never written)"""
+    block as the back halves of twice-as-long tensors (front halves: NaN — never read, not even into a masked tile, where
+    0 * NaN would show — and never written)"""
     from ring_flash_attn import _C
 
     be = _be()
     g = G_["causal+65"]
     x = _ctx(g, *HEADS, 128, BF)
     dev = x.q.device
-    junk = lambda t: torch.cat([torch.randn_like(t.float()).to(t.dtype) * 3, t], dim=1).contiguous()
+    junk = lambda t: torch.cat([torch.full_like(t, float("nan")), t], dim=1).contiguous()
     q2, k2, v2, do2 = junk(x.q), junk(x.k), junk(x.v), junk(x.do)
     B, Sq, H, D = x.q.shape
     halves = dict(q_half=_C.HALF_BACK, k_half=_C.HALF_BACK)
