@@ -32,6 +32,17 @@
  *     argument (a hipStream_t passed as void*).
  *   - All strides are in ELEMENTS of the tensor's own dtype.  The innermost (head_dim) stride
  *     must be 1 and every row start must be 16-byte aligned.
+ *   - Row strides: the batch and head strides (and rfa_sum_slots' slot stride) are free — tensors may lie any 64-bit
+ *     distance apart — but the kernels address the rows of one tile with 32-bit byte offsets, so for every rfa_strides of
+ *     every entry point, with `elt` the size of the tensor's elements (2, or 4 for an fp32 accumulator),
+ *         256 * |row| * elt + D * elt <= 2^31 - 1        (io dtype, D = 128: |row| <= 4194303, so 4194296 elements)
+ *     or the call returns RFA_ERR_ARGS before anything is launched (256: the most rows one tile spans).
+ *   - Extents: B above 65535 where a launch needs it as a grid dimension (rfa_bwd_preprocess*, rfa_merge, rfa_sum_slots; with H
+ *     alike: rfa_lse_flatten / rfa_lse_unflatten, rfa_sink_*, rfa_merge_pair*; rfa_fwd* with a split-KV share count asked for by
+ *     name; rfa_bwd* when the call needs a workspace or carries row ranges) and more than 2^31 - 1 workgroups in a 1-D launch
+ *     (rfa_fwd*: ceil(Sq / 128) * H * B * shares; rfa_bwd*: that without shares, ceil(Sk / 128) * Hk * B * dkdv_nsplit and,
+ *     when the call needs a workspace, ceil(Sk * Hk / 16); the side kernels: ceil(S * H / 16)) return RFA_ERR_SHAPE before
+ *     anything is launched.
  *   - Dense mode (cu_seqlens_* == NULL):  q is (B, Sq, H, D), k/v are (B, Sk, Hk, D), lse is
  *     (B, H, Sq).  Varlen mode: q is (Tq, H, D), k/v (Tk, Hk, D), lse is (H, Tq); `B` is the
  *     number of packed sequences, `Sq`/`Sk` the max sequence lengths, *_batch strides unused.

@@ -23,6 +23,22 @@ inline bool stride_ok(const rfa_strides& s, int elt_bytes) {
   return (s.row % q) == 0 && (s.head % q) == 0 && (s.batch % q) == 0;
 }
 
+// ... and a row stride must leave the kernels' 32-bit descriptor arithmetic room (rfa_kernels.hpp: kDescMaxRows; rfa.h)
+inline bool row_ok(const rfa_strides& s, int D, int elt_bytes) { return desc_row_stride_ok(s.row, D, elt_bytes); }
+// B / H where a launcher makes them grid.y / grid.z, and a 1-D grid's block count (rfa_kernels.hpp)
+inline bool grid_yz_ok(int64_t n) { return n <= kGridYZMax; }
+inline bool grid_x_ok(int64_t nblocks) { return nblocks <= kGridXMax; }
+inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+inline int64_t mul_sat(int64_t a, int64_t b) {                     // a, b >= 0: the product, INT64_MAX where it does not fit
+  return (a <= 0 || b <= 0) ? 0 : (a > INT64_MAX / b ? INT64_MAX : a * b);
+}
+inline int64_t mul_sat(int64_t a, int64_t b, int64_t c, int64_t d = 1) { return mul_sat(mul_sat(a, b), mul_sat(c, d)); }
+
+// the side kernels' grids: B is grid.y, 16 (row, head) pairs per workgroup along grid.x
+inline bool aux_extents_ok(int B, int S, int H) {
+  return grid_yz_ok(B) && grid_x_ok(ceil_div(mul_sat(S, H), 16));
+}
+
 inline int check_common(int dtype, int H, int Hk, int D, int B) {
   if (dtype != RFA_BF16 && dtype != RFA_F16) return RFA_ERR_DTYPE;
   if (D <= 0 || D > kMaxHeadDim || (D % 8) != 0) return RFA_ERR_HEAD_DIM;
@@ -606,6 +622,19 @@ static int fwd_impl(const rfa_fwd_args* a, const rfa_ext_args* ext, int Dv, void
     else if (!bias_args_ok(*a, norm_args(*a), e)) return RFA_ERR_ARGS;
   }
   if (a->B == 0 || a->Sq == 0) return RFA_OK;
+  // what the launchers and the tile loaders' 32-bit descriptor arithmetic cannot express (rfa.h: "row strides", "extents"):
+  // refused from the numbers alone, before a pointer is looked at.  The 1-D grids hold at most one workgroup per 128 query
+  // rows, head, batch entry and split-KV share (the plan shares only under-filled grids by itself: a count that matters
+  // here was asked for by name); the combine pass of such shares has B as grid.y.
+  {
+    const int Dw = Dv > a->D ? Dv : a->D;
+    if (!row_ok(a->q_st, a->D, 2) || !row_ok(a->k_st, a->D, 2) || !row_ok(a->v_st, Dw, 2) ||
+        !(a->out_acc ? row_ok(a->out_acc_st, Dw, 4) : row_ok(a->out_st, Dw, 2)))
+      return RFA_ERR_ARGS;
+    const int64_t shares = a->kv_nsplit > 1 ? (a->kv_nsplit > 8 ? 8 : a->kv_nsplit) : 1;
+    if (!grid_x_ok(mul_sat(ceil_div(eff_len(a->Sq, a->q_half), 128), a->H, a->B, shares))) return RFA_ERR_SHAPE;
+    if (shares > 1 && !grid_yz_ok(a->B)) return RFA_ERR_SHAPE;
+  }
   if (!a->q || !a->k || !a->v) return RFA_ERR_NULL;
   if (a->out_acc) {
     if (!a->lse_acc) return RFA_ERR_NULL;
@@ -709,8 +738,9 @@ int rfa_bwd_preprocess(const rfa_bwd_preprocess_args* a, void* stream) {
   if (!a) return RFA_ERR_NULL;
   int rc = check_common(a->dtype, a->H, a->H, a->D, a->B);
   if (rc) return rc;
-  if (a->Sq < 0) return RFA_ERR_SHAPE;
+  if (a->Sq < 0 || !aux_extents_ok(a->B, a->Sq, a->H)) return RFA_ERR_SHAPE;
   if (a->B == 0 || a->Sq == 0) return RFA_OK;
+  if (!row_ok(a->dout_st, a->D, 2) || !row_ok(a->out_st, a->D, 2)) return RFA_ERR_ARGS;
   if (!a->dout || !a->out || !a->delta) return RFA_ERR_NULL;
   if (!aligned16(a->dout) || !aligned16(a->out) || !stride_ok(a->dout_st, 2) || !stride_ok(a->out_st, 2))
     return RFA_ERR_ALIGN;
@@ -728,9 +758,10 @@ int rfa_bwd_preprocess_lse(const rfa_bwd_preprocess_lse_args* a, void* stream) {
   if (!a) return RFA_ERR_NULL;
   int rc = check_common(a->dtype, a->H, a->H, a->D, a->B);
   if (rc) return rc;
-  if (a->Sq < 0) return RFA_ERR_SHAPE;
+  if (a->Sq < 0 || !aux_extents_ok(a->B, a->Sq, a->H)) return RFA_ERR_SHAPE;
   if (a->reserved != 0 || a->q_half < RFA_HALF_FULL || a->q_half > RFA_HALF_BACK) return RFA_ERR_ARGS;
   if (a->B == 0 || a->Sq == 0) return RFA_OK;
+  if (!row_ok(a->dout_st, a->D, 2) || !row_ok(a->out_st, a->D, 2)) return RFA_ERR_ARGS;
   if (!a->dout || !a->out || !a->delta) return RFA_ERR_NULL;
   if (!aligned16(a->dout) || !aligned16(a->out) || !stride_ok(a->dout_st, 2) || !stride_ok(a->out_st, 2))
     return RFA_ERR_ALIGN;
@@ -1118,6 +1149,21 @@ static int bwd_impl(const rfa_bwd_args* a, const rfa_ext_args* ext, int Dv, void
     else if (a->dkdv_form != RFA_DKDV_128 || a->ds_scratch != nullptr) return RFA_ERR_ARGS;
   }
   if (a->B == 0 || a->Sq == 0 || a->Sk == 0) return RFA_OK;
+  // as in the forward: row strides and 1-D grids the kernels and launchers cannot express are refused from the numbers alone
+  // (dQ: one workgroup per 128 rows, head and batch entry at most; dK/dV: per 128 keys, K/V head, batch entry and share —
+  // the plan shares only under-filled grids by itself)
+  {
+    const int Dw = Dv > a->D ? Dv : a->D;
+    if (!row_ok(a->dout_st, Dw, 2) || !row_ok(a->q_st, a->D, 2) || !row_ok(a->k_st, a->D, 2) || !row_ok(a->v_st, Dw, 2) ||
+        !(a->dq_acc ? row_ok(a->dq_acc_st, a->D, 4) : row_ok(a->dq_st, a->D, 2)) ||
+        !(a->dk_acc ? row_ok(a->dk_acc_st, a->D, 4) && row_ok(a->dv_acc_st, Dw, 4)
+                    : row_ok(a->dk_st, a->D, 2) && row_ok(a->dv_st, Dw, 2)))
+      return RFA_ERR_ARGS;
+    const int64_t shares = a->dkdv_nsplit > 1 ? a->dkdv_nsplit : 1;
+    if (!grid_x_ok(mul_sat(ceil_div(eff_len(a->Sq, a->q_half), 128), a->H, a->B)) ||
+        !grid_x_ok(mul_sat(ceil_div(eff_len(a->Sk, a->k_half), 128), a->Hk, a->B, shares)))
+      return RFA_ERR_SHAPE;
+  }
   if (!a->dout || !a->q || !a->k || !a->v || !a->lse || !a->delta) return RFA_ERR_NULL;
   if (!a->dq && !a->dq_acc) return RFA_ERR_NULL;
   if ((a->dk_acc == nullptr) != (a->dv_acc == nullptr)) return RFA_ERR_ARGS;
@@ -1138,6 +1184,10 @@ static int bwd_impl(const rfa_bwd_args* a, const rfa_ext_args* ext, int Dv, void
   const rfa_bwd_args na = norm_args(*a);
   a = &na;
   const bool ws = bwd_needs_ws(a);
+  // B is grid.y of the pass that sums the workspace's partials (reduce_kernel: 16 (key, K/V head) pairs per workgroup along
+  // grid.x) and of the row ranges' tile-bounds kernel
+  if ((ws || rr != nullptr) && !grid_yz_ok(a->B)) return RFA_ERR_SHAPE;
+  if (ws && !grid_x_ok(ceil_div(mul_sat(a->Sk, a->Hk), 16))) return RFA_ERR_SHAPE;
   if (ws && !a->workspace) return RFA_ERR_NULL;
   if (!aligned16(a->dout) || !aligned16(a->q) || !aligned16(a->k) || !aligned16(a->v))
     return RFA_ERR_ALIGN;
@@ -1322,8 +1372,9 @@ int rfa_merge(const rfa_merge_args* a, void* stream) {
   if (!a) return RFA_ERR_NULL;
   int rc = check_common(a->dtype, a->H, a->H, a->D, a->B);
   if (rc) return rc;
-  if (a->S < 0) return RFA_ERR_SHAPE;
+  if (a->S < 0 || !aux_extents_ok(a->B, a->S, a->H)) return RFA_ERR_SHAPE;
   if (a->B == 0 || a->S == 0) return RFA_OK;
+  if (!row_ok(a->out_acc_st, a->D, 4) || !row_ok(a->block_out_st, a->D, 2)) return RFA_ERR_ARGS;
   if (!a->out_acc || !a->lse_acc || !a->block_out || !a->block_lse) return RFA_ERR_NULL;
   if (!aligned16(a->out_acc) || !aligned16(a->block_out) || !stride_ok(a->out_acc_st, 4) ||
       !stride_ok(a->block_out_st, 2))
@@ -1343,8 +1394,9 @@ int rfa_sum_slots(const rfa_sum_slots_args* a, void* stream) {
   if (!a) return RFA_ERR_NULL;
   int rc = check_common(a->dtype, a->H, a->H, a->D, a->B);
   if (rc) return rc;
-  if (a->S < 0 || a->nslots < 1) return RFA_ERR_SHAPE;
+  if (a->S < 0 || a->nslots < 1 || !aux_extents_ok(a->B, a->S, a->H)) return RFA_ERR_SHAPE;
   if (a->B == 0 || a->S == 0) return RFA_OK;
+  if (!row_ok(a->src_st, a->D, 2) || !row_ok(a->dst_st, a->D, 2)) return RFA_ERR_ARGS;   // (the slot stride is free: 64 bits)
   if (!a->src || !a->dst) return RFA_ERR_NULL;
   if (!aligned16(a->src) || !aligned16(a->dst) || !stride_ok(a->src_st, 2) || !stride_ok(a->dst_st, 2) ||
       (a->slot_stride % 8) != 0)
@@ -1370,7 +1422,7 @@ int rfa_cast(void* dst, const float* src, int64_t n, int32_t dtype, void* stream
 
 int rfa_lse_flatten(float* dst, const float* src, const int32_t* cu_seqlens, int32_t B, int32_t H,
                     int32_t max_seqlen, int64_t dst_head_stride, int64_t dst_row_stride, void* stream) {
-  if (B < 0 || H < 0 || max_seqlen < 0) return RFA_ERR_SHAPE;
+  if (B < 0 || H < 0 || max_seqlen < 0 || !grid_yz_ok(B) || !grid_yz_ok(H)) return RFA_ERR_SHAPE;   // (H, B: grid.y, grid.z)
   if (B == 0 || H == 0 || max_seqlen == 0) return RFA_OK;
   if (!dst || !src || !cu_seqlens) return RFA_ERR_NULL;
   return launch_lse_relayout(dst, src, cu_seqlens, B, H, max_seqlen, dst_head_stride, dst_row_stride,
@@ -1379,7 +1431,7 @@ int rfa_lse_flatten(float* dst, const float* src, const int32_t* cu_seqlens, int
 
 int rfa_lse_unflatten(float* dst, const float* src, const int32_t* cu_seqlens, int32_t B, int32_t H,
                       int32_t max_seqlen, int64_t src_head_stride, int64_t src_row_stride, void* stream) {
-  if (B < 0 || H < 0 || max_seqlen < 0) return RFA_ERR_SHAPE;
+  if (B < 0 || H < 0 || max_seqlen < 0 || !grid_yz_ok(B) || !grid_yz_ok(H)) return RFA_ERR_SHAPE;   // (H, B: grid.y, grid.z)
   if (B == 0 || H == 0 || max_seqlen == 0) return RFA_OK;
   if (!dst || !src || !cu_seqlens) return RFA_ERR_NULL;
   return launch_lse_relayout(dst, src, cu_seqlens, B, H, max_seqlen, src_head_stride, src_row_stride,
@@ -1401,6 +1453,7 @@ int rfa_sink_apply(const rfa_sink_apply_args* a, void* stream) {
   int rc = sink_shape_check(a->dtype, a->B, a->S, a->H, a->D, a->reserved);
   if (rc) return rc;
   if (a->B == 0 || a->S == 0) return RFA_OK;
+  if (!row_ok(a->out_src_st, a->D, 2) || !row_ok(a->out_dst_st, a->D, 2)) return RFA_ERR_ARGS;
   if (!a->out_src || !a->out_dst || !a->lse_src || !a->lse_dst || !a->sinks) return RFA_ERR_NULL;
   if (!aligned16(a->out_src) || !aligned16(a->out_dst) || !stride_ok(a->out_src_st, 2) || !stride_ok(a->out_dst_st, 2))
     return RFA_ERR_ALIGN;
@@ -1427,6 +1480,7 @@ int rfa_sink_grad(const rfa_sink_grad_args* a, void* stream) {
     return hipMemsetAsync(a->dsink, 0, (size_t)a->H * sizeof(float), (hipStream_t)stream) == hipSuccess ? RFA_OK
                                                                                                          : RFA_ERR_LAUNCH;
   }
+  if (!row_ok(a->dout_st, a->D, 2) || !row_ok(a->out_st, a->D, 2)) return RFA_ERR_ARGS;
   if (!a->dout || !a->out || !a->lse || !a->sinks || !a->dsink || !a->workspace) return RFA_ERR_NULL;
   if (!aligned16(a->dout) || !aligned16(a->out) || !aligned16(a->workspace) || !stride_ok(a->dout_st, 2) ||
       !stride_ok(a->out_st, 2))
@@ -1447,6 +1501,7 @@ int rfa_merge_pair(const rfa_merge_pair_args* a, void* stream) {
   int rc = sink_shape_check(a->dtype, a->B, a->S, a->H, a->D, a->reserved);
   if (rc) return rc;
   if (a->B == 0 || a->S == 0) return RFA_OK;
+  if (!row_ok(a->out_a_st, a->D, 2) || !row_ok(a->out_b_st, a->D, 2) || !row_ok(a->out_st, a->D, 2)) return RFA_ERR_ARGS;
   if (!a->out_a || !a->out_b || !a->lse_a || !a->lse_b || !a->out || !a->lse) return RFA_ERR_NULL;
   if (!aligned16(a->out_a) || !aligned16(a->out_b) || !aligned16(a->out) || !stride_ok(a->out_a_st, 2) ||
       !stride_ok(a->out_b_st, 2) || !stride_ok(a->out_st, 2))
@@ -1465,6 +1520,9 @@ int rfa_merge_pair_bwd(const rfa_merge_pair_bwd_args* a, void* stream) {
   int rc = sink_shape_check(a->dtype, a->B, a->S, a->H, a->D, a->reserved);
   if (rc) return rc;
   if (a->B == 0 || a->S == 0) return RFA_OK;
+  if (!row_ok(a->dout_st, a->D, 2) || !row_ok(a->out_a_st, a->D, 2) || !row_ok(a->out_b_st, a->D, 2) ||
+      !row_ok(a->dout_a_st, a->D, 2) || !row_ok(a->dout_b_st, a->D, 2))
+    return RFA_ERR_ARGS;
   if (!a->dout || !a->out_a || !a->out_b || !a->lse_a || !a->lse_b || !a->dout_a || !a->dout_b || !a->dlse_a || !a->dlse_b)
     return RFA_ERR_NULL;
   if (!aligned16(a->dout) || !aligned16(a->out_a) || !aligned16(a->out_b) || !aligned16(a->dout_a) || !aligned16(a->dout_b) ||
@@ -1577,6 +1635,7 @@ int rfa_max_logit(const rfa_max_logit_args* a0, void* stream) {
     band = norm_band(a.Sq, a.q_half, a.Sk, a.k_half, a.causal, a.window, a.window_left, a.window_right, a.mask_shift);
     if (band.empty || dense_len(a.Sq, a.q_half) <= 0 || dense_len(a.Sk, a.k_half) <= 0) attention = false;
   }
+  if (attention && (!row_ok(a.q_st, a.D, 2) || !row_ok(a.k_st, a.D, 2))) return RFA_ERR_ARGS;   // (before any launch)
   if (!attention) return launch_status(launch_max_logit(p, a.dtype, false, (hipStream_t)stream));
   if (!a.q || !a.k || !a.workspace) return RFA_ERR_NULL;
   if (!aligned16(a.q) || !aligned16(a.k) || !aligned16(a.workspace) || !stride_ok(a.q_st, 2) || !stride_ok(a.k_st, 2))

@@ -29,6 +29,7 @@ namespace rfa {
 constexpr int kBgWaves = 4;
 constexpr int kBgThreads = kBgWaves * 64;
 constexpr int kBgRows = kBgWaves * 32;        // query rows (forward, dQ) / keys (dK/dV) per workgroup
+static_assert(kBgRows <= kDescMaxRows, "a buffer descriptor spans at most kDescMaxRows rows (rfa_kernels.hpp)");
 // (per kernel instance: kNK = 4 kQ 16-wide k-steps of a contraction, kNB = 2 kQ 32-wide column blocks of an accumulator
 //  row, kQ = the 64-column quarters of the 256-wide row that hold data: 3 for head dims <= 192, else 4)
 constexpr int kBgOob = 0x7ffffff0;            // byte offset past every descriptor range: the lane reads / DMAs zeros

@@ -458,6 +458,7 @@ constexpr int kKvWaves = 8;
 constexpr int kKvThreads = kKvWaves * 64;
 constexpr int kKvKeys = 128;                       // keys / workgroup
 constexpr int kKvQ = 64;                           // query rows per tile (2 sub-tiles of 32)
+static_assert(kDqKV <= kDescMaxRows && kKvQ <= kDescMaxRows, "a buffer descriptor spans at most kDescMaxRows rows (rfa_kernels.hpp)");
 constexpr int kKvStatBytes = 2 * kKvQ * 4;         // lse[64] + delta[64] per stage
 template <int kD, bool kRng = false> constexpr int kv_smem() {        // 129 KiB (65 KiB at kD = 64); kRng: + the rows' bounds
   return 2 * kKvKeys * HeadGeo<kD>::kRowBytes + 4 * kKvQ * HeadGeo<kD>::kRowBytes + (kRng ? 4 : 2) * kKvStatBytes;

@@ -43,6 +43,7 @@
 namespace rfa {
 
 constexpr int kDsKV = 64;                              // keys per tile = 2 dS blocks per wave
+static_assert(kDsKV <= kDescMaxRows, "a buffer descriptor spans at most kDescMaxRows rows (rfa_kernels.hpp)");
 constexpr int kDsKBytes = kDsKV * kRowBytes;           // 16 KiB K tile
 constexpr int kDsWaveBytes = 2 * kDsBlockBytes;        // 4 KiB of dS per wave and tile
 // Two forms: 8 waves = 256 query rows per workgroup through a 3-stage ring (144 KiB: the headline's grid of 1024

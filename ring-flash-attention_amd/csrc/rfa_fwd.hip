@@ -78,6 +78,7 @@ constexpr int kFwdWavesMax = 8;
 #define RFA_FWD_YOUNG_PRIO 0 // 1: waves 4-7 (the half dispatched second, the loser of every VALU arbitration) run at s_setprio 1
 #endif
 constexpr int kFwdKV = RFA_FWD_KV;          // keys per tile
+static_assert(kFwdKV <= kDescMaxRows, "a buffer descriptor spans at most kDescMaxRows rows (rfa_kernels.hpp)");
 constexpr int kFwdSub = kFwdKV / 32;        // 32-key sub-tiles per tile
 #ifndef RFA_FWD_STAGES
 #define RFA_FWD_STAGES 2     // LDS ring depth: tile j+STAGES-1 is in flight (DMA) while tile j is computed

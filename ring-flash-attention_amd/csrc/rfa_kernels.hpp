@@ -14,6 +14,26 @@ namespace rfa {
 // windowed instances are needed for a left bound, or for a right bound that is not the plain causal one
 inline bool windowed(int causal, int wl, int wr) { return wl >= 0 || (wr >= 0 && !causal); }
 
+// ---- what 32 bits inside a buffer descriptor allow (rfa.h: "row strides") ---------------------------------------------------
+// The tile loaders form a tile's BASE with 64-bit products, but inside the descriptor everything is `int`: a lane's byte
+// offset (row * row_stride + chunk * 8) * 2 and num_records = ((rows - 1) * row_stride + D) * 2, `rows` the rows of ONE
+// descriptor.  kDescMaxRows is the largest such row count the contract allows for: the widest descriptor today spans 128
+// rows (the V tile of the one-launch dK + dV kernels: kBgRows in rfa_bigd.hip, kVdRows in rfa_vdim.hip; K/V, Q/dO tiles
+// span 64, the per-wave Q / out tiles 32), and 256 is the widest tile any workgroup owns (the rows of the 8-wave forward
+// and dQ, the keys of the 256-key dK/dV form), so a loader may span its workgroup's whole tile without changing the
+// contract.  The kernel files static_assert the tile constants their descriptors are sized by today (kFwdKV, kDqKV, kKvQ,
+// kDsKV, kMlKV, kBgRows, kVdRows) against it — a reminder next to the constants, not a proof: a loader that builds a
+// descriptor over another row count has to be checked against kDescMaxRows by whoever writes it.  rfa_api.cpp refuses
+// (RFA_ERR_ARGS, before any launch) a row stride for which kDescMaxRows * row_stride * elt + D * elt would pass 2^31 - 1.
+constexpr int kDescMaxRows = 256;
+constexpr bool desc_row_stride_ok(int64_t row_stride, int D, int elt_bytes) {
+  const int64_t r = row_stride < 0 ? -row_stride : row_stride;
+  return r <= (int64_t)INT32_MAX && (int64_t)kDescMaxRows * r * elt_bytes + (int64_t)D * elt_bytes <= (int64_t)INT32_MAX;
+}
+// ---- what a launch can express: grid.y / grid.z up to 65535, a 1-D grid up to 2^31 - 1 blocks (rfa_api.cpp refuses more) ----
+constexpr int64_t kGridYZMax = 65535;
+constexpr int64_t kGridXMax = INT32_MAX;
+
 // launcher status codes (rfa_api.cpp maps them to rfa_status)
 enum { kLaunchOk = 0, kLaunchFailed = -1, kLaunchAttrFailed = -2 };
 

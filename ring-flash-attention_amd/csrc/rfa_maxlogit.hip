@@ -27,6 +27,8 @@
 
 namespace rfa {
 
+static_assert(kMlKV <= kDescMaxRows, "a buffer descriptor spans at most kDescMaxRows rows (rfa_kernels.hpp)");
+
 // kD: compiled head dim — 64, 128, or 256 = two 128-column parts
 template <int kD>
 struct MlGeo {

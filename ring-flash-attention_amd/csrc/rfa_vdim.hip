@@ -21,6 +21,7 @@ namespace rfa {
 constexpr int kVdWaves = 4;
 constexpr int kVdThreads = kVdWaves * 64;
 constexpr int kVdRows = kVdWaves * 32;        // query rows (forward, dQ) / keys (dK + dV) per workgroup
+static_assert(kVdRows <= kDescMaxRows, "a buffer descriptor spans at most kDescMaxRows rows (rfa_kernels.hpp)");
 constexpr int kVdQ = 3, kVdQv = 2;            // 64-column quarters that hold data: QK side / V side
 constexpr int kVdNK = 4 * kVdQ, kVdNB = 2 * kVdQ;       // 16-wide k-steps of a contraction over D, 32-wide blocks of a D-wide accumulator row
 constexpr int kVdNKv = 4 * kVdQv, kVdNBv = 2 * kVdQv;   // the same over Dv

@@ -42,9 +42,28 @@ def _lse_st(t: torch.Tensor, varlen: bool):
     return t.stride(0), t.stride(1)
 
 
+_DESC_MAX_ROWS = 256     # csrc/rfa_kernels.hpp: kDescMaxRows — the rows one tile's 32-bit byte offsets have to span
+
+
+def _row_stride_ok(t: torch.Tensor) -> bool:
+    """include/rfa.h, "row strides": 256 * |row stride| * element size + D * element size <= 2^31 - 1 for a (B, S, H, D) /
+    (T, H, D) tensor; the batch and head strides are free"""
+    if t.dim() < 3:
+        return True
+    e = t.element_size()
+    return _DESC_MAX_ROWS * abs(t.stride(-3)) * e + t.shape[-1] * e <= 2 ** 31 - 1
+
+
+def _in_contract(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    """an INPUT tensor as the library takes it: t, or a contiguous copy of a view whose row stride the kernels' 32-bit tile
+    offsets cannot express (the library refuses it: RFA_ERR_ARGS) — a legal torch view stays a legal argument"""
+    return t if t is None or _row_stride_ok(t) else t.contiguous()
+
+
 def _rows16(t: torch.Tensor) -> torch.Tensor:
-    """t, or a contiguous copy when a view's rows are off the library's 16-byte contract (last stride 1, 2-byte elements)"""
-    if t.stride(-1) != 1 or any(st % 8 for st in t.stride()[:-1]) or t.data_ptr() % 16:
+    """t, or a contiguous copy when a view's rows are off the library's 16-byte contract (last stride 1, 2-byte elements)
+    or its row stride beyond the library's bound (_row_stride_ok)"""
+    if t.stride(-1) != 1 or any(st % 8 for st in t.stride()[:-1]) or t.data_ptr() % 16 or not _row_stride_ok(t):
         return t.contiguous()
     return t
 
@@ -124,6 +143,7 @@ class HipBackend:
         row j iff start[b, i] <= k_pos0 + j < end[b, i] and the call's own mask allows it (include/rfa.h: rfa_rowrange_args).
         Dense input, head dims <= 128, no dropout, bias or cap."""
         self._check_dev(q, k, v, out, lse, out_acc, lse_acc)
+        q, k, v = _in_contract(q), _in_contract(k), _in_contract(v)
         varlen = cu_seqlens_q is not None
         a = _C.FwdArgs()
         a.q, a.k, a.v = _ptr(q), _ptr(k), _ptr(v)
@@ -186,6 +206,7 @@ class HipBackend:
         becomes sum_d dout*out - dlse, which carries it through every backward kernel (include/rfa.h:
         rfa_bwd_preprocess_lse).  None: the existing call, bit for bit."""
         self._check_dev(dout, out, delta, dlse)
+        dout, out = _in_contract(dout), _in_contract(out)
         varlen = cu_seqlens_q is not None
         a = _C.BwdPreArgs() if dlse is None else _C.BwdPreLseArgs()
         a.dout, a.out, a.delta = _ptr(dout), _ptr(out), _ptr(delta)
@@ -228,6 +249,7 @@ class HipBackend:
         row_ranges: as in fwd, with the forward's values; the same two conditions (rfa_bwd_rr), plus a small tile-bounds
         workspace from torch's caching allocator, per call."""
         self._check_dev(dout, q, k, v, lse, delta, dq, dk, dv, dq_acc, dk_acc, dv_acc)
+        dout, q, k, v = _in_contract(dout), _in_contract(q), _in_contract(k), _in_contract(v)
         varlen = cu_seqlens_q is not None
         a = _C.BwdArgs()
         a.dout, a.q, a.k, a.v = _ptr(dout), _ptr(q), _ptr(k), _ptr(v)
@@ -544,8 +566,7 @@ class HipBackend:
         sink_apply returned (include/rfa.h: rfa_sink_grad) — summed in a fixed order, the same bits on every run.  dout may
         be any strided view whose rows stay 16-byte aligned (anything else is copied)."""
         self._check_dev(dout, out, lse, sinks)
-        if dout.stride(-1) != 1 or any(st % 8 for st in dout.stride()[:-1]) or dout.data_ptr() % 16:
-            dout = dout.contiguous()
+        dout = _rows16(dout)
         if lse.stride(-1) != 1 and lse.shape[-1] != 1:
             lse = lse.contiguous()
         s32 = _sinks_f32(sinks, out)
@@ -584,6 +605,7 @@ class HipBackend:
         looks at, -inf when it looks at none (include/rfa.h: rfa_max_logit).  dst: fp32, contiguous, 1-d, on q's device.  The
         raw scaled dot product: a soft cap, a bias, dropout and sinks do not enter it.  Same bits on every run."""
         self._check_dev(q, k, dst)
+        q, k = _in_contract(q), _in_contract(k)
         varlen = cu_seqlens_q is not None
         a = _C.MaxLogitArgs()
         a.q, a.k = _ptr(q), _ptr(k)

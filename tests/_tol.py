@@ -44,8 +44,11 @@ KINDS = {
 FRO_FLOOR = 0.25
 
 
-def metrics(got, ref):
-    got, ref = got.detach().float().cpu(), ref.detach().float().cpu()
+def metrics(got, ref, on_device=False):
+    """on_device: the same figures computed where the tensors live (tens of millions of elements: no copy to the host)"""
+    got, ref = got.detach().float(), ref.detach().float()
+    if not on_device:
+        got, ref = got.cpu(), ref.cpu()
     fin = torch.isfinite(ref)
     same_pattern = bool(torch.equal(torch.isfinite(got), fin))
     if not fin.any():
@@ -71,12 +74,12 @@ def _log(name, kind, m):
             pass
 
 
-def failures(name, got, ref, kind, scale=1.0):
+def failures(name, got, ref, kind, scale=1.0, on_device=False):
     """list of violated criteria (empty = pass).  scale: multiplies every bound (fp16 / special inputs)."""
     if tuple(got.shape) != tuple(ref.shape):
         return [f"{name}: shape {tuple(got.shape)} vs {tuple(ref.shape)}"]
     atol, rtol, fro, mabs, mrel = (x * scale for x in KINDS[kind])
-    m = metrics(got, ref)
+    m = metrics(got, ref, on_device)
     _log(name, kind, m)
     bad = []
     if not m["same_pattern"]:

@@ -569,3 +569,140 @@ def test_zero_outside_rezeroes_only_the_rows_that_leave_the_range(built):
     assert c2[0].tolist() == [0, 0, 0, 0, 1, 1, 0, 0]
     be.release_scratch()
     assert not be.zero_outside((8, 2), torch.float32, dev, 0, 8).any()
+
+
+# ---- what 32 bits inside a tile's buffer descriptor and a launch's grid cannot express (include/rfa.h: "row strides", "extents")
+ROW_MAX = 4194296           # the largest 16-byte aligned row stride with 256 * row * 2 + 128 * 2 <= 2^31 - 1 (io dtype, D = 128)
+
+
+def _fwd_shape(_C, **kw):
+    a = _C.FwdArgs()
+    a.B, a.Sq, a.Sk, a.H, a.Hk, a.D, a.dtype, a.softmax_scale = 1, 300, 300, 4, 2, 128, 0, 0.125
+    for st in (a.q_st, a.k_st, a.v_st, a.out_st, a.out_acc_st):
+        st.batch, st.row, st.head = 1 << 40, 512, 128
+    for n, v in kw.items():
+        setattr(a, n, v)
+    return a
+
+
+def _bwd_shape(_C, **kw):
+    b = _C.BwdArgs()
+    b.B, b.Sq, b.Sk, b.H, b.Hk, b.D, b.dtype, b.total_k, b.softmax_scale = 1, 300, 300, 4, 2, 128, 0, 300, 0.125
+    for st in (b.dout_st, b.q_st, b.k_st, b.v_st, b.dq_st, b.dk_st, b.dv_st, b.dq_acc_st, b.dk_acc_st, b.dv_acc_st):
+        st.batch, st.row, st.head = 1 << 40, 512, 128
+    for n, v in kw.items():
+        setattr(b, n, v)
+    return b
+
+
+def test_row_stride_bound_without_device(built):
+    """A row stride the kernels' 32-bit tile offsets cannot express is RFA_ERR_ARGS (-8) from every entry point that takes
+    rfa_strides, decided from the numbers alone: every tensor pointer is NULL, so the call just below the bound answers
+    RFA_ERR_NULL (-1) — the check that follows — and nothing can be launched either way.  Batch and head strides are free."""
+    import ctypes as C
+
+    from ring_flash_attn import _C
+    from ring_flash_attn import backend as BK
+
+    lib = _C.load()
+    assert 256 * ROW_MAX * 2 + 128 * 2 <= 2 ** 31 - 1 < 256 * (ROW_MAX + 8) * 2 + 128 * 2
+    ext, vd = _C.ExtArgs(), _C.VdimArgs()
+    ext.softcap, vd.head_dim_v = 2.0, 64
+    fwd_calls = [lambda a: lib.rfa_fwd(C.byref(a), None), lambda a: lib.rfa_fwd_ex(C.byref(a), C.byref(ext), None),
+                 lambda a: (setattr(a, "D", 192), lib.rfa_fwd_vd(C.byref(a), C.byref(vd), None))[1]]   # (192 / 64: MLA-like)
+    for call in fwd_calls:
+        for name in ("q_st", "k_st", "v_st", "out_st"):
+            for row, want in ((ROW_MAX, -1), (ROW_MAX + 8, -8), (1 << 31, -8), (1 << 40, -8)):
+                a = _fwd_shape(_C)
+                getattr(a, name).row = row
+                assert call(a) == want, (name, row)
+    a = _fwd_shape(_C, out_acc=16)                      # the accumulate mode's strides count 4-byte elements
+    a.out_acc_st.row = ROW_MAX // 2 + 8
+    assert lib.rfa_fwd(C.byref(a), None) == -8
+    a.out_acc_st.row, a.out_st.row = ROW_MAX // 2 - 4, 1 << 40          # (and the plain output's stride is not looked at)
+    assert lib.rfa_fwd(C.byref(a), None) == -1
+    for name in ("dout_st", "q_st", "k_st", "v_st", "dq_st", "dk_st", "dv_st"):
+        for row, want in ((ROW_MAX, -1), (ROW_MAX + 8, -8)):
+            b = _bwd_shape(_C)
+            getattr(b, name).row = row
+            assert lib.rfa_bwd(C.byref(b), None) == want, (name, row)
+            b.dkdv_form = _C.DKDV_128
+            assert lib.rfa_bwd_ex(C.byref(b), C.byref(ext), None) == want, (name, row)
+    for name in ("dq_acc_st", "dk_acc_st", "dv_acc_st"):
+        b = _bwd_shape(_C, dq_acc=16, dk_acc=16, dv_acc=16)
+        getattr(b, name).row = ROW_MAX // 2 + 8
+        assert lib.rfa_bwd(C.byref(b), None) == -8, name
+        getattr(b, name).row = ROW_MAX // 2 - 4
+        assert lib.rfa_bwd(C.byref(b), None) == -1, name
+    # the side kernels
+    for cls, call in ((_C.BwdPreArgs, lib.rfa_bwd_preprocess), (_C.BwdPreLseArgs, lib.rfa_bwd_preprocess_lse)):
+        for name in ("dout_st", "out_st"):
+            for row, want in ((ROW_MAX, -1), (ROW_MAX + 8, -8)):
+                p = cls()
+                p.B, p.Sq, p.H, p.D, p.dtype = 1, 300, 4, 128, 0
+                p.dout_st.row = p.out_st.row = 512
+                getattr(p, name).row = row
+                assert call(C.byref(p), None) == want, (cls.__name__, name, row)
+    for row, want in ((ROW_MAX, -1), (ROW_MAX + 8, -8)):
+        s = _C.SumSlotsArgs()
+        s.B, s.S, s.H, s.D, s.dtype, s.nslots, s.slot_stride = 1, 300, 4, 128, 0, 2, 1 << 40      # (the slot stride is free)
+        s.src_st.row, s.dst_st.row = row, 512
+        assert lib.rfa_sum_slots(C.byref(s), None) == want
+        m = _C.MergeArgs()
+        m.B, m.S, m.H, m.D, m.dtype = 1, 300, 4, 128, 0
+        m.out_acc_st.row, m.block_out_st.row = 512, row
+        assert lib.rfa_merge(C.byref(m), None) == want
+        ml = _C.MaxLogitArgs()
+        ml.B, ml.Sq, ml.Sk, ml.H, ml.Hk, ml.D, ml.dtype, ml.softmax_scale = 1, 300, 300, 4, 2, 128, 0, 0.125
+        ml.q_st.row, ml.k_st.row = 512, row
+        ml.max_logit, ml.workspace_bytes = 16, 1 << 30
+        assert lib.rfa_max_logit(C.byref(ml), None) == want
+    # the Python backend's pass-through rule is the same bound: such an input view is copied, not handed over
+    t = torch.empty(1 << 32, dtype=torch.bfloat16, device="meta")        # (strides only: no memory behind it)
+    view = lambda row: torch.as_strided(t, (2, 300, 4, 128), (1 << 30, row, 128, 1))
+    assert BK._row_stride_ok(view(ROW_MAX)) and not BK._row_stride_ok(view(ROW_MAX + 8))
+    assert BK._in_contract(view(ROW_MAX)).stride(1) == ROW_MAX and BK._in_contract(view(ROW_MAX + 8)).stride() == (153600, 512, 128, 1)
+
+
+def test_grid_extent_bounds_without_device(built):
+    """B or H beyond 65535 where a launch needs them as grid.y / grid.z, and more workgroups than a 1-D grid holds, are
+    RFA_ERR_SHAPE (-5) on the host (include/rfa.h: "extents").  The calls that pass answer a later host check — a NULL tensor
+    or workspace (-1) — so nothing is launched either way."""
+    import ctypes as C
+
+    from ring_flash_attn import _C
+
+    lib = _C.load()
+    fwd = lambda **kw: lib.rfa_fwd(C.byref(_fwd_shape(_C, **kw)), None)
+    assert fwd(B=65536) == -1                                           # (B is no grid dimension of the unsplit forward)
+    assert fwd(B=65536, Sq=32, kv_nsplit=2) == -5 and fwd(B=65535, Sq=32, kv_nsplit=2) == -1      # ... of the combine pass it is
+    blocks = lambda S, H, B, shares=1: -(-S // 128) * H * B * shares
+    assert blocks(128 * 32768, 4, 16384) == 2 ** 31 and fwd(Sq=128 * 32768, H=4, Hk=2, B=16384) == -5
+    assert fwd(Sq=128 * 32768 - 128, H=4, Hk=2, B=16384) == -1
+    assert fwd(Sq=2 ** 31 - 1, H=32768, Hk=32768, B=2 ** 31 - 1) == -5  # (no overflow on the way to the answer)
+    assert fwd(Sq=128 * 32768 - 128, H=4, Hk=2, B=16384, kv_nsplit=2) == -5
+    bwd = lambda **kw: lib.rfa_bwd(C.byref(_bwd_shape(_C, **dict(dict(dkdv_form=_C.DKDV_128), **kw))), None)
+    assert bwd(Sq=128 * 32768, Sk=8, B=16384) == -5 and bwd(Sq=128 * 32768 - 128, Sk=8, B=16384) == -1
+    assert bwd(Sq=8, Sk=128 * 32768, B=32768) == -5 and bwd(Sq=8, Sk=128 * 32768 - 128, B=32768) == -1
+    assert bwd(Sq=8, Sk=128 * 32768 - 128, B=32768, dkdv_nsplit=2, dkdv_form=_C.DKDV_256) == -5
+    # B is grid.y of the pass that adds a workspace's partials to the accumulators: tensors non-NULL, the workspace NULL
+    ptrs = dict(dout=16, q=16, k=16, v=16, lse=16, delta=16, dq_acc=16, dk_acc=16, dv_acc=16)
+    assert bwd(Sq=8, Sk=8, B=65536, **ptrs) == -5 and bwd(Sq=8, Sk=8, B=65535, **ptrs) == -1
+    # ... and that pass holds 16 (key, K/V head) pairs per workgroup along grid.x
+    assert bwd(Sq=8, Sk=2 ** 31 - 1, H=32, Hk=32, **ptrs) == -5 and bwd(Sq=8, Sk=2 ** 31 - 1, H=16, Hk=16, **ptrs) == -1
+    # the side kernels: B is grid.y, 16 (row, head) pairs per workgroup along grid.x
+    for cls, call in ((_C.BwdPreArgs, lib.rfa_bwd_preprocess), (_C.BwdPreLseArgs, lib.rfa_bwd_preprocess_lse)):
+        for B, S, H, want in ((65536, 8, 4, -5), (65535, 8, 4, -1), (1, 2 ** 31 - 1, 32, -5), (1, 2 ** 31 - 1, 16, -1)):
+            p = cls()
+            p.B, p.Sq, p.H, p.D, p.dtype = B, S, H, 128, 0
+            assert call(C.byref(p), None) == want, (cls.__name__, B, S, H)
+    for B, S, H, want in ((65536, 8, 4, -5), (65535, 8, 4, -1), (1, 2 ** 31 - 1, 32, -5)):
+        s = _C.SumSlotsArgs()
+        s.B, s.S, s.H, s.D, s.dtype, s.nslots = B, S, H, 128, 0, 2
+        assert lib.rfa_sum_slots(C.byref(s), None) == want
+        m = _C.MergeArgs()
+        m.B, m.S, m.H, m.D, m.dtype = B, S, H, 128, 0
+        assert lib.rfa_merge(C.byref(m), None) == want
+    for B, H, want in ((65536, 4, -5), (4, 65536, -5), (65535, 65535, -1)):
+        assert lib.rfa_lse_flatten(None, None, None, B, H, 8, 8, 1, None) == want
+        assert lib.rfa_lse_unflatten(None, None, None, B, H, 8, 8, 1, None) == want

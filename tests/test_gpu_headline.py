@@ -175,8 +175,10 @@ def test_headline_constant_v_and_split_merge(single_rank_group):
 
 
 def test_max_length_65536_single_gpu(single_rank_group):
-    """The headline's TOTAL sequence (8192 x 8 = 65536) on one GPU: 64-bit addressing, 256 query blocks
-    per head, 1024 KV tiles.  Checks: sampled rows of out/lse/dq in fp64 on the host, and the last 5536 key rows of
+    """The headline's TOTAL sequence (8192 x 8 = 65536) on one GPU: 256 query blocks per head, 1024 KV tiles, the 7-GEMM
+    backward (one head's dS would pass the hand-off's 32-bit block offset).  Its largest tensor holds 67 M elements (128 MiB):
+    it walks long sequences, it does not come near 2^31 elements or 2^32 bytes from a pointer — tests/test_gpu_far_addressing.py
+    does.  Checks: sampled rows of out/lse/dq in fp64 on the host, and the last 5536 key rows of
     dk/dv (+ the same query rows of dq, lse) of one kv head against a full fp64 computation of that sub-problem."""
     import ring_flash_attn as R
 
