@@ -766,6 +766,48 @@ int64_t rfa_rowrange_workspace_bytes(const rfa_bwd_args *args);
 int rfa_fwd_rr(const rfa_fwd_args *args, const rfa_rowrange_args *rr, void *stream);
 int rfa_bwd_rr(const rfa_bwd_args *args, const rfa_rowrange_args *rr, void *stream);
 
+/* Block-sparse masks (BigBird / Longformer window + global + random blocks, block-selected attention, document masks with
+ * shared tokens, a FlexAttention BlockMask's blocks).  Two entry points with a struct of their own; no existing struct changes
+ * (ABI 8 revision 1 stays).  The mask has one byte per pair of 128 query rows and 128 keys (RFA_BLOCK_MASK_SIZE), non-zero =
+ * lit.  Query row i of head h of batch entry b sees key row j of the block iff
+ *     mask[b * batch_stride + h * head_stride + (i / 128) * row_stride + k_blk0 + j / 128] != 0
+ * AND the base arguments' own mask (causal, window, mask_shift) allows the pair.  The columns of a mask row are the key blocks
+ * of the WHOLE sequence (nk_blocks of them); k_blk0 is the column of the block's key row 0 and may have any sign: a column
+ * outside [0, nk_blocks) is dark.  batch_stride / head_stride 0 share the mask between batch entries / query heads (h counts
+ * QUERY heads).  The mask must hold ceil(Sq / 128) rows per (batch entry, head).  A row without a visible key: out = 0,
+ * lse = +inf (-inf into lse_acc by acc_init; an accumulate call leaves it as it was), zero gradients; a call none of whose pairs
+ * is lit runs as a dark block does.  The mask gets no gradient.
+ * The kernels are the 8 x 32 forward, the 7-GEMM dQ kernel and the 128-key dK/dV kernel (csrc: the kBlk instances).  Their tile
+ * walks are list-driven: a forward / dQ workgroup (256 rows = two query blocks) visits only the 64-key tiles of blocks lit for
+ * one of its two query blocks, a dK/dV workgroup (128 keys = one column) only the (64-row Q/dO tile, query head) items lit in
+ * its column for that head.  They read the bytes themselves (64 at a time, kept as bits in scalar registers), so no packed
+ * form is needed: rfa_blockmask_workspace_bytes() is 0 and `workspace` is not looked at (leave it NULL).
+ * Served: dense input, head dims 8 .. 128 (multiples of 8), bf16 / fp16, GQA with at most 64 query heads per K/V head,
+ * causal / window / mask_shift, plain and accumulate outputs, the two-phase backward.  rfa_bwd_bm runs the base arguments'
+ * plan, which must say what the kernels are: dkdv_form = RFA_DKDV_128 and no ds_scratch — the contract of rfa_bwd_rr.
+ * dkdv_nsplit is ignored: that plan has no shares (one workgroup per key block walks all of the column's visited items).
+ * Checks, in this order, before any tensor pointer of the base struct is looked at: NULL args RFA_ERR_NULL; a NULL bm,
+ * struct_bytes below sizeof(rfa_blockmask_args) (or above it with a non-zero tail), a non-zero reserved RFA_ERR_ARGS;
+ * dropout_p > 0, cu_seqlens_q / cu_seqlens_k, q_half / k_half, (rfa_bwd_bm) a ds_scratch or a dkdv_form other than
+ * RFA_DKDV_128 RFA_ERR_ARGS; D above 128 RFA_ERR_HEAD_DIM; a negative stride or nk_blocks, nk_blocks above 2^31 - 1, k_blk0
+ * outside [-2^30, 2^30], more than 64 query heads per K/V head RFA_ERR_ARGS; then the checks of rfa_fwd / rfa_bwd in their
+ * order; then, where the call has work to do, a NULL mask RFA_ERR_NULL. */
+#define RFA_BLOCK_MASK_SIZE 128
+typedef struct {
+  uint32_t struct_bytes;       /* sizeof(rfa_blockmask_args) as the caller compiled it */
+  uint32_t reserved;           /* 0 */
+  const uint8_t *mask;         /* (Bm, Hm, ceil(Sq / 128), nk_blocks) bytes, non-zero = lit; column stride 1 */
+  int64_t batch_stride;        /* bytes between two batch entries (0 = broadcast) */
+  int64_t head_stride;         /* bytes between two query heads (0 = broadcast) */
+  int64_t row_stride;          /* bytes between two query blocks */
+  int64_t nk_blocks;           /* columns of a mask row: key blocks of the whole sequence */
+  int64_t k_blk0;              /* column of key row 0 of this block */
+  void *workspace;             /* rfa_blockmask_workspace_bytes() bytes (0 today: may be NULL) */
+} rfa_blockmask_args;
+int64_t rfa_blockmask_workspace_bytes(const rfa_bwd_args *args);
+int rfa_fwd_bm(const rfa_fwd_args *args, const rfa_blockmask_args *bm, void *stream);
+int rfa_bwd_bm(const rfa_bwd_args *args, const rfa_blockmask_args *bm, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -587,8 +587,35 @@ inline int rr_dim_check(int D, const RowRangeParams& r) {
   return RFA_OK;
 }
 
-// Dv = 0: one head dim (rfa_fwd, rfa_fwd_ex); else the V head dim of rfa_fwd_vd; rr: the row ranges of rfa_fwd_rr
-static int fwd_impl(const rfa_fwd_args* a, const rfa_ext_args* ext, int Dv, void* stream, const RowRangeParams* rr = nullptr);
+// ---- block-sparse masks (rfa.h: rfa_blockmask_args; the kBlk kernel instances) ------------------------------------------------
+// Parsed like the ranges: before any tensor pointer of the base struct is looked at; a longer struct while its tail is zero.
+inline int parse_bm(const rfa_blockmask_args* m, BlockMaskParams* out) {
+  if (m == nullptr || m->struct_bytes < sizeof(rfa_blockmask_args) || m->reserved != 0) return RFA_ERR_ARGS;
+  const unsigned char* src = reinterpret_cast<const unsigned char*>(m);
+  for (uint32_t i = sizeof(rfa_blockmask_args); i < m->struct_bytes; ++i)
+    if (src[i] != 0) return RFA_ERR_ARGS;
+  *out = BlockMaskParams{};
+  out->mask = m->mask;
+  out->bstride = m->batch_stride;
+  out->hstride = m->head_stride;
+  out->rstride = m->row_stride;
+  out->nk_blocks = (int)m->nk_blocks;
+  out->k_blk0 = (int)m->k_blk0;
+  return RFA_OK;
+}
+inline int bm_dim_check(int D, int H, int Hk, const rfa_blockmask_args* m) {
+  if (D > kHeadDim) return RFA_ERR_HEAD_DIM;
+  if (m->batch_stride < 0 || m->head_stride < 0 || m->row_stride < 0 || m->nk_blocks < 0 || m->nk_blocks > 0x7fffffff ||
+      m->k_blk0 < -0x40000000ll || m->k_blk0 > 0x40000000ll)
+    return RFA_ERR_ARGS;
+  if (Hk > 0 && H > 0 && H / Hk > kBmMaxGroup) return RFA_ERR_ARGS;     // (the dK/dV item walk: rfa_blockmask.h)
+  return RFA_OK;
+}
+
+// Dv = 0: one head dim (rfa_fwd, rfa_fwd_ex); else the V head dim of rfa_fwd_vd; rr: the row ranges of rfa_fwd_rr; bm: the
+// block mask of rfa_fwd_bm
+static int fwd_impl(const rfa_fwd_args* a, const rfa_ext_args* ext, int Dv, void* stream, const RowRangeParams* rr = nullptr,
+                    const BlockMaskParams* bm = nullptr);
 int rfa_fwd_ex(const rfa_fwd_args* a, const rfa_ext_args* ext, void* stream) { return fwd_impl(a, ext, 0, stream); }
 int rfa_fwd_vd(const rfa_fwd_args* a, const rfa_vdim_args* vd, void* stream) {
   if (!a) return RFA_ERR_NULL;
@@ -605,7 +632,17 @@ int rfa_fwd_rr(const rfa_fwd_args* a, const rfa_rowrange_args* rr, void* stream)
   return fwd_impl(a, nullptr, 0, stream, &r);
 }
 
-static int fwd_impl(const rfa_fwd_args* a, const rfa_ext_args* ext, int Dv, void* stream, const RowRangeParams* rr) {
+int rfa_fwd_bm(const rfa_fwd_args* a, const rfa_blockmask_args* bm, void* stream) {
+  if (!a) return RFA_ERR_NULL;
+  BlockMaskParams m;
+  if (int rc = parse_bm(bm, &m)) return rc;
+  if (int rc = rr_base_check(a->dropout_p, a->cu_seqlens_q, a->cu_seqlens_k, a->q_half, a->k_half)) return rc;
+  if (int rc = bm_dim_check(a->D, a->H, a->Hk, bm)) return rc;
+  return fwd_impl(a, nullptr, 0, stream, nullptr, &m);
+}
+
+static int fwd_impl(const rfa_fwd_args* a, const rfa_ext_args* ext, int Dv, void* stream, const RowRangeParams* rr,
+                    const BlockMaskParams* bm) {
   if (!a) return RFA_ERR_NULL;
   Ext e;
   if (int rce = parse_ext(ext, &e)) return rce;
@@ -683,8 +720,10 @@ static int fwd_impl(const rfa_fwd_args* a, const rfa_ext_args* ext, int Dv, void
   // RFA_FWD_AUTO / "never split" (`workspace` is ignored), as they do for dropout
   // (a soft cap likewise: the 256-row instances with or without a window)
   // (row ranges likewise: the windowed 256-row instances with kRng, never split)
-  const bool bias = e.slopes != nullptr || e.cap > 0.f || rr != nullptr;
+  // (a block mask likewise: the windowed 256-row instances with kBlk)
+  const bool bias = e.slopes != nullptr || e.cap > 0.f || rr != nullptr || bm != nullptr;
   if (rr != nullptr && (!rr->start || !rr->end)) return RFA_ERR_NULL;
+  if (bm != nullptr && !bm->mask) return RFA_ERR_NULL;
   if (e.slopes != nullptr) set_bias(p, e, a->softmax_scale);
   if (e.cap > 0.f) set_cap(p, e, a->softmax_scale);
   const FwdPlan plan = bias ? FwdPlan{fwd_qrows_per_block(), 1, 0} : fwd_plan(a);
@@ -728,6 +767,7 @@ static int fwd_impl(const rfa_fwd_args* a, const rfa_ext_args* ext, int Dv, void
   if (a->fwd_form < RFA_FWD_AUTO || a->fwd_form > RFA_FWD_P8x32 || a->fwd_form == RFA_FWD_RETIRED_2) return RFA_ERR_ARGS;
   if (Dv) return launch_status(launch_fwd_vd(p, Dv, a->dtype, (hipStream_t)stream));
   if (rr != nullptr) return launch_status(launch_fwd_rr(p, *rr, a->dtype, (hipStream_t)stream));
+  if (bm != nullptr) return launch_status(launch_fwd_bm(p, *bm, a->dtype, (hipStream_t)stream));
   if (a->D > kHeadDim) return launch_status(launch_fwd_big(p, a->dtype, (hipStream_t)stream));
   if (int rc2 = launch_fwd(p, a->dtype, (hipStream_t)stream)) return launch_status(rc2);
   if (ns > 1 && launch_combine(cb, a->dtype, (hipStream_t)stream)) return RFA_ERR_LAUNCH;
@@ -1103,7 +1143,23 @@ int rfa_bwd(const rfa_bwd_args* a, void* stream) { return rfa_bwd_ex(a, nullptr,
 
 // Dv = 0: one head dim (rfa_bwd, rfa_bwd_ex); else the V head dim of rfa_bwd_vd — the same plan, workspace layout (dV in D-wide
 // slots, Dv of them used) and dS hand-off, with the dK + dV and 7-GEMM dQ kernels of rfa_vdim.hip
-static int bwd_impl(const rfa_bwd_args* a, const rfa_ext_args* ext, int Dv, void* stream, const RowRangeParams* rr = nullptr);
+static int bwd_impl(const rfa_bwd_args* a, const rfa_ext_args* ext, int Dv, void* stream, const RowRangeParams* rr = nullptr,
+                    const BlockMaskParams* bm = nullptr);
+// (the kernels read the mask's bytes through windows of bits in scalar registers: no packed form, no workspace)
+int64_t rfa_blockmask_workspace_bytes(const rfa_bwd_args* a) {
+  (void)a;
+  return 0;
+}
+int rfa_bwd_bm(const rfa_bwd_args* a, const rfa_blockmask_args* bm, void* stream) {
+  if (!a) return RFA_ERR_NULL;
+  BlockMaskParams m;
+  if (int rc = parse_bm(bm, &m)) return rc;
+  if (int rc = rr_base_check(a->dropout_p, a->cu_seqlens_q, a->cu_seqlens_k, a->q_half, a->k_half)) return rc;
+  // the masked kernels are the 128-key dK/dV and the 7-GEMM dQ, and the base arguments must say so (as for rfa_bwd_rr)
+  if (a->ds_scratch != nullptr || a->dkdv_form != RFA_DKDV_128) return RFA_ERR_ARGS;
+  if (int rc = bm_dim_check(a->D, a->H, a->Hk, bm)) return rc;
+  return bwd_impl(a, nullptr, 0, stream, nullptr, &m);
+}
 int64_t rfa_rowrange_workspace_bytes(const rfa_bwd_args* a) {
   if (!a || a->B <= 0 || a->Sq <= 0) return 0;
   return (int64_t)a->B * ((a->Sq + kRrTileRows - 1) / kRrTileRows) * (int64_t)sizeof(int2);
@@ -1127,7 +1183,8 @@ int rfa_bwd_vd(const rfa_bwd_args* a, const rfa_vdim_args* vd, void* stream) {
   return bwd_impl(a, nullptr, Dv, stream);
 }
 
-static int bwd_impl(const rfa_bwd_args* a, const rfa_ext_args* ext, int Dv, void* stream, const RowRangeParams* rr) {
+static int bwd_impl(const rfa_bwd_args* a, const rfa_ext_args* ext, int Dv, void* stream, const RowRangeParams* rr,
+                    const BlockMaskParams* bm) {
   if (!a) return RFA_ERR_NULL;
   Ext e;
   if (int rce = parse_ext(ext, &e)) return rce;
@@ -1205,6 +1262,7 @@ static int bwd_impl(const rfa_bwd_args* a, const rfa_ext_args* ext, int Dv, void
     if (!rr->start || !rr->end || !rr->tile_bounds) return RFA_ERR_NULL;
     if (!aligned16(rr->tile_bounds)) return RFA_ERR_ALIGN;
   }
+  if (bm != nullptr && !bm->mask) return RFA_ERR_NULL;
   hipStream_t st = (hipStream_t)stream;
   BwdParams p{};
   p.dout = a->dout; p.q = a->q; p.k = a->k; p.v = a->v; p.lse = a->lse; p.delta = a->delta;
@@ -1327,10 +1385,10 @@ static int bwd_impl(const rfa_bwd_args* a, const rfa_ext_args* ext, int Dv, void
       mark(2);
     } else {
       if (!(a->phases & RFA_BWD_SKIP_DQ))
-        if (int rc2 = Dv ? launch_bwd_dq_vd(p, Dv, a->dtype, st) : rr ? launch_bwd_dq_rr(p, *rr, a->dtype, st) : launch_bwd_dq(p, a->dtype, st)) return launch_status(rc2);
+        if (int rc2 = Dv ? launch_bwd_dq_vd(p, Dv, a->dtype, st) : rr ? launch_bwd_dq_rr(p, *rr, a->dtype, st) : bm ? launch_bwd_dq_bm(p, *bm, a->dtype, st) : launch_bwd_dq(p, a->dtype, st)) return launch_status(rc2);
       mark(1);
       if (!(a->phases & RFA_BWD_SKIP_DKDV))
-        if (int rc2 = Dv ? launch_bwd_dkdv_vd(p, Dv, a->dtype, st) : rr ? launch_bwd_dkdv_rr(p, *rr, a->dtype, st) : launch_bwd_dkdv(p, a->dtype, st)) return launch_status(rc2);
+        if (int rc2 = Dv ? launch_bwd_dkdv_vd(p, Dv, a->dtype, st) : rr ? launch_bwd_dkdv_rr(p, *rr, a->dtype, st) : bm ? launch_bwd_dkdv_bm(p, *bm, a->dtype, st) : launch_bwd_dkdv(p, a->dtype, st)) return launch_status(rc2);
       mark(2);
     }
   } else {

@@ -98,8 +98,13 @@ template <int kD> constexpr int dq_smem() { return 4 * kDqKV * HeadGeo<kD>::kRow
 // log2 e) with softcap's exponent constant: no register lives across the GEMMs.  With or without a window; no dropout, no bias.
 // kRng: per-row key ranges (rfa.h: rfa_rowrange_args; rfa_rowrange.h), as in the forward — the lane's two bounds intersect the
 // band's in the mask, the workgroup's tile range is cut to the (min lo, max hi) of its rows.  The windowed instances only.
-template <typename T, int kD, bool kFullD, bool kWin, bool kDrop = false, bool kBias = false, bool kCap = false, bool kRng = false>
-__global__ __launch_bounds__(kDqThreads, 2) void dq_kernel(const std::conditional_t<kRng, BwdParamsRr, BwdParams> p) {
+// kBlk: a block-sparse mask (rfa.h: rfa_blockmask_args; rfa_blockmask.h), as in the forward — the workgroup walks the list of
+// key tiles lit for one of its two query blocks (LDS stage = position in the list & 1, the prefetch fetches the next visited
+// tile), a wave whose own query block is dark for a visited tile is not active.  The windowed instances only, not with kRng.
+template <typename T, int kD, bool kFullD, bool kWin, bool kDrop = false, bool kBias = false, bool kCap = false, bool kRng = false,
+          bool kBlk = false>
+__global__ __launch_bounds__(kDqThreads, 2) void dq_kernel(const bwd_params_t<kRng, kBlk> p) {
+  static_assert(!kBlk || (kWin && !kDrop && !kBias && !kCap && !kRng), "block masks: the windowed instances");
   static_assert(!kRng || (kWin && !kDrop && !kBias && !kCap), "row ranges: the windowed instances");
   static_assert(!kBias || (!kWin && !kDrop), "ALiBi: the instances without a window or dropout");
   static_assert(!kCap || (!kDrop && !kBias), "soft-capping: the instances without dropout or bias");
@@ -192,8 +197,34 @@ __global__ __launch_bounds__(kDqThreads, 2) void dq_kernel(const std::conditiona
   if (kRng && rr_wg_lo > kmin) kmin = rr_wg_lo;
   kmin = kmin > 0 ? (kmin < lk ? kmin : lk) : 0;          // (a shifted band may start behind the last key)
   const int jt0 = (kmin / kDqKV) & ~1;                  // first tile (even: LDS stage = j & 1)
+  // kBlk: the walk's state — the current window of 64 key blocks as bits (the union of the workgroup's two query blocks, and
+  // this wave's own), all in scalar registers — and the first visited tile; none: the existing empty path
+  uint64_t bm_u = 0, bm_m = 0;
+  int bm_w = -1, bm_j0 = 0, bm_n = 0;
+  bool bm_act0 = false;
+  auto bm_fill = [&](int w) {
+    if constexpr (kBlk) {
+      const int nqb = (lq + kBmBlock - 1) / kBmBlock, qb0 = 2 * qblk;
+      const uint8_t* r0 = p.bm.mask + (int64_t)b * p.bm.bstride + (int64_t)h * p.bm.hstride + (int64_t)qb0 * p.bm.rstride;
+      const bool a0 = bm_lit(r0, p.bm.nk_blocks, p.bm.k_blk0, 64 * w + lane);
+      const bool a1 = qb0 + 1 < nqb && bm_lit(r0 + p.bm.rstride, p.bm.nk_blocks, p.bm.k_blk0, 64 * w + lane);
+      const uint64_t m0 = __ballot(a0), m1 = __ballot(a1);
+      bm_m = wave < kDqWaves / 2 ? m0 : m1;
+      return bm_union(m0, m1);
+    } else {
+      return (uint64_t)0;
+    }
+  };
+  if constexpr (kBlk) {
+    const int j0 = bm_next_visited(bm_fill, bm_w, bm_u, kmin / kDqKV, ntiles);
+    if (j0 < ntiles) {
+      bm_j0 = j0;
+      bm_n = ntiles;
+      bm_act0 = bm_tile_lit(bm_m, bm_w, j0);
+    }
+  }
   // rows wholly outside the band (a block of a longer sequence: p.shift) add nothing to dq_acc: no tile, no store
-  if (jt0 >= ntiles && p.dq_acc != nullptr && !p.acc_init) return;
+  if ((kBlk ? bm_n == 0 : jt0 >= ntiles) && p.dq_acc != nullptr && !p.acc_init) return;
 
   const int sc = tid % kChunks;
   const int sr = tid / kChunks;
@@ -285,22 +316,26 @@ __global__ __launch_bounds__(kDqThreads, 2) void dq_kernel(const std::conditiona
 
   typedef std::integral_constant<int, 0> stage0_t;
   typedef std::integral_constant<int, 1> stage1_t;
-  load_tile(jt0, stage0_t{});   // unconditional (rows past the end read as zero): one path into the loop
+  load_tile(kBlk ? bm_j0 : jt0, stage0_t{});   // unconditional (rows past the end read as zero): one path into the loop
   write_tile(stage0_t{});
   wait_all_vmem();
   __syncthreads();
 
   // One KV tile.  The LDS stage is a compile-time constant (the tile loop is unrolled by two), so every
   // LDS address in here is a per-lane table entry plus an instruction immediate: no address arithmetic.
-  auto tile_step = [&](int j, auto stage) {
+  // (jn: the tile fetched now — j + 1, kBlk: the next visited one, ntiles if none; act: kBlk, this wave's query block sees tile j)
+  // ahead(): kBlk, the walk's next step — behind the prefetch's issue, so that its scalar chain runs beside the tile's MFMAs
+  auto tile_step = [&](int j, int jn, bool act, auto stage, auto&& ahead) {
     constexpr int kStage = decltype(stage)::value;
     constexpr int kbo = kStage * kDqTileBytes;            // K stage
     constexpr int vbo = (2 + kStage) * kDqTileBytes;      // V stage
     typedef std::integral_constant<int, kStage ^ 1> next_t;
-    if (j + 1 < ntiles) load_tile(j + 1, next_t{});
+    if (kBlk ? jn < bm_n : j + 1 < ntiles) load_tile(kBlk ? jn : j + 1, next_t{});
+    ahead();
     const int kt0 = j * kDqKV;
-    const bool active = (qw0 < lq) && !(hi && kt0 > qw0 + 31 + off + wr) &&
-                        !(lo && kt0 + kDqKV - 1 < qw0 + off - wl) && (!kRng || (kt0 < rr_w.hi && kt0 + kDqKV > rr_w.lo));
+    const bool active_b = (qw0 < lq) && !(hi && kt0 > qw0 + 31 + off + wr) &&
+                          !(lo && kt0 + kDqKV - 1 < qw0 + off - wl) && (!kRng || (kt0 < rr_w.hi && kt0 + kDqKV > rr_w.lo));
+    const bool active = kBlk ? (active_b && act) : active_b;
     if (active) {
       const bool need_mask = (kt0 + kDqKV > lk) || (hi && kt0 + kDqKV - 1 > qw0 + off + wr) ||
                              (lo && kt0 < qw0 + 31 + off - wl);
@@ -403,13 +438,34 @@ __global__ __launch_bounds__(kDqThreads, 2) void dq_kernel(const std::conditiona
         }
       }
     }
-    if (j + 1 < ntiles) write_tile(next_t{});
+    if (kBlk ? jn < bm_n : j + 1 < ntiles) write_tile(next_t{});
     if (kDma) wait_all_vmem();                           // the DMA of tile j+1 must have landed before the barrier
     __syncthreads();
   };
-  for (int j = jt0; j < ntiles; j += 2) {
-    tile_step(j, stage0_t{});
-    if (j + 1 < ntiles) tile_step(j + 1, stage1_t{});
+  if constexpr (kBlk) {
+    // (j: the tile computed, jn: the one fetched meanwhile, jnn: the one after it, found while tile j is computed)
+    int j = bm_j0, jn = bm_n, jnn = bm_n;
+    bool act = bm_act0, actn = false, actnn = false;
+    if (j < bm_n) {
+      jn = bm_next_visited(bm_fill, bm_w, bm_u, j + 1, bm_n);
+      actn = bm_tile_lit(bm_m, bm_w, jn);
+    }
+    auto ahead = [&]() {
+      jnn = jn < bm_n ? bm_next_visited(bm_fill, bm_w, bm_u, jn + 1, bm_n) : bm_n;
+      actnn = bm_tile_lit(bm_m, bm_w, jnn);
+    };
+    while (j < bm_n) {
+      tile_step(j, jn, act, stage0_t{}, ahead);
+      if (jn >= bm_n) break;
+      j = jn; act = actn; jn = jnn; actn = actnn;
+      tile_step(j, jn, act, stage1_t{}, ahead);
+      j = jn; act = actn; jn = jnn; actn = actnn;
+    }
+  } else {
+    for (int j = jt0; j < ntiles; j += 2) {
+      tile_step(j, j + 1, true, stage0_t{}, [] {});
+      if (j + 1 < ntiles) tile_step(j + 1, j + 2, true, stage1_t{}, [] {});
+    }
   }
 
   if (qrow >= lq) return;
@@ -483,8 +539,13 @@ template <int kD, bool kRng = false> constexpr int kv_smem() {        // 129 KiB
 // kCap: logit soft-capping, as in dq_kernel (the 128-key instances with or without a window; dp is dO V^T - delta when the
 // factor 1 - t^2 is applied)
 template <typename T, int kD, bool kFullD, bool kSpill, bool kWin, bool kWide, bool kDrop = false, bool kBal = false, bool kMap = false,
-          bool kBias = false, bool kCap = false, bool kRng = false>
-__global__ __launch_bounds__(kKvThreads, 2) void dkdv_kernel(const std::conditional_t<kRng, BwdParamsRr, BwdParams> p) {
+          bool kBias = false, bool kCap = false, bool kRng = false, bool kBlk = false>
+__global__ __launch_bounds__(kKvThreads, 2) void dkdv_kernel(const bwd_params_t<kRng, kBlk> p) {
+  // kBlk: a block-sparse mask (rfa.h: rfa_blockmask_args; rfa_blockmask.h).  The workgroup's 128 keys are one key block, a
+  // column of the mask; it walks the (Q/dO tile, query head) items lit in that column FOR THAT HEAD — tiles from the top down,
+  // the heads of a tile upward, as the dense walk does — from a window of bits in scalar registers (bm_item_prev).  An item
+  // is wholly lit: no predicate beside the band's.  The windowed 128-key instances only, not with kRng.
+  static_assert(!kBlk || (kWin && !kSpill && !kWide && !kDrop && !kBias && !kCap && !kRng), "block masks: the windowed 128-key instances");
   // kRng: per-row key ranges (rfa.h: rfa_rowrange_args; rfa_rowrange.h).  This kernel owns keys: the rows' bounds of a Q/dO
   // tile travel like lse and delta (waves 2 and 3 stage them, rebased and clamped, behind the two statistics) and enter the
   // mask; the tile walk visits only the tiles whose (min lo, max hi) pair — p.rr.tile_bounds, made by rowrange_bounds_kernel —
@@ -639,6 +700,29 @@ __global__ __launch_bounds__(kKvThreads, 2) void dkdv_kernel(const std::conditio
     ntile_q = __builtin_amdgcn_readfirstlane(cnt);
     rr_bot = __builtin_amdgcn_readfirstlane(bot);
   }
+  // kBlk: the walk's window (even / odd tiles of 64 / Gp query blocks x Gp heads), the count of visited items and the first
+  uint64_t bm_we = 0, bm_wo = 0;
+  int bm_w = -1, bm_cnt = 0, bm_jn = 0;
+  const int bm_gpw = kBlk ? bm_gp(G) : 1;
+  auto bm_fill = [&](int wq, uint64_t& we, uint64_t& wo) {
+    if constexpr (kBlk) {
+      const BmCol col = bm_col(p.bm.mask + (int64_t)b * p.bm.bstride + (int64_t)h0 * p.bm.hstride, p.bm.hstride, p.bm.rstride,
+                               (lq + kBmBlock - 1) / kBmBlock, p.bm.nk_blocks, p.bm.k_blk0, kblk);
+      we = __ballot(bm_item_lit(col, G, bm_gpw, wq, lane, 0, jt0, jt1));
+      wo = __ballot(bm_item_lit(col, G, bm_gpw, wq, lane, 1, jt0, jt1));
+    }
+  };
+  BmItem bm_it{-1, 0};
+  if constexpr (kBlk) {
+    const int per = 64 / bm_gpw;
+    for (int wq = (jt0 >> 1) / per; 2 * wq * per < jt1; ++wq) {
+      uint64_t we, wo;
+      bm_fill(wq, we, wo);
+      bm_cnt += bm_item_count(we, wo);
+    }
+    bm_it = bm_item_prev(bm_fill, bm_w, bm_we, bm_wo, bm_gpw, bm_walk_start(jt1), 64, jt0);
+    jtop = bm_it.j;
+  }
   auto rr_prev = [&](int jj) {                         // the next visited tile below jj (below rr_bot: none left)
     if constexpr (kRng) {
       int2 pr;
@@ -728,7 +812,7 @@ __global__ __launch_bounds__(kKvThreads, 2) void dkdv_kernel(const std::conditio
   // time, so the (kv head = XCD) L2 serves a tile to all co-resident key blocks.  (Walking upward from
   // jt0, head after head, spreads them over the whole sequence and every tile is re-fetched from HBM per
   // workgroup: 3.5x the fabric traffic, measured.)
-  int ld_g = 0, ld_j = jtop > 0 ? jtop : 0;           // (head in group, tile) the next load_tile() fetches
+  int ld_g = kBlk ? bm_it.g : 0, ld_j = jtop > 0 ? jtop : 0;   // (head in group, tile) the next load_tile() fetches
   int ld_c = 0;                                       // kBal: tiles the loader has finished
   // Round 6 (second session): the loader's addresses are RUNNING 64-bit scalars — the next head of the tile is one add, a
   // new tile one multiply — instead of four base + head * stride + tile * 64 * stride products per tile-step.  The loop
@@ -746,12 +830,26 @@ __global__ __launch_bounds__(kKvThreads, 2) void dkdv_kernel(const std::conditio
   const T* ld_q = qbase0 + ld_j * q_tile_e;
   const T* ld_do = dobase0 + ld_j * do_tile_e;
   const float* ld_st = st_base0 + ld_j * kKvQ;
+  if constexpr (kBlk) {                                // (the first item's head)
+    ld_q += ld_g * p.q_st.head;
+    ld_do += ld_g * p.dout_st.head;
+    ld_st += ld_g * st_head_e;
+  }
   auto load_tile = [&]() {
     const int j = RFA_KV_X_LOAD == 2 ? 0 : ld_j;       // (2: measurement, every load hits the same hot tile)
     const T* qtile = RFA_KV_X_LOAD == 2 ? qbase0 : ld_q;
     const T* dotile = RFA_KV_X_LOAD == 2 ? dobase0 : ld_do;
     const float* sttile = ld_st;
-    if (++ld_g >= G) {
+    if constexpr (kBlk) {
+      // the item behind this one in the mask's column (none: the loader is not called again)
+      bm_jn = ld_j;                                    // the tile of the item in flight: what the tile loop computes next
+      const BmItem it = bm_item_prev(bm_fill, bm_w, bm_we, bm_wo, bm_gpw, ld_j, ld_g, jt0);
+      ld_j = it.j > 0 ? it.j : 0;
+      ld_g = it.g;
+      ld_q = qbase0 + ld_j * q_tile_e + ld_g * p.q_st.head;
+      ld_do = dobase0 + ld_j * do_tile_e + ld_g * p.dout_st.head;
+      ld_st = st_base0 + ld_j * kKvQ + ld_g * st_head_e;
+    } else if (++ld_g >= G) {
       ld_g = 0;
       if (kBal) {
         ++ld_c;
@@ -879,7 +977,7 @@ __global__ __launch_bounds__(kKvThreads, 2) void dkdv_kernel(const std::conditio
 #elif RFA_KV_PRIO == 2
   if (wave >= kKvWaves / 2) __builtin_amdgcn_s_setprio(1);   // the half dispatched second (loses every VALU arbitration)
 #endif
-  const int ntile = ntile_q * G;
+  const int ntile = kBlk ? bm_cnt : ntile_q * G;
   int j = jtop, cg = 0, jc = 0;
   // dS scratch rows of tile j's two sub-tiles (blocks from the head's base: formed when j changes, not per tile-step) and
   // the base of the current head's share of the scratch
@@ -887,6 +985,7 @@ __global__ __launch_bounds__(kKvThreads, 2) void dkdv_kernel(const std::conditio
   int ds_rlen0 = kSpill ? ds_rowlen(p, 2 * j, ds_nkb) : 0;
   const char* ds_hp = ds_b;
   for (int f = 0; f < ntile; ++f) {
+    if constexpr (kBlk) j = bm_jn;                     // (the walk is the loader's: the item it fetched last is computed now)
     if (RFA_KV_X_LOAD && f + 1 < ntile) load_tile();
     int nact = 0;                                      // sub-tiles this wave computed (= pairs of spill stores issued)
     bool active = false;
@@ -1301,13 +1400,14 @@ __global__ __launch_bounds__(kKvThreads, 2) void dkdv_kernel(const std::conditio
   }   // segment loop
 }
 
-template <typename T, int kD, bool kFullD, bool kWin, bool kDrop = false, bool kBias = false, bool kCap = false, bool kRng = false>
-static int launch_dq_t(const std::conditional_t<kRng, BwdParamsRr, BwdParams>& p, hipStream_t stream) {
+template <typename T, int kD, bool kFullD, bool kWin, bool kDrop = false, bool kBias = false, bool kCap = false, bool kRng = false,
+          bool kBlk = false>
+static int launch_dq_t(const bwd_params_t<kRng, kBlk>& p, hipStream_t stream) {
   static std::atomic<unsigned long long> attr_done{0};
-  if (int rc = opt_in_dynamic_lds((const void*)dq_kernel<T, kD, kFullD, kWin, kDrop, kBias, kCap, kRng>, dq_smem<kD>(), attr_done)) return rc;
+  if (int rc = opt_in_dynamic_lds((const void*)dq_kernel<T, kD, kFullD, kWin, kDrop, kBias, kCap, kRng, kBlk>, dq_smem<kD>(), attr_done)) return rc;
   const int64_t nblocks = (int64_t)p.nqblk * p.H * p.B;
   if (nblocks <= 0) return 0;
-  hipLaunchKernelGGL((dq_kernel<T, kD, kFullD, kWin, kDrop, kBias, kCap, kRng>), dim3((unsigned)nblocks), dim3(kDqThreads), dq_smem<kD>(), stream, p);
+  hipLaunchKernelGGL((dq_kernel<T, kD, kFullD, kWin, kDrop, kBias, kCap, kRng, kBlk>), dim3((unsigned)nblocks), dim3(kDqThreads), dq_smem<kD>(), stream, p);
   return hipGetLastError() == hipSuccess ? kLaunchOk : kLaunchFailed;
 }
 
@@ -1317,10 +1417,10 @@ __global__ void zero_words_kernel(unsigned* w, int n) {
 }
 
 template <typename T, int kD, bool kFullD, bool kSpill, bool kWin, bool kWide = false, bool kDrop = false, bool kBal = false, bool kMap = false,
-          bool kBias = false, bool kCap = false, bool kRng = false>
-static int launch_dkdv_t(const std::conditional_t<kRng, BwdParamsRr, BwdParams>& p, hipStream_t stream) {
+          bool kBias = false, bool kCap = false, bool kRng = false, bool kBlk = false>
+static int launch_dkdv_t(const bwd_params_t<kRng, kBlk>& p, hipStream_t stream) {
   static std::atomic<unsigned long long> attr_done{0};
-  if (int rc = opt_in_dynamic_lds((const void*)dkdv_kernel<T, kD, kFullD, kSpill, kWin, kWide, kDrop, kBal, kMap, kBias, kCap, kRng>, kv_smem<kD, kRng>(), attr_done)) return rc;
+  if (int rc = opt_in_dynamic_lds((const void*)dkdv_kernel<T, kD, kFullD, kSpill, kWin, kWide, kDrop, kBal, kMap, kBias, kCap, kRng, kBlk>, kv_smem<kD, kRng>(), attr_done)) return rc;
   // one workgroup per (key block, K/V head) [x tile-range split of the 256-key form]
   const int64_t nblocks = (int64_t)p.nkblk * p.Hk * p.B * ((kWide && !kBal) ? p.nsplit : 1);
   if (nblocks <= 0) return 0;
@@ -1332,7 +1432,7 @@ static int launch_dkdv_t(const std::conditional_t<kRng, BwdParamsRr, BwdParams>&
     hipLaunchKernelGGL(zero_words_kernel, dim3((unsigned)((nflags + 255) / 256)), dim3(256), 0, stream, p.pair_flags, nflags);
     if (hipGetLastError() != hipSuccess) return kLaunchFailed;
   }
-  hipLaunchKernelGGL((dkdv_kernel<T, kD, kFullD, kSpill, kWin, kWide, kDrop, kBal, kMap, kBias, kCap, kRng>), dim3((unsigned)nblocks), dim3(kKvThreads), (kv_smem<kD, kRng>()), stream, p);
+  hipLaunchKernelGGL((dkdv_kernel<T, kD, kFullD, kSpill, kWin, kWide, kDrop, kBal, kMap, kBias, kCap, kRng, kBlk>), dim3((unsigned)nblocks), dim3(kKvThreads), (kv_smem<kD, kRng>()), stream, p);
   return hipGetLastError() == hipSuccess ? kLaunchOk : kLaunchFailed;
 }
 
@@ -1380,6 +1480,34 @@ int launch_bwd_dkdv_rr(const BwdParams& p, const RowRangeParams& r, int dtype, h
     if (hipGetLastError() != hipSuccess) return kLaunchFailed;
   }
   return dtype == 0 ? launch_dkdv_rng<bf16_t>(pr, stream) : launch_dkdv_rng<f16_t>(pr, stream);
+}
+
+// ---- block-sparse masks: the launchers of the kBlk instances (the same four layouts as the ranged ones) -------------------------
+template <typename T>
+static int launch_dq_blk(const BwdParamsBm& p, hipStream_t stream) {
+  if (p.D == 128) return launch_dq_t<T, 128, true, true, false, false, false, false, true>(p, stream);
+  if (p.D > 64) return launch_dq_t<T, 128, false, true, false, false, false, false, true>(p, stream);
+  if (p.D == 64) return launch_dq_t<T, 64, true, true, false, false, false, false, true>(p, stream);
+  return launch_dq_t<T, 64, false, true, false, false, false, false, true>(p, stream);
+}
+template <typename T>
+static int launch_dkdv_blk(const BwdParamsBm& p, hipStream_t stream) {
+  if (p.D == 128) return launch_dkdv_t<T, 128, true, false, true, false, false, false, false, false, false, false, true>(p, stream);
+  if (p.D > 64) return launch_dkdv_t<T, 128, false, false, true, false, false, false, false, false, false, false, true>(p, stream);
+  if (p.D == 64) return launch_dkdv_t<T, 64, true, false, true, false, false, false, false, false, false, false, true>(p, stream);
+  return launch_dkdv_t<T, 64, false, false, true, false, false, false, false, false, false, false, true>(p, stream);
+}
+int launch_bwd_dq_bm(const BwdParams& p, const BlockMaskParams& m, int dtype, hipStream_t stream) {
+  BwdParamsBm pb;
+  static_cast<BwdParams&>(pb) = p;
+  pb.bm = m;
+  return dtype == 0 ? launch_dq_blk<bf16_t>(pb, stream) : launch_dq_blk<f16_t>(pb, stream);
+}
+int launch_bwd_dkdv_bm(const BwdParams& p, const BlockMaskParams& m, int dtype, hipStream_t stream) {
+  BwdParamsBm pb;
+  static_cast<BwdParams&>(pb) = p;
+  pb.bm = m;
+  return dtype == 0 ? launch_dkdv_blk<bf16_t>(pb, stream) : launch_dkdv_blk<f16_t>(pb, stream);
 }
 
 template <typename T, bool kWin, bool kDrop>

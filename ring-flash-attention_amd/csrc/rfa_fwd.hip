@@ -99,9 +99,16 @@ template <int kD> constexpr int fwd_smem() { return 2 * kFwdStages * kFwdKV * He
 // kRng: per-row key ranges (rfa.h: rfa_rowrange_args; rfa_rowrange.h) — each lane holds its row's two bounds, rebased by k_pos0
 // and clamped to the block; they intersect the band's bounds in the mask, and the workgroup's tile range is cut to the
 // (min lo, max hi) of its rows.  Built on the windowed 256-row instances; no dropout, bias or cap.
+// kBlk: a block-sparse mask (rfa.h: rfa_blockmask_args; rfa_blockmask.h) — one byte per (128 query rows, 128 keys).  The tile
+// walk is list-driven: the workgroup visits only the key tiles of blocks lit for one of its two query blocks (waves 0 - 3 hold
+// the first, 4 - 7 the second), the LDS stage is the position in that list modulo the ring depth, the prefetch fetches the
+// next VISITED tile, and a wave whose own query block is dark for a visited tile is not active.  Every (wave, tile) pair is
+// wholly lit or dark: no per-element predicate, the band's mask is untouched.  Built like kRng; not together with it.
 template <typename T, int kD, bool kFullD, bool kWin, bool kDrop = false, int kW = kFwdWavesMax, bool kBias = false, bool kCap = false,
-          bool kRng = false>
-__global__ __launch_bounds__(kW * 64, 2) void fwd_kernel(const std::conditional_t<kRng, FwdParamsRr, FwdParams> p) {
+          bool kRng = false, bool kBlk = false>
+__global__ __launch_bounds__(kW * 64, 2) void fwd_kernel(const fwd_params_t<kRng, kBlk> p) {
+  static_assert(!kBlk || (kWin && !kDrop && !kBias && !kCap && !kRng && kW == kFwdWavesMax && kFwdStages == 2),
+                "block masks: the windowed 256-row instances, two LDS stages");
   static_assert(!kRng || (kWin && !kDrop && !kBias && !kCap && kW == kFwdWavesMax), "row ranges: the windowed 256-row instances");
   static_assert(!kBias || (!kWin && !kDrop), "ALiBi: the instances without a window or dropout");
   static_assert(!kCap || (!kDrop && !kBias && kW == kFwdWavesMax), "soft-capping: the 256-row instances without dropout or bias");
@@ -195,6 +202,34 @@ __global__ __launch_bounds__(kW * 64, 2) void fwd_kernel(const std::conditional_
     jt0 = rt.jt0;
     ntiles = rt.ntiles;
   }
+  // kBlk: the walk's state — the current window of 64 key blocks as bits (the union of the workgroup's two query blocks, and
+  // this wave's own), all in scalar registers — and the first visited tile; none: the path of a dark block
+  uint64_t bm_u = 0, bm_m = 0;
+  int bm_w = -1;
+  bool bm_act0 = false;
+  auto bm_fill = [&](int w) {
+    if constexpr (kBlk) {
+      const int nqb = (lq + kBmBlock - 1) / kBmBlock, qb0 = 2 * qblk;
+      const uint8_t* r0 = p.bm.mask + (int64_t)b * p.bm.bstride + (int64_t)h * p.bm.hstride + (int64_t)qb0 * p.bm.rstride;
+      const bool a0 = bm_lit(r0, p.bm.nk_blocks, p.bm.k_blk0, 64 * w + lane);
+      const bool a1 = qb0 + 1 < nqb && bm_lit(r0 + p.bm.rstride, p.bm.nk_blocks, p.bm.k_blk0, 64 * w + lane);
+      const uint64_t m0 = __ballot(a0), m1 = __ballot(a1);
+      bm_m = wave < kFwdWaves / 2 ? m0 : m1;
+      return bm_union(m0, m1);
+    } else {
+      return (uint64_t)0;
+    }
+  };
+  if constexpr (kBlk) {
+    const int j0 = bm_next_visited(bm_fill, bm_w, bm_u, kmin / kFwdKV, ntiles);
+    if (j0 < ntiles) {
+      jt0 = j0;
+      bm_act0 = bm_tile_lit(bm_m, bm_w, j0);
+    } else {
+      jt0 = 0;
+      ntiles = 0;
+    }
+  }
   if (nsplit > 1) {
     // this workgroup's contiguous share of the tiles [jt0, ntiles), a multiple of the ring depth long (stage = j % stages)
     int chunk = (ntiles - jt0 + nsplit - 1) / nsplit;
@@ -240,8 +275,13 @@ __global__ __launch_bounds__(kW * 64, 2) void fwd_kernel(const std::conditional_
     const int nv = rows > 0 ? ((rows - 1) * (int)p.v_st.row + p.D) * 2 : 0;
     const T* kt = ld_k;
     const T* vt = ld_v;
-    ld_k += k_tile_e;
-    ld_v += v_tile_e;
+    if constexpr (kBlk) {                      // (a visited list jumps: base + tile * stride)
+      kt = kbase + j * k_tile_e;
+      vt = vbase + j * v_tile_e;
+    } else {
+      ld_k += k_tile_e;
+      ld_v += v_tile_e;
+    }
     if (kDma) {
       const dma_rsrc_t rk = make_dma_rsrc(kt, nk), rv = make_dma_rsrc(vt, nv);
 #pragma unroll
@@ -334,18 +374,22 @@ __global__ __launch_bounds__(kW * 64, 2) void fwd_kernel(const std::conditional_
 
   // One KV tile.  The LDS stage is a compile-time constant (the tile loop is unrolled by the ring depth),
   // so every LDS address in here is a per-lane table entry plus an instruction immediate.
-  auto tile_step = [&](int j, auto stage) {
+  // (jn: the tile fetched now — j + kDist, kBlk: the next visited one, ntiles if none; act: kBlk, this wave's query block sees tile j)
+  // ahead(): kBlk, the walk's next step — behind the prefetch's issue, so that its scalar chain runs beside the tile's MFMAs
+  auto tile_step = [&](int j, int jn, bool act, auto stage, auto&& ahead) {
     constexpr int kStage = decltype(stage)::value;
     constexpr int kbo = kStage * kFwdTileBytes;                   // K stage
     constexpr int vbo = kStage * kFwdTileBytes;                   // V stage, relative to the V region (whose base is part of voff)
     typedef std::integral_constant<int, (kStage + kDist) % kFwdStages> fill_t;   // stage refilled now
     typedef std::integral_constant<int, (kStage + 1) % kFwdStages> next_t;
-    const bool more = j + kDist < ntiles;
-    if (more) load_tile(j + kDist, fill_t{});
+    const bool more = jn < ntiles;
+    if (more) load_tile(jn, fill_t{});
+    ahead();
 
     const int kt0 = j * kFwdKV;
-    const bool active = (qw0 < lq) && !(hi && kt0 > qw0 + 31 + off + wr) &&
-                        !(lo && kt0 + kFwdKV - 1 < qw0 + off - wl) && (!kRng || (kt0 < rr_w.hi && kt0 + kFwdKV > rr_w.lo));
+    const bool active_b = (qw0 < lq) && !(hi && kt0 > qw0 + 31 + off + wr) &&
+                          !(lo && kt0 + kFwdKV - 1 < qw0 + off - wl) && (!kRng || (kt0 < rr_w.hi && kt0 + kFwdKV > rr_w.lo));
+    const bool active = kBlk ? (active_b && act) : active_b;
     if (active) {
       // ---------------- S^T = K Q^T ----------------
       f32x16 s[kFwdSub];
@@ -530,16 +574,36 @@ __global__ __launch_bounds__(kW * 64, 2) void fwd_kernel(const std::conditional_
     }
     __syncthreads();
   };
-  if (kFwdStages == 3) {
+  if constexpr (kBlk) {
+    // the visited list, two entries per trip (stage = position in the list modulo the ring depth)
+    // (j: the tile computed, jn: the one fetched meanwhile, jnn: the one after it, found while tile j is computed)
+    int j = jt0, jn = ntiles, jnn = ntiles;
+    bool act = bm_act0, actn = false, actnn = false;
+    if (j < ntiles) {
+      jn = bm_next_visited(bm_fill, bm_w, bm_u, j + 1, ntiles);
+      actn = bm_tile_lit(bm_m, bm_w, jn);
+    }
+    auto ahead = [&]() {
+      jnn = jn < ntiles ? bm_next_visited(bm_fill, bm_w, bm_u, jn + 1, ntiles) : ntiles;
+      actnn = bm_tile_lit(bm_m, bm_w, jnn);
+    };
+    while (j < ntiles) {
+      tile_step(j, jn, act, std::integral_constant<int, 0>{}, ahead);
+      if (jn >= ntiles) break;
+      j = jn; act = actn; jn = jnn; actn = actnn;
+      tile_step(j, jn, act, std::integral_constant<int, 1>{}, ahead);
+      j = jn; act = actn; jn = jnn; actn = actnn;
+    }
+  } else if (kFwdStages == 3) {
     for (int j = jt0; j < ntiles; j += 3) {
-      tile_step(j, std::integral_constant<int, 0>{});
-      if (j + 1 < ntiles) tile_step(j + 1, std::integral_constant<int, 1>{});
-      if (j + 2 < ntiles) tile_step(j + 2, std::integral_constant<int, 2 % kFwdStages>{});
+      tile_step(j, j + kDist, true, std::integral_constant<int, 0>{}, [] {});
+      if (j + 1 < ntiles) tile_step(j + 1, j + 1 + kDist, true, std::integral_constant<int, 1>{}, [] {});
+      if (j + 2 < ntiles) tile_step(j + 2, j + 2 + kDist, true, std::integral_constant<int, 2 % kFwdStages>{}, [] {});
     }
   } else {
     for (int j = jt0; j < ntiles; j += 2) {
-      tile_step(j, std::integral_constant<int, 0>{});
-      if (j + 1 < ntiles) tile_step(j + 1, std::integral_constant<int, 1>{});
+      tile_step(j, j + kDist, true, std::integral_constant<int, 0>{}, [] {});
+      if (j + 1 < ntiles) tile_step(j + 1, j + 1 + kDist, true, std::integral_constant<int, 1>{}, [] {});
     }
   }
 
@@ -959,13 +1023,13 @@ static int launch_fwd_persist(const FwdParams& p, hipStream_t stream) {
 }
 
 template <typename T, int kD, bool kFullD, bool kWin, bool kDrop = false, int kW = kFwdWavesMax, bool kBias = false, bool kCap = false,
-          bool kRng = false>
-static int launch_fwd_w(const std::conditional_t<kRng, FwdParamsRr, FwdParams>& p, hipStream_t stream) {
+          bool kRng = false, bool kBlk = false>
+static int launch_fwd_w(const fwd_params_t<kRng, kBlk>& p, hipStream_t stream) {
   static std::atomic<unsigned long long> attr_done{0};
-  if (int rc = opt_in_dynamic_lds((const void*)fwd_kernel<T, kD, kFullD, kWin, kDrop, kW, kBias, kCap, kRng>, fwd_smem<kD>(), attr_done)) return rc;
+  if (int rc = opt_in_dynamic_lds((const void*)fwd_kernel<T, kD, kFullD, kWin, kDrop, kW, kBias, kCap, kRng, kBlk>, fwd_smem<kD>(), attr_done)) return rc;
   const int64_t nblocks = (int64_t)p.nqblk * p.H * p.B * (p.kv_nsplit > 1 ? p.kv_nsplit : 1);
   if (nblocks <= 0) return 0;
-  hipLaunchKernelGGL((fwd_kernel<T, kD, kFullD, kWin, kDrop, kW, kBias, kCap, kRng>), dim3((unsigned)nblocks), dim3(kW * 64), fwd_smem<kD>(), stream, p);
+  hipLaunchKernelGGL((fwd_kernel<T, kD, kFullD, kWin, kDrop, kW, kBias, kCap, kRng, kBlk>), dim3((unsigned)nblocks), dim3(kW * 64), fwd_smem<kD>(), stream, p);
   return hipGetLastError() == hipSuccess ? kLaunchOk : kLaunchFailed;
 }
 template <typename T, int kD, bool kFullD, bool kWin, bool kDrop = false>
@@ -1023,6 +1087,21 @@ int launch_fwd_rr(const FwdParams& p, const RowRangeParams& r, int dtype, hipStr
   static_cast<FwdParams&>(pr) = p;
   pr.rr = r;
   return dtype == 0 ? launch_fwd_rng<bf16_t>(pr, stream) : launch_fwd_rng<f16_t>(pr, stream);
+}
+
+// block-sparse masks (rfa_api.cpp: the conditions of the ranged call): the windowed instances with kBlk, the same four layouts
+template <typename T>
+static int launch_fwd_blk(const FwdParamsBm& p, hipStream_t stream) {
+  if (p.D == 128) return launch_fwd_w<T, 128, true, true, false, kFwdWavesMax, false, false, false, true>(p, stream);
+  if (p.D > 64) return launch_fwd_w<T, 128, false, true, false, kFwdWavesMax, false, false, false, true>(p, stream);
+  if (p.D == 64) return launch_fwd_w<T, 64, true, true, false, kFwdWavesMax, false, false, false, true>(p, stream);
+  return launch_fwd_w<T, 64, false, true, false, kFwdWavesMax, false, false, false, true>(p, stream);
+}
+int launch_fwd_bm(const FwdParams& p, const BlockMaskParams& m, int dtype, hipStream_t stream) {
+  FwdParamsBm pb;
+  static_cast<FwdParams&>(pb) = p;
+  pb.bm = m;
+  return dtype == 0 ? launch_fwd_blk<bf16_t>(pb, stream) : launch_fwd_blk<f16_t>(pb, stream);
 }
 
 int launch_fwd(const FwdParams& p, int dtype, hipStream_t stream) {

@@ -6,8 +6,10 @@
 #include "rfa_seqhead_index.h"
 #include "rfa_maxlogit_band.h"
 #include "rfa_rowrange.h"
+#include "rfa_blockmask.h"
 
 #include <atomic>
+#include <type_traits>
 
 namespace rfa {
 
@@ -332,6 +334,29 @@ constexpr bool kRngPadded128 = true;           // the zero-padded 128-wide dK/dV
 int launch_fwd_rr(const FwdParams& p, const RowRangeParams& r, int dtype, hipStream_t stream);
 int launch_bwd_dq_rr(const BwdParams& p, const RowRangeParams& r, int dtype, hipStream_t stream);
 int launch_bwd_dkdv_rr(const BwdParams& p, const RowRangeParams& r, int dtype, hipStream_t stream);   // (fills tile_bounds first)
+
+// block-sparse masks (rfa.h: rfa_blockmask_args; arithmetic: rfa_blockmask.h): the kBlk instances of the same three kernels —
+// one byte per (query block, key block) pair of 128 x 128 positions; the tile walks become list-driven.  As above, the block
+// travels behind the parameter block of before, whose layout (and every other kernel's kernarg) stays as it is.
+struct BlockMaskParams {
+  const uint8_t* mask;          // (Bm, Hm, nq blocks, nk_blocks) bytes, non-zero = lit
+  int64_t bstride, hstride;     // bytes between two batch entries / query heads (0: shared)
+  int64_t rstride;              // bytes between two query blocks
+  int nk_blocks;                // columns of the mask: key blocks of the whole sequence
+  int k_blk0;                   // column of the block's key row 0 (any sign)
+};
+struct FwdParamsBm : FwdParams {
+  BlockMaskParams bm;
+};
+struct BwdParamsBm : BwdParams {
+  BlockMaskParams bm;
+};
+template <bool kRng, bool kBlk> using fwd_params_t = std::conditional_t<kBlk, FwdParamsBm, std::conditional_t<kRng, FwdParamsRr, FwdParams>>;
+template <bool kRng, bool kBlk> using bwd_params_t = std::conditional_t<kBlk, BwdParamsBm, std::conditional_t<kRng, BwdParamsRr, BwdParams>>;
+constexpr int kBmMaxGroup = 64;                // query heads per K/V head the dK/dV item walk holds in one window (rfa_blockmask.h)
+int launch_fwd_bm(const FwdParams& p, const BlockMaskParams& m, int dtype, hipStream_t stream);
+int launch_bwd_dq_bm(const BwdParams& p, const BlockMaskParams& m, int dtype, hipStream_t stream);
+int launch_bwd_dkdv_bm(const BwdParams& p, const BlockMaskParams& m, int dtype, hipStream_t stream);
 
 int launch_preprocess(const PreParams& p, int dtype, hipStream_t stream);
 // soft cap + bounded window at head dims 65 .. 127: the zero-padded 128-wide dK/dV instance with both flags needs 40 bytes of

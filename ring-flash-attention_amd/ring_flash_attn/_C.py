@@ -302,6 +302,27 @@ class RowRangeArgs(C.Structure):
             self.struct_bytes = C.sizeof(RowRangeArgs)
 
 
+BLOCK_MASK_SIZE = 128             # RFA_BLOCK_MASK_SIZE: query rows / keys per byte of a block mask
+
+
+class BlockMaskArgs(C.Structure):
+    """rfa_blockmask_args: the block-sparse mask of a block call (mask: uint8 (Bm, Hm, nq, nk_blocks), one byte per pair of
+    128 query rows and 128 keys; the strides in bytes, 0 = broadcast; k_blk0: the column of the block's key row 0);
+    struct_bytes is filled in here"""
+    _fields_ = [
+        ("struct_bytes", C.c_uint32), ("reserved", C.c_uint32),
+        ("mask", C.c_void_p),
+        ("batch_stride", C.c_int64), ("head_stride", C.c_int64), ("row_stride", C.c_int64),
+        ("nk_blocks", C.c_int64), ("k_blk0", C.c_int64),
+        ("workspace", C.c_void_p),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if not self.struct_bytes:
+            self.struct_bytes = C.sizeof(BlockMaskArgs)
+
+
 # every symbol include/rfa.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "rfa_abi_version": (C.c_int, []),
@@ -342,6 +363,9 @@ SYMBOLS = {
     "rfa_fwd_rr": (C.c_int, [C.POINTER(FwdArgs), C.POINTER(RowRangeArgs), C.c_void_p]),
     "rfa_bwd_rr": (C.c_int, [C.POINTER(BwdArgs), C.POINTER(RowRangeArgs), C.c_void_p]),
     "rfa_rowrange_workspace_bytes": (C.c_int64, [C.POINTER(BwdArgs)]),
+    "rfa_fwd_bm": (C.c_int, [C.POINTER(FwdArgs), C.POINTER(BlockMaskArgs), C.c_void_p]),
+    "rfa_bwd_bm": (C.c_int, [C.POINTER(BwdArgs), C.POINTER(BlockMaskArgs), C.c_void_p]),
+    "rfa_blockmask_workspace_bytes": (C.c_int64, [C.POINTER(BwdArgs)]),
 }
 
 _lib = None
@@ -394,6 +418,10 @@ def load():
     for name in ("rfa_fwd_rr", "rfa_bwd_rr", "rfa_rowrange_workspace_bytes"):
         if not hasattr(lib, name):
             raise RuntimeError(f"ring_flash_attn: librfa_hip.so has no {name} (the row-range entry points); rebuild")
+    # ... and the pair with a block-sparse mask
+    for name in ("rfa_fwd_bm", "rfa_bwd_bm", "rfa_blockmask_workspace_bytes"):
+        if not hasattr(lib, name):
+            raise RuntimeError(f"ring_flash_attn: librfa_hip.so has no {name} (the block-mask entry points); rebuild")
     for name, (res, args) in SYMBOLS.items():
         fn = getattr(lib, name)  # AttributeError if the .so is stale
         fn.restype = res

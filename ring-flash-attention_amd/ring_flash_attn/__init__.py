@@ -72,6 +72,10 @@ from ._api import merge_attn, with_lse_grad
 # per-row key ranges (interval masks: documents on dense input, prefix-LM, shared prefixes): with_row_ranges(func, start, end)
 # lets query row i see the keys start[i] <= j < end[i] (global positions) in the dense ring and zigzag functions
 from ._api import with_row_ranges
+# block-sparse masks (window + global + random blocks, block-selected attention, document masks with shared tokens):
+# with_block_mask(func, block_mask) lets local query block i see key block j of the unsharded sequence iff block_mask[.., i, j],
+# in blocks of BLOCK_MASK_SIZE = 128 positions, in the dense ring and zigzag functions
+from ._api import BLOCK_MASK_SIZE, with_block_mask
 # DeepSpeed-Ulysses head parallelism in front of the dense schedules ("USP"): with_ulysses(func, ulysses_group) exchanges heads
 # for rows around `func`; make_usp_groups(func, ulysses_size) makes the (Ulysses, ring) groups of func's family
 from .ulysses import make_usp_groups, with_ulysses

@@ -448,6 +448,135 @@ def with_row_ranges(func, start, end):
     return _opaque(ranged)
 
 
+# ---- block-sparse masks (ring_flash_attn.with_block_mask) -----------------------------------------------------------------
+# Local query block i sees key block j of the unsharded sequence iff block_mask[b or 0, h or 0, i, j] and the call's own mask
+# allows the pair; blocks of BLOCK_MASK_SIZE = 128 positions.  Bound like the ranges above: read ONCE, in the autograd
+# Function's forward, kept on the node (ctx.block_mask) and handed to the schedule's forward and backward as `block_mask=` — a
+# backward reads nothing ambient.  The schedules give every block call the rows of the mask that belong to its query rows and
+# the mask column of its key row 0 (include/rfa.h: rfa_blockmask_args).
+from . import _C as _C_abi
+
+BLOCK_MASK_SIZE = _C_abi.BLOCK_MASK_SIZE
+BLOCK_MASK_MAX_GROUP = 64         # query heads per K/V head the dK/dV item walk holds in one window (csrc/rfa_kernels.hpp: kBmMaxGroup)
+_block_mask = contextvars.ContextVar("ring_flash_attn_block_mask", default=None)
+
+
+def _check_block_mask_tensor(mask):
+    """ValueError unless the mask is a contiguous 4-d bool tensor"""
+    if not isinstance(mask, torch.Tensor) or mask.dtype != torch.bool or mask.dim() != 4 or not mask.is_contiguous():
+        got = f"{tuple(mask.shape)} {mask.dtype}, contiguous={mask.is_contiguous()}" if isinstance(mask, torch.Tensor) else repr(mask)
+        raise ValueError(f"ring_flash_attn.with_block_mask: block_mask must be a contiguous bool tensor of shape (Bm, Hm, NQ, NK); got {got}")
+
+
+def checked_block_mask(q, k, v, dropout_p, alibi_slopes, what, group):
+    """the mask bound to this public call by `with_block_mask`, or None.  ValueError: a mask that does not fit the call, local
+    lengths that are no multiple of the block on a multi-rank group.  NotImplementedError: dropout, alibi_slopes, head dims
+    above 128, more than 64 query heads per K/V head, a value head dim of its own, a backend without `serves_block_mask` — all before anything is exchanged, from
+    numbers every rank has alike."""
+    mask = _block_mask.get()
+    if mask is None:
+        return None
+    from .utils import group_rank_world
+
+    _check_block_mask_tensor(mask)
+    world = group_rank_world(group)[1]
+    B, Sq, H = q.shape[0], q.shape[1], q.shape[2]
+    Sk = k.shape[1]
+    if world > 1:
+        zigzag = what.lower().startswith("zigzag")      # (only the dense ring and zigzag functions bind a mask)
+        unit, per = (Sq // 2, "half of the local length") if zigzag else (Sq, "the local length")
+        if Sq != Sk or (zigzag and Sq % 2) or unit % BLOCK_MASK_SIZE:
+            raise ValueError(f"ring_flash_attn: {what} with a block mask on {world} ranks needs {per} to be a multiple of "
+                             f"{BLOCK_MASK_SIZE}; got a local length of {Sq} (keys: {Sk})")
+    nq, nk = -(-Sq // BLOCK_MASK_SIZE), -(-(world * Sk) // BLOCK_MASK_SIZE)
+    if (mask.shape[0] not in (1, B) or mask.shape[1] not in (1, H) or tuple(mask.shape[2:]) != (nq, nk) or mask.device != q.device):
+        raise ValueError(f"ring_flash_attn: {what}: block_mask must be ({{1, {B}}}, {{1, {H}}}, {nq}, {nk}) on {q.device} — this "
+                         f"rank's query blocks against the key blocks of the whole sequence; got {tuple(mask.shape)} on {mask.device}")
+    if dropout_p and dropout_p > 0:
+        raise NotImplementedError(f"ring_flash_attn: {what} with a block mask together with dropout is not supported")
+    if alibi_slopes is not None:
+        raise NotImplementedError(f"ring_flash_attn: {what} with a block mask together with alibi_slopes is not supported")
+    if q.shape[-1] > 128:
+        raise NotImplementedError(f"ring_flash_attn: {what} with a block mask serves head dims up to 128, not {q.shape[-1]}")
+    if k.shape[2] > 0 and H // k.shape[2] > BLOCK_MASK_MAX_GROUP:
+        raise NotImplementedError(f"ring_flash_attn: {what} with a block mask serves at most {BLOCK_MASK_MAX_GROUP} query heads per "
+                                  f"K/V head, not {H} / {k.shape[2]}")
+    if v.shape[-1] != q.shape[-1]:
+        raise NotImplementedError(f"ring_flash_attn: {what} with a block mask does not serve a value head dim ({v.shape[-1]}) "
+                                  f"that differs from q's ({q.shape[-1]})")
+    from .backend import get_backend
+
+    be = get_backend()
+    if not getattr(be, "serves_block_mask", False):
+        raise NotImplementedError(f"ring_flash_attn: {what} with a block mask needs a backend that serves `block_mask` "
+                                  f"(serves_block_mask); {getattr(be, 'name', type(be).__name__)!r} does not")
+    return mask
+
+
+def block_mask_extra(ctx):
+    """the `block_mask=` keyword of the schedule's forward / backward of a bound node; nothing for an unbound one"""
+    mask = getattr(ctx, "block_mask", None)
+    return {} if mask is None else {"block_mask": mask}
+
+
+def with_block_mask(func, block_mask):
+    """A block-sparse mask — window + global + random blocks (BigBird, Longformer), block-selected attention, document masks
+    with shared tokens, the blocks of a FlexAttention BlockMask — for the dense ring and zigzag functions:
+
+        attn = with_block_mask(zigzag_ring_flash_attn_func, block_mask)     # bool (Bm, Hm, NQ, NK), contiguous, on q's device
+        out = attn(q, k, v, causal=True)
+
+    returns a callable with `func`'s signature and return value in which local query row i sees key j iff
+    block_mask[b or 0, h or 0, i // 128, pos(j) // 128] AND the call's own mask (`causal`, `window_size`) allows the pair — the
+    diagonal blocks of a causal block mask are just True with causal=True.  Bm in {1, B} and Hm in {1, H} (H: QUERY heads; 1
+    broadcasts).  NQ = ceil(S_local / 128): THIS rank's query blocks in the order of q's rows (zigzag: the first chunk's blocks,
+    then the second chunk's); NK = ceil(W S_local / 128): the key blocks of the unsharded sequence in natural order (pos(j): the
+    global position, as for with_row_ranges).  A row without a visible key: out = 0, lse as for every such row, zero gradients.
+    The mask gets no gradient; dq, dk, dv are exact.  The kernels skip every key tile (forward, dQ) and every (query tile,
+    head) item (dK/dV) in a dark block.  A zigzag call may be non-causal.
+    `block_mask=None`: `func` itself.  Served: ring_flash_attn_{,kvpacked_,qkvpacked_}func and
+    zigzag_ring_flash_attn_{,kvpacked_,qkvpacked_}func or a `with_lse_grad` result of one (with_block_mask goes on the outside),
+    on any group, with windows, GQA (at most 64 query heads per K/V head), return_attn_probs, bf16 / fp16, head dims 8 .. 128.
+    TypeError: any other callable — the *_varlen, stripe_, llama3_ and zigzag_llama3_ families and with_softcap / with_sinks /
+    with_max_logit / with_ulysses / with_row_ranges / with_block_mask results.  ValueError: a mask that is not a contiguous bool
+    4-d tensor; at the call, a shape or device that does not fit q, and on a multi-rank group a local length (zigzag: half of
+    it) that is no multiple of 128 (at one rank any lengths are served, tail blocks are partial, Sq != Sk is fine).
+    NotImplementedError at the call, before anything is exchanged: dropout_p > 0, alibi_slopes, head dims above 128, more than
+    64 query heads per K/V head, a value head dim of its own, a backend that does not serve it.  The mask is bound to the call and kept on the autograd node —
+    activation checkpointing re-runs the wrapped call and binds it again.  Under torch.compile the call runs eagerly behind a
+    graph break."""
+    import functools
+
+    import ring_flash_attn as pkg
+
+    for marker, what in (("_rfa_block_mask", "with_block_mask"), ("_rfa_row_ranges", "with_row_ranges"), ("_rfa_softcap", "with_softcap"),
+                         ("_rfa_sinks", "with_sinks"), ("_rfa_max_logit", "with_max_logit"), ("_rfa_ulysses", "with_ulysses")):
+        if getattr(func, marker, False):
+            raise TypeError(f"ring_flash_attn.with_block_mask: `func` is a {what} result; not served")
+    served = {id(getattr(pkg, n)) for n in ROW_RANGE_FUNCS}
+    f = func
+    # (a with_lse_grad result carries the marker on both of its layers and leads to the public function it wraps)
+    while id(f) not in served and getattr(f, "_rfa_lse_grad", False) and hasattr(f, "__wrapped__"):
+        f = f.__wrapped__
+    if id(f) not in served:
+        raise TypeError("ring_flash_attn.with_block_mask: `func` must be one of ring_flash_attn_{,kvpacked_,qkvpacked_}func and "
+                        f"zigzag_ring_flash_attn_{{,kvpacked_,qkvpacked_}}func or a with_lse_grad result of one, got {func!r}")
+    if block_mask is None:
+        return func
+    _check_block_mask_tensor(block_mask)
+
+    @functools.wraps(func, updated=())              # (updated=(): as in with_softcap)
+    def masked(*args, **kwargs):
+        token = _block_mask.set(block_mask)
+        try:
+            return func(*args, **kwargs)
+        finally:
+            _block_mask.reset(token)
+
+    masked._rfa_block_mask = True                    # (the other binders refuse a masked function)
+    return _opaque(masked)
+
+
 # ---- attention over the union of two key sets (ring_flash_attn.merge_attn) ------------------------------------------------
 def _check_merge_args(out_a, lse_a, out_b, lse_b):
     ts = (out_a, lse_a, out_b, lse_b)
@@ -803,6 +932,7 @@ def make_autograd_function(name, forward_impl, backward_impl, n_lead, window_rin
             ctx.softcap = checked_softcap(dropout_p, alibi_slopes, q, name, window_size, causal)
             ctx.lse_grad = checked_lse_grad(ctx, name)
             ctx.row_ranges = checked_row_ranges(q, k, v, dropout_p, alibi_slopes, name)
+            ctx.block_mask = checked_block_mask(q, k, v, dropout_p, alibi_slopes, name, group)
             sinks = checked_sinks(sinks, q, name)
             q, k, v = _prep_qkv(q, k, v, group)
             tensors_lead = ()
@@ -812,6 +942,7 @@ def make_autograd_function(name, forward_impl, backward_impl, n_lead, window_rin
                 tensors_lead = (cu,)
             keep, extra = _keep_list(ctx, forward_impl)
             extra.update(row_ranges_extra(ctx))
+            extra.update(block_mask_extra(ctx))
             ctx.dropout = (dropout_p, draw_dropout_seed()) if dropout_p and dropout_p > 0 else (0.0, None)
             if ctx.dropout[1] is not None:
                 extra["dropout_seed"] = ctx.dropout[1]
@@ -844,6 +975,7 @@ def make_autograd_function(name, forward_impl, backward_impl, n_lead, window_rin
             dout, lse_kw = lse_grad_kw(ctx, dout, args, out, softmax_lse)
             extra.update(lse_kw)
             extra.update(row_ranges_extra(ctx))
+            extra.update(block_mask_extra(ctx))
             if ctx.dropout[1] is not None:
                 extra["dropout_seed"] = ctx.dropout[1]
             with softcap_scope(ctx.softcap):
@@ -889,6 +1021,7 @@ def make_packed_function(name, base_fn, forward_impl, backward_impl, n_lead, pac
             ctx.softcap = checked_softcap(dropout_p, alibi_slopes, q, name, window_size, causal)
             ctx.lse_grad = checked_lse_grad(ctx, name)
             ctx.row_ranges = checked_row_ranges(q, k, v, dropout_p, alibi_slopes, name)
+            ctx.block_mask = checked_block_mask(q, k, v, dropout_p, alibi_slopes, name, group)
             sinks = checked_sinks(sinks, q, name)
             q, k, v = _prep_qkv(q, k, v, group, packed_travel=packed_travel and n_packed == 2)
             tensors_lead = ()
@@ -898,6 +1031,7 @@ def make_packed_function(name, base_fn, forward_impl, backward_impl, n_lead, pac
                 tensors_lead = (cu,)
             keep, extra = _keep_list(ctx, forward_impl)
             extra.update(row_ranges_extra(ctx))
+            extra.update(block_mask_extra(ctx))
             ctx.dropout = (dropout_p, draw_dropout_seed()) if dropout_p and dropout_p > 0 else (0.0, None)
             if ctx.dropout[1] is not None:
                 extra["dropout_seed"] = ctx.dropout[1]
@@ -931,6 +1065,7 @@ def make_packed_function(name, base_fn, forward_impl, backward_impl, n_lead, pac
             dout, lse_kw = lse_grad_kw(ctx, dout, args, out, softmax_lse)
             extra.update(lse_kw)
             extra.update(row_ranges_extra(ctx))
+            extra.update(block_mask_extra(ctx))
             shape, dtype, device = ctx.packed_meta
             dpacked = torch.empty(shape, dtype=dtype, device=device)
             views = [dpacked.select(pack_dim, i) for i in range(n_packed)]

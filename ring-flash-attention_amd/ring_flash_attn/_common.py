@@ -125,6 +125,18 @@ def row_ranges_kw(row_ranges, k_pos0, rows=None):
     return {"row_ranges": (start, end, int(k_pos0))}
 
 
+def block_mask_kw(block_mask, k_blk0, qblocks=None):
+    """the `block_mask=` keyword of a block call whose key row 0 sits in mask column `k_blk0` (global key position / 128), for
+    the query blocks `qblocks` (a slice of this rank's rows of the mask: a view, its strides go to the library) —
+    ring_flash_attn.with_block_mask; nothing without a mask, so that backends that predate the keyword keep serving plain calls"""
+    if block_mask is None:
+        return {}
+    mask = block_mask[0] if isinstance(block_mask, tuple) else block_mask
+    if qblocks is not None:
+        mask = mask[:, :, qblocks]
+    return {"block_mask": (mask, int(k_blk0))}
+
+
 def dlse_kw(dlse):
     """the `dlse=` keyword of a backward's bwd_preprocess (the gradient of lse, ring_flash_attn.with_lse_grad); nothing
     without one, so that backends that predate the keyword keep serving plain calls"""

@@ -97,6 +97,7 @@ class HipBackend:
     serves_merge_pair = True         # merge_pair / merge_pair_bwd (include/rfa.h: rfa_merge_pair, rfa_merge_pair_bwd): ring_flash_attn.merge_attn
     serves_vdim = True               # fwd / bwd take a `v` whose head dim differs from q's (include/rfa.h: rfa_fwd_vd, rfa_bwd_vd): MLA 192 / 128
     serves_row_ranges = True         # fwd / bwd take `row_ranges=(start, end, k_pos0)` (include/rfa.h: rfa_fwd_rr, rfa_bwd_rr): ring_flash_attn.with_row_ranges
+    serves_block_mask = True         # fwd / bwd take `block_mask=(mask_view, k_blk0)` (include/rfa.h: rfa_fwd_bm, rfa_bwd_bm): ring_flash_attn.with_block_mask
     serves_dropout_positions = True  # `dropout=` takes the position maps (q_map, k_map): what dropout over a dense ring, zigzag or stripe schedule needs
 
     def __init__(self):
@@ -125,7 +126,7 @@ class HipBackend:
     def fwd(self, q, k, v, *, softmax_scale, causal, cu_seqlens_q=None, cu_seqlens_k=None,
             max_seqlen_q=None, max_seqlen_k=None, q_half=HALF_FULL, k_half=HALF_FULL,
             out=None, lse=None, out_acc=None, lse_acc=None, acc_init=False, window=(-1, -1), dropout=None,
-            mask_shift=0, mask_shift_lens=0, alibi=None, softcap=0.0, row_ranges=None):
+            mask_shift=0, mask_shift_lens=0, alibi=None, softcap=0.0, row_ranges=None, block_mask=None):
         """Block attention.  Plain mode fills (out, lse); accumulate mode merges into the fp32
         (out_acc, lse_acc) pair (fused update_out_and_lse).  Dense: q (B,Sq,H,D); varlen: (T,H,D).
         dropout: (p, seed, q_pos_offset, k_pos_offset, head_offset), the same plus the position maps (q_map, k_map) —
@@ -141,7 +142,11 @@ class HipBackend:
         row_ranges: (start, end, k_pos0) or None — int32 (B, Sq) tensors on q's device (row stride 1; the batch stride is
         free, so a schedule passes slices) holding GLOBAL key positions, and the global position of k's row 0: row i sees key
         row j iff start[b, i] <= k_pos0 + j < end[b, i] and the call's own mask allows it (include/rfa.h: rfa_rowrange_args).
-        Dense input, head dims <= 128, no dropout, bias or cap."""
+        Dense input, head dims <= 128, no dropout, bias or cap.
+        block_mask: (mask_view, k_blk0) or None — a bool / uint8 (Bm, Hm, ceil(Sq / 128), NK) tensor on q's device (Bm in {1, B},
+        Hm in {1, H}; column stride 1, the other strides are free, so a schedule passes slices) and the mask column of k's row 0:
+        row i of query head h sees key row j iff mask[b, h, i // 128, k_blk0 + j // 128] (columns outside [0, NK) are dark)
+        and the call's own mask allows it (include/rfa.h: rfa_blockmask_args).  The conditions of row_ranges; not with them."""
         self._check_dev(q, k, v, out, lse, out_acc, lse_acc)
         q, k, v = _in_contract(q), _in_contract(k), _in_contract(v)
         varlen = cu_seqlens_q is not None
@@ -182,8 +187,12 @@ class HipBackend:
         # workspace for the partial (out, lse) pairs: a few tens of MB, only for the calls that split
         vd = _vdim_args(q, v, alibi, softcap, dropout)
         rr = _rowrange_args(row_ranges, q, alibi, softcap, dropout, vd, varlen)
+        bm = _blockmask_args(block_mask, q, alibi, softcap, dropout, vd, varlen, rr)
         if rr is not None:                        # per-row key ranges: the kRng instances of the 8 x 32 form, never split
             _C.check(self.lib.rfa_fwd_rr(C.byref(a), C.byref(rr), _stream(q)), "rfa_fwd_rr")
+            return
+        if bm is not None:                        # a block-sparse mask: the kBlk instances of the same form
+            _C.check(self.lib.rfa_fwd_bm(C.byref(a), C.byref(bm), _stream(q)), "rfa_fwd_bm")
             return
         if vd is not None:                        # a value head dim of its own (csrc/rfa_vdim.hip): never split either
             _C.check(self.lib.rfa_fwd_vd(C.byref(a), C.byref(vd), _stream(q)), "rfa_fwd_vd")
@@ -236,7 +245,7 @@ class HipBackend:
             k_half=HALF_FULL, dq=None, dk=None, dv=None, dq_acc=None, dk_acc=None, dv_acc=None,
             acc_init=False, deterministic=False, phases=_C.BWD_ALL, partials=None, ds_scratch=None,
             window=(-1, -1), prof_events=None, dropout=None, mask_shift=0, mask_shift_lens=0, alibi=None,
-            softcap=0.0, row_ranges=None):
+            softcap=0.0, row_ranges=None, block_mask=None):
         """dQ/dK/dV of one block.  Plain outputs (io dtype) or `+=` into fp32 accumulators.
         phases=BWD_COMPUTE / BWD_REDUCE splits the call so a ring step can overlap the kernels
         with the arrival of the dk/dv accumulators it adds into: the COMPUTE call RETURNS the buffer
@@ -247,7 +256,8 @@ class HipBackend:
         alibi, softcap: as in fwd, with the forward's values; such a call names the 128-key dK/dV form and takes no dS scratch —
         what rfa_bwd_ex asks of the base arguments (include/rfa.h).
         row_ranges: as in fwd, with the forward's values; the same two conditions (rfa_bwd_rr), plus a small tile-bounds
-        workspace from torch's caching allocator, per call."""
+        workspace from torch's caching allocator, per call.
+        block_mask: as in fwd, with the forward's values; the same two conditions (rfa_bwd_bm); no workspace."""
         self._check_dev(dout, q, k, v, lse, delta, dq, dk, dv, dq_acc, dk_acc, dv_acc)
         dout, q, k, v = _in_contract(dout), _in_contract(q), _in_contract(k), _in_contract(v)
         varlen = cu_seqlens_q is not None
@@ -312,9 +322,10 @@ class HipBackend:
         vd = _vdim_args(q, v, alibi, softcap, dropout)    # (rfa_bwd_vd runs the base arguments' own plan and scratch)
         ext = _ext_args(alibi, q, softcap)
         rr = _rowrange_args(row_ranges, q, alibi, softcap, dropout, vd, varlen)
-        if ext is not None or rr is not None:
+        bm = _blockmask_args(block_mask, q, alibi, softcap, dropout, vd, varlen, rr)
+        if ext is not None or rr is not None or bm is not None:
             a.dkdv_form, a.dkdv_nsplit, ds_scratch = _C.DKDV_128, 0, None
-        if ext is None and rr is None and ds_scratch is None and not reduce_only and _spill_enabled():
+        if ext is None and rr is None and bm is None and ds_scratch is None and not reduce_only and _spill_enabled():
             ds_scratch = self.bwd_ds_scratch(a, q.device)
         if ds_scratch is not None and not reduce_only:
             a.ds_scratch = ds_scratch.data_ptr()
@@ -338,6 +349,8 @@ class HipBackend:
             tb = torch.empty(max(nb, 16), dtype=torch.uint8, device=q.device)
             rr.tile_bounds = tb.data_ptr()
             _C.check(self.lib.rfa_bwd_rr(C.byref(a), C.byref(rr), _stream(q)), "rfa_bwd_rr")
+        elif bm is not None:
+            _C.check(self.lib.rfa_bwd_bm(C.byref(a), C.byref(bm), _stream(q)), "rfa_bwd_bm")
         elif vd is not None:
             _C.check(self.lib.rfa_bwd_vd(C.byref(a), C.byref(vd), _stream(q)), "rfa_bwd_vd")
         elif ext is not None:
@@ -797,6 +810,37 @@ def _rowrange_args(row_ranges, q, alibi, softcap, dropout, vd, varlen):
     rr.k_pos0 = int(k_pos0)
     rr._keep = (start, end)                       # (the tensors live as long as the struct does)
     return rr
+
+
+def _blockmask_args(block_mask, q, alibi, softcap, dropout, vd, varlen, rr=None):
+    """rfa_blockmask_args of a call with `block_mask=(mask_view, k_blk0)`, or None: the call without one.  What the masked
+    kernels do not have is refused here, before the library is called.  Strides of broadcast dims are 0."""
+    if block_mask is None:
+        return None
+    mask, k_blk0 = block_mask
+    if (alibi is not None and alibi[0] is not None) or check_softcap(softcap) or (dropout is not None and dropout[0] > 0):
+        raise NotImplementedError("ring_flash_attn: a block mask together with alibi, softcap or dropout is not served")
+    if rr is not None:
+        raise NotImplementedError("ring_flash_attn: a block mask together with row ranges is not served")
+    if vd is not None or varlen or q.shape[-1] > 128:
+        raise NotImplementedError("ring_flash_attn: block masks are served for dense input with one head dim up to 128")
+    B, Sq, H = q.shape[0], q.shape[1], q.shape[2]
+    nq = (Sq + _C.BLOCK_MASK_SIZE - 1) // _C.BLOCK_MASK_SIZE
+    if (not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8) or mask.dim() != 4
+            or mask.device != q.device or mask.shape[0] not in (1, B) or mask.shape[1] not in (1, H) or mask.shape[2] != nq
+            or (mask.shape[3] > 1 and mask.stride(3) != 1)):
+        got = f"{tuple(mask.shape)} {mask.dtype} on {mask.device}" if isinstance(mask, torch.Tensor) else repr(mask)
+        raise ValueError(f"block_mask: the mask must be a bool / uint8 tensor of shape ({{1, {B}}}, {{1, {H}}}, {nq}, NK) on "
+                         f"{q.device} with column stride 1; got {got}")
+    bm = _C.BlockMaskArgs()
+    bm.mask = mask.data_ptr()                     # (bool and uint8 are both one byte per element, non-zero = True)
+    bm.batch_stride = mask.stride(0) if mask.shape[0] > 1 else 0
+    bm.head_stride = mask.stride(1) if mask.shape[1] > 1 else 0
+    bm.row_stride = mask.stride(2) if mask.shape[2] > 1 else 0
+    bm.nk_blocks = mask.shape[3]
+    bm.k_blk0 = int(k_blk0)
+    bm._keep = mask                               # (the tensor lives as long as the struct does)
+    return bm
 
 
 def _vdim_args(q, v, alibi, softcap, dropout):

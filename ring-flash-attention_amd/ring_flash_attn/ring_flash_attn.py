@@ -21,13 +21,16 @@ unbounded walks all W steps, and the causal diagonal moves with the same t * S a
 Per-row key ranges (ring_flash_attn.with_row_ranges) take that route as well: the block at signed rank distance t holds the
 keys of rank r - t, so its key row 0 sits at global position k_pos0 = (r - t) S; every block call gets this rank's
 (start, end) and that one number (`row_ranges=`, include/rfa.h: rfa_rowrange_args), and the kernels skip what no row sees.
+
+Block-sparse masks (ring_flash_attn.with_block_mask) travel the same way: every block call gets this rank's rows of the mask
+(all of them) and the mask column of its key row 0, k_blk0 = (r - t) S / 128 (`block_mask=`, include/rfa.h: rfa_blockmask_args).
 """
 import torch
 
 from . import _C
 from .backend import get_backend
 from .utils import RingComm, single_rank
-from ._common import alibi_kw, dlse_kw, out_shape, row_ranges_kw, dropout_arg, global_window, pos_map, require_dropout_positions, require_mask_shift
+from ._common import alibi_kw, block_mask_kw, dlse_kw, out_shape, row_ranges_kw, dropout_arg, global_window, pos_map, require_dropout_positions, require_mask_shift
 from ._api import make_autograd_function, make_dense_api, _grad_buffers
 
 
@@ -57,7 +60,7 @@ def ring_window_plan(rank, world_size, S, causal, window):
     return n_steps, dists
 
 
-def _band(causal, window, t, S, alibi_slopes=None, row_ranges=None, rank=0):
+def _band(causal, window, t, S, alibi_slopes=None, row_ranges=None, rank=0, block_mask=None):
     """keywords of a block call t ranks off the diagonal (the shift only where it is not zero: backends that predate
     it serve the diagonal block unchanged; the bias only where there is one; the ranges only where there are some, with the
     global position of the block's key row 0)"""
@@ -67,10 +70,11 @@ def _band(causal, window, t, S, alibi_slopes=None, row_ranges=None, rank=0):
     kw.update(alibi_kw(alibi_slopes, t * S))
     if row_ranges is not None:
         kw["row_ranges"] = (row_ranges[0], row_ranges[1], (rank - t) * S)
+    kw.update(block_mask_kw(block_mask, (rank - t) * S // 128))
     return kw
 
 
-def _ring_window_forward(be, comm, q, k, v, softmax_scale, causal, window, alibi_slopes=None, row_ranges=None):
+def _ring_window_forward(be, comm, q, k, v, softmax_scale, causal, window, alibi_slopes=None, row_ranges=None, block_mask=None):
     B, S, H, D = q.shape
     n_steps, dists = ring_window_plan(comm.rank, comm.world_size, S, causal, window)
     out_acc = torch.empty(out_shape(q, v), dtype=torch.float32, device=q.device)
@@ -82,7 +86,7 @@ def _ring_window_forward(be, comm, q, k, v, softmax_scale, causal, window, alibi
             next_k, next_v = comm.send_recv_kv(k, v)
         if dists[step] is not None:
             be.fwd(q, k, v, softmax_scale=softmax_scale, out_acc=out_acc, lse_acc=lse_acc, acc_init=first,
-                   **_band(causal, window, dists[step], S, alibi_slopes, row_ranges, comm.rank))
+                   **_band(causal, window, dists[step], S, alibi_slopes, row_ranges, comm.rank, block_mask))
             first = False
         if step + 1 != n_steps:
             comm.wait()
@@ -91,7 +95,7 @@ def _ring_window_forward(be, comm, q, k, v, softmax_scale, causal, window, alibi
 
 
 def _ring_window_backward(be, process_group, kv_comm, d_kv_comm, dout, q, k, v, softmax_lse, delta, softmax_scale,
-                          causal, window, deterministic, alibi_slopes=None, row_ranges=None):
+                          causal, window, deterministic, alibi_slopes=None, row_ranges=None, block_mask=None):
     B, S, H, D = q.shape
     world = kv_comm.world_size
     n_steps, dists = ring_window_plan(kv_comm.rank, world, S, causal, window)
@@ -104,7 +108,7 @@ def _ring_window_backward(be, process_group, kv_comm, d_kv_comm, dout, q, k, v, 
         if step + 1 != n_steps:
             next_k, next_v = kv_comm.send_recv_kv(k, v)
         if dists[step] is not None:
-            band = _band(causal, window, dists[step], S, alibi_slopes, row_ranges, kv_comm.rank)
+            band = _band(causal, window, dists[step], S, alibi_slopes, row_ranges, kv_comm.rank, block_mask)
             if dq is None:                       # step 0: the diagonal block always computes
                 dq = torch.empty((B, S, H, D), dtype=torch.float32, device=q.device)
                 be.bwd(dout, q, k, v, softmax_lse, delta, softmax_scale=softmax_scale,
@@ -161,8 +165,10 @@ def ring_flash_attn_forward(
     deterministic=False,
     dropout_seed=None,
     row_ranges=None,
+    block_mask=None,
 ):
-    """row_ranges: (start, end) of a call bound by with_row_ranges — this rank's rows, global key positions — or None"""
+    """row_ranges: (start, end) of a call bound by with_row_ranges — this rank's rows, global key positions — or None;
+    block_mask: the (Bm, Hm, NQ, NK) mask of a call bound by with_block_mask — this rank's query blocks, all key blocks — or None"""
     be = get_backend()
     comm = RingComm(process_group)
     B, S, H, D = q.shape
@@ -171,18 +177,18 @@ def ring_flash_attn_forward(
         out = torch.empty(out_shape(q, v), dtype=q.dtype, device=q.device)
         lse = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
         be.fwd(q, k, v, softmax_scale=softmax_scale, causal=causal, out=out, lse=lse, window=window_size, dropout=dropout_arg(dropout_p, dropout_seed),
-               **alibi_kw(alibi_slopes), **row_ranges_kw(row_ranges, 0))
+               **alibi_kw(alibi_slopes), **row_ranges_kw(row_ranges, 0), **block_mask_kw(block_mask, 0))
         return out, lse
     drop = _ring_dropout(be, comm, S, dropout_p, dropout_seed)
 
     win = global_window(window_size, causal, comm.world_size * S)
     if alibi_slopes is not None:                 # (never together with a window: _api._check_unsupported)
         win = (-1, -1)
-    if row_ranges is not None and win is None:   # (the ranges ride on the windowed route's bookkeeping, with or without a window)
+    if (row_ranges is not None or block_mask is not None) and win is None:   # (ranges and block masks ride on the windowed route's bookkeeping, with or without a window)
         win = (-1, -1)
     if win is not None:
         require_mask_shift(be, "ring_flash_attn")
-        return _ring_window_forward(be, comm, q, k, v, softmax_scale, causal, win, alibi_slopes, row_ranges)
+        return _ring_window_forward(be, comm, q, k, v, softmax_scale, causal, win, alibi_slopes, row_ranges, block_mask)
 
     out_acc = torch.empty(out_shape(q, v), dtype=torch.float32, device=q.device)
     lse_acc = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
@@ -224,6 +230,7 @@ def ring_flash_attn_backward(
     out_grads=None,
     dlse=None,
     row_ranges=None,
+    block_mask=None,
 ):
     be = get_backend()
     kv_comm = RingComm(process_group)
@@ -241,18 +248,18 @@ def ring_flash_attn_backward(
         dq, dk, dv = _grad_buffers(out_grads, q, k, v)
         be.bwd(dout, q, k, v, softmax_lse, delta, softmax_scale=softmax_scale, causal=causal,
                dq=dq, dk=dk, dv=dv, deterministic=deterministic, window=window_size, dropout=dropout_arg(dropout_p, dropout_seed),
-               **alibi_kw(alibi_slopes), **row_ranges_kw(row_ranges, 0))
+               **alibi_kw(alibi_slopes), **row_ranges_kw(row_ranges, 0), **block_mask_kw(block_mask, 0))
         return dq, dk, dv
     drop = _ring_dropout(be, kv_comm, S, dropout_p, dropout_seed)
 
     win = global_window(window_size, causal, kv_comm.world_size * S)
     if alibi_slopes is not None:
         win = (-1, -1)
-    if row_ranges is not None and win is None:
+    if (row_ranges is not None or block_mask is not None) and win is None:
         win = (-1, -1)
     if win is not None:
         return _ring_window_backward(be, process_group, kv_comm, d_kv_comm, dout, q, k, v, softmax_lse, delta,
-                                     softmax_scale, causal, win, deterministic, alibi_slopes, row_ranges)
+                                     softmax_scale, causal, win, deterministic, alibi_slopes, row_ranges, block_mask)
 
     dq = None
     dk = torch.empty(k.shape, dtype=torch.float32, device=q.device)

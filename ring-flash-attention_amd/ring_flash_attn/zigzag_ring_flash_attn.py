@@ -52,7 +52,7 @@ from . import _C, config
 from .backend import get_backend
 from .utils import Agreement, AllGatherComm, RingComm, SourceArrivals, all_to_all_async, reduce_scatter_async, single_rank
 from ._api import make_autograd_function, make_dense_api, _grad_buffers
-from ._common import alibi_kw, dlse_kw, out_shape, row_ranges_kw, packed_pair, dropout_arg, global_window, require_dropout_positions, require_mask_shift, zigzag_map
+from ._common import alibi_kw, block_mask_kw, dlse_kw, out_shape, row_ranges_kw, packed_pair, dropout_arg, global_window, require_dropout_positions, require_mask_shift, zigzag_map
 
 
 def gather_scratch_bytes(k: torch.Tensor, world: int, wire_fp32: bool) -> int:
@@ -192,13 +192,20 @@ def zigzag_window_pairs(rank, src, world, C, window_left, causal=True):
     return sorted(pairs, key=lambda p: p[2] != 0)
 
 
+def _half_blocks(S, hq):
+    """the rows of a block mask (query blocks of 128 rows) that belong to half `hq` of this rank's S rows (S / 2 a multiple of
+    128: ring_flash_attn.with_block_mask checks it at the call)"""
+    n = (S // 2) // 128
+    return slice(hq * n, (hq + 1) * n)
+
+
 def _halves(S):
     C = S // 2
     return (slice(0, C), slice(C, S))
 
 
 def _zigzag_window_forward(be, process_group, comm, q, k, v, softmax_scale, window, alibi_slopes=None, row_ranges=None,
-                           causal=True):
+                           causal=True, block_mask=None):
     B, S, H, D = q.shape
     W, rank = comm.world_size, comm.rank
     hs = _halves(S)
@@ -211,7 +218,8 @@ def _zigzag_window_forward(be, process_group, comm, q, k, v, softmax_scale, wind
             band = {"mask_shift": shift} if shift else {}
             be.fwd(q[:, hs[hq]], ks[:, hs[hk]], vs[:, hs[hk]], softmax_scale=softmax_scale, causal=causal, window=window,
                    out_acc=out_acc[:, hs[hq]], lse_acc=lse_acc[:, :, hs[hq]], acc_init=not started[hq], **band,
-                   **alibi_kw(alibi_slopes, shift), **row_ranges_kw(row_ranges, (src, 2 * W - 1 - src)[hk] * (S // 2), hs[hq]))
+                   **alibi_kw(alibi_slopes, shift), **row_ranges_kw(row_ranges, (src, 2 * W - 1 - src)[hk] * (S // 2), hs[hq]),
+                   **block_mask_kw(block_mask, (src, 2 * W - 1 - src)[hk] * (S // 2) // 128, _half_blocks(S, hq)))
             started[hq] = True
 
     mode = exchange_mode(k, W, q, process_group, v)
@@ -238,7 +246,7 @@ def _zigzag_window_forward(be, process_group, comm, q, k, v, softmax_scale, wind
 
 
 def _zigzag_window_backward(be, process_group, kv_comm, d_kv_comm, dout, q, k, v, softmax_lse, delta, softmax_scale,
-                            window, deterministic, kept, alibi_slopes=None, row_ranges=None, causal=True):
+                            window, deterministic, kept, alibi_slopes=None, row_ranges=None, causal=True, block_mask=None):
     B, S, H, D = q.shape
     W, rank = kv_comm.world_size, kv_comm.rank
     hs = _halves(S)
@@ -252,7 +260,8 @@ def _zigzag_window_backward(be, process_group, kv_comm, d_kv_comm, dout, q, k, v
             be.bwd(dout[:, hs[hq]], q[:, hs[hq]], ks[:, hs[hk]], vs[:, hs[hk]], lse_h[hq], delta_h[hq],
                    softmax_scale=softmax_scale, causal=causal, window=window, dq_acc=dq[:, hs[hq]],
                    dk_acc=dk[:, hs[hk]], dv_acc=dv[:, hs[hk]], deterministic=deterministic, **band,
-                   **alibi_kw(alibi_slopes, shift), **row_ranges_kw(row_ranges, (src, 2 * W - 1 - src)[hk] * (S // 2), hs[hq]))
+                   **alibi_kw(alibi_slopes, shift), **row_ranges_kw(row_ranges, (src, 2 * W - 1 - src)[hk] * (S // 2), hs[hq]),
+                   **block_mask_kw(block_mask, (src, 2 * W - 1 - src)[hk] * (S // 2) // 128, _half_blocks(S, hq)))
 
     mode = exchange_mode(k, W, q, process_group, v)
     if mode in ("gather", "gather_ps"):
@@ -334,11 +343,15 @@ def zigzag_ring_flash_attn_forward(
     dropout_seed=None,
     keep=None,
     row_ranges=None,
+    block_mask=None,
 ):
     """keep: a list (or None) the gather form appends its gathered K/V buffers to — the autograd Function saves them
     for the backward (`kept=`).  row_ranges: (start, end) of a call bound by with_row_ranges — this rank's rows in q's
-    order, global key positions — or None; such a call may be non-causal"""
-    assert causal == True or row_ranges is not None, "zigzag ring is meaningless for causal=False"
+    order, global key positions — or None; such a call may be non-causal.  block_mask: the (Bm, Hm, NQ, NK) mask of a call
+    bound by with_block_mask — the query blocks of this rank's two chunks in q's order, all key blocks in natural order — or
+    None; such a call may be non-causal too: each (query chunk, key chunk) pair gets its chunk's rows of the mask and
+    k_blk0 = ck C / 128"""
+    assert causal == True or row_ranges is not None or block_mask is not None, "zigzag ring is meaningless for causal=False"
     be = get_backend()
     comm = RingComm(process_group)
     B, S, H, D = q.shape
@@ -348,18 +361,18 @@ def zigzag_ring_flash_attn_forward(
         out = torch.empty(out_shape(q, v), dtype=q.dtype, device=q.device)
         lse = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
         be.fwd(q, k, v, softmax_scale=softmax_scale, causal=bool(causal), out=out, lse=lse, window=window_size, dropout=dropout_arg(dropout_p, dropout_seed),
-               **alibi_kw(alibi_slopes), **row_ranges_kw(row_ranges, 0))
+               **alibi_kw(alibi_slopes), **row_ranges_kw(row_ranges, 0), **block_mask_kw(block_mask, 0))
         return out, lse
     drop = _zigzag_dropout(be, comm.rank, comm.world_size, half, dropout_p, dropout_seed)
 
     win = global_window(window_size, bool(causal), comm.world_size * S)
     if alibi_slopes is not None:                 # (never together with a window: _api._check_unsupported)
         win = (-1, -1)
-    if row_ranges is not None and win is None:   # (the ranges take the per-pair route, with or without a window)
+    if (row_ranges is not None or block_mask is not None) and win is None:   # (ranges and block masks take the per-pair route, with or without a window)
         win = (-1, -1)
     if win is not None:
         require_mask_shift(be, "zigzag_ring_flash_attn")
-        return _zigzag_window_forward(be, process_group, comm, q, k, v, softmax_scale, win, alibi_slopes, row_ranges, bool(causal))
+        return _zigzag_window_forward(be, process_group, comm, q, k, v, softmax_scale, win, alibi_slopes, row_ranges, bool(causal), block_mask)
 
     out_acc = torch.empty(out_shape(q, v), dtype=torch.float32, device=q.device)
     lse_acc = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
@@ -429,9 +442,10 @@ def zigzag_ring_flash_attn_backward(
     dlse=None,
     kept=None,
     row_ranges=None,
+    block_mask=None,
 ):
     """kept: the gathered K/V buffers the forward handed over (`keep=`), or None"""
-    assert causal == True or row_ranges is not None, "zigzag ring is meaningless for causal=False"
+    assert causal == True or row_ranges is not None or block_mask is not None, "zigzag ring is meaningless for causal=False"
     be = get_backend()
     kv_comm = RingComm(process_group)
     d_kv_comm = RingComm(process_group)
@@ -449,18 +463,18 @@ def zigzag_ring_flash_attn_backward(
         dq, dk, dv = _grad_buffers(out_grads, q, k, v)
         be.bwd(dout, q, k, v, softmax_lse, delta, softmax_scale=softmax_scale, causal=bool(causal),
                dq=dq, dk=dk, dv=dv, deterministic=deterministic, window=window_size, dropout=dropout_arg(dropout_p, dropout_seed),
-               **alibi_kw(alibi_slopes), **row_ranges_kw(row_ranges, 0))
+               **alibi_kw(alibi_slopes), **row_ranges_kw(row_ranges, 0), **block_mask_kw(block_mask, 0))
         return dq, dk, dv
     drop = _zigzag_dropout(be, kv_comm.rank, kv_comm.world_size, half, dropout_p, dropout_seed)
 
     win = global_window(window_size, bool(causal), kv_comm.world_size * S)
     if alibi_slopes is not None:
         win = (-1, -1)
-    if row_ranges is not None and win is None:
+    if (row_ranges is not None or block_mask is not None) and win is None:
         win = (-1, -1)
     if win is not None:
         return _zigzag_window_backward(be, process_group, kv_comm, d_kv_comm, dout, q, k, v, softmax_lse, delta,
-                                       softmax_scale, win, deterministic, kept, alibi_slopes, row_ranges, bool(causal))
+                                       softmax_scale, win, deterministic, kept, alibi_slopes, row_ranges, bool(causal), block_mask)
 
     dq = torch.empty((B, S, H, D), dtype=torch.float32, device=q.device)
 
