@@ -580,6 +580,62 @@ typedef struct {
 } rfa_seq_head_args;
 int rfa_seq_head_copy(const rfa_seq_head_args *args, void *stream);
 
+/* Rotary position embedding of q and k at GLOBAL positions (ring_flash_attn.apply_rotary; csrc/rfa_rotary.hip).  Up to two
+ * tensors of one call — q (B, S, H, D) and k (B, S, Hk, D), or packed (T, H, D) as B = 1, S = T — share rows, positions and
+ * tables and go through one launch.  No attention kernel knows about it and no existing struct changes (ABI 8 revision 1 stays).
+ * Of every (row, head) the columns [rot_offset, rot_offset + R) are rotated by the angles of the row's position pos:
+ *     interleaved == 0 (GPT-NeoX halves)   x1 = column rot_offset + c,     x2 = column rot_offset + c + R/2,   c < R/2
+ *     interleaved == 1 (GPT-J)             x1 = column rot_offset + 2 c,   x2 = column rot_offset + 2 c + 1,   c < R/2
+ *     o1 = x1 cos[pos, c] - x2 sin[pos, c],    o2 = x2 cos[pos, c] + x1 sin[pos, c]          (conj != 0: sin -> -sin)
+ * in fp32, each result rounded once to the io dtype; the bits of an element depend on its values and its position alone.  The
+ * other columns pass through: copied when dst != src, never touched when dst == src (in place).  conj is the inverse rotation
+ * and, applied to the incoming gradients, the backward.
+ *   cos, sin: (P, R/2), contiguous, table_dtype = the io dtype or RFA_ROTARY_TABLE_F32.
+ *   positions != NULL: int32, row i of batch entry b sits at pos_offset + positions[b * pos_batch + i] (pos_batch 0: one row of
+ *   positions for every batch entry).  NULL: the position map with the meaning of rfa_fwd_args.q_pos_* —
+ *       pos(i) = (pos_split == 0 || i < pos_split) ? pos_offset + i * pos_stride : pos_offset2 + (i - pos_split) * pos_stride
+ *   (pos_stride 0 reads as 1).  Where the tables are read the position is clamped to [0, P - 1]: no value of `positions` makes
+ *   the kernel read outside them; a map that leaves [0, P - 1] is refused on the host.
+ *   Each tensor: src read at the src strides, dst written at the dst strides (element strides, last stride 1, rows 16-byte
+ *   aligned); dst == src needs equal strides.  Apart from that a dst must not overlap any src.
+ * Checks, in this order and before any pointer is read: NULL struct RFA_ERR_NULL; struct_bytes != sizeof, reserved != 0,
+ * ntensors outside 1..2, interleaved or conj outside 0..1, a non-zero pad RFA_ERR_ARGS; dtype, or a table_dtype that is neither
+ * dtype nor RFA_ROTARY_TABLE_F32, RFA_ERR_DTYPE; D not a multiple of 8 in 8..256, R not a positive multiple of 16 (interleaved:
+ * of 8), rot_offset negative or not a multiple of 8, rot_offset + R > D RFA_ERR_HEAD_DIM; B < 0, S < 0, P < 1, B * S above
+ * 2^31 - 1 RFA_ERR_SHAPE; an H <= 0, of any tensor, RFA_ERR_HEADS; then a tensor's unit count (one thread each: B S H times
+ * R/16 — interleaved R/8 — plus, out of place, (D - R)/8) above 2^31 - 1 RFA_ERR_SHAPE; B == 0 or S == 0: RFA_OK, nothing is
+ * launched; NULL src, dst, cos or sin RFA_ERR_NULL; pointers or strides off the 16-byte contract RFA_ERR_ALIGN; dst == src with
+ * differing strides, a negative pos_batch, and with the map a negative pos_stride, a pos_split outside 0..S-1 or a position
+ * outside [0, P - 1] RFA_ERR_ARGS. */
+#define RFA_ROTARY_TABLE_F32 2
+typedef struct {
+  const void *src;
+  void *dst;               /* == src: in place */
+  int64_t src_batch, src_row, src_head; /* element strides */
+  int64_t dst_batch, dst_row, dst_head;
+  int32_t H;
+  int32_t pad;             /* 0 */
+} rfa_rotary_tensor;
+typedef struct {
+  uint32_t struct_bytes;   /* sizeof(rfa_rotary_args) */
+  uint32_t reserved;       /* 0 */
+  int32_t ntensors;        /* 1..2 */
+  int32_t B, S, D;         /* packed input: B = 1, S = T */
+  int32_t dtype;           /* rfa_dtype */
+  int32_t R, rot_offset;
+  int32_t interleaved, conj;
+  int32_t table_dtype;     /* dtype, or RFA_ROTARY_TABLE_F32 */
+  rfa_rotary_tensor t[2];
+  const void *cos, *sin;   /* (P, R/2), 16-byte aligned */
+  int64_t P;
+  const int32_t *positions; /* (B, S) / (S,) int32, or NULL: the map */
+  int64_t pos_batch;       /* elements between two batch entries of positions (0 = shared) */
+  int64_t pos_offset;      /* added to positions[], or the map's first offset */
+  int32_t pos_stride, pos_split;
+  int64_t pos_offset2;
+} rfa_rotary_args;
+int rfa_rotary(const rfa_rotary_args *args, void *stream);
+
 /* Per-head max attention logit (QK-Clip / MuonClip; Transformer Engine's and Megatron's `max_logit`): for every query head h
  *     max_logit[h] = max over batch b, query row i and the keys j that row i SEES of  softmax_scale * q[b,i,h,:] . k[b,j,h/G,:]
  * for one block call — the raw scaled dot product (no soft cap, bias, dropout or sink enters it), -inf for a head that sees no

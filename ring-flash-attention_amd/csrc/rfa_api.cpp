@@ -1650,6 +1650,76 @@ int rfa_seq_head_copy(const rfa_seq_head_args* a, void* stream) {
   return launch_seq_head_copy(p, (hipStream_t)stream) ? RFA_ERR_LAUNCH : RFA_OK;
 }
 
+// ---- rotary position embedding (rfa.h; csrc/rfa_rotary.hip) ------------------------------------------------------------------
+int rfa_rotary(const rfa_rotary_args* a, void* stream) {
+  if (!a) return RFA_ERR_NULL;
+  if (a->struct_bytes != sizeof(rfa_rotary_args) || a->reserved != 0) return RFA_ERR_ARGS;
+  if (a->ntensors < 1 || a->ntensors > 2) return RFA_ERR_ARGS;
+  if (a->interleaved < 0 || a->interleaved > 1 || a->conj < 0 || a->conj > 1) return RFA_ERR_ARGS;
+  for (int k = 0; k < a->ntensors; ++k)
+    if (a->t[k].pad != 0) return RFA_ERR_ARGS;
+  if (a->dtype != RFA_BF16 && a->dtype != RFA_F16) return RFA_ERR_DTYPE;
+  if (a->table_dtype != a->dtype && a->table_dtype != RFA_ROTARY_TABLE_F32) return RFA_ERR_DTYPE;
+  if (a->D <= 0 || a->D > kMaxHeadDim || (a->D % 8) != 0) return RFA_ERR_HEAD_DIM;
+  if (a->R <= 0 || (a->R % (a->interleaved ? 8 : 16)) != 0) return RFA_ERR_HEAD_DIM;
+  if (a->rot_offset < 0 || (a->rot_offset % 8) != 0 || a->rot_offset > a->D - a->R) return RFA_ERR_HEAD_DIM;
+  if (a->B < 0 || a->S < 0 || a->P < 1) return RFA_ERR_SHAPE;
+  const int64_t rows = (int64_t)a->B * a->S;
+  if (rows > INT32_MAX) return RFA_ERR_SHAPE;
+  for (int k = 0; k < a->ntensors; ++k)                        // every tensor's heads before any tensor's unit count
+    if (a->t[k].H <= 0) return RFA_ERR_HEADS;
+  RotaryParams p{};
+  p.g.B = (uint32_t)a->B; p.g.S = (uint32_t)a->S; p.g.R = (uint32_t)a->R; p.g.rot_off = (uint32_t)a->rot_offset;
+  p.g.rot_units = (uint32_t)(a->interleaved ? a->R / 8 : a->R / 16);
+  p.g.interleaved = a->interleaved;
+  for (int k = 0; k < a->ntensors; ++k) {
+    const rfa_rotary_tensor& s = a->t[k];
+    const int64_t uph = rotary_units_per_head((uint32_t)a->D, (uint32_t)a->R, a->interleaved, s.dst == s.src);
+    // (rows and H fit 31 bits each, uph <= 32: the products fit 62 and 36 bits)
+    if (rows * s.H > INT32_MAX || rows * s.H * uph > INT32_MAX) return RFA_ERR_SHAPE;
+    RotaryTensor& t = p.t[k];
+    t.sb = s.src_batch; t.sr = s.src_row; t.sh = s.src_head;
+    t.db = s.dst_batch; t.dr = s.dst_row; t.dh = s.dst_head;
+    t.H = (uint32_t)s.H; t.uph = (uint32_t)uph; t.nunits = (uint32_t)(rows * s.H * uph);
+    p.src[k] = s.src; p.dst[k] = s.dst;
+  }
+  if (a->B == 0 || a->S == 0) return RFA_OK;
+  if (!a->cos || !a->sin) return RFA_ERR_NULL;
+  for (int k = 0; k < a->ntensors; ++k)
+    if (!a->t[k].src || !a->t[k].dst) return RFA_ERR_NULL;
+  if (!aligned16(a->cos) || !aligned16(a->sin)) return RFA_ERR_ALIGN;
+  for (int k = 0; k < a->ntensors; ++k) {
+    const rfa_rotary_tensor& s = a->t[k];
+    if (!aligned16(s.src) || !aligned16(s.dst) || (s.src_batch % 8) || (s.src_row % 8) || (s.src_head % 8) ||
+        (s.dst_batch % 8) || (s.dst_row % 8) || (s.dst_head % 8))
+      return RFA_ERR_ALIGN;
+  }
+  for (int k = 0; k < a->ntensors; ++k) {
+    const rfa_rotary_tensor& s = a->t[k];
+    if (s.dst == s.src && (s.src_batch != s.dst_batch || s.src_row != s.dst_row || s.src_head != s.dst_head)) return RFA_ERR_ARGS;
+  }
+  if (a->pos_batch < 0) return RFA_ERR_ARGS;
+  const uint32_t stride = a->pos_stride > 0 ? (uint32_t)a->pos_stride : 1u;
+  if (!a->positions) {
+    if (a->pos_stride < 0 || a->pos_split < 0 || a->pos_split > a->S - 1) return RFA_ERR_ARGS;
+    // the map's pieces are monotone: their ends bound every position
+    const uint32_t ends[4] = {0u, (uint32_t)(a->pos_split ? a->pos_split - 1 : a->S - 1), (uint32_t)a->pos_split, (uint32_t)(a->S - 1)};
+    // (an offset beyond 2^40 names no table row; refused here so that the sums below cannot overflow)
+    if (a->pos_offset < -(1ll << 40) || a->pos_offset > (1ll << 40) || a->pos_offset2 < -(1ll << 40) || a->pos_offset2 > (1ll << 40))
+      return RFA_ERR_ARGS;
+    for (int e = 0; e < 4; ++e) {
+      const int64_t pos = rotary_map_pos(a->pos_offset, stride, a->pos_split, a->pos_offset2, ends[e]);
+      if (pos < 0 || pos > a->P - 1) return RFA_ERR_ARGS;
+    }
+  }
+  p.cos = a->cos; p.sin = a->sin; p.P = a->P;
+  p.positions = a->positions; p.pos_batch = a->pos_batch;
+  p.pos_off = a->pos_offset; p.pos_off2 = a->pos_offset2; p.pos_stride = stride; p.pos_split = a->pos_split;
+  p.conj = a->conj;
+  p.ntensors = a->ntensors;
+  return launch_rotary(p, a->dtype, a->table_dtype == RFA_ROTARY_TABLE_F32, (hipStream_t)stream) ? RFA_ERR_LAUNCH : RFA_OK;
+}
+
 // ---- per-head max attention logit (rfa.h; csrc/rfa_maxlogit.hip) ------------------------------------------------------------
 // everything that needs no tensor pointer, in the header's order; *nqblk = blocks of 256 query rows per batch entry
 static int max_logit_check(const rfa_max_logit_args* a, int* nqblk) {

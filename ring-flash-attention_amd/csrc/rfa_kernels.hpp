@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include "rfa_common.hpp"
 #include "rfa_seqhead_index.h"
+#include "rfa_rotary_index.h"
 #include "rfa_maxlogit_band.h"
 #include "rfa_rowrange.h"
 #include "rfa_blockmask.h"
@@ -267,6 +268,26 @@ struct SeqHeadParams {
   int ntensors;
 };
 int launch_seq_head_copy(const SeqHeadParams& p, hipStream_t stream);
+
+// rotary position embedding (rfa_rotary.hip; index arithmetic: rfa_rotary_index.h): up to two tensors (q, k) per launch, one
+// thread per unit.  positions != NULL: row i of batch entry b sits at pos_off + positions[b * pos_batch + i]; NULL: at the
+// position map (pos_off, pos_stride, pos_split, pos_off2).  Either way clamped to [0, P - 1] where the tables are read.
+struct RotaryParams {
+  RotaryGeom g;
+  RotaryTensor t[2];
+  const void* src[2];
+  void* dst[2];             // == src[k]: in place
+  const void *cos, *sin;    // (P, R/2), contiguous, fp32 or the io dtype
+  int64_t P;
+  const int32_t* positions;
+  int64_t pos_batch;
+  int64_t pos_off, pos_off2;
+  uint32_t pos_stride;
+  int32_t pos_split;
+  int32_t conj;             // s -> -s: the inverse rotation = the backward
+  int ntensors;
+};
+int launch_rotary(const RotaryParams& p, int dtype, bool table_f32, hipStream_t stream);
 
 // per-head max attention logit (rfa_maxlogit.hip; tile arithmetic: rfa_maxlogit_band.h): the forward's S phase alone.
 // Workgroup (batch b, query block qb, head h) stores the max of its UNSCALED visible scores to

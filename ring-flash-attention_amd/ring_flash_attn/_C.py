@@ -200,6 +200,44 @@ class SeqHeadArgs(C.Structure):
             self.struct_bytes = C.sizeof(SeqHeadArgs)
 
 
+ROTARY_TABLE_F32 = 2              # RFA_ROTARY_TABLE_F32: fp32 cos / sin tables (otherwise the io dtype's code)
+
+
+class RotaryTensor(C.Structure):
+    """rfa_rotary_tensor: one tensor of a rotary call — read at the src strides, written at the dst strides"""
+    _fields_ = [
+        ("src", C.c_void_p), ("dst", C.c_void_p),
+        ("src_batch", C.c_int64), ("src_row", C.c_int64), ("src_head", C.c_int64),
+        ("dst_batch", C.c_int64), ("dst_row", C.c_int64), ("dst_head", C.c_int64),
+        ("H", C.c_int32), ("pad", C.c_int32),
+    ]
+
+
+class RotaryArgs(C.Structure):
+    """rfa_rotary_args: rotary position embedding of up to two tensors at global positions; struct_bytes is filled in here"""
+    _fields_ = [
+        ("struct_bytes", C.c_uint32), ("reserved", C.c_uint32),
+        ("ntensors", C.c_int32),
+        ("B", C.c_int32), ("S", C.c_int32), ("D", C.c_int32),
+        ("dtype", C.c_int32),
+        ("R", C.c_int32), ("rot_offset", C.c_int32),
+        ("interleaved", C.c_int32), ("conj", C.c_int32),
+        ("table_dtype", C.c_int32),
+        ("t", RotaryTensor * 2),
+        ("cos", C.c_void_p), ("sin", C.c_void_p),
+        ("P", C.c_int64),
+        ("positions", C.c_void_p), ("pos_batch", C.c_int64),
+        ("pos_offset", C.c_int64),
+        ("pos_stride", C.c_int32), ("pos_split", C.c_int32),
+        ("pos_offset2", C.c_int64),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if not self.struct_bytes:
+            self.struct_bytes = C.sizeof(RotaryArgs)
+
+
 class MaxLogitArgs(C.Structure):
     """rfa_max_logit_args: the per-head max attention logit of one block call; struct_bytes is filled in here"""
     _fields_ = [
@@ -353,6 +391,7 @@ SYMBOLS = {
     "rfa_sink_grad": (C.c_int, [C.POINTER(SinkGradArgs), C.c_void_p]),
     "rfa_sink_grad_workspace_bytes": (C.c_int64, [C.POINTER(SinkGradArgs)]),
     "rfa_seq_head_copy": (C.c_int, [C.POINTER(SeqHeadArgs), C.c_void_p]),
+    "rfa_rotary": (C.c_int, [C.POINTER(RotaryArgs), C.c_void_p]),
     "rfa_max_logit": (C.c_int, [C.POINTER(MaxLogitArgs), C.c_void_p]),
     "rfa_max_logit_workspace_bytes": (C.c_int64, [C.POINTER(MaxLogitArgs)]),
     "rfa_bwd_preprocess_lse": (C.c_int, [C.POINTER(BwdPreLseArgs), C.c_void_p]),
@@ -422,6 +461,9 @@ def load():
     for name in ("rfa_fwd_bm", "rfa_bwd_bm", "rfa_blockmask_workspace_bytes"):
         if not hasattr(lib, name):
             raise RuntimeError(f"ring_flash_attn: librfa_hip.so has no {name} (the block-mask entry points); rebuild")
+    # ... and the rotary embedding (a struct of its own)
+    if not hasattr(lib, "rfa_rotary"):
+        raise RuntimeError("ring_flash_attn: librfa_hip.so has no rfa_rotary (the rotary embedding entry point); rebuild")
     for name, (res, args) in SYMBOLS.items():
         fn = getattr(lib, name)  # AttributeError if the .so is stale
         fn.restype = res

@@ -79,3 +79,7 @@ from ._api import BLOCK_MASK_SIZE, with_block_mask
 # DeepSpeed-Ulysses head parallelism in front of the dense schedules ("USP"): with_ulysses(func, ulysses_group) exchanges heads
 # for rows around `func`; make_usp_groups(func, ulysses_size) makes the (Ulysses, ring) groups of func's family
 from .ulysses import make_usp_groups, with_ulysses
+# rotary position embedding at GLOBAL positions for sharded q / k: apply_rotary(q, k, cos, sin, layout=func, group=group)
+# rotates this rank's shards in one streaming kernel; local_positions(func, n_local, group=group) is the global position of
+# every local row for the sharding `func` expects (dense and packed families)
+from .rotary import apply_rotary, local_positions

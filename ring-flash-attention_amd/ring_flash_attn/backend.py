@@ -98,6 +98,7 @@ class HipBackend:
     serves_vdim = True               # fwd / bwd take a `v` whose head dim differs from q's (include/rfa.h: rfa_fwd_vd, rfa_bwd_vd): MLA 192 / 128
     serves_row_ranges = True         # fwd / bwd take `row_ranges=(start, end, k_pos0)` (include/rfa.h: rfa_fwd_rr, rfa_bwd_rr): ring_flash_attn.with_row_ranges
     serves_block_mask = True         # fwd / bwd take `block_mask=(mask_view, k_blk0)` (include/rfa.h: rfa_fwd_bm, rfa_bwd_bm): ring_flash_attn.with_block_mask
+    serves_rotary = True             # rotary (include/rfa.h: rfa_rotary): ring_flash_attn.apply_rotary
     serves_dropout_positions = True  # `dropout=` takes the position maps (q_map, k_map): what dropout over a dense ring, zigzag or stripe schedule needs
 
     def __init__(self):
@@ -691,6 +692,45 @@ class HipBackend:
         if not slots.is_contiguous():
             raise ValueError("seq_head_copy: the slot buffer must be contiguous")
         _C.check(self.lib.rfa_seq_head_copy(C.byref(a), _stream(slots)), "rfa_seq_head_copy")
+
+    # ------------------------------------------------------------------ rotary embedding (apply_rotary)
+    def rotary(self, srcs, dsts, cos, sin, *, positions=None, pos_map=None, interleaved=False, rot_offset=0, conj=False):
+        """one launch of the rotary embedding (include/rfa.h: rfa_rotary) for one or two tensors that share rows and positions.
+        srcs / dsts: (B,S,H,D) or packed (T,H,D), io dtype, any strides with last stride 1 and 16-byte aligned rows; dsts[k] is
+        srcs[k] for in place.  cos / sin: (P, R/2) contiguous, fp32 or the io dtype.  positions: int32 (S,) / (B,S) / (T,),
+        row stride 1, to which pos_map's offset is added — or None: the rows sit at pos_map = (offset, (stride, split,
+        offset2)) (_common.pos_map).  conj: the inverse rotation (the backward)."""
+        self._check_dev(cos, sin, positions, *srcs, *dsts)
+        t0 = srcs[0]
+        packed = t0.dim() == 3
+        a = _C.RotaryArgs()
+        a.ntensors = len(srcs)
+        a.B, a.S = (1, t0.shape[0]) if packed else (t0.shape[0], t0.shape[1])
+        a.D, a.dtype = t0.shape[-1], self._dtype(t0)
+        a.R, a.rot_offset = 2 * cos.shape[1], int(rot_offset)
+        a.interleaved, a.conj = int(bool(interleaved)), int(bool(conj))
+        a.table_dtype = _C.ROTARY_TABLE_F32 if cos.dtype == torch.float32 else self._dtype(cos)
+        if not cos.is_contiguous() or not sin.is_contiguous() or cos.shape != sin.shape or cos.dtype != sin.dtype:
+            raise ValueError("rotary: cos and sin are contiguous (P, R/2) tensors of one shape and dtype")
+        for d, s, o in zip(a.t, srcs, dsts):
+            if s.dtype != t0.dtype or o.dtype != t0.dtype or s.shape != o.shape or s.stride(-1) != 1 or o.stride(-1) != 1:
+                raise ValueError("rotary: sources and destinations share one dtype and shape; last (head_dim) stride must be 1")
+            d.src, d.dst, d.H = s.data_ptr(), o.data_ptr(), s.shape[-2]
+            # (the stride of a dimension of length 1 is never used: 0, whatever torch reports for it)
+            ss, os_ = ([st if n > 1 else 0 for n, st in zip(t.shape, t.stride())] for t in (s, o))
+            d.src_batch, d.src_row, d.src_head = (0 if packed else ss[0]), ss[-3], ss[-2]
+            d.dst_batch, d.dst_row, d.dst_head = (0 if packed else os_[0]), os_[-3], os_[-2]
+        a.cos, a.sin, a.P = cos.data_ptr(), sin.data_ptr(), cos.shape[0]
+        off, (stride, split, off2) = pos_map if pos_map is not None else (0, (1, 0, 0))
+        a.pos_offset = int(off)
+        if positions is not None:
+            if positions.dtype != torch.int32 or (positions.stride(-1) != 1 and positions.shape[-1] != 1):
+                raise ValueError("rotary: positions are int32 with row stride 1")
+            a.positions = positions.data_ptr()
+            a.pos_batch = positions.stride(0) if positions.dim() == 2 and positions.shape[0] > 1 else 0
+        else:
+            a.pos_stride, a.pos_split, a.pos_offset2 = int(stride), int(split), int(off2)
+        _C.check(self.lib.rfa_rotary(C.byref(a), _stream(t0)), "rfa_rotary")
 
     def sum_slots(self, src: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
         """dst[...] = sum over dim 0 of src (io dtype, summed in fp32).  src: (W, B, S, H, D) or (W, T, H, D), each slot
