@@ -636,6 +636,91 @@ typedef struct {
 } rfa_rotary_args;
 int rfa_rotary(const rfa_rotary_args *args, void *stream);
 
+/* Per-head RMSNorm of q and k fused with the rotary embedding (ring_flash_attn.apply_qk_norm_rotary; csrc/rfa_qknorm.hip) — what
+ * Qwen3, Gemma-3 and OLMo-style models run in front of attention: q = rope(rmsnorm_D(q) * w_q), k likewise.  Up to two tensors of
+ * one call share rows, positions and tables and go through ONE launch per direction; structs of their own, no existing struct
+ * changes (ABI 8 revision 1 stays).  Tensors, tables and positions are rfa_rotary's (t[k].src = the input x, t[k].dst = the
+ * output — backward: dx); out of place only.  Of every (row, head), in fp32 with ONE rounding to the io dtype at the end:
+ *     rstd = rsqrt(sum_c x_c^2 / D + eps),   a_c = weight_offset + weight[c],   y_c = (x_c * rstd) * a_c
+ *     columns [rot_offset, rot_offset + R) of y rotated as rfa_rotary rotates them (the same expression), the others y
+ * The norm runs over all D columns.  R == 0 is the norm alone: cos, sin, P and the position fields are not looked at.
+ *   weight[k]: (D,), contiguous, 16-byte aligned, weight_dtype = the io dtype or RFA_QK_NORM_WEIGHT_F32.
+ * Backward (rfa_qk_norm_rotary_bwd), with g = the conjugate rotation of dout in fp32 (pass-through columns: dout), xh = x rstd
+ * (rstd recomputed from x by the forward's own code: nothing but x is kept):
+ *     m = (1/D) sum_c g_c a_c xh_c,    dx_c = rstd (g_c a_c - xh_c m)   rounded once
+ *     dweight[k][c] = sum over batch, rows and heads of g_c xh_c        fp32 (D,), OVERWRITTEN; NULL: not wanted
+ * one launch for dx of both tensors and the per-workgroup partials of dweight, plus one small launch that folds the partials in
+ * a fixed order: no atomics, two runs give the same bits.  The bits of an element depend on the row's values, the weight and the
+ * position alone — not on the strides, on whether a second tensor rode along, or on how the position was delivered.
+ *   workspace: rfa_qk_norm_rotary_bwd_workspace_bytes(args) bytes (a function of ntensors, B, S, D and the H alone; 0 for
+ *   arguments the checks below refuse before a pointer is needed), 16-byte aligned, needed where a dweight is asked for; its
+ *   contents on entry do not matter.
+ * Checks, in this order and before any pointer is read: NULL struct RFA_ERR_NULL; struct_bytes != sizeof, reserved != 0,
+ * ntensors outside 1..2, interleaved outside 0..1, a non-zero pad, an eps that is negative or not finite, a weight_offset that
+ * is not finite RFA_ERR_ARGS; dtype, a table_dtype that is neither dtype nor RFA_ROTARY_TABLE_F32, a weight_dtype that is
+ * neither dtype nor RFA_QK_NORM_WEIGHT_F32 RFA_ERR_DTYPE; D not a multiple of 8 in 8..256, R negative or not a multiple of 16
+ * (interleaved: of 8), rot_offset negative or not a multiple of 8, rot_offset + R > D RFA_ERR_HEAD_DIM; B < 0, S < 0, with
+ * R > 0 a P < 1, B * S above 2^31 - 1 RFA_ERR_SHAPE; an H <= 0, of any tensor, RFA_ERR_HEADS; then a tensor's B S H above
+ * 2^31 - 1 RFA_ERR_SHAPE; B == 0 or S == 0: RFA_OK, nothing is launched or written; NULL src, dst, weight (backward: dout; a
+ * dweight without a workspace), with R > 0 a NULL cos or sin RFA_ERR_NULL; pointers or strides off the 16-byte contract (a
+ * dweight: 4 bytes) RFA_ERR_ALIGN; dst == src (backward also dst == dout), a negative pos_batch, with R > 0 and the map a
+ * negative pos_stride, a pos_split outside 0..S-1 or a position outside [0, P - 1], a workspace_bytes below the stated size
+ * RFA_ERR_ARGS. */
+#define RFA_QK_NORM_WEIGHT_F32 2
+typedef struct {
+  uint32_t struct_bytes;   /* sizeof(rfa_qk_norm_rotary_args) */
+  uint32_t reserved;       /* 0 */
+  int32_t ntensors;        /* 1..2 */
+  int32_t B, S, D;         /* packed input: B = 1, S = T */
+  int32_t dtype;           /* rfa_dtype */
+  int32_t R, rot_offset;   /* R == 0: the norm alone */
+  int32_t interleaved;
+  int32_t table_dtype;     /* dtype, or RFA_ROTARY_TABLE_F32 */
+  int32_t weight_dtype;    /* dtype, or RFA_QK_NORM_WEIGHT_F32 */
+  float eps, weight_offset;
+  rfa_rotary_tensor t[2];  /* src = x, dst = the output */
+  const void *weight[2];   /* (D,) */
+  const void *cos, *sin;   /* (P, R/2), 16-byte aligned; R == 0: not looked at */
+  int64_t P;
+  const int32_t *positions;
+  int64_t pos_batch;
+  int64_t pos_offset;
+  int32_t pos_stride, pos_split;
+  int64_t pos_offset2;
+} rfa_qk_norm_rotary_args;
+typedef struct {
+  const void *dout;        /* the gradient of the output, shaped like it */
+  int64_t dout_batch, dout_row, dout_head; /* element strides */
+} rfa_qk_norm_grad;
+typedef struct {
+  uint32_t struct_bytes;   /* sizeof(rfa_qk_norm_rotary_bwd_args) */
+  uint32_t reserved;       /* 0 */
+  int32_t ntensors;
+  int32_t B, S, D;
+  int32_t dtype;
+  int32_t R, rot_offset;
+  int32_t interleaved;
+  int32_t table_dtype;
+  int32_t weight_dtype;
+  float eps, weight_offset;
+  rfa_rotary_tensor t[2];  /* src = x, dst = dx */
+  const void *weight[2];
+  const void *cos, *sin;
+  int64_t P;
+  const int32_t *positions;
+  int64_t pos_batch;
+  int64_t pos_offset;
+  int32_t pos_stride, pos_split;
+  int64_t pos_offset2;
+  rfa_qk_norm_grad g[2];
+  float *dweight[2];       /* fp32 (D,), overwritten; NULL: not wanted */
+  void *workspace;
+  int64_t workspace_bytes;
+} rfa_qk_norm_rotary_bwd_args;
+int rfa_qk_norm_rotary_fwd(const rfa_qk_norm_rotary_args *args, void *stream);
+int rfa_qk_norm_rotary_bwd(const rfa_qk_norm_rotary_bwd_args *args, void *stream);
+int64_t rfa_qk_norm_rotary_bwd_workspace_bytes(const rfa_qk_norm_rotary_bwd_args *args);
+
 /* Per-head max attention logit (QK-Clip / MuonClip; Transformer Engine's and Megatron's `max_logit`): for every query head h
  *     max_logit[h] = max over batch b, query row i and the keys j that row i SEES of  softmax_scale * q[b,i,h,:] . k[b,j,h/G,:]
  * for one block call — the raw scaled dot product (no soft cap, bias, dropout or sink enters it), -inf for a head that sees no

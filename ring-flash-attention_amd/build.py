@@ -27,9 +27,9 @@ SELFTEST_SRC = os.path.join(ROOT, "tests", "native", "selftest.cpp")
 SELFTEST_BIN = os.path.join(ROOT, "tests", "native", "selftest")
 
 HIP_SOURCES = ["rfa_fwd.hip", "rfa_bwd.hip", "rfa_bigd.hip", "rfa_dqs.hip", "rfa_aux.hip", "rfa_sink.hip", "rfa_seqhead.hip",
-               "rfa_maxlogit.hip", "rfa_mergepair.hip", "rfa_vdim.hip", "rfa_rotary.hip"]
+               "rfa_maxlogit.hip", "rfa_mergepair.hip", "rfa_vdim.hip", "rfa_rotary.hip", "rfa_qknorm.hip"]
 API_SOURCE = "rfa_api.cpp"
-HEADERS = ["rfa_common.hpp", "rfa_kernels.hpp", "rfa_seqhead_index.h", "rfa_rotary_index.h", "rfa_maxlogit_band.h", "rfa_rowrange.h", "rfa_blockmask.h", os.path.join(ROOT, "include", "rfa.h")]
+HEADERS = ["rfa_common.hpp", "rfa_kernels.hpp", "rfa_seqhead_index.h", "rfa_rotary_index.h", "rfa_rotary_math.hpp", "rfa_qknorm_index.h", "rfa_maxlogit_band.h", "rfa_rowrange.h", "rfa_blockmask.h", os.path.join(ROOT, "include", "rfa.h")]
 EXPORTS_MAP = "rfa_exports.map"          # linker version script: only rfa_* is bindable
 
 

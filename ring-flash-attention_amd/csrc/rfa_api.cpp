@@ -1720,6 +1720,144 @@ int rfa_rotary(const rfa_rotary_args* a, void* stream) {
   return launch_rotary(p, a->dtype, a->table_dtype == RFA_ROTARY_TABLE_F32, (hipStream_t)stream) ? RFA_ERR_LAUNCH : RFA_OK;
 }
 
+// ---- per-head QK RMSNorm + rotary (rfa.h; csrc/rfa_qknorm.hip) ---------------------------------------------------------------
+extern "C++" {
+// the checks the forward and the backward struct share, in the header's order: `upto` 0 stops in front of "no rows" (everything
+// that needs no pointer: what the workspace size depends on), 1 runs them all.  RFA_OK with *launch == false: nothing to do.
+template <typename A>
+static int qk_norm_check(const A* a, int upto, QkNormParams* p, bool* launch) {
+  *launch = false;
+  if (!a) return RFA_ERR_NULL;
+  if (a->struct_bytes != sizeof(A) || a->reserved != 0) return RFA_ERR_ARGS;
+  if (a->ntensors < 1 || a->ntensors > 2) return RFA_ERR_ARGS;
+  if (a->interleaved < 0 || a->interleaved > 1) return RFA_ERR_ARGS;
+  for (int k = 0; k < a->ntensors; ++k)
+    if (a->t[k].pad != 0) return RFA_ERR_ARGS;
+  if (!(a->eps >= 0.f) || !(a->eps <= FLT_MAX) || !(a->weight_offset >= -FLT_MAX && a->weight_offset <= FLT_MAX)) return RFA_ERR_ARGS;
+  if (a->dtype != RFA_BF16 && a->dtype != RFA_F16) return RFA_ERR_DTYPE;
+  if (a->table_dtype != a->dtype && a->table_dtype != RFA_ROTARY_TABLE_F32) return RFA_ERR_DTYPE;
+  if (a->weight_dtype != a->dtype && a->weight_dtype != RFA_QK_NORM_WEIGHT_F32) return RFA_ERR_DTYPE;
+  if (a->D <= 0 || a->D > kMaxHeadDim || (a->D % 8) != 0) return RFA_ERR_HEAD_DIM;
+  if (a->R < 0 || (a->R % (a->interleaved ? 8 : 16)) != 0) return RFA_ERR_HEAD_DIM;
+  if (a->rot_offset < 0 || (a->rot_offset % 8) != 0 || a->rot_offset > a->D - a->R) return RFA_ERR_HEAD_DIM;
+  if (a->B < 0 || a->S < 0 || (a->R > 0 && a->P < 1)) return RFA_ERR_SHAPE;
+  const int64_t rows = (int64_t)a->B * a->S;
+  if (rows > INT32_MAX) return RFA_ERR_SHAPE;
+  for (int k = 0; k < a->ntensors; ++k)
+    if (a->t[k].H <= 0) return RFA_ERR_HEADS;
+  for (int k = 0; k < a->ntensors; ++k) {
+    if (rows * a->t[k].H > INT32_MAX) return RFA_ERR_SHAPE;
+    const rfa_rotary_tensor& s = a->t[k];
+    QkNormTensor& t = p->t[k];
+    t.xb = s.src_batch; t.xr = s.src_row; t.xh = s.src_head;
+    t.ob = s.dst_batch; t.orow = s.dst_row; t.oh = s.dst_head;
+    t.H = (uint32_t)s.H; t.nitems = (uint32_t)(rows * s.H);
+    p->x[k] = s.src; p->out[k] = s.dst; p->weight[k] = a->weight[k];
+  }
+  QkNormGeom& g = p->g;
+  g.B = (uint32_t)a->B; g.S = (uint32_t)a->S; g.D = (uint32_t)a->D; g.R = (uint32_t)a->R; g.rot_off = (uint32_t)a->rot_offset;
+  g.interleaved = a->interleaved; g.chunks = g.D / 8; g.group = qknorm_group(g.D);
+  p->ntensors = a->ntensors;
+  for (int k = 0; k < a->ntensors; ++k) {
+    p->nparts[k] = qknorm_parts(p->t[k].nitems, g.group);
+    p->walk[k] = qknorm_walk(p->t[k].nitems, p->nparts[k], g.group);
+  }
+  p->eps = a->eps; p->weight_offset = a->weight_offset;
+  if (a->B == 0 || a->S == 0 || upto == 0) return RFA_OK;
+  *launch = true;
+  for (int k = 0; k < a->ntensors; ++k)
+    if (!a->t[k].src || !a->t[k].dst || !a->weight[k]) return RFA_ERR_NULL;
+  if (a->R > 0 && (!a->cos || !a->sin)) return RFA_ERR_NULL;
+  return RFA_OK;
+}
+
+// the checks behind the NULL checks: alignment, then the rest
+template <typename A>
+static int qk_norm_check_rest(const A* a) {
+  if (a->R > 0 && (!aligned16(a->cos) || !aligned16(a->sin))) return RFA_ERR_ALIGN;
+  for (int k = 0; k < a->ntensors; ++k) {
+    const rfa_rotary_tensor& s = a->t[k];
+    if (!aligned16(s.src) || !aligned16(s.dst) || !aligned16(a->weight[k]) || (s.src_batch % 8) || (s.src_row % 8) ||
+        (s.src_head % 8) || (s.dst_batch % 8) || (s.dst_row % 8) || (s.dst_head % 8))
+      return RFA_ERR_ALIGN;
+  }
+  return RFA_OK;
+}
+
+template <typename A>
+static int qk_norm_check_map(const A* a, QkNormParams* p) {
+  for (int k = 0; k < a->ntensors; ++k)
+    if (a->t[k].dst == a->t[k].src) return RFA_ERR_ARGS;
+  if (a->pos_batch < 0) return RFA_ERR_ARGS;
+  const uint32_t stride = a->pos_stride > 0 ? (uint32_t)a->pos_stride : 1u;
+  if (a->R > 0 && !a->positions) {
+    if (a->pos_stride < 0 || a->pos_split < 0 || a->pos_split > a->S - 1) return RFA_ERR_ARGS;
+    const uint32_t ends[4] = {0u, (uint32_t)(a->pos_split ? a->pos_split - 1 : a->S - 1), (uint32_t)a->pos_split, (uint32_t)(a->S - 1)};
+    if (a->pos_offset < -(1ll << 40) || a->pos_offset > (1ll << 40) || a->pos_offset2 < -(1ll << 40) || a->pos_offset2 > (1ll << 40))
+      return RFA_ERR_ARGS;
+    for (int e = 0; e < 4; ++e) {
+      const int64_t pos = rotary_map_pos(a->pos_offset, stride, a->pos_split, a->pos_offset2, ends[e]);
+      if (pos < 0 || pos > a->P - 1) return RFA_ERR_ARGS;
+    }
+  }
+  if (a->R > 0) {
+    p->cos = a->cos; p->sin = a->sin; p->P = a->P;
+    p->positions = a->positions; p->pos_batch = a->pos_batch;
+    p->pos_off = a->pos_offset; p->pos_off2 = a->pos_offset2; p->pos_stride = stride; p->pos_split = a->pos_split;
+  }
+  return RFA_OK;
+}
+}  // extern "C++"
+
+int rfa_qk_norm_rotary_fwd(const rfa_qk_norm_rotary_args* a, void* stream) {
+  QkNormParams p{};
+  bool launch = false;
+  int rc = qk_norm_check(a, 1, &p, &launch);
+  if (rc != RFA_OK || !launch) return rc;
+  if ((rc = qk_norm_check_rest(a)) != RFA_OK) return rc;
+  if ((rc = qk_norm_check_map(a, &p)) != RFA_OK) return rc;
+  return launch_qknorm_fwd(p, a->dtype, a->table_dtype == RFA_ROTARY_TABLE_F32, a->weight_dtype == RFA_QK_NORM_WEIGHT_F32,
+                           (hipStream_t)stream) ? RFA_ERR_LAUNCH : RFA_OK;
+}
+
+int64_t rfa_qk_norm_rotary_bwd_workspace_bytes(const rfa_qk_norm_rotary_bwd_args* a) {
+  QkNormParams p{};
+  bool launch = false;
+  if (qk_norm_check(a, 0, &p, &launch) != RFA_OK) return 0;
+  return qknorm_workspace_bytes(1, p.nparts[0] + p.nparts[1], p.g.D);
+}
+
+int rfa_qk_norm_rotary_bwd(const rfa_qk_norm_rotary_bwd_args* a, void* stream) {
+  QkNormParams p{};
+  bool launch = false;
+  int rc = qk_norm_check(a, 1, &p, &launch);
+  if (rc != RFA_OK || !launch) return rc;
+  bool any = false;
+  for (int k = 0; k < a->ntensors; ++k) {
+    if (!a->g[k].dout) return RFA_ERR_NULL;
+    any = any || a->dweight[k] != nullptr;
+  }
+  if (any && !a->workspace) return RFA_ERR_NULL;
+  if ((rc = qk_norm_check_rest(a)) != RFA_OK) return rc;
+  for (int k = 0; k < a->ntensors; ++k) {
+    const rfa_qk_norm_grad& g = a->g[k];
+    if (!aligned16(g.dout) || (g.dout_batch % 8) || (g.dout_row % 8) || (g.dout_head % 8)) return RFA_ERR_ALIGN;
+    if (a->dweight[k] && ((uintptr_t)a->dweight[k] % 4) != 0) return RFA_ERR_ALIGN;
+  }
+  if (any && !aligned16(a->workspace)) return RFA_ERR_ALIGN;
+  if ((rc = qk_norm_check_map(a, &p)) != RFA_OK) return rc;
+  for (int k = 0; k < a->ntensors; ++k) {
+    if (a->t[k].dst == a->g[k].dout) return RFA_ERR_ARGS;
+    p.dout[k] = a->g[k].dout;
+    p.t[k].gb = a->g[k].dout_batch; p.t[k].gr = a->g[k].dout_row; p.t[k].gh = a->g[k].dout_head;
+    p.dweight[k] = a->dweight[k];
+  }
+  if (any && a->workspace_bytes < qknorm_workspace_bytes(1, p.nparts[0] + p.nparts[1], p.g.D)) return RFA_ERR_ARGS;
+  p.workspace = (float*)a->workspace;
+  return launch_qknorm_bwd(p, a->dtype, a->table_dtype == RFA_ROTARY_TABLE_F32, a->weight_dtype == RFA_QK_NORM_WEIGHT_F32,
+                           (hipStream_t)stream) ? RFA_ERR_LAUNCH : RFA_OK;
+}
+
 // ---- per-head max attention logit (rfa.h; csrc/rfa_maxlogit.hip) ------------------------------------------------------------
 // everything that needs no tensor pointer, in the header's order; *nqblk = blocks of 256 query rows per batch entry
 static int max_logit_check(const rfa_max_logit_args* a, int* nqblk) {

@@ -5,6 +5,7 @@
 #include "rfa_common.hpp"
 #include "rfa_seqhead_index.h"
 #include "rfa_rotary_index.h"
+#include "rfa_qknorm_index.h"
 #include "rfa_maxlogit_band.h"
 #include "rfa_rowrange.h"
 #include "rfa_blockmask.h"
@@ -288,6 +289,33 @@ struct RotaryParams {
   int ntensors;
 };
 int launch_rotary(const RotaryParams& p, int dtype, bool table_f32, hipStream_t stream);
+
+// per-head QK RMSNorm fused with the rotary embedding (rfa_qknorm.hip; index arithmetic: rfa_qknorm_index.h): up to two tensors
+// (q, k) per launch, one lane per 16-byte chunk, one (row, head) per lane group.  Positions as in RotaryParams; R == 0 (cos ==
+// sin == NULL) is the norm alone.  Backward: dout / dx per tensor, dweight[k] != NULL asks for that tensor's fp32 (D,) weight
+// gradient (workspace: tensor 0's nparts[0] partials, then tensor 1's nparts[1]; then the fold launch).
+struct QkNormParams {
+  QkNormGeom g;
+  QkNormTensor t[2];
+  const void* x[2];
+  void* out[2];             // forward: y; backward: dx
+  const void* dout[2];      // backward only
+  const void* weight[2];    // (D,), fp32 or the io dtype
+  float* dweight[2];        // backward: fp32 (D,) or NULL
+  float* workspace;
+  uint32_t nparts[2], walk[2]; // backward, per tensor (a function of ITS items alone): workgroups = partials, items a lane group walks
+  float eps, weight_offset;
+  const void *cos, *sin;
+  int64_t P;
+  const int32_t* positions;
+  int64_t pos_batch;
+  int64_t pos_off, pos_off2;
+  uint32_t pos_stride;
+  int32_t pos_split;
+  int ntensors;
+};
+int launch_qknorm_fwd(const QkNormParams& p, int dtype, bool table_f32, bool weight_f32, hipStream_t stream);
+int launch_qknorm_bwd(const QkNormParams& p, int dtype, bool table_f32, bool weight_f32, hipStream_t stream);
 
 // per-head max attention logit (rfa_maxlogit.hip; tile arithmetic: rfa_maxlogit_band.h): the forward's S phase alone.
 // Workgroup (batch b, query block qb, head h) stores the max of its UNSCALED visible scores to

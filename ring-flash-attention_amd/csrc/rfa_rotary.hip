@@ -17,23 +17,9 @@
 // grid: x = ceil(max over tensors of nunits / 256), y = tensor of the call.
 #include "rfa_common.hpp"
 #include "rfa_kernels.hpp"
+#include "rfa_rotary_math.hpp"     // rot(), load_tab(): shared with rfa_qknorm.hip
 
 namespace rfa {
-
-// (o1, o2) of one pair; the product that is subtracted / added is rounded to fp32 first, the other one is fused
-__device__ __forceinline__ void rot(float x1, float x2, float c, float s, float& o1, float& o2) {
-  o1 = __builtin_fmaf(x1, c, -(x2 * s));
-  o2 = __builtin_fmaf(x2, c, x1 * s);
-}
-
-// N consecutive values of a cos / sin row as fp32 (N * sizeof(TT) bytes, aligned to that)
-template <typename TT, int N>
-__device__ __forceinline__ void load_tab(const TT* p, float (&f)[N]) {
-  typedef TT vecn __attribute__((ext_vector_type(N)));
-  const vecn v = *(const vecn*)p;
-#pragma unroll
-  for (int e = 0; e < N; ++e) f[e] = (float)v[e];
-}
 
 template <typename T, typename TT>
 __global__ __launch_bounds__(256) void rotary_kernel(const RotaryParams p) {

@@ -238,6 +238,57 @@ class RotaryArgs(C.Structure):
             self.struct_bytes = C.sizeof(RotaryArgs)
 
 
+QK_NORM_WEIGHT_F32 = 2            # RFA_QK_NORM_WEIGHT_F32: fp32 norm weights (otherwise the io dtype's code)
+
+_QK_NORM_HEAD = [
+    ("struct_bytes", C.c_uint32), ("reserved", C.c_uint32),
+    ("ntensors", C.c_int32),
+    ("B", C.c_int32), ("S", C.c_int32), ("D", C.c_int32),
+    ("dtype", C.c_int32),
+    ("R", C.c_int32), ("rot_offset", C.c_int32),
+    ("interleaved", C.c_int32),
+    ("table_dtype", C.c_int32), ("weight_dtype", C.c_int32),
+    ("eps", C.c_float), ("weight_offset", C.c_float),
+    ("t", RotaryTensor * 2),
+    ("weight", C.c_void_p * 2),
+    ("cos", C.c_void_p), ("sin", C.c_void_p),
+    ("P", C.c_int64),
+    ("positions", C.c_void_p), ("pos_batch", C.c_int64),
+    ("pos_offset", C.c_int64),
+    ("pos_stride", C.c_int32), ("pos_split", C.c_int32),
+    ("pos_offset2", C.c_int64),
+]
+
+
+class QkNormRotaryArgs(C.Structure):
+    """rfa_qk_norm_rotary_args: per-head RMSNorm + rotary of up to two tensors, forward; struct_bytes is filled in here"""
+    _fields_ = list(_QK_NORM_HEAD)
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if not self.struct_bytes:
+            self.struct_bytes = C.sizeof(QkNormRotaryArgs)
+
+
+class QkNormGrad(C.Structure):
+    """rfa_qk_norm_grad: the incoming gradient of one tensor and its element strides"""
+    _fields_ = [("dout", C.c_void_p), ("dout_batch", C.c_int64), ("dout_row", C.c_int64), ("dout_head", C.c_int64)]
+
+
+class QkNormRotaryBwdArgs(C.Structure):
+    """rfa_qk_norm_rotary_bwd_args: the forward's fields, then the gradients, dweight and the workspace"""
+    _fields_ = list(_QK_NORM_HEAD) + [
+        ("g", QkNormGrad * 2),
+        ("dweight", C.c_void_p * 2),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if not self.struct_bytes:
+            self.struct_bytes = C.sizeof(QkNormRotaryBwdArgs)
+
+
 class MaxLogitArgs(C.Structure):
     """rfa_max_logit_args: the per-head max attention logit of one block call; struct_bytes is filled in here"""
     _fields_ = [
@@ -392,6 +443,9 @@ SYMBOLS = {
     "rfa_sink_grad_workspace_bytes": (C.c_int64, [C.POINTER(SinkGradArgs)]),
     "rfa_seq_head_copy": (C.c_int, [C.POINTER(SeqHeadArgs), C.c_void_p]),
     "rfa_rotary": (C.c_int, [C.POINTER(RotaryArgs), C.c_void_p]),
+    "rfa_qk_norm_rotary_fwd": (C.c_int, [C.POINTER(QkNormRotaryArgs), C.c_void_p]),
+    "rfa_qk_norm_rotary_bwd": (C.c_int, [C.POINTER(QkNormRotaryBwdArgs), C.c_void_p]),
+    "rfa_qk_norm_rotary_bwd_workspace_bytes": (C.c_int64, [C.POINTER(QkNormRotaryBwdArgs)]),
     "rfa_max_logit": (C.c_int, [C.POINTER(MaxLogitArgs), C.c_void_p]),
     "rfa_max_logit_workspace_bytes": (C.c_int64, [C.POINTER(MaxLogitArgs)]),
     "rfa_bwd_preprocess_lse": (C.c_int, [C.POINTER(BwdPreLseArgs), C.c_void_p]),

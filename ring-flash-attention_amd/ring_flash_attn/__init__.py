@@ -83,3 +83,6 @@ from .ulysses import make_usp_groups, with_ulysses
 # rotates this rank's shards in one streaming kernel; local_positions(func, n_local, group=group) is the global position of
 # every local row for the sharding `func` expects (dense and packed families)
 from .rotary import apply_rotary, local_positions
+# per-head QK RMSNorm (Qwen3, Gemma-3, OLMo) fused with that rotation: apply_qk_norm_rotary(q, k, w_q, w_k, cos, sin,
+# layout=func, group=group) is one launch per direction, one rounding, and a reproducible weight gradient
+from .qk_norm import apply_qk_norm_rotary

@@ -99,6 +99,7 @@ class HipBackend:
     serves_row_ranges = True         # fwd / bwd take `row_ranges=(start, end, k_pos0)` (include/rfa.h: rfa_fwd_rr, rfa_bwd_rr): ring_flash_attn.with_row_ranges
     serves_block_mask = True         # fwd / bwd take `block_mask=(mask_view, k_blk0)` (include/rfa.h: rfa_fwd_bm, rfa_bwd_bm): ring_flash_attn.with_block_mask
     serves_rotary = True             # rotary (include/rfa.h: rfa_rotary): ring_flash_attn.apply_rotary
+    serves_qk_norm = True            # qk_norm_rotary_fwd / _bwd (include/rfa.h: rfa_qk_norm_rotary_fwd / _bwd): ring_flash_attn.apply_qk_norm_rotary
     serves_dropout_positions = True  # `dropout=` takes the position maps (q_map, k_map): what dropout over a dense ring, zigzag or stripe schedule needs
 
     def __init__(self):
@@ -731,6 +732,87 @@ class HipBackend:
         else:
             a.pos_stride, a.pos_split, a.pos_offset2 = int(stride), int(split), int(off2)
         _C.check(self.lib.rfa_rotary(C.byref(a), _stream(t0)), "rfa_rotary")
+
+    # ------------------------------------------------------------------ QK RMSNorm + rotary (apply_qk_norm_rotary)
+    def _qk_norm_args(self, a, xs, outs, weights, cos, sin, positions, pos_map, interleaved, rot_offset, eps, weight_offset):
+        """the fields rfa_qk_norm_rotary_args and rfa_qk_norm_rotary_bwd_args share"""
+        self._check_dev(cos, sin, positions, *xs, *outs, *weights)
+        t0 = xs[0]
+        packed = t0.dim() == 3
+        a.ntensors = len(xs)
+        a.B, a.S = (1, t0.shape[0]) if packed else (t0.shape[0], t0.shape[1])
+        a.D, a.dtype = t0.shape[-1], self._dtype(t0)
+        a.rot_offset, a.interleaved = int(rot_offset), int(bool(interleaved))
+        a.eps, a.weight_offset = float(eps), float(weight_offset)
+        if (cos is None) != (sin is None):
+            raise ValueError("qk_norm_rotary: cos and sin come together (both None: the norm alone)")
+        if cos is not None:
+            if not cos.is_contiguous() or not sin.is_contiguous() or cos.shape != sin.shape or cos.dtype != sin.dtype:
+                raise ValueError("qk_norm_rotary: cos and sin are contiguous (P, R/2) tensors of one shape and dtype")
+            a.R, a.P = 2 * cos.shape[1], cos.shape[0]
+            a.cos, a.sin = cos.data_ptr(), sin.data_ptr()
+            a.table_dtype = _C.ROTARY_TABLE_F32 if cos.dtype == torch.float32 else self._dtype(cos)
+        else:
+            a.table_dtype = a.dtype
+        w0 = weights[0]
+        a.weight_dtype = _C.QK_NORM_WEIGHT_F32 if w0.dtype == torch.float32 else self._dtype(w0)
+        for k, (d, s, o, w) in enumerate(zip(a.t, xs, outs, weights)):
+            if s.dtype != t0.dtype or o.dtype != t0.dtype or s.shape != o.shape or s.stride(-1) != 1 or o.stride(-1) != 1:
+                raise ValueError("qk_norm_rotary: inputs and outputs share one dtype and shape; last (head_dim) stride must be 1")
+            if w.dtype != w0.dtype or tuple(w.shape) != (a.D,) or not w.is_contiguous():
+                raise ValueError("qk_norm_rotary: the weights are contiguous (D,) tensors of one dtype")
+            d.src, d.dst, d.H = s.data_ptr(), o.data_ptr(), s.shape[-2]
+            a.weight[k] = w.data_ptr()
+            ss, os_ = ([st if n > 1 else 0 for n, st in zip(t.shape, t.stride())] for t in (s, o))
+            d.src_batch, d.src_row, d.src_head = (0 if packed else ss[0]), ss[-3], ss[-2]
+            d.dst_batch, d.dst_row, d.dst_head = (0 if packed else os_[0]), os_[-3], os_[-2]
+        off, (stride, split, off2) = pos_map if pos_map is not None else (0, (1, 0, 0))
+        a.pos_offset = int(off)
+        if positions is not None:
+            if positions.dtype != torch.int32 or (positions.stride(-1) != 1 and positions.shape[-1] != 1):
+                raise ValueError("qk_norm_rotary: positions are int32 with row stride 1")
+            a.positions = positions.data_ptr()
+            a.pos_batch = positions.stride(0) if positions.dim() == 2 and positions.shape[0] > 1 else 0
+        else:
+            a.pos_stride, a.pos_split, a.pos_offset2 = int(stride), int(split), int(off2)
+        return packed
+
+    def qk_norm_rotary_fwd(self, xs, outs, weights, cos, sin, *, positions=None, pos_map=None, interleaved=False, rot_offset=0,
+                           eps=1e-6, weight_offset=0.0):
+        """one launch of the per-head RMSNorm + rotary (include/rfa.h: rfa_qk_norm_rotary_fwd) for one or two tensors that share
+        rows and positions: outs[k] = rope((xs[k] rstd) (weight_offset + weights[k])).  xs / outs as in `rotary` (out of place);
+        weights: (D,) contiguous, fp32 or the io dtype; cos = sin = None: the norm alone."""
+        a = _C.QkNormRotaryArgs()
+        self._qk_norm_args(a, xs, outs, weights, cos, sin, positions, pos_map, interleaved, rot_offset, eps, weight_offset)
+        _C.check(self.lib.rfa_qk_norm_rotary_fwd(C.byref(a), _stream(xs[0])), "rfa_qk_norm_rotary_fwd")
+
+    def qk_norm_rotary_bwd(self, xs, douts, dxs, weights, dweights, cos, sin, *, positions=None, pos_map=None, interleaved=False,
+                           rot_offset=0, eps=1e-6, weight_offset=0.0):
+        """the backward (include/rfa.h: rfa_qk_norm_rotary_bwd): dxs[k] from xs[k] and douts[k] in one launch; dweights[k] an
+        fp32 (D,) tensor that is overwritten with this call's weight gradient, or None.  The workspace is allocated here."""
+        a = _C.QkNormRotaryBwdArgs()
+        packed = self._qk_norm_args(a, xs, dxs, weights, cos, sin, positions, pos_map, interleaved, rot_offset, eps, weight_offset)
+        self._check_dev(*douts, *[d for d in dweights if d is not None])
+        for k, (g, x, dw) in enumerate(zip(douts, xs, dweights)):
+            if g.dtype != x.dtype or g.shape != x.shape or g.stride(-1) != 1:
+                raise ValueError("qk_norm_rotary: a gradient has its tensor's dtype and shape; last (head_dim) stride must be 1")
+            gs = [st if n > 1 else 0 for n, st in zip(g.shape, g.stride())]
+            a.g[k].dout = g.data_ptr()
+            a.g[k].dout_batch, a.g[k].dout_row, a.g[k].dout_head = (0 if packed else gs[0]), gs[-3], gs[-2]
+            if dw is not None:
+                if dw.dtype != torch.float32 or tuple(dw.shape) != (a.D,) or not dw.is_contiguous():
+                    raise ValueError("qk_norm_rotary: dweight is a contiguous fp32 (D,) tensor")
+                a.dweight[k] = dw.data_ptr()
+        ws = None
+        if any(d is not None for d in dweights):
+            need = int(self.lib.rfa_qk_norm_rotary_bwd_workspace_bytes(C.byref(a)))
+            ws = torch.empty(max(need, 16), dtype=torch.uint8, device=xs[0].device)
+            a.workspace, a.workspace_bytes = ws.data_ptr(), need
+        _C.check(self.lib.rfa_qk_norm_rotary_bwd(C.byref(a), _stream(xs[0])), "rfa_qk_norm_rotary_bwd")
+        if a.B == 0 or a.S == 0:                                   # (nothing was launched: an empty sum)
+            for dw in dweights:
+                if dw is not None:
+                    dw.zero_()
 
     def sum_slots(self, src: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
         """dst[...] = sum over dim 0 of src (io dtype, summed in fp32).  src: (W, B, S, H, D) or (W, T, H, D), each slot

@@ -150,6 +150,66 @@ def _conforms(t):
     return t.stride(-1) == 1 and t.data_ptr() % 16 == 0 and all(st % 8 == 0 for n, st in zip(t.shape[:-1], t.stride()[:-1]) if n > 1)
 
 
+def _check_qk(who, q, k):
+    """the shape / dtype checks of q and k that apply_rotary and apply_qk_norm_rotary share; returns (packed, D)"""
+    if q.dim() not in (3, 4):
+        raise ValueError(f"{who}: q must be (B, S, H, D) or packed (T, H, D), got {tuple(q.shape)}")
+    if q.dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError(f"{who}: bf16 / fp16 only, got {q.dtype}")
+    D = q.shape[-1]
+    if D % 8 or not 8 <= D <= 256:
+        raise ValueError(f"{who}: head dim {D} is not a multiple of 8 in 8 .. 256")
+    if k is not None and (k.dim() != q.dim() or k.shape[:-2] != q.shape[:-2] or k.shape[-1] != D or k.dtype != q.dtype or
+                          k.device != q.device):
+        raise ValueError(f"{who}: k must share q's batch, rows, head dim, dtype and device: {tuple(q.shape)} vs {tuple(k.shape)}")
+    return q.dim() == 3, D
+
+
+def _check_tables_positions(who, q, packed, D, cos, sin, layout, group, positions, offset, interleaved, rot_offset):
+    """the checks of the tables, the rotated columns and the positions that apply_rotary and apply_qk_norm_rotary share, in
+    apply_rotary's order; cos = sin = None (apply_qk_norm_rotary's norm alone) is R = 0: no table, no bound on the positions.
+    Returns (positions, pos_map, interleaved, rot_offset) as the backend takes them."""
+    P = R = 0
+    interleaved = bool(interleaved)
+    if cos is not None:
+        if cos.dim() != 2 or cos.shape != sin.shape or cos.dtype != sin.dtype or not cos.is_contiguous() or not sin.is_contiguous():
+            raise ValueError(f"{who}: cos and sin must be contiguous (P, R/2) tensors of one shape and dtype")
+        if cos.dtype not in (torch.float32, q.dtype) or cos.device != q.device or sin.device != q.device:
+            raise ValueError(f"{who}: cos / sin must be fp32 or {q.dtype} on q's device")
+        P, R = cos.shape[0], 2 * cos.shape[1]
+        if P < 1 or R < 1 or R % (8 if interleaved else 16):
+            raise ValueError(f"{who}: the rotary width R = {R} must be a positive multiple of {8 if interleaved else 16} "
+                             f"({'interleaved' if interleaved else 'halves'}), with at least one table row")
+    rot_offset, offset = int(rot_offset), int(offset)
+    if rot_offset < 0 or rot_offset % 8 or rot_offset + R > D:
+        raise ValueError(f"{who}: rot_offset {rot_offset} must be a multiple of 8 with rot_offset + R = {rot_offset + R} <= D = {D}")
+    if layout is not None and positions is not None:
+        raise ValueError(f"{who}: at most one of `layout` and `positions`")
+    S = q.shape[0] if packed else q.shape[1]
+    if positions is not None:
+        want = ((S,),) if packed else ((S,), (q.shape[0], S))
+        if not isinstance(positions, torch.Tensor) or positions.dtype != torch.int32 or tuple(positions.shape) not in want or \
+                positions.device != q.device:
+            raise ValueError(f"{who}: positions must be an int32 tensor of shape {' or '.join(map(str, want))} on q's device")
+        return positions.contiguous(), pos_map(offset), interleaved, rot_offset
+    if layout is not None:
+        family = _family(layout, who.rsplit(".", 1)[-1])
+        if family not in _DENSE:
+            raise TypeError(f"{who}: `layout` serves the nine dense functions; for {family} pass "
+                            "positions=local_positions(func, T, cu_seqlens=...)")
+        if packed:
+            raise ValueError(f"{who}: `layout` needs (B, S, H, D) input")
+        off, rest = _dense_map(family, S, *_rank_world(group, None, None))
+        pm = (off + offset, (rest[0], rest[1], rest[2] + offset if rest[1] else 0))
+    else:
+        pm = pos_map(offset)
+    if S and cos is not None:
+        lo, hi = _map_bounds(pm, S)
+        if lo < 0 or hi > P - 1:
+            raise ValueError(f"{who}: the rows sit at positions {lo} .. {hi}, the tables have {P} rows")
+    return None, pm, interleaved, rot_offset
+
+
 class _Rotary(torch.autograd.Function):
     """the rotation of one or two tensors in one launch; backward: the same kernel with the conjugate flag on the incoming
     gradients.  Saved: cos, sin, the positions (or the map's numbers) and the flags — neither inputs nor outputs."""
@@ -233,56 +293,10 @@ def apply_rotary(q, k=None, cos=None, sin=None, *, layout=None, group=None, posi
     if not isinstance(cos, torch.Tensor) or not isinstance(sin, torch.Tensor):
         raise ValueError(f"{who}: cos and sin must be tensors of shape (P, R/2)")
     tensors = [q] if k is None else [q, k]
-    if q.dim() not in (3, 4):
-        raise ValueError(f"{who}: q must be (B, S, H, D) or packed (T, H, D), got {tuple(q.shape)}")
-    if q.dtype not in (torch.bfloat16, torch.float16):
-        raise ValueError(f"{who}: bf16 / fp16 only, got {q.dtype}")
-    packed = q.dim() == 3
-    D = q.shape[-1]
-    if D % 8 or not 8 <= D <= 256:
-        raise ValueError(f"{who}: head dim {D} is not a multiple of 8 in 8 .. 256")
-    if k is not None and (k.dim() != q.dim() or k.shape[:-2] != q.shape[:-2] or k.shape[-1] != D or k.dtype != q.dtype or
-                          k.device != q.device):
-        raise ValueError(f"{who}: k must share q's batch, rows, head dim, dtype and device: {tuple(q.shape)} vs {tuple(k.shape)}")
-    if cos.dim() != 2 or cos.shape != sin.shape or cos.dtype != sin.dtype or not cos.is_contiguous() or not sin.is_contiguous():
-        raise ValueError(f"{who}: cos and sin must be contiguous (P, R/2) tensors of one shape and dtype")
-    if cos.dtype not in (torch.float32, q.dtype) or cos.device != q.device or sin.device != q.device:
-        raise ValueError(f"{who}: cos / sin must be fp32 or {q.dtype} on q's device")
-    P, R = cos.shape[0], 2 * cos.shape[1]
-    interleaved, inplace = bool(interleaved), bool(inplace)
-    if P < 1 or R < 1 or R % (8 if interleaved else 16):
-        raise ValueError(f"{who}: the rotary width R = {R} must be a positive multiple of {8 if interleaved else 16} "
-                         f"({'interleaved' if interleaved else 'halves'}), with at least one table row")
-    rot_offset, offset = int(rot_offset), int(offset)
-    if rot_offset < 0 or rot_offset % 8 or rot_offset + R > D:
-        raise ValueError(f"{who}: rot_offset {rot_offset} must be a multiple of 8 with rot_offset + R = {rot_offset + R} <= D = {D}")
-    if layout is not None and positions is not None:
-        raise ValueError(f"{who}: at most one of `layout` and `positions`")
-    S = q.shape[0] if packed else q.shape[1]
-    pm = None
-    if positions is not None:
-        want = ((S,),) if packed else ((S,), (q.shape[0], S))
-        if not isinstance(positions, torch.Tensor) or positions.dtype != torch.int32 or tuple(positions.shape) not in want or \
-                positions.device != q.device:
-            raise ValueError(f"{who}: positions must be an int32 tensor of shape {' or '.join(map(str, want))} on q's device")
-        positions = positions.contiguous()
-        pm = pos_map(offset)
-    else:
-        if layout is not None:
-            family = _family(layout, "apply_rotary")
-            if family not in _DENSE:
-                raise TypeError(f"{who}: `layout` serves the nine dense functions; for {family} pass "
-                                "positions=local_positions(func, T, cu_seqlens=...)")
-            if packed:
-                raise ValueError(f"{who}: `layout` needs (B, S, H, D) input")
-            off, rest = _dense_map(family, S, *_rank_world(group, None, None))
-            pm = (off + offset, (rest[0], rest[1], rest[2] + offset if rest[1] else 0))
-        else:
-            pm = pos_map(offset)
-        if S:
-            lo, hi = _map_bounds(pm, S)
-            if lo < 0 or hi > P - 1:
-                raise ValueError(f"{who}: the rows sit at positions {lo} .. {hi}, the tables have {P} rows")
+    packed, D = _check_qk(who, q, k)
+    positions, pm, interleaved, rot_offset = _check_tables_positions(who, q, packed, D, cos, sin, layout, group, positions, offset,
+                                                                      interleaved, rot_offset)
+    inplace = bool(inplace)
     if inplace and not all(_conforms(t) for t in tensors):
         raise ValueError(f"{who}: inplace=True needs last stride 1, a 16-byte aligned start and strides that are multiples of 8")
     meta = (pm, interleaved, rot_offset, inplace)
