@@ -12,11 +12,29 @@ stripe schedules (the reference declares dropout over a ring unsupported, README
 still raise here); window_size works with every schedule; the two together raise;
 return_attn_probs=True -> (out, softmax_lse, None); `group=None` is the default process group;
 inputs are the caller's LOCAL shard.
+
+The layer is four things, each written once:
+    ScheduleSpec    what a schedule family serves and how its public functions are shaped; built once per family and handed to
+                    the node factory (make_autograd_function) and to the API factory (make_api) alike.
+    the node body   _node_forward / _node_backward: the plain, kv-packed and qkv-packed autograd Functions are adapters that
+                    select views and say where the gradients land.  call_preamble is the per-call list of refusals, in ONE
+                    order, for these nodes and for the two llama3 families.
+    the binders     with_softcap, with_sinks, with_max_logit, with_lse_grad, with_row_ranges, with_block_mask (and
+                    ulysses.with_ulysses) are _admit + _bind: `_RULES` is the one table that says which functions a binder
+                    serves, which other binders' results it takes and what it answers otherwise; _bind makes the callable.
+    _refuse         the clauses every call-level feature repeats (dropout, alibi_slopes, head dims above 128, a value head dim
+                    of its own, a backend that does not serve it), parameterised by the feature's name.
+A new call-level feature is a row of `_RULES`, a `checked_*` in call_preamble and its keyword to the schedules.
 """
+import contextvars
+import functools
+import inspect
+from typing import NamedTuple, Optional
+
 import torch
 
 from ._common import _prep_qkv, _as_cu, check_alibi_slopes, draw_dropout_seed, require_alibi
-from .backend import softcap_scope
+from .backend import get_backend, softcap_scope
 from .utils import audit_verify
 
 
@@ -25,8 +43,6 @@ def _opaque(fn):
     cannot trace: behind `torch.compiler.disable` a compiled caller graph-breaks around them and runs them
     eagerly, with identical results (multi-rank groups; llama3)."""
     try:
-        import functools
-
         wrapped = torch.compiler.disable(fn)
         functools.update_wrapper(wrapped, fn)
         return wrapped
@@ -40,19 +56,15 @@ def _single_rank(group) -> bool:
     return dist.get_world_size(group) == 1
 
 
-def _compilable(fn, lower, multi=None):
-    """Public callable = `fn` (eager: the autograd Functions above, opaque to dynamo) except while dynamo is
-    TRACING it on a single-rank group: then `lower(...)` expresses the call with the registered custom
+def _compilable(fn, lower, multi):
+    """Public callable = `fn` (eager: the autograd Functions below, opaque to dynamo) except while dynamo is
+    TRACING it on a single-rank group: then `lower(bound)` — bound: the call's arguments by name — expresses the call
+    with the registered custom
     operators (_ops.py: rfa::attn_fwd / rfa::attn_bwd, fake kernels + autograd formula), so `torch.compile`
     captures the operator in its graph instead of breaking it (the reference runs its tests a second time under
-    torch.compile: test/test.sh:23-25).  `multi(...)`, where the schedule has one: the same for a multi-rank group —
+    torch.compile: test/test.sh:23-25).  `multi(bound)`: the same for a multi-rank group —
     the whole schedule as one operator per direction (_ops.py: rfa::sched_fwd / rfa::sched_bwd)."""
-    import functools
-
     eager = _opaque(fn)
-
-    import inspect
-
     sig = inspect.signature(fn)
 
     @functools.wraps(fn)
@@ -67,14 +79,36 @@ def _compilable(fn, lower, multi=None):
             # (a bias runs the eager autograd path too: the registered operators have no biased form)
             if not bound.get("dropout_p", 0.0) and bound.get("alibi_slopes", None) is None:
                 if _single_rank(bound.get("group", None)):
-                    return lower(*args, **kwargs)
-                # several ranks: the whole schedule as one registered operator (_ops.py: rfa::sched_fwd / sched_bwd),
-                # where the schedule has one — windowed calls and llama3 keep the eager path behind a graph break
-                if multi is not None and not has_window(bound.get("window_size", (-1, -1))):
-                    return multi(*args, **kwargs)
+                    return lower(bound)
+                # several ranks: the whole schedule as one registered operator (_ops.py: rfa::sched_fwd / sched_bwd)
+                # — windowed calls keep the eager path behind a graph break
+                if not has_window(bound.get("window_size", (-1, -1))):
+                    return multi(bound)
         return eager(*args, **kwargs)
 
     return public
+
+
+# ---- the refusals every call-level feature shares ---------------------------------------------------------------------------
+def _refuse(what, feature, q=None, v=None, dropout_p=None, alibi_slopes=None, backend=None):
+    """NotImplementedError for `what` (the function the message names) with `feature` ("softcap", "row ranges", "a block
+    mask" ...) in a call it is not served in — the clauses, in their one order, each only for what is handed in: dropout_p > 0,
+    alibi_slopes, q's head dim above 128, v's head dim differing from q's, and `backend` = (serves_* attribute, how the message
+    spells what is missing): a backend without it.  Before anything is exchanged, from numbers every rank has alike."""
+    if dropout_p and dropout_p > 0:
+        raise NotImplementedError(f"ring_flash_attn: {what} with {feature} together with dropout is not supported")
+    if alibi_slopes is not None:
+        raise NotImplementedError(f"ring_flash_attn: {what} with {feature} together with alibi_slopes is not supported")
+    if q is not None and q.shape[-1] > 128:
+        raise NotImplementedError(f"ring_flash_attn: {what} with {feature} serves head dims up to 128, not {q.shape[-1]}")
+    if v is not None and v.shape[-1] != q.shape[-1]:
+        raise NotImplementedError(f"ring_flash_attn: {what} with {feature} does not serve a value head dim ({v.shape[-1]}) "
+                                  f"that differs from q's ({q.shape[-1]})")
+    if backend is not None:
+        be = get_backend()
+        if not getattr(be, backend[0], False):
+            raise NotImplementedError(f"ring_flash_attn: {what} with {feature} needs a backend that serves {backend[1]}; "
+                                      f"{getattr(be, 'name', type(be).__name__)!r} does not")
 
 
 def _check_unsupported(dropout_p, window_size, alibi_slopes, windows_ok=False, dropout_ok=None, alibi_ok=False):
@@ -134,10 +168,7 @@ def checked_alibi(alibi_slopes, q, batch, what):
     if alibi_slopes is None:
         return None
     slopes = check_alibi_slopes(alibi_slopes, q, batch)
-    if q.shape[-1] > 128:
-        raise NotImplementedError(f"ring_flash_attn: {what} with alibi_slopes serves head dims up to 128, not {q.shape[-1]}")
-    from .backend import get_backend
-
+    _refuse(what, "alibi_slopes", q)
     require_alibi(get_backend(), what)
     return slopes
 
@@ -148,17 +179,12 @@ def checked_softcap(dropout_p, alibi_slopes, q, what, window_size=None, causal=F
     window_size (-1, 0) with `causal` bounds nothing), a backend that does not serve a cap: NotImplementedError before anything is
     exchanged, on every rank alike.  Read ONCE, in the autograd Function's forward, and kept on the node: the backward runs
     under `softcap_scope(ctx.softcap)` and reads nothing ambient."""
-    from .backend import get_backend, pending_softcap, softcap_scope
+    from .backend import pending_softcap
 
     cap = pending_softcap()
     if not cap:
         return 0.0
-    if dropout_p and dropout_p > 0:
-        raise NotImplementedError(f"ring_flash_attn: {what} with softcap together with dropout is not supported")
-    if alibi_slopes is not None:
-        raise NotImplementedError(f"ring_flash_attn: {what} with softcap together with alibi_slopes is not supported")
-    if q.shape[-1] > 128:
-        raise NotImplementedError(f"ring_flash_attn: {what} with softcap serves head dims up to 128, not {q.shape[-1]}")
+    _refuse(what, "softcap", q, dropout_p=dropout_p, alibi_slopes=alibi_slopes)
     bounded = has_window(window_size) and (window_size[0] >= 0 or not causal)
     if bounded and 64 < q.shape[-1] < 128:
         raise NotImplementedError(f"ring_flash_attn: {what} with softcap and a sliding window serves head dims up to 64 "
@@ -196,13 +222,130 @@ def checked_vdim(q, k, v, dropout_p, alibi_slopes, what, served=True):
         raise NotImplementedError(f"ring_flash_attn: {what} with dropout and a value head dim that differs from q's is not supported")
     if alibi_slopes is not None:
         raise NotImplementedError(f"ring_flash_attn: {what} with alibi_slopes and a value head dim that differs from q's is not supported")
-    from .backend import get_backend
-
-    be = get_backend()
-    if not getattr(be, "serves_vdim", False):
-        raise NotImplementedError(f"ring_flash_attn: {what} with a value head dim that differs from q's needs a backend that "
-                                  f"serves it (serves_vdim); {getattr(be, 'name', type(be).__name__)!r} does not")
+    _refuse(what, "a value head dim that differs from q's", backend=("serves_vdim", "it (serves_vdim)"))
     return True
+
+
+# ---- the binders: one table, one resolver, one wrapper ---------------------------------------------------------------------
+# A binder (with_softcap, with_sinks ...) takes one of the package's public attention functions — or another binder's result,
+# where the table says so — and returns a callable with the same signature that runs it with a value bound to the call.  Which
+# binder takes what is a rule of the package, and `_RULES` is the one place it is written down: a row names the attribute the
+# binder's results carry, the public functions it serves, the binders whose results (of a served function) it takes as well,
+# what it answers to everything else, and the answers of its own to particular binders' results.
+ROW_RANGE_FUNCS = tuple(f"{p}_{s}" for p in ("ring_flash_attn", "zigzag_ring_flash_attn") for s in ("func", "kvpacked_func", "qkvpacked_func"))
+DENSE_FUNCS = ROW_RANGE_FUNCS + tuple(f"stripe_flash_attn_{s}" for s in ("func", "kvpacked_func", "qkvpacked_func"))
+
+
+class _Rule(NamedTuple):
+    marker: str                       # the attribute its results carry
+    serves: Optional[tuple]           # the public functions it binds (None: all 21)
+    over: tuple                       # the binders whose results, of a served function, it binds as well
+    expects: str                      # TypeError for anything else, up to the repr of `func`
+    refuses: dict                     # binder -> TypeError of its own for that binder's results
+
+
+def _not_served(*binders):
+    return {b: f"`func` is a {b} result; not served" for b in binders}
+
+
+_ANY_FUNC = "`func` must be one of the package's public attention functions (ring_flash_attn.*_func)"
+_RANGED_FUNC = ("`func` must be one of ring_flash_attn_{,kvpacked_,qkvpacked_}func and zigzag_ring_flash_attn_{,kvpacked_,qkvpacked_}func "
+                "or a with_lse_grad result of one, got ")
+_RULES = {
+    "with_softcap": _Rule("_rfa_softcap", None, (), _ANY_FUNC + ", got ", {}),
+    "with_sinks": _Rule("_rfa_sinks", None, (), _ANY_FUNC + ", got ", {
+        "with_softcap": "`func` is a with_softcap result; soft-capping together with sinks is not served yet (the cap and the "
+                        "sinks would have to be bound to one call)"}),
+    "with_max_logit": _Rule("_rfa_max_logit", None, ("with_softcap", "with_sinks"),
+                            _ANY_FUNC + " or a with_softcap / with_sinks result of one, got ", {
+        "with_ulysses": "`func` is a with_ulysses result; the exchange renumbers the heads a rank computes — not served yet "
+                        "(bind with_max_logit to the function and read the head slices)",
+        "with_max_logit": "`func` is a with_max_logit result already"}),
+    "with_lse_grad": _Rule("_rfa_lse_grad", None, ("with_softcap",), _ANY_FUNC + " or a with_softcap result of one, got ",
+                           _not_served("with_lse_grad", "with_sinks", "with_max_logit", "with_ulysses")),
+    "with_row_ranges": _Rule("_rfa_row_ranges", ROW_RANGE_FUNCS, ("with_lse_grad",), _RANGED_FUNC,
+                             _not_served("with_row_ranges", "with_softcap", "with_sinks", "with_max_logit", "with_ulysses")),
+    "with_block_mask": _Rule("_rfa_block_mask", ROW_RANGE_FUNCS, ("with_lse_grad",), _RANGED_FUNC,
+                             _not_served("with_block_mask", "with_row_ranges", "with_softcap", "with_sinks", "with_max_logit",
+                                         "with_ulysses")),
+    "with_ulysses": _Rule("_rfa_ulysses", DENSE_FUNCS, ("with_softcap",),
+                          "`func` must be one of the nine dense functions (ring_, zigzag_ring_ and "
+                          "stripe_flash_attn_{,kvpacked_,qkvpacked_}func) or a with_softcap result of one; the *_varlen families, "
+                          "llama3_* and zigzag_llama3_* are a follow-up; got ", {
+        "with_sinks": "`func` is a with_sinks result; sinks are per head and would need slicing and a scattered gradient under "
+                      "the head exchange: follow-up",
+        "with_ulysses": "`func` is already a with_ulysses result"}),
+}
+_public = {}                          # id -> name of the package's 21 public attention functions (made at the first bind)
+
+
+def _resolve(func):
+    """(the public name `func` leads to or None, the binders passed on the way — outermost first).  A binder's result
+    carries its marker on both of its layers (the callable and its dynamo-opaque wrapper) and leads, by `__wrapped__`, to what
+    it wraps."""
+    if not _public:
+        import ring_flash_attn as pkg
+
+        _public.update((id(getattr(pkg, n)), n) for n in dir(pkg) if n.endswith("_func"))
+    passed, f = [], func
+    while id(f) not in _public:
+        binder = next((b for b, rule in _RULES.items() if getattr(f, rule.marker, False)), None)
+        if binder is None:
+            return None, tuple(passed)
+        if not passed or passed[-1] != binder:
+            passed.append(binder)
+        if not hasattr(f, "__wrapped__"):
+            return None, tuple(passed)
+        f = f.__wrapped__
+    return _public[id(f)], tuple(passed)
+
+
+def _admit(binder, func, who=None):
+    """the public name behind `func` if the table lets `binder` bind it; TypeError — in the name of `who`, the binder itself
+    by default — otherwise"""
+    rule = _RULES[binder]
+    name, passed = _resolve(func)
+    if passed and passed[0] in rule.refuses:
+        raise TypeError(f"ring_flash_attn.{who or binder}: {rule.refuses[passed[0]]}")
+    if (name is None or (rule.serves is not None and name not in rule.serves)
+            or not (passed == () or (len(passed) == 1 and passed[0] in rule.over))):
+        raise TypeError(f"ring_flash_attn.{who or binder}: {rule.expects}{func!r}")
+    return name
+
+
+class _binding:
+    """`with _binding(var, value):` — the context variable holds `value` inside"""
+    __slots__ = ("var", "value", "token")
+
+    def __init__(self, var, value):
+        self.var, self.value = var, value
+
+    def __enter__(self):
+        self.token = self.var.set(self.value)
+
+    def __exit__(self, *exc):
+        self.var.reset(self.token)
+        return False
+
+
+def _bind(binder, func, scope=None, before=None, body=None):
+    """`binder`'s result for `func`: a callable with func's signature and name that runs every call inside a fresh `scope()`
+    (a context manager: the value is bound for the duration of the call and nothing stays behind it, raised or returned),
+    after `before(args, kwargs)` where the binder checks something per call — or runs `body(*args, **kwargs)`, for a binder
+    that does more around `func` than bind a value; marked as the table says; opaque to dynamo."""
+    if body is None:
+        def body(*args, **kwargs):
+            if before is not None:
+                before(args, kwargs)
+            with scope():
+                return func(*args, **kwargs)
+
+    # (updated=(): `func`'s own attributes are not copied — a function that is already opaque to dynamo carries the marker
+    #  that makes torch.compiler.disable unwrap to ITS original, which would drop this wrapper; another binder's marker is
+    #  not carried over either)
+    bound = functools.wraps(func, updated=())(body)
+    setattr(bound, _RULES[binder].marker, True)
+    return _opaque(bound)
 
 
 def with_softcap(func, softcap):
@@ -219,28 +362,13 @@ def with_softcap(func, softcap):
     The value is bound to the call and kept on the autograd node — activation checkpointing re-runs the wrapped call and
     gets the same cap; there is no user-managed context.  Under torch.compile the capped call runs eagerly behind a graph
     break (the registered operators have no capped form)."""
-    import functools
+    from .backend import check_softcap
 
-    import ring_flash_attn as pkg
-    from .backend import check_softcap, softcap_scope
-
-    public = {id(getattr(pkg, n)): n for n in dir(pkg) if n.endswith("_func")}
-    if id(func) not in public:
-        raise TypeError("ring_flash_attn.with_softcap: `func` must be one of the package's public attention functions "
-                        f"(ring_flash_attn.*_func), got {func!r}")
+    _admit("with_softcap", func)
     cap = check_softcap(softcap)
     if not cap:
         return func
-
-    # (updated=(): `func`'s own attributes are not copied — a function that is already opaque to dynamo carries the marker
-    #  that makes torch.compiler.disable unwrap to ITS original, which would drop this wrapper)
-    @functools.wraps(func, updated=())
-    def capped(*args, **kwargs):
-        with softcap_scope(cap):
-            return func(*args, **kwargs)
-
-    capped._rfa_softcap = cap                        # (with_sinks refuses to wrap a capped function)
-    return _opaque(capped)
+    return _bind("with_softcap", func, lambda: softcap_scope(cap))
 
 
 # ---- a gradient for the returned lse (ring_flash_attn.with_lse_grad) ------------------------------------------------------
@@ -249,8 +377,6 @@ def with_softcap(func, softcap):
 # schedule's backward computes delta takes `dlse=`.  The binding is read once, at the public entry of the forward, and kept on
 # the node (ctx.lse_grad); a backward reads ctx and the gradients autograd hands it, nothing ambient.  An unbound node is the
 # node it always was: it never looks at the gradient of lse.
-import contextvars
-
 _lse_grad = contextvars.ContextVar("ring_flash_attn_lse_grad", default=False)
 
 
@@ -260,12 +386,7 @@ def checked_lse_grad(ctx, what):
     `dlse=` — before anything is exchanged, on every rank alike."""
     if not _lse_grad.get():
         return False
-    from .backend import get_backend
-
-    be = get_backend()
-    if not getattr(be, "serves_lse_grad", False):
-        raise NotImplementedError(f"ring_flash_attn: {what} with a gradient for lse needs a backend that serves `lse_grad` "
-                                  f"(bwd_preprocess(dlse=)); {getattr(be, 'name', type(be).__name__)!r} does not")
+    _refuse(what, "a gradient for lse", backend=("serves_lse_grad", "`lse_grad` (bwd_preprocess(dlse=))"))
     ctx.set_materialize_grads(False)
     return True
 
@@ -306,32 +427,8 @@ def with_lse_grad(func):
     backend that does not serve it.  An lse that the loss does not use costs nothing: the backward is the plain one, bit for
     bit; a loss that uses lse alone is served too.  Double backward is not.  Under torch.compile the call runs eagerly behind a
     graph break."""
-    import functools
-
-    import ring_flash_attn as pkg
-
-    for marker, what in (("_rfa_lse_grad", "with_lse_grad"), ("_rfa_sinks", "with_sinks"), ("_rfa_max_logit", "with_max_logit"),
-                         ("_rfa_ulysses", "with_ulysses")):
-        if getattr(func, marker, False):
-            raise TypeError(f"ring_flash_attn.with_lse_grad: `func` is a {what} result; not served")
-    public = {id(getattr(pkg, n)): n for n in dir(pkg) if n.endswith("_func")}
-    f = func
-    while id(f) not in public and getattr(f, "_rfa_softcap", None) and hasattr(f, "__wrapped__"):
-        f = f.__wrapped__                            # (a with_softcap result leads to the public function it wraps)
-    if id(f) not in public:
-        raise TypeError("ring_flash_attn.with_lse_grad: `func` must be one of the package's public attention functions "
-                        f"(ring_flash_attn.*_func) or a with_softcap result of one, got {func!r}")
-
-    @functools.wraps(func, updated=())              # (updated=(): as in with_softcap; the cap's marker is NOT carried over)
-    def bound(*args, **kwargs):
-        token = _lse_grad.set(True)
-        try:
-            return func(*args, **kwargs)
-        finally:
-            _lse_grad.reset(token)
-
-    bound._rfa_lse_grad = True
-    return _opaque(bound)
+    _admit("with_lse_grad", func)
+    return _bind("with_lse_grad", func, lambda: _binding(_lse_grad, True))
 
 
 # ---- per-row key ranges (ring_flash_attn.with_row_ranges) -----------------------------------------------------------------
@@ -341,8 +438,6 @@ def with_lse_grad(func):
 # handed to the schedule's forward and backward as `row_ranges=` — a backward reads nothing ambient.  The schedules give every
 # block call the slice that belongs to its query rows and the global position of its key row 0 (include/rfa.h: rfa_rowrange_args).
 _row_ranges = contextvars.ContextVar("ring_flash_attn_row_ranges", default=None)
-
-ROW_RANGE_FUNCS = tuple(f"{p}_{s}" for p in ("ring_flash_attn", "zigzag_ring_flash_attn") for s in ("func", "kvpacked_func", "qkvpacked_func"))
 
 
 def _check_row_range_tensors(start, end, q=None):
@@ -368,21 +463,7 @@ def checked_row_ranges(q, k, v, dropout_p, alibi_slopes, what):
     if rr is None:
         return None
     _check_row_range_tensors(rr[0], rr[1], q)
-    if dropout_p and dropout_p > 0:
-        raise NotImplementedError(f"ring_flash_attn: {what} with row ranges together with dropout is not supported")
-    if alibi_slopes is not None:
-        raise NotImplementedError(f"ring_flash_attn: {what} with row ranges together with alibi_slopes is not supported")
-    if q.shape[-1] > 128:
-        raise NotImplementedError(f"ring_flash_attn: {what} with row ranges serves head dims up to 128, not {q.shape[-1]}")
-    if v.shape[-1] != q.shape[-1]:
-        raise NotImplementedError(f"ring_flash_attn: {what} with row ranges does not serve a value head dim ({v.shape[-1]}) "
-                                  f"that differs from q's ({q.shape[-1]})")
-    from .backend import get_backend
-
-    be = get_backend()
-    if not getattr(be, "serves_row_ranges", False):
-        raise NotImplementedError(f"ring_flash_attn: {what} with row ranges needs a backend that serves `row_ranges` "
-                                  f"(serves_row_ranges); {getattr(be, 'name', type(be).__name__)!r} does not")
+    _refuse(what, "row ranges", q, v, dropout_p, alibi_slopes, backend=("serves_row_ranges", "`row_ranges` (serves_row_ranges)"))
     return rr
 
 
@@ -414,38 +495,13 @@ def with_row_ranges(func, start, end):
     the call, before anything is exchanged: dropout_p > 0, alibi_slopes, head dims above 128, a value head dim of its own, a
     backend that does not serve it.  The tensors are bound to the call and kept on the autograd node — activation
     checkpointing re-runs the wrapped call and binds them again.  Under torch.compile the call runs eagerly behind a graph break."""
-    import functools
-
-    import ring_flash_attn as pkg
-
-    for marker, what in (("_rfa_row_ranges", "with_row_ranges"), ("_rfa_softcap", "with_softcap"), ("_rfa_sinks", "with_sinks"),
-                         ("_rfa_max_logit", "with_max_logit"), ("_rfa_ulysses", "with_ulysses")):
-        if getattr(func, marker, False):
-            raise TypeError(f"ring_flash_attn.with_row_ranges: `func` is a {what} result; not served")
-    served = {id(getattr(pkg, n)) for n in ROW_RANGE_FUNCS}
-    f = func
-    # (a with_lse_grad result carries the marker on both of its layers and leads to the public function it wraps)
-    while id(f) not in served and getattr(f, "_rfa_lse_grad", False) and hasattr(f, "__wrapped__"):
-        f = f.__wrapped__
-    if id(f) not in served:
-        raise TypeError("ring_flash_attn.with_row_ranges: `func` must be one of ring_flash_attn_{,kvpacked_,qkvpacked_}func and "
-                        f"zigzag_ring_flash_attn_{{,kvpacked_,qkvpacked_}}func or a with_lse_grad result of one, got {func!r}")
+    _admit("with_row_ranges", func)
     if (start is None) != (end is None):
         raise ValueError("ring_flash_attn.with_row_ranges: start and end come together (both tensors, or both None)")
     if start is None:
         return func
     _check_row_range_tensors(start, end)
-
-    @functools.wraps(func, updated=())              # (updated=(): as in with_softcap)
-    def ranged(*args, **kwargs):
-        token = _row_ranges.set((start, end))
-        try:
-            return func(*args, **kwargs)
-        finally:
-            _row_ranges.reset(token)
-
-    ranged._rfa_row_ranges = True                    # (the other binders refuse a ranged function)
-    return _opaque(ranged)
+    return _bind("with_row_ranges", func, lambda: _binding(_row_ranges, (start, end)))
 
 
 # ---- block-sparse masks (ring_flash_attn.with_block_mask) -----------------------------------------------------------------
@@ -468,11 +524,11 @@ def _check_block_mask_tensor(mask):
         raise ValueError(f"ring_flash_attn.with_block_mask: block_mask must be a contiguous bool tensor of shape (Bm, Hm, NQ, NK); got {got}")
 
 
-def checked_block_mask(q, k, v, dropout_p, alibi_slopes, what, group):
+def checked_block_mask(q, k, v, dropout_p, alibi_slopes, what, group, zigzag=False):
     """the mask bound to this public call by `with_block_mask`, or None.  ValueError: a mask that does not fit the call, local
     lengths that are no multiple of the block on a multi-rank group.  NotImplementedError: dropout, alibi_slopes, head dims
     above 128, more than 64 query heads per K/V head, a value head dim of its own, a backend without `serves_block_mask` — all before anything is exchanged, from
-    numbers every rank has alike."""
+    numbers every rank has alike.  zigzag: the schedule's local rows are two chunks (ScheduleSpec.zigzag)."""
     mask = _block_mask.get()
     if mask is None:
         return None
@@ -483,7 +539,6 @@ def checked_block_mask(q, k, v, dropout_p, alibi_slopes, what, group):
     B, Sq, H = q.shape[0], q.shape[1], q.shape[2]
     Sk = k.shape[1]
     if world > 1:
-        zigzag = what.lower().startswith("zigzag")      # (only the dense ring and zigzag functions bind a mask)
         unit, per = (Sq // 2, "half of the local length") if zigzag else (Sq, "the local length")
         if Sq != Sk or (zigzag and Sq % 2) or unit % BLOCK_MASK_SIZE:
             raise ValueError(f"ring_flash_attn: {what} with a block mask on {world} ranks needs {per} to be a multiple of "
@@ -492,24 +547,11 @@ def checked_block_mask(q, k, v, dropout_p, alibi_slopes, what, group):
     if (mask.shape[0] not in (1, B) or mask.shape[1] not in (1, H) or tuple(mask.shape[2:]) != (nq, nk) or mask.device != q.device):
         raise ValueError(f"ring_flash_attn: {what}: block_mask must be ({{1, {B}}}, {{1, {H}}}, {nq}, {nk}) on {q.device} — this "
                          f"rank's query blocks against the key blocks of the whole sequence; got {tuple(mask.shape)} on {mask.device}")
-    if dropout_p and dropout_p > 0:
-        raise NotImplementedError(f"ring_flash_attn: {what} with a block mask together with dropout is not supported")
-    if alibi_slopes is not None:
-        raise NotImplementedError(f"ring_flash_attn: {what} with a block mask together with alibi_slopes is not supported")
-    if q.shape[-1] > 128:
-        raise NotImplementedError(f"ring_flash_attn: {what} with a block mask serves head dims up to 128, not {q.shape[-1]}")
+    _refuse(what, "a block mask", q, dropout_p=dropout_p, alibi_slopes=alibi_slopes)
     if k.shape[2] > 0 and H // k.shape[2] > BLOCK_MASK_MAX_GROUP:
         raise NotImplementedError(f"ring_flash_attn: {what} with a block mask serves at most {BLOCK_MASK_MAX_GROUP} query heads per "
                                   f"K/V head, not {H} / {k.shape[2]}")
-    if v.shape[-1] != q.shape[-1]:
-        raise NotImplementedError(f"ring_flash_attn: {what} with a block mask does not serve a value head dim ({v.shape[-1]}) "
-                                  f"that differs from q's ({q.shape[-1]})")
-    from .backend import get_backend
-
-    be = get_backend()
-    if not getattr(be, "serves_block_mask", False):
-        raise NotImplementedError(f"ring_flash_attn: {what} with a block mask needs a backend that serves `block_mask` "
-                                  f"(serves_block_mask); {getattr(be, 'name', type(be).__name__)!r} does not")
+    _refuse(what, "a block mask", q, v, backend=("serves_block_mask", "`block_mask` (serves_block_mask)"))
     return mask
 
 
@@ -545,36 +587,11 @@ def with_block_mask(func, block_mask):
     64 query heads per K/V head, a value head dim of its own, a backend that does not serve it.  The mask is bound to the call and kept on the autograd node —
     activation checkpointing re-runs the wrapped call and binds it again.  Under torch.compile the call runs eagerly behind a
     graph break."""
-    import functools
-
-    import ring_flash_attn as pkg
-
-    for marker, what in (("_rfa_block_mask", "with_block_mask"), ("_rfa_row_ranges", "with_row_ranges"), ("_rfa_softcap", "with_softcap"),
-                         ("_rfa_sinks", "with_sinks"), ("_rfa_max_logit", "with_max_logit"), ("_rfa_ulysses", "with_ulysses")):
-        if getattr(func, marker, False):
-            raise TypeError(f"ring_flash_attn.with_block_mask: `func` is a {what} result; not served")
-    served = {id(getattr(pkg, n)) for n in ROW_RANGE_FUNCS}
-    f = func
-    # (a with_lse_grad result carries the marker on both of its layers and leads to the public function it wraps)
-    while id(f) not in served and getattr(f, "_rfa_lse_grad", False) and hasattr(f, "__wrapped__"):
-        f = f.__wrapped__
-    if id(f) not in served:
-        raise TypeError("ring_flash_attn.with_block_mask: `func` must be one of ring_flash_attn_{,kvpacked_,qkvpacked_}func and "
-                        f"zigzag_ring_flash_attn_{{,kvpacked_,qkvpacked_}}func or a with_lse_grad result of one, got {func!r}")
+    _admit("with_block_mask", func)
     if block_mask is None:
         return func
     _check_block_mask_tensor(block_mask)
-
-    @functools.wraps(func, updated=())              # (updated=(): as in with_softcap)
-    def masked(*args, **kwargs):
-        token = _block_mask.set(block_mask)
-        try:
-            return func(*args, **kwargs)
-        finally:
-            _block_mask.reset(token)
-
-    masked._rfa_block_mask = True                    # (the other binders refuse a masked function)
-    return _opaque(masked)
+    return _bind("with_block_mask", func, lambda: _binding(_block_mask, block_mask))
 
 
 # ---- attention over the union of two key sets (ring_flash_attn.merge_attn) ------------------------------------------------
@@ -598,8 +615,6 @@ def _check_merge_args(out_a, lse_a, out_b, lse_b):
 class _MergeAttn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, out_a, lse_a, out_b, lse_b):
-        from .backend import get_backend
-
         out, lse = get_backend().merge_pair(out_a, lse_a, out_b, lse_b)
         ctx.save_for_backward(out_a, lse_a, out_b, lse_b)
         ctx.set_materialize_grads(False)
@@ -608,8 +623,6 @@ class _MergeAttn(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, dout, dlse):
-        from .backend import get_backend
-
         out_a, lse_a, out_b, lse_b = ctx.saved_tensors
         if dout is None:
             dout = torch.zeros_like(out_a)
@@ -638,8 +651,6 @@ def merge_attn(out_a, lse_a, out_b, lse_b):
     ValueError: mismatched shapes or dtypes, an lse that is not float32 in the layout belonging to out, tensors on different
     devices.  NotImplementedError: a backend that does not serve it."""
     _check_merge_args(out_a, lse_a, out_b, lse_b)
-    from .backend import get_backend
-
     be = get_backend()
     if not getattr(be, "serves_merge_pair", False):
         raise NotImplementedError("ring_flash_attn.merge_attn needs a backend that serves `merge_pair` / `merge_pair_bwd`; "
@@ -657,8 +668,6 @@ merge_attn = _opaque(merge_attn)
 # it to its autograd Function as ONE extra trailing argument of `apply` (sink_args: nothing for a call without sinks — such a
 # call builds the node it always built), and the node saves it.  The binding is read there, at the public entry of the
 # forward, and nowhere else: a backward reads its saved tensors only.
-import contextvars
-
 _sinks = contextvars.ContextVar("ring_flash_attn_sinks", default=None)
 
 
@@ -684,12 +693,7 @@ def checked_sinks(sinks, q, what):
         got = f"{tuple(sinks.shape)} {sinks.dtype} on {sinks.device}" if isinstance(sinks, torch.Tensor) else repr(sinks)
         raise ValueError(f"ring_flash_attn: {what} with sinks needs a floating tensor of shape ({H},) on {q.device}, one "
                          f"logit per query head; got {got}")
-    from .backend import get_backend
-
-    be = get_backend()
-    if not getattr(be, "serves_sinks", False):
-        raise NotImplementedError(f"ring_flash_attn: {what} with sinks needs a backend that serves `sink_apply` / `sink_grad`; "
-                                  f"{getattr(be, 'name', type(be).__name__)!r} does not")
+    _refuse(what, "sinks", backend=("serves_sinks", "`sink_apply` / `sink_grad`"))
     return sinks
 
 
@@ -697,8 +701,6 @@ def apply_sinks(sinks, out, lse):
     """(out', lse') of the call with sinks from the schedule's merged (out, lse); the pair itself without sinks"""
     if sinks is None:
         return out, lse
-    from .backend import get_backend
-
     return get_backend().sink_apply(out, lse, sinks, varlen=out.dim() == 3)
 
 
@@ -709,8 +711,6 @@ def sinks_grad(ctx, sinks, dout, out, lse):
         return ()
     if not ctx.needs_input_grad[-1]:
         return (None,)
-    from .backend import get_backend
-
     return (get_backend().sink_grad(dout, out, lse, sinks, varlen=out.dim() == 3).to(sinks.dtype),)
 
 
@@ -735,33 +735,13 @@ def with_sinks(func, sinks):
     together are not served yet.  NotImplementedError at the call: a backend that does not serve sinks.
     The tensor is bound to the call and saved on the autograd node — activation checkpointing re-runs the wrapped call and
     binds it again; the backward reads nothing ambient.  Under torch.compile the call runs eagerly behind a graph break."""
-    import functools
-
-    import ring_flash_attn as pkg
-
-    if getattr(func, "_rfa_softcap", None):
-        raise TypeError("ring_flash_attn.with_sinks: `func` is a with_softcap result; soft-capping together with sinks is not "
-                        "served yet (the cap and the sinks would have to be bound to one call)")
-    public = {id(getattr(pkg, n)): n for n in dir(pkg) if n.endswith("_func")}
-    if id(func) not in public:
-        raise TypeError("ring_flash_attn.with_sinks: `func` must be one of the package's public attention functions "
-                        f"(ring_flash_attn.*_func), got {func!r}")
+    _admit("with_sinks", func)
     if sinks is None:
         return func
     if not isinstance(sinks, torch.Tensor) or not sinks.is_floating_point() or sinks.dim() != 1:
         raise ValueError("ring_flash_attn.with_sinks: sinks must be a floating tensor of shape (H,), one logit per query "
                          f"head; got {tuple(sinks.shape) if isinstance(sinks, torch.Tensor) else sinks!r}")
-
-    @functools.wraps(func, updated=())              # (updated=(): as in with_softcap)
-    def sunk(*args, **kwargs):
-        token = _sinks.set(sinks)
-        try:
-            return func(*args, **kwargs)
-        finally:
-            _sinks.reset(token)
-
-    sunk._rfa_sinks = True                           # (with_ulysses refuses to wrap a function with sinks)
-    return _opaque(sunk)
+    return _bind("with_sinks", func, lambda: _binding(_sinks, sinks))
 
 
 # ---- per-head max attention logit (ring_flash_attn.with_max_logit) ---------------------------------------------------------
@@ -805,39 +785,23 @@ def with_max_logit(func, max_logit):
     device, or that requires grad; at the call: softmax_scale <= 0.  NotImplementedError at the call, before anything is
     exchanged: a backend that does not serve `max_logit`.  Under torch.compile the call runs eagerly behind a graph break.
     The separate pass over q and k costs about a forward's S GEMM (profiles/max_logit.md)."""
-    import functools
-    import inspect
-
-    import ring_flash_attn as pkg
     from .backend import max_logit_scope, require_max_logit
 
-    if getattr(func, "_rfa_ulysses", False):
-        raise TypeError("ring_flash_attn.with_max_logit: `func` is a with_ulysses result; the exchange renumbers the heads a "
-                        "rank computes — not served yet (bind with_max_logit to the function and read the head slices)")
-    if getattr(func, "_rfa_max_logit", False):
-        raise TypeError("ring_flash_attn.with_max_logit: `func` is a with_max_logit result already")
-    public = {id(getattr(pkg, n)): n for n in dir(pkg) if n.endswith("_func")}
-    if id(func) not in public and not getattr(func, "_rfa_softcap", None) and not getattr(func, "_rfa_sinks", False):
-        raise TypeError("ring_flash_attn.with_max_logit: `func` must be one of the package's public attention functions "
-                        f"(ring_flash_attn.*_func) or a with_softcap / with_sinks result of one, got {func!r}")
+    name = _admit("with_max_logit", func)
     if max_logit is None:
         return func
     _check_max_logit_tensor(max_logit)
     sig = inspect.signature(func)
 
-    @functools.wraps(func, updated=())               # (updated=(): as in with_softcap)
-    def measured(*args, **kwargs):
+    def check_call(args, kwargs):
         bound = sig.bind(*args, **kwargs).arguments
         _check_max_logit_tensor(max_logit, next(iter(bound.values())))
         scale = bound.get("softmax_scale", None)
         if scale is not None and not scale > 0:
             raise ValueError(f"ring_flash_attn.with_max_logit: softmax_scale must be positive, got {scale!r}")
-        require_max_logit(public.get(id(func), getattr(func, "__name__", "the call")) + " with max_logit")
-        with max_logit_scope(max_logit):
-            return func(*args, **kwargs)
+        require_max_logit(name + " with max_logit")
 
-    measured._rfa_max_logit = True
-    return _opaque(measured)
+    return _bind("with_max_logit", func, lambda: max_logit_scope(max_logit), before=check_call)
 
 
 def has_window(window_size) -> bool:
@@ -906,192 +870,186 @@ def _split_kept(ctx, more):
     return tensors_lead, ({"kept": tuple(kept)} if kept else {})
 
 
-def make_autograd_function(name, forward_impl, backward_impl, n_lead, window_ring=False, dropout_ring=False,
-                           alibi_ring=False, vdim=False):
-    """n_lead: number of non-tensor positional arguments between (q,k,v) and the common tail
-    (0 for the batch API, 2 = (cu_seqlens, max_seqlen) for varlen).  window_ring: the schedule serves a sliding window
-    on a multi-rank group (every ring family does: dense and varlen ring and zigzag, stripe).  dropout_ring: it serves
-    dropout there (the dense ring, zigzag and stripe schedules: every block call is told the global positions of its
-    rows, _common.dropout_arg).  alibi_ring: it serves alibi_slopes there (the dense ring and zigzag schedules).
-    vdim: it serves a `v` whose head dim differs from q's (the five ring-type families, on any group: checked_vdim)."""
+class ScheduleSpec(NamedTuple):
+    """What one schedule family is, said once (at the end of its module) and read by the node factory and the API factory:
+    name            of its autograd Function, which is what a refusal's message names ("RingFlashAttnFunc")
+    prefix          of its three public functions ("ring_flash_attn" -> ring_flash_attn_{,kvpacked_,qkvpacked_}func)
+    n_lead          non-tensor positional arguments between (q, k, v) and the common tail: 0 for the batch API, 2 =
+                    (cu_seqlens, max_seqlen) for varlen
+    pack_dim        the dimension `kv` / `qkv` stack their tensors on
+    window_ring     it serves a sliding window on a multi-rank group (every ring family does)
+    dropout_ring    it serves dropout there (the dense ring, zigzag and stripe schedules: every block call is told the global
+                    positions of its rows, _common.dropout_arg)
+    alibi_ring      it serves alibi_slopes there (the dense ring and zigzag schedules)
+    vdim            it serves a `v` whose head dim differs from q's (the five ring-type families, on any group: checked_vdim)
+    zigzag          a rank's rows are two chunks of the sequence
+    must_be_causal  the layout only means something for causal attention
+    packed_travel   the schedule exchanges a packed `kv` as one buffer and writes dK/dV straight into the packed gradient
+                    (`out_grads`) at any world size"""
+    name: str
+    prefix: Optional[str] = None
+    n_lead: int = 0
+    pack_dim: int = 2
+    window_ring: bool = False
+    dropout_ring: bool = False
+    alibi_ring: bool = False
+    vdim: bool = False
+    zigzag: bool = False
+    must_be_causal: bool = False
+    packed_travel: bool = False
+
+
+def call_preamble(ctx, what, q, k, v, sinks, dropout_p, window_size, alibi_slopes, causal, group, batch, *, vdim,
+                  window_ring, dropout_ring, alibi_ring, alibi_single=True, masks=None, before_alibi=None):
+    """Every refusal of one public call, in the ONE order in which they have always been asked — which error wins when two
+    apply is observable — before anything is exchanged, on every rank alike; called first thing by the forward of every autograd
+    node of the package.  Puts what the call bound on the node (ctx.softcap, ctx.lse_grad, ctx.row_ranges, ctx.block_mask: a
+    backward reads these, nothing ambient) and returns (alibi_slopes, sinks) as validated.
+    what: the name the messages carry.  batch: sequences in the call, for a (batch, H) bias.  vdim: the function serves a value
+    head dim of its own.  window_ring / dropout_ring / alibi_ring: it serves these on a multi-rank group (on a single-rank one
+    every function does; alibi_single False: not even there).  masks: the ScheduleSpec of a family that row ranges and block
+    masks can be bound to; None — the llama3 families, which the binders never let such a binding reach — reads neither.
+    before_alibi(alibi_slopes): a refusal of the function's own that belongs in front of the bias' validation."""
+    checked_vdim(q, k, v, dropout_p, alibi_slopes, what, served=vdim)
+    single = window_ok_for(group)
+    _check_unsupported(dropout_p, window_size, alibi_slopes, windows_ok=single or window_ring, dropout_ok=single or dropout_ring,
+                       alibi_ok=(single and alibi_single) or alibi_ring)
+    if before_alibi is not None:
+        before_alibi(alibi_slopes)
+    alibi_slopes = checked_alibi(alibi_slopes, q, batch, what)
+    ctx.softcap = checked_softcap(dropout_p, alibi_slopes, q, what, window_size, causal)
+    ctx.lse_grad = checked_lse_grad(ctx, what)
+    ctx.row_ranges = ctx.block_mask = None
+    if masks is not None:
+        ctx.row_ranges = checked_row_ranges(q, k, v, dropout_p, alibi_slopes, what)
+        ctx.block_mask = checked_block_mask(q, k, v, dropout_p, alibi_slopes, what, group, zigzag=masks.zigzag)
+    return alibi_slopes, checked_sinks(sinks, q, what)
+
+
+def _node_forward(ctx, spec, what, forward_impl, q, k, v, rest, packed_travel=False):
+    """the forward of every generic autograd Function: (q, k, v) as the adapter selected them, `rest` = the lead arguments,
+    the eight of the common tail and, inside a with_sinks call, the sinks"""
+    n_lead = spec.n_lead
+    rest, sinks = split_sinks(rest, n_lead + 8)
+    lead = rest[:n_lead]
+    (dropout_p, softmax_scale, causal, window_size, alibi_slopes, deterministic,
+     return_softmax, group) = rest[n_lead:]
+    if softmax_scale is None:
+        softmax_scale = q.shape[-1] ** (-0.5)
+    alibi_slopes, sinks = call_preamble(
+        ctx, what, q, k, v, sinks, dropout_p, window_size, alibi_slopes, causal, group, (len(lead[0]) - 1) if n_lead else q.shape[0],
+        vdim=spec.vdim, window_ring=spec.window_ring, dropout_ring=spec.dropout_ring, alibi_ring=spec.alibi_ring, masks=spec)
+    q, k, v = _prep_qkv(q, k, v, group, packed_travel=packed_travel)
+    tensors_lead = ()
+    if n_lead:
+        cu = _as_cu(lead[0], q.device)
+        lead = (cu,) + tuple(lead[1:])
+        tensors_lead = (cu,)
+    keep, extra = _keep_list(ctx, forward_impl)
+    extra.update(row_ranges_extra(ctx))
+    extra.update(block_mask_extra(ctx))
+    ctx.dropout = (dropout_p, draw_dropout_seed()) if dropout_p and dropout_p > 0 else (0.0, None)
+    if ctx.dropout[1] is not None:
+        extra["dropout_seed"] = ctx.dropout[1]
+    with softcap_scope(ctx.softcap):
+        out, softmax_lse = forward_impl(
+            group, q, k, v, *lead, softmax_scale=softmax_scale, dropout_p=dropout_p, causal=causal,
+            window_size=window_size, alibi_slopes=alibi_slopes, deterministic=False, **extra,
+        )
+    audit_verify(group, f"{what} forward")          # (config.exchange_check: a no-op otherwise)
+    # (with sinks: out', lse' are what the backward is handed and what the call returns)
+    out, softmax_lse = apply_sinks(sinks, out, softmax_lse)
+    ctx.save_for_backward(q, k, v, out, softmax_lse, *tensors_lead, *(keep or ()), *(() if sinks is None else (sinks,)))
+    ctx.has_sinks = sinks is not None
+    _hold_kept(ctx, keep)
+    ctx.n_lead_t, ctx.n_keep = len(tensors_lead), len(keep or ())
+    ctx.lead_rest = tuple(lead[1:]) if n_lead else ()
+    ctx.softmax_scale = softmax_scale
+    ctx.causal = causal
+    ctx.deterministic = deterministic
+    ctx.group = group
+    ctx.window_size = tuple(window_size)
+    ctx.alibi_slopes = alibi_slopes             # (no gradient, as in flash_attn: held, not saved for backward)
+    return out if not return_softmax else (out, softmax_lse, None)
+
+
+def _node_backward(ctx, spec, what, backward_impl, dout, args, out_grads=None):
+    """the backward of every generic autograd Function -> ((dq, dk, dv), the gradients of everything behind the tensors: None
+    for the plain arguments, the sinks' gradient inside a with_sinks call).  out_grads: (dq, dk, dv) views the schedule is to
+    write into, None where it allocates (the packed adapters); it may still return tensors of its own (W > 1)."""
+    q, k, v, out, softmax_lse, *more = ctx.saved_tensors
+    sinks = more.pop() if ctx.has_sinks else None
+    tensors_lead, extra = _split_kept(ctx, more)
+    dout, lse_kw = lse_grad_kw(ctx, dout, args, out, softmax_lse)
+    extra.update(lse_kw)
+    extra.update(row_ranges_extra(ctx))
+    extra.update(block_mask_extra(ctx))
+    if ctx.dropout[1] is not None:
+        extra["dropout_seed"] = ctx.dropout[1]
+    if out_grads is not None:
+        extra["out_grads"] = out_grads
+    with softcap_scope(ctx.softcap):
+        grads = backward_impl(
+            ctx.group, dout, q, k, v, out, softmax_lse, *tensors_lead, *ctx.lead_rest,
+            softmax_scale=ctx.softmax_scale, dropout_p=ctx.dropout[0], causal=ctx.causal,
+            window_size=ctx.window_size, alibi_slopes=ctx.alibi_slopes, deterministic=ctx.deterministic, **extra,
+        )
+    _release_kept(ctx)
+    audit_verify(ctx.group, f"{what} backward")
+    return tuple(grads), (None,) * (spec.n_lead + 8) + sinks_grad(ctx, sinks, dout, out, softmax_lse)
+
+
+def make_autograd_function(spec, forward_impl, backward_impl, n_lead=0, **serves):
+    """the autograd Function of a family's (q, k, v) entry from its schedule's `*_forward` / `*_backward`.  spec: the
+    family's ScheduleSpec — or the Function's name, with n_lead and the spec's `window_ring`, `dropout_ring`, `alibi_ring`,
+    `vdim` as keywords."""
+    if not isinstance(spec, ScheduleSpec):
+        spec = ScheduleSpec(name=spec, n_lead=n_lead, **serves)
 
     class _Fn(torch.autograd.Function):
         @staticmethod
         def forward(ctx, q, k, v, *rest):
-            rest, sinks = split_sinks(rest, n_lead + 8)
-            lead = rest[:n_lead]
-            (dropout_p, softmax_scale, causal, window_size, alibi_slopes, deterministic,
-             return_softmax, group) = rest[n_lead:]
-            if softmax_scale is None:
-                softmax_scale = q.shape[-1] ** (-0.5)
-            checked_vdim(q, k, v, dropout_p, alibi_slopes, name, served=vdim)
-            single = window_ok_for(group)
-            _check_unsupported(dropout_p, window_size, alibi_slopes, windows_ok=single or window_ring, dropout_ok=single or dropout_ring,
-                               alibi_ok=single or alibi_ring)
-            alibi_slopes = checked_alibi(alibi_slopes, q, (len(lead[0]) - 1) if n_lead else q.shape[0], name)
-            ctx.softcap = checked_softcap(dropout_p, alibi_slopes, q, name, window_size, causal)
-            ctx.lse_grad = checked_lse_grad(ctx, name)
-            ctx.row_ranges = checked_row_ranges(q, k, v, dropout_p, alibi_slopes, name)
-            ctx.block_mask = checked_block_mask(q, k, v, dropout_p, alibi_slopes, name, group)
-            sinks = checked_sinks(sinks, q, name)
-            q, k, v = _prep_qkv(q, k, v, group)
-            tensors_lead = ()
-            if n_lead:
-                cu = _as_cu(lead[0], q.device)
-                lead = (cu,) + tuple(lead[1:])
-                tensors_lead = (cu,)
-            keep, extra = _keep_list(ctx, forward_impl)
-            extra.update(row_ranges_extra(ctx))
-            extra.update(block_mask_extra(ctx))
-            ctx.dropout = (dropout_p, draw_dropout_seed()) if dropout_p and dropout_p > 0 else (0.0, None)
-            if ctx.dropout[1] is not None:
-                extra["dropout_seed"] = ctx.dropout[1]
-            with softcap_scope(ctx.softcap):
-                out, softmax_lse = forward_impl(
-                    group, q, k, v, *lead, softmax_scale=softmax_scale, dropout_p=dropout_p, causal=causal,
-                    window_size=window_size, alibi_slopes=alibi_slopes, deterministic=False, **extra,
-                )
-            audit_verify(group, f"{name} forward")          # (config.exchange_check: a no-op otherwise)
-            # (with sinks: out', lse' are what the backward is handed and what the call returns)
-            out, softmax_lse = apply_sinks(sinks, out, softmax_lse)
-            ctx.save_for_backward(q, k, v, out, softmax_lse, *tensors_lead, *(keep or ()), *(() if sinks is None else (sinks,)))
-            ctx.has_sinks = sinks is not None
-            _hold_kept(ctx, keep)
-            ctx.n_lead_t, ctx.n_keep = len(tensors_lead), len(keep or ())
-            ctx.lead_rest = tuple(lead[1:]) if n_lead else ()
-            ctx.softmax_scale = softmax_scale
-            ctx.causal = causal
-            ctx.deterministic = deterministic
-            ctx.group = group
-            ctx.window_size = tuple(window_size)
-            ctx.alibi_slopes = alibi_slopes             # (no gradient, as in flash_attn: held, not saved for backward)
-            return out if not return_softmax else (out, softmax_lse, None)
+            return _node_forward(ctx, spec, spec.name, forward_impl, q, k, v, rest)
 
         @staticmethod
         def backward(ctx, dout, *args):
-            q, k, v, out, softmax_lse, *more = ctx.saved_tensors
-            sinks = more.pop() if ctx.has_sinks else None
-            tensors_lead, extra = _split_kept(ctx, more)
-            dout, lse_kw = lse_grad_kw(ctx, dout, args, out, softmax_lse)
-            extra.update(lse_kw)
-            extra.update(row_ranges_extra(ctx))
-            extra.update(block_mask_extra(ctx))
-            if ctx.dropout[1] is not None:
-                extra["dropout_seed"] = ctx.dropout[1]
-            with softcap_scope(ctx.softcap):
-                dq, dk, dv = backward_impl(
-                    ctx.group, dout, q, k, v, out, softmax_lse, *tensors_lead, *ctx.lead_rest,
-                    softmax_scale=ctx.softmax_scale, dropout_p=ctx.dropout[0], causal=ctx.causal,
-                    window_size=ctx.window_size, alibi_slopes=ctx.alibi_slopes, deterministic=ctx.deterministic, **extra,
-                )
-            _release_kept(ctx)
-            audit_verify(ctx.group, f"{name} backward")
-            return (dq, dk, dv) + (None,) * (n_lead + 8) + sinks_grad(ctx, sinks, dout, out, softmax_lse)
+            grads, tail = _node_backward(ctx, spec, spec.name, backward_impl, dout, args)
+            return grads + tail
 
-    _Fn.__name__ = _Fn.__qualname__ = name
+    _Fn.__name__ = _Fn.__qualname__ = spec.name
     return _Fn
 
 
-def make_packed_function(name, base_fn, forward_impl, backward_impl, n_lead, pack_dim, n_packed, packed_travel=False,
-                         window_ring=False, dropout_ring=False, alibi_ring=False):
-    """autograd Function for the packed entry points (`kv` = 2 tensors, `qkv` = 3 tensors stacked on
-    `pack_dim`).  Same math as `base_fn`; the only difference is where the gradients land: ONE packed
+def _packed_function(spec, forward_impl, backward_impl, n_packed):
+    """autograd Function for the packed entry points (`kv` = 2 tensors, `qkv` = 3 tensors stacked on spec.pack_dim).  Same
+    math as the family's plain Function; the only difference is where the gradients land: ONE packed
     buffer whose slices are handed to the schedule as output views (`out_grads`), instead of letting
     autograd build the packed gradient from three slice-gradients (zero-fill + copy + add kernels
-    per step).  Falls back to the generic path when the schedule returns fresh tensors (W > 1)."""
+    per step); a gradient the schedule returned in a tensor of its own (W > 1) is copied into its slice."""
+    what = spec.name + ("KVPacked" if n_packed == 2 else "QKVPacked")
+    n_own = 3 - n_packed                                # tensors in front of the packed one: q of (q, kv), none of (qkv,)
 
     class _PFn(torch.autograd.Function):
         @staticmethod
         def forward(ctx, *args):
-            n_t = 1 if n_packed == 3 else 2                 # (qkv,) or (q, kv)
-            tensors, rest = args[:n_t], args[n_t:]
-            packed = tensors[-1]
-            parts = [packed.select(pack_dim, i) for i in range(n_packed)]
-            q, k, v = (parts if n_packed == 3 else [tensors[0]] + parts)
-            rest, sinks = split_sinks(rest, n_lead + 8)
-            lead = rest[:n_lead]
-            (dropout_p, softmax_scale, causal, window_size, alibi_slopes, deterministic,
-             return_softmax, group) = rest[n_lead:]
-            if softmax_scale is None:
-                softmax_scale = q.shape[-1] ** (-0.5)
-            single = window_ok_for(group)
-            _check_unsupported(dropout_p, window_size, alibi_slopes, windows_ok=single or window_ring, dropout_ok=single or dropout_ring,
-                               alibi_ok=single or alibi_ring)
-            alibi_slopes = checked_alibi(alibi_slopes, q, (len(lead[0]) - 1) if n_lead else q.shape[0], name)
-            ctx.softcap = checked_softcap(dropout_p, alibi_slopes, q, name, window_size, causal)
-            ctx.lse_grad = checked_lse_grad(ctx, name)
-            ctx.row_ranges = checked_row_ranges(q, k, v, dropout_p, alibi_slopes, name)
-            ctx.block_mask = checked_block_mask(q, k, v, dropout_p, alibi_slopes, name, group)
-            sinks = checked_sinks(sinks, q, name)
-            q, k, v = _prep_qkv(q, k, v, group, packed_travel=packed_travel and n_packed == 2)
-            tensors_lead = ()
-            if n_lead:
-                cu = _as_cu(lead[0], q.device)
-                lead = (cu,) + tuple(lead[1:])
-                tensors_lead = (cu,)
-            keep, extra = _keep_list(ctx, forward_impl)
-            extra.update(row_ranges_extra(ctx))
-            extra.update(block_mask_extra(ctx))
-            ctx.dropout = (dropout_p, draw_dropout_seed()) if dropout_p and dropout_p > 0 else (0.0, None)
-            if ctx.dropout[1] is not None:
-                extra["dropout_seed"] = ctx.dropout[1]
-            with softcap_scope(ctx.softcap):
-                out, softmax_lse = forward_impl(
-                    group, q, k, v, *lead, softmax_scale=softmax_scale, dropout_p=dropout_p, causal=causal,
-                    window_size=window_size, alibi_slopes=alibi_slopes, deterministic=False, **extra,
-                )
-            audit_verify(group, f"{name} forward")          # (config.exchange_check: a no-op otherwise)
-            # (with sinks: out', lse' are what the backward is handed and what the call returns)
-            out, softmax_lse = apply_sinks(sinks, out, softmax_lse)
-            ctx.save_for_backward(q, k, v, out, softmax_lse, *tensors_lead, *(keep or ()), *(() if sinks is None else (sinks,)))
-            ctx.has_sinks = sinks is not None
-            _hold_kept(ctx, keep)
-            ctx.n_lead_t, ctx.n_keep = len(tensors_lead), len(keep or ())
-            ctx.lead_rest = tuple(lead[1:]) if n_lead else ()
-            ctx.softmax_scale = softmax_scale
-            ctx.causal = causal
-            ctx.deterministic = deterministic
-            ctx.group = group
-            ctx.window_size = tuple(window_size)
-            ctx.alibi_slopes = alibi_slopes             # (no gradient, as in flash_attn: held, not saved for backward)
+            packed = args[n_own]
             ctx.packed_meta = (packed.shape, packed.dtype, packed.device)
-            return out if not return_softmax else (out, softmax_lse, None)
+            # (one packed tensor has one width, so the preamble's checked_vdim has nothing to refuse here)
+            return _node_forward(ctx, spec, what, forward_impl, *args[:n_own], *(packed.select(spec.pack_dim, i) for i in range(n_packed)),
+                                 args[n_own + 1:], packed_travel=spec.packed_travel and n_packed == 2)
 
         @staticmethod
         def backward(ctx, dout, *args):
-            q, k, v, out, softmax_lse, *more = ctx.saved_tensors
-            sinks = more.pop() if ctx.has_sinks else None
-            tensors_lead, extra = _split_kept(ctx, more)
-            dout, lse_kw = lse_grad_kw(ctx, dout, args, out, softmax_lse)
-            extra.update(lse_kw)
-            extra.update(row_ranges_extra(ctx))
-            extra.update(block_mask_extra(ctx))
             shape, dtype, device = ctx.packed_meta
             dpacked = torch.empty(shape, dtype=dtype, device=device)
-            views = [dpacked.select(pack_dim, i) for i in range(n_packed)]
-            if n_packed == 3:
-                out_grads = tuple(views)
-            else:
-                out_grads = (None, views[0], views[1])
-            if ctx.dropout[1] is not None:
-                extra["dropout_seed"] = ctx.dropout[1]
-            with softcap_scope(ctx.softcap):
-                dq, dk, dv = backward_impl(
-                    ctx.group, dout, q, k, v, out, softmax_lse, *tensors_lead, *ctx.lead_rest,
-                    softmax_scale=ctx.softmax_scale, dropout_p=ctx.dropout[0], causal=ctx.causal,
-                    window_size=ctx.window_size, alibi_slopes=ctx.alibi_slopes, deterministic=ctx.deterministic,
-                    out_grads=out_grads, **extra,
-                )
-            got = (dq, dk, dv)[3 - n_packed:]
-            for view, g in zip(views, got):
+            views = tuple(dpacked.select(spec.pack_dim, i) for i in range(n_packed))
+            grads, tail = _node_backward(ctx, spec, what, backward_impl, dout, args, out_grads=(None,) * n_own + views)
+            for view, g in zip(views, grads[n_own:]):
                 if g.data_ptr() != view.data_ptr():       # schedule returned its own tensor
                     view.copy_(g)
-            grads = (dpacked,) if n_packed == 3 else (dq, dpacked)
-            _release_kept(ctx)
-            audit_verify(ctx.group, f"{name} backward")
-            return grads + (None,) * (n_lead + 8) + sinks_grad(ctx, sinks, dout, out, softmax_lse)
+            return grads[:n_own] + (dpacked,) + tail
 
-    _PFn.__name__ = _PFn.__qualname__ = name
+    _PFn.__name__ = _PFn.__qualname__ = what
     return _PFn
 
 
@@ -1103,152 +1061,72 @@ def _grad_buffers(out_grads, q, k, v):
             og[2] if og[2] is not None else torch.empty_like(v))
 
 
-def make_dense_api(fn, prefix, forward_impl=None, backward_impl=None, packed_travel=False, window_ring=False,
-                   dropout_ring=False, alibi_ring=False):
-    """(B,S,H,D) API: returns (func, kvpacked_func, qkvpacked_func).  packed_travel: the schedule exchanges a
-    packed `kv` as one buffer and writes dK/dV straight into the packed gradient (`out_grads`) at any world size.
-    window_ring, dropout_ring, alibi_ring: as in make_autograd_function (pass the same values to both)."""
-    kv_fn = qkv_fn = None
-    if forward_impl is not None:
-        kv_fn = make_packed_function(fn.__name__ + "KVPacked", fn, forward_impl, backward_impl, 0, 2, 2,
-                                     packed_travel=packed_travel, window_ring=window_ring, dropout_ring=dropout_ring,
-                                     alibi_ring=alibi_ring)
-        qkv_fn = make_packed_function(fn.__name__ + "QKVPacked", fn, forward_impl, backward_impl, 0, 2, 3,
-                                      window_ring=window_ring, dropout_ring=dropout_ring, alibi_ring=alibi_ring)
+def make_api(spec, fn, forward_impl, backward_impl):
+    """(func, kvpacked_func, qkvpacked_func) of a family: the (B,S,H,D) API, or with spec.n_lead == 2 the (T,H,D) +
+    (cu_seqlens, max_seqlen) one.  fn: the family's autograd Function (make_autograd_function with the same spec); the packed
+    entry points get Functions of their own (gradients land in ONE packed buffer, see _packed_function)."""
+    from . import _ops
 
-    def func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
-             alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None):
-        return fn.apply(q, k, v, dropout_p, softmax_scale, causal, window_size, alibi_slopes,
-                        deterministic, return_attn_probs, group, *sink_args())
+    kv_fn, qkv_fn = (_packed_function(spec, forward_impl, backward_impl, n) for n in (2, 3))
+    if spec.n_lead == 0:
+        def func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
+                 alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None):
+            return fn.apply(q, k, v, dropout_p, softmax_scale, causal, window_size, alibi_slopes,
+                            deterministic, return_attn_probs, group, *sink_args())
 
-    def kvpacked_func(q, kv, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
-                      alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None):
-        if kv_fn is not None:
+        def kvpacked_func(q, kv, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
+                          alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None):
             return kv_fn.apply(q, kv, dropout_p, softmax_scale, causal, window_size, alibi_slopes,
                                deterministic, return_attn_probs, group, *sink_args())
-        return fn.apply(q, kv[:, :, 0], kv[:, :, 1], dropout_p, softmax_scale, causal, window_size,
-                        alibi_slopes, deterministic, return_attn_probs, group, *sink_args())
 
-    def qkvpacked_func(qkv, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
-                       alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None):
-        if qkv_fn is not None:
+        def qkvpacked_func(qkv, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
+                           alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None):
             return qkv_fn.apply(qkv, dropout_p, softmax_scale, causal, window_size, alibi_slopes,
                                 deterministic, return_attn_probs, group, *sink_args())
-        return fn.apply(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], dropout_p, softmax_scale, causal,
-                        window_size, alibi_slopes, deterministic, return_attn_probs, group, *sink_args())
+    else:
+        def func(q, k, v, cu_seqlens, max_seqlen, dropout_p=0.0, softmax_scale=None, causal=False,
+                 window_size=(-1, -1), alibi_slopes=None, deterministic=False, return_attn_probs=False,
+                 group=None):
+            return fn.apply(q, k, v, cu_seqlens, max_seqlen, dropout_p, softmax_scale, causal, window_size,
+                            alibi_slopes, deterministic, return_attn_probs, group, *sink_args())
 
-    must_be_causal = prefix in ("zigzag_ring_flash_attn", "stripe_flash_attn")
-
-    def lower(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1), alibi_slopes=None,
-              deterministic=False, return_attn_probs=False, group=None):
-        from ._ops import single_device_attention
-
-        _check_unsupported(dropout_p, window_size, alibi_slopes, windows_ok=True)
-        assert causal or not must_be_causal, f"{prefix} is meaningless for causal=False"
-        return single_device_attention(q, k, v, None, 0, softmax_scale, causal, return_attn_probs, window_size)
-
-    def lower_kv(q, kv, *a, **kw):
-        return lower(q, kv[:, :, 0], kv[:, :, 1], *a, **kw)
-
-    def lower_qkv(qkv, *a, **kw):
-        return lower(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], *a, **kw)
-
-    multi = multi_kv = multi_qkv = None
-    if forward_impl is not None:
-        from . import _ops
-
-        _ops.register_schedule(prefix, forward_impl, backward_impl)
-
-        def multi(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1), alibi_slopes=None,
-                  deterministic=False, return_attn_probs=False, group=None):
-            _check_unsupported(dropout_p, window_size, alibi_slopes, windows_ok=False)
-            assert causal or not must_be_causal, f"{prefix} is meaningless for causal=False"
-            return _ops.multi_rank_attention(prefix, q, k, v, None, 0, softmax_scale, causal, return_attn_probs, group)
-
-        def multi_kv(q, kv, *a, **kw):
-            return multi(q, kv[:, :, 0], kv[:, :, 1], *a, **kw)
-
-        def multi_qkv(qkv, *a, **kw):
-            return multi(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], *a, **kw)
-
-    for f, suffix in ((func, "func"), (kvpacked_func, "kvpacked_func"), (qkvpacked_func, "qkvpacked_func")):
-        f.__name__ = f.__qualname__ = f"{prefix}_{suffix}"
-    return (_compilable(func, lower, multi), _compilable(kvpacked_func, lower_kv, multi_kv),
-            _compilable(qkvpacked_func, lower_qkv, multi_qkv))
-
-
-def make_varlen_api(fn, prefix, forward_impl=None, backward_impl=None, window_ring=False):
-    """(T,H,D) + (cu_seqlens, max_seqlen) API.  With the schedule's forward / backward the packed entry points get
-    their own autograd Function (gradients land in ONE packed buffer, see make_packed_function).
-    window_ring: as in make_autograd_function (pass the same value to both)."""
-    kv_fn = qkv_fn = None
-    if forward_impl is not None:
-        kv_fn = make_packed_function(fn.__name__ + "KVPacked", fn, forward_impl, backward_impl, 2, 1, 2,
-                                     window_ring=window_ring)
-        qkv_fn = make_packed_function(fn.__name__ + "QKVPacked", fn, forward_impl, backward_impl, 2, 1, 3,
-                                      window_ring=window_ring)
-
-    def func(q, k, v, cu_seqlens, max_seqlen, dropout_p=0.0, softmax_scale=None, causal=False,
-             window_size=(-1, -1), alibi_slopes=None, deterministic=False, return_attn_probs=False,
-             group=None):
-        return fn.apply(q, k, v, cu_seqlens, max_seqlen, dropout_p, softmax_scale, causal, window_size,
-                        alibi_slopes, deterministic, return_attn_probs, group, *sink_args())
-
-    def kvpacked_func(q, kv, cu_seqlens, max_seqlen, dropout_p=0.0, softmax_scale=None, causal=False,
-                      window_size=(-1, -1), alibi_slopes=None, deterministic=False,
-                      return_attn_probs=False, group=None):
-        if kv_fn is not None:
+        def kvpacked_func(q, kv, cu_seqlens, max_seqlen, dropout_p=0.0, softmax_scale=None, causal=False,
+                          window_size=(-1, -1), alibi_slopes=None, deterministic=False,
+                          return_attn_probs=False, group=None):
             return kv_fn.apply(q, kv, cu_seqlens, max_seqlen, dropout_p, softmax_scale, causal, window_size,
                                alibi_slopes, deterministic, return_attn_probs, group, *sink_args())
-        return fn.apply(q, kv[:, 0], kv[:, 1], cu_seqlens, max_seqlen, dropout_p, softmax_scale, causal,
-                        window_size, alibi_slopes, deterministic, return_attn_probs, group, *sink_args())
 
-    def qkvpacked_func(qkv, cu_seqlens, max_seqlen, dropout_p=0.0, softmax_scale=None, causal=False,
-                       window_size=(-1, -1), alibi_slopes=None, deterministic=False,
-                       return_attn_probs=False, group=None):
-        if qkv_fn is not None:
+        def qkvpacked_func(qkv, cu_seqlens, max_seqlen, dropout_p=0.0, softmax_scale=None, causal=False,
+                           window_size=(-1, -1), alibi_slopes=None, deterministic=False,
+                           return_attn_probs=False, group=None):
             return qkv_fn.apply(qkv, cu_seqlens, max_seqlen, dropout_p, softmax_scale, causal, window_size,
                                 alibi_slopes, deterministic, return_attn_probs, group, *sink_args())
-        return fn.apply(qkv[:, 0], qkv[:, 1], qkv[:, 2], cu_seqlens, max_seqlen, dropout_p, softmax_scale,
-                        causal, window_size, alibi_slopes, deterministic, return_attn_probs, group, *sink_args())
 
-    must_be_causal = prefix.startswith("zigzag")
+    # what dynamo traces instead (_compilable): the call as registered operators, from its arguments by name — one text for
+    # the three forms and for both APIs (a dense call has no cu_seqlens: None, 0)
+    def traced(a, windows_ok):
+        if "qkv" in a:
+            q, k, v = [a["qkv"].select(spec.pack_dim, i) for i in range(3)]
+        elif "kv" in a:
+            q, (k, v) = a["q"], [a["kv"].select(spec.pack_dim, i) for i in range(2)]
+        else:
+            q, k, v = a["q"], a["k"], a["v"]
+        causal, window_size = a.get("causal", False), a.get("window_size", (-1, -1))
+        _check_unsupported(a.get("dropout_p", 0.0), window_size, a.get("alibi_slopes", None), windows_ok=windows_ok)
+        assert causal or not spec.must_be_causal, f"{spec.prefix} is meaningless for causal=False"
+        return (q, k, v, a.get("cu_seqlens", None), a.get("max_seqlen", 0), a.get("softmax_scale", None), causal,
+                a.get("return_attn_probs", False)), window_size
 
-    def lower(q, k, v, cu_seqlens, max_seqlen, dropout_p=0.0, softmax_scale=None, causal=False,
-              window_size=(-1, -1), alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None):
-        from ._ops import single_device_attention
+    def lower(a):
+        args, window_size = traced(a, True)
+        return _ops.single_device_attention(*args, window_size)
 
-        _check_unsupported(dropout_p, window_size, alibi_slopes, windows_ok=True)
-        assert causal or not must_be_causal, f"{prefix} is meaningless for causal=False"
-        return single_device_attention(q, k, v, cu_seqlens, max_seqlen, softmax_scale, causal, return_attn_probs,
-                                       window_size)
+    _ops.register_schedule(spec.prefix, forward_impl, backward_impl)
 
-    def lower_kv(q, kv, *a, **kw):
-        return lower(q, kv[:, 0], kv[:, 1], *a, **kw)
-
-    def lower_qkv(qkv, *a, **kw):
-        return lower(qkv[:, 0], qkv[:, 1], qkv[:, 2], *a, **kw)
-
-    multi = multi_kv = multi_qkv = None
-    if forward_impl is not None:
-        from . import _ops
-
-        _ops.register_schedule(prefix, forward_impl, backward_impl)
-
-        def multi(q, k, v, cu_seqlens, max_seqlen, dropout_p=0.0, softmax_scale=None, causal=False,
-                  window_size=(-1, -1), alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None):
-            _check_unsupported(dropout_p, window_size, alibi_slopes, windows_ok=False)
-            assert causal or not must_be_causal, f"{prefix} is meaningless for causal=False"
-            return _ops.multi_rank_attention(prefix, q, k, v, cu_seqlens, max_seqlen, softmax_scale, causal,
-                                             return_attn_probs, group)
-
-        def multi_kv(q, kv, *a, **kw):
-            return multi(q, kv[:, 0], kv[:, 1], *a, **kw)
-
-        def multi_qkv(qkv, *a, **kw):
-            return multi(qkv[:, 0], qkv[:, 1], qkv[:, 2], *a, **kw)
+    def multi(a):
+        args, _ = traced(a, False)
+        return _ops.multi_rank_attention(spec.prefix, *args, a.get("group", None))
 
     for f, suffix in ((func, "func"), (kvpacked_func, "kvpacked_func"), (qkvpacked_func, "qkvpacked_func")):
-        f.__name__ = f.__qualname__ = f"{prefix}_{suffix}"
-    return (_compilable(func, lower, multi), _compilable(kvpacked_func, lower_kv, multi_kv),
-            _compilable(qkvpacked_func, lower_qkv, multi_qkv))
+        f.__name__ = f.__qualname__ = f"{spec.prefix}_{suffix}"
+    return tuple(_compilable(f, lower, multi) for f in (func, kvpacked_func, qkvpacked_func))

@@ -153,7 +153,7 @@ _SCHEDULES = {}
 
 
 def register_schedule(name: str, forward_impl, backward_impl):
-    """_api.make_dense_api / make_varlen_api register their (forward, backward) schedule under the public prefix"""
+    """_api.make_api registers a family's (forward, backward) schedule under its public prefix"""
     _SCHEDULES[name] = (forward_impl, backward_impl)
 
 

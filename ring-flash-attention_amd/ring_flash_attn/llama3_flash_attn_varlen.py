@@ -27,8 +27,7 @@ import torch
 from . import config
 from .backend import get_backend, heads_from
 from .utils import AllGatherComm as Comm, group_rank_world, reduce_scatter_async, single_rank
-from ._api import (_check_unsupported, _opaque, apply_sinks, checked_alibi, checked_sinks, checked_softcap, checked_vdim, sink_args, sinks_grad,
-                   softcap_scope, window_ok_for, checked_lse_grad, lse_grad_kw)
+from ._api import _check_unsupported, _opaque, apply_sinks, call_preamble, sink_args, sinks_grad, softcap_scope, lse_grad_kw
 from ._common import alibi_kw, dlse_kw, _as_cu, dropout_arg, draw_dropout_seed, packed_pair
 
 
@@ -320,14 +319,12 @@ def _l3_forward(ctx, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seql
                 dropout_p, softmax_scale, causal, window_size, alibi_slopes, deterministic, return_softmax, group, sinks=None):
     if softmax_scale is None:
         softmax_scale = q.shape[-1] ** (-0.5)
-    checked_vdim(q, k, v, dropout_p, alibi_slopes, "llama3_flash_attn_varlen_func", served=False)   # (the gathers stack K and V)
-    # K/V are gathered: one kernel sees them all.  A bias needs the global distance i - j: on several ranks the bottom-right
-    # alignment against the truncated cu_seqlens_k yields it for causal calls only (the slopes are sliced per head group)
-    _check_unsupported(dropout_p, window_size, alibi_slopes, windows_ok=True, alibi_ok=window_ok_for(group) or bool(causal))
-    alibi_slopes = checked_alibi(alibi_slopes, q, len(cu_seqlens_q) - 1, "llama3_flash_attn_varlen_func")
-    ctx.softcap = checked_softcap(dropout_p, alibi_slopes, q, "llama3_flash_attn_varlen_func", window_size, causal)
-    ctx.lse_grad = checked_lse_grad(ctx, "llama3_flash_attn_varlen_func")
-    sinks = checked_sinks(sinks, q, "llama3_flash_attn_varlen_func")
+    # no value head dim of its own: the gathers stack K and V.  K/V are gathered, so one kernel sees them all: windows and
+    # dropout on any group.  A bias needs the global distance i - j: on several ranks the bottom-right alignment against the
+    # truncated cu_seqlens_k yields it for causal calls only (the slopes are sliced per head group)
+    alibi_slopes, sinks = call_preamble(
+        ctx, "llama3_flash_attn_varlen_func", q, k, v, sinks, dropout_p, window_size, alibi_slopes, causal, group,
+        len(cu_seqlens_q) - 1, vdim=False, window_ring=True, dropout_ring=True, alibi_ring=bool(causal))
     # (strided views — the halves of a packed kv — are fine: the kernels take strides, and the all-gather sources are
     #  made contiguous per head group where they are posted)
     q, k, v = (t if t.stride(-1) == 1 else t.contiguous() for t in (q, k, v))

@@ -31,7 +31,7 @@ from . import _C
 from .backend import get_backend
 from .utils import RingComm, single_rank
 from ._common import alibi_kw, block_mask_kw, dlse_kw, out_shape, row_ranges_kw, dropout_arg, global_window, pos_map, require_dropout_positions, require_mask_shift
-from ._api import make_autograd_function, make_dense_api, _grad_buffers
+from ._api import ScheduleSpec, make_autograd_function, make_api, _grad_buffers
 
 
 def ring_window_plan(rank, world_size, S, causal, window):
@@ -301,12 +301,10 @@ def ring_flash_attn_backward(
     return be.cast(dq, q.dtype), be.cast(next_dk, q.dtype), be.cast(next_dv, q.dtype)
 
 
-RingFlashAttnFunc = make_autograd_function(
-    "RingFlashAttnFunc", ring_flash_attn_forward, ring_flash_attn_backward, 0, vdim=True, window_ring=True, dropout_ring=True,
-    alibi_ring=True)
+SPEC = ScheduleSpec("RingFlashAttnFunc", "ring_flash_attn", vdim=True, window_ring=True, dropout_ring=True, alibi_ring=True)
+RingFlashAttnFunc = make_autograd_function(SPEC, ring_flash_attn_forward, ring_flash_attn_backward)
 (
     ring_flash_attn_func,
     ring_flash_attn_kvpacked_func,
     ring_flash_attn_qkvpacked_func,
-) = make_dense_api(RingFlashAttnFunc, "ring_flash_attn", ring_flash_attn_forward, ring_flash_attn_backward, window_ring=True,
-                   dropout_ring=True, alibi_ring=True)
+) = make_api(SPEC, RingFlashAttnFunc, ring_flash_attn_forward, ring_flash_attn_backward)

@@ -22,7 +22,7 @@ from . import _C
 from .backend import get_backend
 from .utils import RingComm, single_rank
 from ._common import alibi_kw, dlse_kw, out_shape, dropout_arg, global_window, require_mask_shift_lens
-from ._api import make_autograd_function, make_varlen_api, _grad_buffers
+from ._api import ScheduleSpec, make_autograd_function, make_api, _grad_buffers
 
 
 def _band(causal, win, step, rank, world):
@@ -165,11 +165,10 @@ def ring_flash_attn_varlen_backward(
     return be.cast(dq, q.dtype), be.cast(next_dk, q.dtype), be.cast(next_dv, q.dtype)
 
 
-RingFlashAttnVarlenFunc = make_autograd_function(
-    "RingFlashAttnVarlenFunc", ring_flash_attn_varlen_forward, ring_flash_attn_varlen_backward, 2, window_ring=True, vdim=True)
+SPEC = ScheduleSpec("RingFlashAttnVarlenFunc", "ring_flash_attn_varlen", n_lead=2, pack_dim=1, window_ring=True, vdim=True)
+RingFlashAttnVarlenFunc = make_autograd_function(SPEC, ring_flash_attn_varlen_forward, ring_flash_attn_varlen_backward)
 (
     ring_flash_attn_varlen_func,
     ring_flash_attn_varlen_kvpacked_func,
     ring_flash_attn_varlen_qkvpacked_func,
-) = make_varlen_api(RingFlashAttnVarlenFunc, "ring_flash_attn_varlen", ring_flash_attn_varlen_forward, ring_flash_attn_varlen_backward,
-                    window_ring=True)
+) = make_api(SPEC, RingFlashAttnVarlenFunc, ring_flash_attn_varlen_forward, ring_flash_attn_varlen_backward)

@@ -22,7 +22,7 @@ from . import _C
 from .backend import get_backend
 from .utils import RingComm, single_rank
 from ._common import alibi_kw, dlse_kw, out_shape, dropout_arg, global_window, require_dropout_positions, require_mask_shift, stripe_map
-from ._api import make_autograd_function, make_dense_api, _grad_buffers
+from ._api import ScheduleSpec, make_autograd_function, make_api, _grad_buffers
 
 
 def stripe_window_band(rank, src, world, window_left):
@@ -248,11 +248,10 @@ def stripe_flash_attn_backward(
     return be.cast(dq, q.dtype), be.cast(next_dk, q.dtype), be.cast(next_dv, q.dtype)
 
 
-StripeFlashAttnFunc = make_autograd_function(
-    "StripeFlashAttnFunc", stripe_flash_attn_forward, stripe_flash_attn_backward, 0, vdim=True, window_ring=True, dropout_ring=True)
+SPEC = ScheduleSpec("StripeFlashAttnFunc", "stripe_flash_attn", vdim=True, window_ring=True, dropout_ring=True, must_be_causal=True)
+StripeFlashAttnFunc = make_autograd_function(SPEC, stripe_flash_attn_forward, stripe_flash_attn_backward)
 (
     stripe_flash_attn_func,
     stripe_flash_attn_kvpacked_func,
     stripe_flash_attn_qkvpacked_func,
-) = make_dense_api(StripeFlashAttnFunc, "stripe_flash_attn", stripe_flash_attn_forward, stripe_flash_attn_backward,
-                   window_ring=True, dropout_ring=True)
+) = make_api(SPEC, StripeFlashAttnFunc, stripe_flash_attn_forward, stripe_flash_attn_backward)

@@ -19,14 +19,13 @@ holds chunks g and 2W-1-g of 2W; the merged front is chunks rho U .. rho U + U-1
 The layout change on either side of the all-to-all is one launch of the backend's `seq_head_copy` (HIP: csrc/rfa_seqhead.hip)
 for all tensors of the call; q, k and v travel in ONE buffer and one collective per direction.
 """
-import functools
 import inspect
 
 import torch
 import torch.distributed as dist
 
 from . import _C
-from ._api import _opaque
+from ._api import _admit, _bind, checked_vdim
 from .utils import all_to_all_async, audit_verify
 
 _LAYOUT = {"ring_flash_attn": _C.SEQHEAD_CONTIGUOUS, "zigzag_ring_flash_attn": _C.SEQHEAD_ZIGZAG,
@@ -35,27 +34,11 @@ _FORMS = ("_qkvpacked_func", "_kvpacked_func", "_func")
 
 
 def _resolve(func, who):
-    """(layout, form) of one of the nine dense public functions, or of a with_softcap result of one; TypeError otherwise"""
-    import ring_flash_attn as pkg
-
-    if getattr(func, "_rfa_sinks", False):
-        raise TypeError(f"ring_flash_attn.{who}: `func` is a with_sinks result; sinks are per head and would need slicing and "
-                        "a scattered gradient under the head exchange: follow-up")
-    if getattr(func, "_rfa_ulysses", False):
-        raise TypeError(f"ring_flash_attn.{who}: `func` is already a with_ulysses result")
-    public = {id(getattr(pkg, n)): n for n in dir(pkg) if n.endswith("_func")}
-    f = func
-    # (a with_softcap result carries the marker on both of its layers and leads to the public function it wraps)
-    while id(f) not in public and getattr(f, "_rfa_softcap", None) and hasattr(f, "__wrapped__"):
-        f = f.__wrapped__
-    name = public.get(id(f))
-    if name is not None:
-        for form in _FORMS:
-            if name.endswith(form) and name[:-len(form)] in _LAYOUT:
-                return _LAYOUT[name[:-len(form)]], form
-    raise TypeError(f"ring_flash_attn.{who}: `func` must be one of the nine dense functions (ring_, zigzag_ring_ and "
-                    "stripe_flash_attn_{,kvpacked_,qkvpacked_}func) or a with_softcap result of one; the *_varlen families, "
-                    f"llama3_* and zigzag_llama3_* are a follow-up; got {func!r}")
+    """(layout, form) of one of the nine dense public functions, or of a with_softcap result of one; TypeError otherwise
+    (_api._RULES: the row of with_ulysses)"""
+    name = _admit("with_ulysses", func, who)
+    form = next(f for f in _FORMS if name.endswith(f))
+    return _LAYOUT[name[:-len(form)]], form
 
 
 def make_usp_groups(func, ulysses_size, group=None):
@@ -226,7 +209,6 @@ def with_ulysses(func, ulysses_group):
     sig = inspect.signature(func)
     names = {"_func": ("q", "k", "v"), "_kvpacked_func": ("q", "kv"), "_qkvpacked_func": ("qkv",)}[form]
 
-    @functools.wraps(func, updated=())               # (updated=(): as in with_softcap)
     def exchanged(*args, **kwargs):
         U = dist.get_world_size(ulysses_group)
         if U == 1:
@@ -249,8 +231,7 @@ def with_ulysses(func, ulysses_group):
             return (_RowsForHeads.apply(ulysses_group, U, layout, out), _lse_back(ulysses_group, U, layout, lse), rest)
         return _RowsForHeads.apply(ulysses_group, U, layout, res)
 
-    exchanged._rfa_ulysses = True
-    return _opaque(exchanged)
+    return _bind("with_ulysses", func, body=exchanged)
 
 
 def _check_call(func, tensors, names, layout, U, a):
@@ -269,8 +250,6 @@ def _check_call(func, tensors, names, layout, U, a):
         if not isinstance(t, torch.Tensor) or t.dim() != want:
             raise ValueError(f"ring_flash_attn: with_ulysses({what}): {n} must be a {want}-dimensional tensor")
     if names == ("q", "k", "v"):                     # (q, k, v travel in one buffer of one width)
-        from ._api import checked_vdim
-
         checked_vdim(*tensors, a.get("dropout_p"), a.get("alibi_slopes"), f"with_ulysses({what})", served=False)
     S = tensors[0].shape[1]
     if any(t.shape[1] != S or t.shape[0] != tensors[0].shape[0] for t in tensors):

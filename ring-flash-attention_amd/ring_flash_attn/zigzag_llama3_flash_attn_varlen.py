@@ -26,8 +26,7 @@ llama3_flash_attn_varlen_func; all heads are processed per call.
 """
 import torch
 
-from ._api import (_check_unsupported, _opaque, apply_sinks, checked_alibi, checked_sinks, checked_softcap, checked_vdim, sink_args, sinks_grad,
-                   softcap_scope, window_ok_for, checked_lse_grad, lse_grad_kw)
+from ._api import _opaque, apply_sinks, call_preamble, sink_args, sinks_grad, softcap_scope, lse_grad_kw
 from ._common import _as_cu, alibi_kw, dlse_kw
 from .backend import get_backend
 from .llama3_flash_attn_varlen import llama3_flash_attn_prepare_cu_seqlens
@@ -127,22 +126,24 @@ def zigzag_llama3_flash_attn_varlen_backward(process_group, dout, q, k, v, out, 
     return dq, be.cast(dk, k.dtype), be.cast(dv, v.dtype)
 
 
+def _one_bias_per_head(slopes):
+    if slopes is not None and slopes.dim() != 1:
+        raise NotImplementedError("zigzag_llama3_flash_attn_varlen_func: alibi_slopes per sequence, (B, H), are not "
+                                  "supported (the two stream slices hold different sequences); pass (H,)")
+
+
 class ZigZagLlama3FlashAttnVarlenFunc(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, cu_seqlens, heads_k_stride, dropout_p, softmax_scale, causal, window_size, alibi_slopes,
                 deterministic, return_softmax, group, sinks=None):
         if softmax_scale is None:
             softmax_scale = q.shape[-1] ** (-0.5)
-        checked_vdim(q, k, v, dropout_p, alibi_slopes, "zigzag_llama3_flash_attn_varlen_func", served=False)   # (the gathers stack K and V)
-        _check_unsupported(dropout_p, window_size, alibi_slopes, windows_ok=True,   # K/V are gathered
-                           alibi_ok=window_ok_for(group) and bool(causal))
-        if alibi_slopes is not None and alibi_slopes.dim() != 1:
-            raise NotImplementedError("zigzag_llama3_flash_attn_varlen_func: alibi_slopes per sequence, (B, H), are not "
-                                      "supported (the two stream slices hold different sequences); pass (H,)")
-        alibi_slopes = checked_alibi(alibi_slopes, q, 0, "zigzag_llama3_flash_attn_varlen_func")
-        ctx.softcap = checked_softcap(dropout_p, alibi_slopes, q, "zigzag_llama3_flash_attn_varlen_func", window_size, causal)
-        ctx.lse_grad = checked_lse_grad(ctx, "zigzag_llama3_flash_attn_varlen_func")
-        sinks = checked_sinks(sinks, q, "zigzag_llama3_flash_attn_varlen_func")
+        # no value head dim of its own: the gathers stack K and V.  K/V are gathered: windows on any group (dropout is refused
+        # below); a bias on a single-rank group only, and there for causal calls only
+        alibi_slopes, sinks = call_preamble(
+            ctx, "zigzag_llama3_flash_attn_varlen_func", q, k, v, sinks, dropout_p, window_size, alibi_slopes, causal, group, 0,
+            vdim=False, window_ring=True, dropout_ring=True, alibi_ring=False, alibi_single=bool(causal),
+            before_alibi=_one_bias_per_head)
         if dropout_p and dropout_p > 0:
             raise NotImplementedError("zigzag_llama3_flash_attn_varlen_func: dropout is not supported")
         if q.shape[0] % 2 != 0 or k.shape[0] != q.shape[0] or v.shape[0] != q.shape[0]:

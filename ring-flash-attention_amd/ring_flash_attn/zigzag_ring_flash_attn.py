@@ -51,7 +51,7 @@ import torch
 from . import _C, config
 from .backend import get_backend
 from .utils import Agreement, AllGatherComm, RingComm, SourceArrivals, all_to_all_async, reduce_scatter_async, single_rank
-from ._api import make_autograd_function, make_dense_api, _grad_buffers
+from ._api import ScheduleSpec, make_autograd_function, make_api, _grad_buffers
 from ._common import alibi_kw, block_mask_kw, dlse_kw, out_shape, row_ranges_kw, packed_pair, dropout_arg, global_window, require_dropout_positions, require_mask_shift, zigzag_map
 
 
@@ -639,13 +639,11 @@ def zigzag_ring_flash_attn_backward(
 
 zigzag_ring_flash_attn_forward.keeps_for_backward = True
 
-ZigZagRingFlashAttnFunc = make_autograd_function(
-    "ZigZagRingFlashAttnFunc", zigzag_ring_flash_attn_forward, zigzag_ring_flash_attn_backward, 0, window_ring=True,
-    dropout_ring=True, alibi_ring=True, vdim=True)
+SPEC = ScheduleSpec("ZigZagRingFlashAttnFunc", "zigzag_ring_flash_attn", window_ring=True, dropout_ring=True, alibi_ring=True,
+                    vdim=True, zigzag=True, must_be_causal=True, packed_travel=True)
+ZigZagRingFlashAttnFunc = make_autograd_function(SPEC, zigzag_ring_flash_attn_forward, zigzag_ring_flash_attn_backward)
 (
     zigzag_ring_flash_attn_func,
     zigzag_ring_flash_attn_kvpacked_func,
     zigzag_ring_flash_attn_qkvpacked_func,
-) = make_dense_api(ZigZagRingFlashAttnFunc, "zigzag_ring_flash_attn", zigzag_ring_flash_attn_forward,
-                   zigzag_ring_flash_attn_backward, packed_travel=True, window_ring=True, dropout_ring=True,
-                   alibi_ring=True)
+) = make_api(SPEC, ZigZagRingFlashAttnFunc, zigzag_ring_flash_attn_forward, zigzag_ring_flash_attn_backward)

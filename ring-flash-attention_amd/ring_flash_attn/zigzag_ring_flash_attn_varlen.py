@@ -34,7 +34,7 @@ from . import _C, config
 from .backend import get_backend, HALF_FRONT, HALF_BACK
 from .utils import AllGatherComm, RingComm, all_to_all_async, reduce_scatter_async, single_rank
 from ._common import alibi_kw, dlse_kw, out_shape, dropout_arg, global_window, require_mask_shift_lens
-from ._api import make_autograd_function, make_varlen_api, _grad_buffers
+from ._api import ScheduleSpec, make_autograd_function, make_api, _grad_buffers
 
 
 def varlen_exchange_mode() -> str:
@@ -376,12 +376,11 @@ def zigzag_ring_flash_attn_varlen_backward(
     return be.cast(dq, q.dtype), be.cast(next_dk, q.dtype), be.cast(next_dv, q.dtype)
 
 
-ZigZagRingFlashAttnVarlenFunc = make_autograd_function(
-    "ZigZagRingFlashAttnVarlenFunc", zigzag_ring_flash_attn_varlen_forward,
-    zigzag_ring_flash_attn_varlen_backward, 2, window_ring=True, vdim=True)
+SPEC = ScheduleSpec("ZigZagRingFlashAttnVarlenFunc", "zigzag_ring_flash_attn_varlen", n_lead=2, pack_dim=1, window_ring=True, vdim=True,
+                    zigzag=True, must_be_causal=True)
+ZigZagRingFlashAttnVarlenFunc = make_autograd_function(SPEC, zigzag_ring_flash_attn_varlen_forward, zigzag_ring_flash_attn_varlen_backward)
 (
     zigzag_ring_flash_attn_varlen_func,
     zigzag_ring_flash_attn_varlen_kvpacked_func,
     zigzag_ring_flash_attn_varlen_qkvpacked_func,
-) = make_varlen_api(ZigZagRingFlashAttnVarlenFunc, "zigzag_ring_flash_attn_varlen", zigzag_ring_flash_attn_varlen_forward, zigzag_ring_flash_attn_varlen_backward,
-                    window_ring=True)
+) = make_api(SPEC, ZigZagRingFlashAttnVarlenFunc, zigzag_ring_flash_attn_varlen_forward, zigzag_ring_flash_attn_varlen_backward)

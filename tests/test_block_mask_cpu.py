@@ -353,7 +353,8 @@ def test_checkpointing_reruns_with_the_mask(built, single_rank_group):
             ins = [t.clone().requires_grad_(True) for t in (q, k, v)]
             rec.seen = {"fwd": [], "bwd": []}
             out = checkpoint(attn, *ins, use_reentrant=False, causal=True) if ckpt else attn(*ins, causal=True)
-            assert R._api._block_mask.get() is None                   # nothing stays bound behind the call
+            assert R._api._row_ranges.get() is None and R._api._block_mask.get() is None    # nothing stays bound behind the call
+            assert R._api._sinks.get() is None and R._api._lse_grad.get() is False
             out.backward(do)
             assert len(rec.seen["fwd"]) == (2 if ckpt else 1) and len(rec.seen["bwd"]) == 1
             assert all(n == (0, (2, 4, 2, 2), 0, (2, 256)) for n in rec.seen["fwd"] + rec.seen["bwd"])
