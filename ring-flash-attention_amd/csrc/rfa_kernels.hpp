@@ -6,6 +6,7 @@
 #include "rfa_seqhead_index.h"
 #include "rfa_rotary_index.h"
 #include "rfa_qknorm_index.h"
+#include "rfa_qktoken_index.h"
 #include "rfa_maxlogit_band.h"
 #include "rfa_rowrange.h"
 #include "rfa_blockmask.h"
@@ -316,6 +317,34 @@ struct QkNormParams {
 };
 int launch_qknorm_fwd(const QkNormParams& p, int dtype, bool table_f32, bool weight_f32, hipStream_t stream);
 int launch_qknorm_bwd(const QkNormParams& p, int dtype, bool table_f32, bool weight_f32, hipStream_t stream);
+
+// token-wide QK RMSNorm (one rstd per token over all H * D columns; OLMo-2) fused with the rotary embedding (rfa_qktoken.hip;
+// index arithmetic: rfa_qktoken_index.h): up to two tensors (q, k) per launch, one team of 1, 2 or 4 waves per token row.
+// Positions as in RotaryParams; R == 0 is the norm alone.  weight[k]: (H_k * D,).  Backward: dweight[k] != NULL asks for that
+// tensor's fp32 (H_k * D,) weight gradient (workspace: tensor 0's nparts[0] partials, then tensor 1's; then the fold launch).
+struct QkTokenParams {
+  QkTokenGeom g;
+  QkTokenTensor t[2];
+  const void* x[2];
+  void* out[2];             // forward: y; backward: dx
+  const void* dout[2];      // backward only
+  const void* weight[2];
+  float* dweight[2];
+  float* workspace;
+  uint32_t nparts[2], walk[2]; // backward, per tensor (a function of ITS rows and width alone)
+  float eps, weight_offset;
+  const void *cos, *sin;
+  int64_t P;
+  const int32_t* positions;
+  int64_t pos_batch;
+  int64_t pos_off, pos_off2;
+  uint32_t pos_stride;
+  int32_t pos_split;
+  int32_t table_f32, weight_f32;
+  int ntensors;
+};
+int launch_qktoken_fwd(const QkTokenParams& p, int dtype, hipStream_t stream);
+int launch_qktoken_bwd(const QkTokenParams& p, int dtype, hipStream_t stream);
 
 // per-head max attention logit (rfa_maxlogit.hip; tile arithmetic: rfa_maxlogit_band.h): the forward's S phase alone.
 // Workgroup (batch b, query block qb, head h) stores the max of its UNSCALED visible scores to

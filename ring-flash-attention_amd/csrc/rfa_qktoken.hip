@@ -1,0 +1,480 @@
+// rfa_qktoken.hip — RMSNorm of q and k over ALL heads of a token, fused with the rotary embedding at GLOBAL positions (gfx950;
+// include/rfa.h: rfa_qk_token_norm_rotary_fwd / _bwd; ring_flash_attn.apply_qk_token_norm_rotary).  OLMo-2 / OLMo-3 compute
+//     q = rope(rmsnorm_{H D}(q_proj(x)) * w_q),   k = rope(rmsnorm_{Hk D}(k_proj(x)) * w_k)
+// with ONE rstd per token over the whole projection width N = H D (up to 16384) and a weight of N entries.  rfa_qknorm.hip keeps
+// a (row, head) inside 32 lanes with one chunk per lane; here a row is up to 2048 chunks, its statistic crosses heads and —
+// with 2 or 4 waves — waves, and the halves pairing's partner is in general another wave's.  The design:
+//
+// OWNERSHIP (rfa_qktoken_index.h).  A token row belongs to a TEAM of 64, 128 or 256 lanes — 1, 2 or 4 waves of one 256-thread
+//   workgroup, chosen from N alone — so a workgroup holds 4, 2 or 1 rows at a time.  Team lane l owns the 16-byte chunks
+//   l + j * team, j < K (K <= 8): a wave's loads and stores cover consecutive 1 KiB runs.  x (backward: x and dO) stays in
+//   registers in the io dtype (4 VGPRs a chunk) and is widened where it is used: x is read from HBM once per direction, every
+//   output written once, all offsets 64 bits wide.  q and k share one launch (blockIdx.y), each with ITS team; K is a template
+//   parameter of the launch (2, 4, 8: the larger tensor's need) that only bounds the unrolled chunk loop.
+// LDS, one barrier per row sum:
+//   stage  halves pairing only: the row's chunks in the io dtype as they were loaded (forward x, backward dO), 16 B x chunks x
+//          rows in flight <= 32 KiB.  The partner chunk R/16 further on / back is read from here and taken through the owner's
+//          own expression (forward: (x rstd) a with the partner's weight), so both lanes of a pair hold the same bits.
+//          Interleaved pairs are in-lane; the norm alone stages nothing.
+//   tab    the token's cos / sin row, widened to fp32, fetched from memory ONCE for all heads of the row (R/2 values each)
+//   red    one partial row sum per wave
+//   The staging, the tables and the first row sum's partials are all written in front of the SAME barrier.
+// SUMMATION ORDERS (the tests' tolerances are derived from these):
+//   row sums (sum x^2; backward also sum (g a) xh): in a lane j = 0 .. K-1, e = 0 .. 7 as ONE chain of fmas starting from 0 (a
+//     chunk that does not exist adds nothing), then the xor butterfly over the wave with masks 32, 16, .. 1, then the team's
+//     waves' sums from LDS added in wave order starting from the first: 8 K + 6 + (team/64 - 1) <= 73 roundings.  Every lane of
+//     the team ends with the same bits; they depend on (N, the row's values) alone.
+//   rstd = rsqrt(ss / N + eps) (one division, one addition, the hardware's rsqrt) by ONE device function in both directions.
+//   forward: y = (x rstd) a, a = weight_offset + w, then rot() of rfa_rotary_math.hpp on the rotated columns; one rounding.
+//   backward: g = rot() with s -> -s of dO (fp32, not rounded), xh = x rstd, m = (sum (g a) xh) / N,
+//     dx = rstd (g a - xh m) with the subtraction as ONE fma; one rounding.
+//   dw (per tensor): a lane adds g xh of its own columns (fma) over the `walk` rows its team visits, row (it * nparts + p) * slots
+//     + slot for it = 0, 1, ..; the workgroup adds its `slots` teams in slot order through LDS and stores ONE fp32 (N,) partial;
+//     the fold kernel adds a column's nparts partials in 8 runs of ceil(nparts/8) consecutive ones, then the 8 sums in order.
+//     Longest chain: walk + slots + ceil(nparts/8) + 8 additions.  No atomics; nparts = min(ceil(rows/slots), 512) is a
+//     function of the tensor's shape alone, so its weight gradient's bits do not depend on the tensor that rides along.
+// grid: forward x = max over tensors of ceil(rows/slots), y = tensor; backward x = max over tensors of nparts, y = tensor.
+#include "rfa_common.hpp"
+#include "rfa_kernels.hpp"
+#include "rfa_rotary_math.hpp"
+
+namespace rfa {
+namespace {
+
+enum { kTokNone = 0, kTokHalves = 1, kTokInterleaved = 2 };
+constexpr uint32_t kStageBytes = 32768;       // 16 B x (4 rows x 128 | 2 rows x 512 | 1 row x 2048) chunks
+constexpr uint32_t kTabFloats = 128;          // R / 2 <= 128
+constexpr uint32_t kMaxSlots = 4;
+
+typedef float f32x8 __attribute__((ext_vector_type(8)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+template <typename T>
+__device__ __forceinline__ void widen(const vec8<T>& v, float (&f)[8]) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) f[e] = (float)v[e];
+}
+
+template <typename T>
+__device__ __forceinline__ void store8(T* p, const float (&f)[8]) {
+  f32x8 v;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) v[e] = f[e];
+  *(vec8<T>*)p = __builtin_convertvector(v, vec8<T>);
+}
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int m = 32; m; m >>= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
+
+// the team's sum of the per-wave sums in `red` (written in front of the last barrier), in wave order
+__device__ __forceinline__ float team_total(const float* red, uint32_t team, uint32_t wave) {
+  const uint32_t nw = team >> 6, fw = wave & ~(nw - 1);
+  float total = red[fw];
+  for (uint32_t j = 1; j < nw; ++j) total += red[fw + j];
+  return total;
+}
+
+__device__ __forceinline__ float row_rstd(float ss, uint32_t N, float eps) { return rsqrtf(ss / (float)N + eps); }
+
+// a_c = weight_offset + w_c of the 8 columns of chunk c
+template <typename T>
+__device__ __forceinline__ void load_scale(const QkTokenParams& p, const void* weight, uint32_t c, float (&a)[8]) {
+  if (p.weight_f32) {
+    float lo[4], hi[4];
+    load_tab<float, 4>((const float*)weight + 8 * (size_t)c, lo);
+    load_tab<float, 4>((const float*)weight + 8 * (size_t)c + 4, hi);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      a[e] = p.weight_offset + lo[e];
+      a[4 + e] = p.weight_offset + hi[e];
+    }
+  } else {
+    float w[8];
+    load_tab<T, 8>((const T*)weight + 8 * (size_t)c, w);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) a[e] = p.weight_offset + w[e];
+  }
+}
+
+// a wave-uniform 64-bit value held in vector registers.  The backward keeps more uniform values live across its walk than there
+// are scalar registers; strides and position offsets only ever enter per-lane (vector) arithmetic, so they live there
+__device__ __forceinline__ int64_t in_vgpr(int64_t v) {
+  asm volatile("" : "+v"(v));
+  return v;
+}
+
+__device__ __forceinline__ uint32_t in_vgpr(uint32_t v) {
+  asm volatile("" : "+v"(v));
+  return v;
+}
+
+// the row's cos / sin values into tab[0 / 1][slot][0 .. R/2), widened; by the row's own team, once for all its heads
+template <typename T>
+__device__ __forceinline__ void stage_tables(const QkTokenParams& p, float (*tab)[kMaxSlots][kTabFloats], uint32_t slot, uint32_t tl,
+                                             uint32_t team, uint32_t row, int64_t pos_off, int64_t pos_off2, int64_t pos_batch,
+                                             int64_t P) {
+  const uint32_t b = row / p.g.S, i = row % p.g.S;
+  int64_t pos = p.positions ? pos_off + (int64_t)p.positions[(int64_t)b * pos_batch + i]
+                            : rotary_map_pos(pos_off, p.pos_stride, p.pos_split, pos_off2, i);
+  pos = rotary_clamp_pos(pos, P);
+  const uint32_t half = p.g.R / 2;
+  const int64_t at = pos * (int64_t)half;
+  for (uint32_t j = tl; j < half; j += team) {
+    if (p.table_f32) {
+      tab[0][slot][j] = ((const float*)p.cos)[at + j];
+      tab[1][slot][j] = ((const float*)p.sin)[at + j];
+    } else {
+      tab[0][slot][j] = (float)((const T*)p.cos)[at + j];
+      tab[1][slot][j] = (float)((const T*)p.sin)[at + j];
+    }
+  }
+}
+
+// the chunk's 8 columns after the rotation (CONJ: the inverse one); v the chunk's values, pv its partner's (halves only)
+template <int MODE, bool CONJ>
+__device__ __forceinline__ void rotate8(const float (&v)[8], const float (&pv)[8], float (&o)[8], int kind, const float* c,
+                                        const float* s) {
+  if constexpr (MODE == kTokHalves) {
+    const bool lo = kind == kQkTokenLo;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      float o1, o2;
+      rot(lo ? v[e] : pv[e], lo ? pv[e] : v[e], c[e], CONJ ? -s[e] : s[e], o1, o2);
+      o[e] = lo ? o1 : o2;
+    }
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) rot(v[2 * e], v[2 * e + 1], c[e], CONJ ? -s[e] : s[e], o[2 * e], o[2 * e + 1]);
+  }
+}
+
+// lane tl's j-th chunk, tl + j * team, exists: a uniform test for all j but one (every lane has its first chunks / team ones)
+__device__ __forceinline__ bool has_chunk(uint32_t j, uint32_t tl, uint32_t jfull, uint32_t tail) {
+  return j < jfull || (j == jfull && tl < tail);
+}
+
+// (head << 16 | first column) and (kind << 16 | table column) of the lane's chunks: functions of the chunk alone
+template <int K>
+__device__ __forceinline__ void lane_roles(const QkTokenGeom& g, const QkTokenTensor& t, uint32_t tl, uint32_t (&hc)[K],
+                                           uint32_t (&kt)[K]) {
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    const uint32_t c = tl + j * t.team;
+    QkTokenRole r{};
+    r.kind = kQkTokenPass;
+    if (c < t.chunks) qktoken_role(g, c, &r);
+    hc[j] = r.head << 16 | r.col;
+    kt[j] = (uint32_t)r.kind << 16 | r.tcol;
+  }
+}
+
+template <typename T, int MODE, int K>
+__global__ __launch_bounds__(256) void qktoken_fwd_kernel(const QkTokenParams p) {
+  __shared__ __attribute__((aligned(16))) unsigned char stage_raw[MODE == kTokHalves ? kStageBytes : 16];
+  __shared__ float tab[2][kMaxSlots][kTabFloats];
+  __shared__ float red[4];
+  const int k = blockIdx.y;
+  const QkTokenTensor t = p.t[k];
+  const uint32_t team = t.team, slots = qktoken_slots(team);
+  if ((uint64_t)blockIdx.x * slots >= t.rows) return;            // (the whole workgroup: the other tensor needs more of them)
+  const uint32_t slot = threadIdx.x / team, tl = threadIdx.x % team, wave = threadIdx.x >> 6;
+  const uint32_t jfull = t.chunks / team, tail = t.chunks % team;
+  const T* xp = (const T*)p.x[k];
+  T* outp = (T*)p.out[k];
+  const void* wp = p.weight[k];
+  const uint64_t row64 = qktoken_row(0, 0, blockIdx.x, slot, team);
+  const bool rlive = row64 < t.rows;
+  const uint32_t row = rlive ? (uint32_t)row64 : 0u;
+  vec8<T>* stage = (vec8<T>*)stage_raw;
+  uint32_t hc[K], kt[K];
+  lane_roles<K>(p.g, t, tl, hc, kt);
+  vec8<T> xv[K];
+  float ss = 0.f;
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    const uint32_t c = tl + j * team;
+    const bool own = rlive && has_chunk(j, tl, jfull, tail);
+    xv[j] = zero8<T>();
+    if (own) {
+      xv[j] = *(const vec8<T>*)(xp + qktoken_offset(p.g, row, hc[j] >> 16, hc[j] & 0xffffu, t.xb, t.xr, t.xh));
+      if constexpr (MODE == kTokHalves) stage[slot * t.chunks + c] = xv[j];
+    }
+    float x[8];
+    widen<T>(xv[j], x);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) ss = __builtin_fmaf(x[e], x[e], ss);
+  }
+  if (MODE != kTokNone && rlive) stage_tables<T>(p, tab, slot, tl, team, row, p.pos_off, p.pos_off2, p.pos_batch, p.P);
+  ss = wave_sum(ss);
+  if ((threadIdx.x & 63u) == 0) red[wave] = ss;
+  __syncthreads();
+  const float rstd = row_rstd(team_total(red, team, wave), t.N, p.eps);
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    const uint32_t c = tl + j * team;
+    if (!(rlive && has_chunk(j, tl, jfull, tail))) continue;
+    const int kind = (int)(kt[j] >> 16);
+    const uint32_t tcol = kt[j] & 0xffffu;
+    float x[8], a[8], y[8], o[8];
+    widen<T>(xv[j], x);
+    load_scale<T>(p, wp, c, a);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) y[e] = (x[e] * rstd) * a[e];
+    if (MODE != kTokNone && kind != kQkTokenPass) {
+      float py[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      if constexpr (MODE == kTokHalves) {
+        const uint32_t pc = kind == kQkTokenLo ? c + p.g.R / 16 : c - p.g.R / 16;
+        float px[8], pa[8];
+        widen<T>(stage[slot * t.chunks + pc], px);
+        load_scale<T>(p, wp, pc, pa);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) py[e] = (px[e] * rstd) * pa[e];
+      }
+      rotate8<MODE == kTokNone ? kTokInterleaved : MODE, false>(y, py, o, kind, &tab[0][slot][tcol], &tab[1][slot][tcol]);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o[e] = y[e];
+    }
+    store8<T>(outp + qktoken_offset(p.g, row, hc[j] >> 16, hc[j] & 0xffffu, t.ob, t.orow, t.oh), o);
+  }
+}
+
+template <typename T, int MODE, int K>
+__global__ __launch_bounds__(256) void qktoken_bwd_kernel(const QkTokenParams p) {
+  __shared__ __attribute__((aligned(16))) unsigned char stage_raw[kStageBytes];   // dO rows (halves); at the end the teams' dw
+  __shared__ float tab[2][kMaxSlots][kTabFloats];
+  __shared__ float red[2][4];
+  const int k = blockIdx.y;
+  QkTokenTensor t = p.t[k];
+  t.xb = in_vgpr(t.xb), t.xr = in_vgpr(t.xr), t.xh = in_vgpr(t.xh);
+  t.ob = in_vgpr(t.ob), t.orow = in_vgpr(t.orow), t.oh = in_vgpr(t.oh);
+  t.gb = in_vgpr(t.gb), t.gr = in_vgpr(t.gr), t.gh = in_vgpr(t.gh);
+  const int64_t pos_off = in_vgpr(p.pos_off), pos_off2 = in_vgpr(p.pos_off2), pos_batch = in_vgpr(p.pos_batch), tabP = in_vgpr(p.P);
+  const uint32_t team = t.team, slots = qktoken_slots(team);
+  const uint32_t nparts = p.nparts[k], walk = p.walk[k];
+  if (blockIdx.x >= nparts) return;                              // (the whole workgroup: the other tensor has more partials)
+  const uint32_t slot = threadIdx.x / team, tl = threadIdx.x % team, wave = threadIdx.x >> 6;
+  const uint32_t teamv = in_vgpr(team);                          // (j * team: K more scalars otherwise)
+  const uint32_t jfull = t.chunks / team, tail = in_vgpr(t.chunks % team);
+  const T* xp = (const T*)in_vgpr((int64_t)p.x[k]);               // (bases of per-lane addresses: see in_vgpr)
+  T* outp = (T*)in_vgpr((int64_t)p.out[k]);
+  const void* wp = (const void*)in_vgpr((int64_t)p.weight[k]);
+  const uint32_t wantv = p.dweight[k] != nullptr ? 1u : 0u;      // (tested through in_vgpr: its lane mask is formed at each use)
+  const T* dp = (const T*)in_vgpr((int64_t)p.dout[k]);
+  vec8<T>* stage = (vec8<T>*)stage_raw;
+  uint32_t hc[K], kt[K];
+  lane_roles<K>(p.g, t, tl, hc, kt);
+  float acc[K][8];
+#pragma unroll
+  for (int j = 0; j < K; ++j)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[j][e] = 0.f;
+  for (uint32_t it = 0; it < walk; ++it) {
+    if (qktoken_row(it, nparts, blockIdx.x, 0, team) >= t.rows) break;   // (the whole workgroup, and every later step)
+    const uint64_t row64 = qktoken_row(it, nparts, blockIdx.x, slot, team);
+    const bool rlive = row64 < t.rows;
+    const uint32_t row = rlive ? (uint32_t)row64 : 0u;
+    const bool want_dw = in_vgpr(wantv) != 0;
+    vec8<T> xv[K], dv[K];
+    float ss = 0.f;
+    if constexpr (MODE != kTokNone) {
+      // (the roles do not change from step to step; made opaque here so that the lane masks of the K chunks' kinds are formed
+      //  where they are used, not all kept in scalar registers across the walk — which spilled them)
+#pragma unroll
+      for (int j = 0; j < K; ++j) asm volatile("" : "+v"(kt[j]));
+    }
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+      const uint32_t c = tl + j * teamv;
+      const bool own = rlive && has_chunk(j, tl, jfull, tail);
+      xv[j] = zero8<T>();
+      dv[j] = zero8<T>();
+      if (own) {
+        const uint32_t head = hc[j] >> 16, col = hc[j] & 0xffffu;
+        xv[j] = *(const vec8<T>*)(xp + qktoken_offset(p.g, row, head, col, t.xb, t.xr, t.xh));
+        dv[j] = *(const vec8<T>*)(dp + qktoken_offset(p.g, row, head, col, t.gb, t.gr, t.gh));
+        if constexpr (MODE == kTokHalves) stage[slot * t.chunks + c] = dv[j];
+      }
+      float x[8];
+      widen<T>(xv[j], x);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) ss = __builtin_fmaf(x[e], x[e], ss);
+    }
+    if (MODE != kTokNone && rlive) stage_tables<T>(p, tab, slot, tl, team, row, pos_off, pos_off2, pos_batch, tabP);
+    ss = wave_sum(ss);
+    if ((threadIdx.x & 63u) == 0) red[0][wave] = ss;
+    __syncthreads();
+    // (a slot past the tensor's end holds zeros: with eps == 0 its rsqrt(0) is inf — such a row counts with rstd 0 and its
+    //  lanes skip the arithmetic, whose tables were not staged)
+    const float rs = row_rstd(team_total(red[0], team, wave), t.N, p.eps);
+    const float rstd = rlive ? rs : 0.f;
+    float ga[K][8];
+    float ms = 0.f;
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+      const uint32_t c = tl + j * teamv;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) ga[j][e] = 0.f;
+      if (!(rlive && has_chunk(j, tl, jfull, tail))) continue;
+      const int kind = (int)(kt[j] >> 16);
+      const uint32_t tcol = kt[j] & 0xffffu;
+      float x[8], d[8], a[8], g[8];
+      widen<T>(xv[j], x);
+      widen<T>(dv[j], d);
+      load_scale<T>(p, wp, c, a);
+      if (MODE != kTokNone && kind != kQkTokenPass) {
+        float pd[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if constexpr (MODE == kTokHalves) {
+          const uint32_t pc = kind == kQkTokenLo ? c + p.g.R / 16 : c - p.g.R / 16;
+          widen<T>(stage[slot * t.chunks + pc], pd);
+        }
+        rotate8<MODE == kTokNone ? kTokInterleaved : MODE, true>(d, pd, g, kind, &tab[0][slot][tcol], &tab[1][slot][tcol]);
+      } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) g[e] = d[e];
+      }
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float xh = x[e] * rstd;
+        ga[j][e] = g[e] * a[e];
+        ms = __builtin_fmaf(ga[j][e], xh, ms);
+        if (want_dw) acc[j][e] = __builtin_fmaf(g[e], xh, acc[j][e]);
+      }
+    }
+    ms = wave_sum(ms);
+    if ((threadIdx.x & 63u) == 0) red[1][wave] = ms;
+    __syncthreads();
+    const float m = team_total(red[1], team, wave) / (float)t.N;
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+      const uint32_t c = tl + j * teamv;
+      if (!(rlive && has_chunk(j, tl, jfull, tail))) continue;
+      float x[8], dx[8];
+      widen<T>(xv[j], x);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) dx[e] = rstd * __builtin_fmaf(-(x[e] * rstd), m, ga[j][e]);
+      store8<T>(outp + qktoken_offset(p.g, row, hc[j] >> 16, hc[j] & 0xffffu, t.ob, t.orow, t.oh), dx);
+    }
+  }
+  if (in_vgpr(wantv) == 0) return;                                          // (uniform over the workgroup)
+  // the teams of the workgroup, in slot order: slots 1 .. hand theirs over through LDS ((slots - 1) N floats <= 16 KiB)
+  float* hand = (float*)stage_raw;
+  if (slots > 1) {
+    __syncthreads();                                             // (the last step's reads of `stage` are done)
+    if (slot > 0) {
+#pragma unroll
+      for (int j = 0; j < K; ++j) {
+        const uint32_t c = tl + j * teamv;
+        if (!has_chunk(j, tl, jfull, tail)) continue;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) hand[(size_t)(slot - 1) * t.N + 8 * c + e] = acc[j][e];
+      }
+    }
+    __syncthreads();
+  }
+  if (slot > 0) return;
+  float* part = p.workspace + (k ? (size_t)p.nparts[0] * p.t[0].N : (size_t)0) + (size_t)blockIdx.x * t.N;
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    const uint32_t c = tl + j * teamv;
+    if (!has_chunk(j, tl, jfull, tail)) continue;
+    for (uint32_t s = 1; s < slots; ++s)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) acc[j][e] += hand[(size_t)(s - 1) * t.N + 8 * c + e];
+    f32x4 lo, hi;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      lo[e] = acc[j][e];
+      hi[e] = acc[j][4 + e];
+    }
+    *(f32x4*)(part + 8 * c) = lo;
+    *(f32x4*)(part + 8 * c + 4) = hi;
+  }
+}
+
+// dweight[k][c] = the nparts partials of column c: 8 runs of consecutive partials, then the runs in order
+__global__ __launch_bounds__(256) void qktoken_fold_kernel(const QkTokenParams p) {
+  __shared__ float runs[kQkTokenFoldSlices][kQkTokenFoldCols];
+  const int k = blockIdx.y;
+  if (!p.dweight[k]) return;
+  const uint32_t N = p.t[k].N, lane = threadIdx.x % kQkTokenFoldCols, j = threadIdx.x / kQkTokenFoldCols;
+  const uint32_t c = blockIdx.x * kQkTokenFoldCols + lane;
+  if (blockIdx.x * kQkTokenFoldCols >= N) return;                // (the whole workgroup: the other tensor is wider)
+  const uint32_t nparts = p.nparts[k], len = qktoken_fold_len(nparts);
+  const uint32_t lo = j * len < nparts ? j * len : nparts, hi = lo + len < nparts ? lo + len : nparts;
+  const float* base = p.workspace + (k ? (size_t)p.nparts[0] * p.t[0].N : (size_t)0);
+  float sum = 0.f;
+  if (c < N)
+    for (uint32_t q = lo; q < hi; ++q) sum += base[(size_t)q * N + c];
+  runs[j][lane] = sum;
+  __syncthreads();
+  if (j == 0 && c < N) {
+    float total = 0.f;
+    for (int r = 0; r < kQkTokenFoldSlices; ++r) total += runs[r][lane];
+    p.dweight[k][c] = total;
+  }
+}
+
+template <typename T, int MODE, int K>
+void launch_k(const QkTokenParams& p, bool bwd, dim3 grid, hipStream_t stream) {
+  const dim3 block(kQkTokenThreads);
+  if (bwd) hipLaunchKernelGGL((qktoken_bwd_kernel<T, MODE, K>), grid, block, 0, stream, p);
+  else hipLaunchKernelGGL((qktoken_fwd_kernel<T, MODE, K>), grid, block, 0, stream, p);
+}
+
+template <typename T, int MODE>
+void launch_m(const QkTokenParams& p, bool bwd, dim3 grid, hipStream_t stream) {
+  uint32_t need = 0;
+  for (int i = 0; i < p.ntensors; ++i) {
+    const uint32_t per = qktoken_per_lane(p.t[i].N);
+    need = per > need ? per : need;
+  }
+  if (need <= 2) launch_k<T, MODE, 2>(p, bwd, grid, stream);
+  else if (need <= 4) launch_k<T, MODE, 4>(p, bwd, grid, stream);
+  else launch_k<T, MODE, 8>(p, bwd, grid, stream);
+}
+
+template <typename T>
+void launch_t(const QkTokenParams& p, bool bwd, dim3 grid, hipStream_t stream) {
+  if (p.g.R == 0) launch_m<T, kTokNone>(p, bwd, grid, stream);
+  else if (p.g.interleaved) launch_m<T, kTokInterleaved>(p, bwd, grid, stream);
+  else launch_m<T, kTokHalves>(p, bwd, grid, stream);
+}
+
+}  // namespace
+
+int launch_qktoken_fwd(const QkTokenParams& p, int dtype, hipStream_t stream) {
+  uint32_t blocks = 0;
+  for (int i = 0; i < p.ntensors; ++i) {
+    const uint32_t n = qktoken_blocks(p.t[i].rows, p.t[i].team);
+    blocks = n > blocks ? n : blocks;
+  }
+  if (blocks == 0) return 0;
+  const dim3 grid(blocks, (unsigned)p.ntensors);
+  if (dtype == 0) launch_t<bf16_t>(p, false, grid, stream);
+  else launch_t<f16_t>(p, false, grid, stream);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_qktoken_bwd(const QkTokenParams& p, int dtype, hipStream_t stream) {
+  const uint32_t blocks = p.ntensors > 1 && p.nparts[1] > p.nparts[0] ? p.nparts[1] : p.nparts[0];
+  if (blocks == 0) return 0;
+  const dim3 grid(blocks, (unsigned)p.ntensors);
+  if (dtype == 0) launch_t<bf16_t>(p, true, grid, stream);
+  else launch_t<f16_t>(p, true, grid, stream);
+  if (hipGetLastError() != hipSuccess) return -1;
+  uint32_t widest = 0;
+  for (int i = 0; i < p.ntensors; ++i)
+    if (p.dweight[i]) widest = p.t[i].N > widest ? p.t[i].N : widest;
+  if (widest) {
+    const dim3 fgrid((widest + kQkTokenFoldCols - 1) / kQkTokenFoldCols, (unsigned)p.ntensors);
+    hipLaunchKernelGGL(qktoken_fold_kernel, fgrid, dim3(kQkTokenThreads), 0, stream, p);
+    if (hipGetLastError() != hipSuccess) return -1;
+  }
+  return 0;
+}
+
+}  // namespace rfa

@@ -289,6 +289,34 @@ class QkNormRotaryBwdArgs(C.Structure):
             self.struct_bytes = C.sizeof(QkNormRotaryBwdArgs)
 
 
+QK_TOKEN_NORM_MAX_WIDTH = 16384   # RFA_QK_TOKEN_NORM_MAX_WIDTH: H * D of one tensor of the token-wide norm
+
+
+class QkTokenNormRotaryArgs(C.Structure):
+    """rfa_qk_token_norm_rotary_args: RMSNorm over all heads of a token + rotary of up to two tensors, forward (the per-head
+    struct's fields; weight[k] is (H_k * D,)); struct_bytes is filled in here"""
+    _fields_ = list(_QK_NORM_HEAD)
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if not self.struct_bytes:
+            self.struct_bytes = C.sizeof(QkTokenNormRotaryArgs)
+
+
+class QkTokenNormRotaryBwdArgs(C.Structure):
+    """rfa_qk_token_norm_rotary_bwd_args: the forward's fields, then the gradients, dweight and the workspace"""
+    _fields_ = list(_QK_NORM_HEAD) + [
+        ("g", QkNormGrad * 2),
+        ("dweight", C.c_void_p * 2),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if not self.struct_bytes:
+            self.struct_bytes = C.sizeof(QkTokenNormRotaryBwdArgs)
+
+
 class MaxLogitArgs(C.Structure):
     """rfa_max_logit_args: the per-head max attention logit of one block call; struct_bytes is filled in here"""
     _fields_ = [
@@ -446,6 +474,9 @@ SYMBOLS = {
     "rfa_qk_norm_rotary_fwd": (C.c_int, [C.POINTER(QkNormRotaryArgs), C.c_void_p]),
     "rfa_qk_norm_rotary_bwd": (C.c_int, [C.POINTER(QkNormRotaryBwdArgs), C.c_void_p]),
     "rfa_qk_norm_rotary_bwd_workspace_bytes": (C.c_int64, [C.POINTER(QkNormRotaryBwdArgs)]),
+    "rfa_qk_token_norm_rotary_fwd": (C.c_int, [C.POINTER(QkTokenNormRotaryArgs), C.c_void_p]),
+    "rfa_qk_token_norm_rotary_bwd": (C.c_int, [C.POINTER(QkTokenNormRotaryBwdArgs), C.c_void_p]),
+    "rfa_qk_token_norm_rotary_bwd_workspace_bytes": (C.c_int64, [C.POINTER(QkTokenNormRotaryBwdArgs)]),
     "rfa_max_logit": (C.c_int, [C.POINTER(MaxLogitArgs), C.c_void_p]),
     "rfa_max_logit_workspace_bytes": (C.c_int64, [C.POINTER(MaxLogitArgs)]),
     "rfa_bwd_preprocess_lse": (C.c_int, [C.POINTER(BwdPreLseArgs), C.c_void_p]),

@@ -86,3 +86,6 @@ from .rotary import apply_rotary, local_positions
 # per-head QK RMSNorm (Qwen3, Gemma-3, OLMo) fused with that rotation: apply_qk_norm_rotary(q, k, w_q, w_k, cos, sin,
 # layout=func, group=group) is one launch per direction, one rounding, and a reproducible weight gradient
 from .qk_norm import apply_qk_norm_rotary
+# the same fused with ONE statistic per token over all heads (OLMo-2 / OLMo-3 normalise the whole projection width):
+# apply_qk_token_norm_rotary(q, k, w_q, w_k, cos, sin, layout=func, group=group), weights of H * D entries
+from .qk_norm import apply_qk_token_norm_rotary

@@ -100,6 +100,7 @@ class HipBackend:
     serves_block_mask = True         # fwd / bwd take `block_mask=(mask_view, k_blk0)` (include/rfa.h: rfa_fwd_bm, rfa_bwd_bm): ring_flash_attn.with_block_mask
     serves_rotary = True             # rotary (include/rfa.h: rfa_rotary): ring_flash_attn.apply_rotary
     serves_qk_norm = True            # qk_norm_rotary_fwd / _bwd (include/rfa.h: rfa_qk_norm_rotary_fwd / _bwd): ring_flash_attn.apply_qk_norm_rotary
+    serves_qk_token_norm = True      # qk_token_norm_rotary_fwd / _bwd (include/rfa.h: rfa_qk_token_norm_rotary_fwd / _bwd): apply_qk_token_norm_rotary
     serves_dropout_positions = True  # `dropout=` takes the position maps (q_map, k_map): what dropout over a dense ring, zigzag or stripe schedule needs
 
     def __init__(self):
@@ -809,6 +810,62 @@ class HipBackend:
             ws = torch.empty(max(need, 16), dtype=torch.uint8, device=xs[0].device)
             a.workspace, a.workspace_bytes = ws.data_ptr(), need
         _C.check(self.lib.rfa_qk_norm_rotary_bwd(C.byref(a), _stream(xs[0])), "rfa_qk_norm_rotary_bwd")
+        if a.B == 0 or a.S == 0:                                   # (nothing was launched: an empty sum)
+            for dw in dweights:
+                if dw is not None:
+                    dw.zero_()
+
+    # ------------------------------------------------------------------ token-wide QK RMSNorm + rotary (apply_qk_token_norm_rotary)
+    def _qk_token_norm_args(self, a, xs, outs, weights, cos, sin, positions, pos_map, interleaved, rot_offset, eps, weight_offset):
+        """the fields rfa_qk_token_norm_rotary_args and _bwd_args share: the per-head call's, with (H * D,) weights (the view
+        handed to _qk_norm_args stands in for the (D,) check there)"""
+        for x, w in zip(xs, weights):
+            if w.numel() != x.shape[-2] * x.shape[-1] or not w.is_contiguous() or w.dim() not in (1, 2) or \
+                    (w.dim() == 2 and tuple(w.shape) != tuple(x.shape[-2:])):
+                raise ValueError("qk_token_norm_rotary: the weights are contiguous (H * D,) or (H, D) tensors of one dtype")
+            if x.shape[-2] * x.shape[-1] > _C.QK_TOKEN_NORM_MAX_WIDTH:
+                raise ValueError(f"qk_token_norm_rotary: H * D is at most {_C.QK_TOKEN_NORM_MAX_WIDTH}")
+        D = xs[0].shape[-1]
+        packed = self._qk_norm_args(a, xs, outs, [w.reshape(-1)[:D] for w in weights], cos, sin, positions, pos_map, interleaved,
+                                    rot_offset, eps, weight_offset)
+        for k, w in enumerate(weights):
+            a.weight[k] = w.data_ptr()
+        return packed
+
+    def qk_token_norm_rotary_fwd(self, xs, outs, weights, cos, sin, *, positions=None, pos_map=None, interleaved=False,
+                                 rot_offset=0, eps=1e-6, weight_offset=0.0):
+        """one launch of the RMSNorm over all heads of a token + rotary (include/rfa.h: rfa_qk_token_norm_rotary_fwd) for one or
+        two tensors that share rows and positions.  xs / outs as in `rotary` (out of place); weights[k]: (H_k * D,) or (H_k, D)
+        contiguous, fp32 or the io dtype; cos = sin = None: the norm alone."""
+        a = _C.QkTokenNormRotaryArgs()
+        self._qk_token_norm_args(a, xs, outs, weights, cos, sin, positions, pos_map, interleaved, rot_offset, eps, weight_offset)
+        _C.check(self.lib.rfa_qk_token_norm_rotary_fwd(C.byref(a), _stream(xs[0])), "rfa_qk_token_norm_rotary_fwd")
+
+    def qk_token_norm_rotary_bwd(self, xs, douts, dxs, weights, dweights, cos, sin, *, positions=None, pos_map=None,
+                                 interleaved=False, rot_offset=0, eps=1e-6, weight_offset=0.0):
+        """the backward (include/rfa.h: rfa_qk_token_norm_rotary_bwd): dxs[k] from xs[k] and douts[k] in one launch; dweights[k]
+        a contiguous fp32 tensor of H_k * D elements that is overwritten with this call's weight gradient, or None.  The
+        workspace is allocated here."""
+        a = _C.QkTokenNormRotaryBwdArgs()
+        packed = self._qk_token_norm_args(a, xs, dxs, weights, cos, sin, positions, pos_map, interleaved, rot_offset, eps,
+                                          weight_offset)
+        self._check_dev(*douts, *[d for d in dweights if d is not None])
+        for k, (g, x, dw) in enumerate(zip(douts, xs, dweights)):
+            if g.dtype != x.dtype or g.shape != x.shape or g.stride(-1) != 1:
+                raise ValueError("qk_token_norm_rotary: a gradient has its tensor's dtype and shape; last (head_dim) stride must be 1")
+            gs = [st if n > 1 else 0 for n, st in zip(g.shape, g.stride())]
+            a.g[k].dout = g.data_ptr()
+            a.g[k].dout_batch, a.g[k].dout_row, a.g[k].dout_head = (0 if packed else gs[0]), gs[-3], gs[-2]
+            if dw is not None:
+                if dw.dtype != torch.float32 or dw.numel() != x.shape[-2] * x.shape[-1] or not dw.is_contiguous():
+                    raise ValueError("qk_token_norm_rotary: dweight is a contiguous fp32 tensor of H * D elements")
+                a.dweight[k] = dw.data_ptr()
+        ws = None
+        if any(d is not None for d in dweights):
+            need = int(self.lib.rfa_qk_token_norm_rotary_bwd_workspace_bytes(C.byref(a)))
+            ws = torch.empty(max(need, 16), dtype=torch.uint8, device=xs[0].device)
+            a.workspace, a.workspace_bytes = ws.data_ptr(), need
+        _C.check(self.lib.rfa_qk_token_norm_rotary_bwd(C.byref(a), _stream(xs[0])), "rfa_qk_token_norm_rotary_bwd")
         if a.B == 0 or a.S == 0:                                   # (nothing was launched: an empty sum)
             for dw in dweights:
                 if dw is not None:
