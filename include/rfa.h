@@ -636,6 +636,50 @@ typedef struct {
 } rfa_rotary_args;
 int rfa_rotary(const rfa_rotary_args *args, void *stream);
 
+/* Rotary position embedding with the angles formed in the kernel, one to four position axes per row (M-RoPE)
+ * (ring_flash_attn.apply_rotary_freqs; csrc/rfa_rotfreq.hip).  Tensors, columns, pairings, dst == src and conj are rfa_rotary's;
+ * a struct of its own, no existing struct changes (ABI 8 revision 1 stays).  There are no tables: per rotated pair c < R/2 of
+ * row i of batch entry b, in fp32,
+ *     pos  = positions != NULL ? pos_offset + positions[axis(c) * pos_axis + b * pos_batch + i] : the position map of rfa_rotary
+ *     ang  = (float)pos * inv_freq[c]        one multiply, rounded once; (float) rounds to nearest
+ *     cos' = scaling * cosf(ang),  sin' = scaling * sinf(ang)       the precise functions, full range reduction
+ *     o1 = x1 cos' - x2 sin',  o2 = x2 cos' + x1 sin'               (conj != 0: sin' -> -sin'), as rfa_rotary forms them
+ * each result rounded once to the io dtype.  axis(c) is the 2-bit code of frequency c: bits 2 (c % 32) and 2 (c % 32) + 1 of
+ * freq_axis[c / 32] — all zero for one axis.  positions: int32, any value; (naxes, B, S) with element strides pos_axis, pos_batch
+ * (0: shared by the batch entries), 1.  The angles of a row are computed once per workgroup for all heads of both tensors.
+ * Checks, in this order and before any pointer is read: NULL struct RFA_ERR_NULL; struct_bytes != sizeof, reserved != 0,
+ * ntensors outside 1..2, interleaved or conj outside 0..1, a non-zero pad (of a tensor or the struct's), naxes outside 1..4, a
+ * scaling that is not finite or not > 0 RFA_ERR_ARGS; dtype RFA_ERR_DTYPE; D not a multiple of 8 in 8..256, R not a positive
+ * multiple of 16 (interleaved: of 8), rot_offset negative or not a multiple of 8, rot_offset + R > D RFA_ERR_HEAD_DIM; B < 0,
+ * S < 0, B * S above 2^31 - 1 RFA_ERR_SHAPE; an H <= 0, of any tensor, RFA_ERR_HEADS; then a tensor's unit count (rfa_rotary's)
+ * above 2^31 - 1 RFA_ERR_SHAPE; an axis code >= naxes among the first R/2, or a non-zero bit behind them, RFA_ERR_ARGS; B == 0 or
+ * S == 0: RFA_OK, nothing is launched; NULL src, dst or inv_freq RFA_ERR_NULL; tensor pointers or strides off the 16-byte
+ * contract, or an inv_freq off 4 bytes, RFA_ERR_ALIGN; dst == src with differing strides, a negative pos_batch or pos_axis, a
+ * pos_offset beyond +-2^40, naxes > 1 with positions == NULL, and with the map a negative pos_stride, a pos_split outside 0..S-1 or a position outside
+ * [0, 2^31 - 1] RFA_ERR_ARGS. */
+typedef struct {
+  uint32_t struct_bytes;   /* sizeof(rfa_rotary_freqs_args) */
+  uint32_t reserved;       /* 0 */
+  int32_t ntensors;        /* 1..2 */
+  int32_t B, S, D;         /* packed input: B = 1, S = T */
+  int32_t dtype;           /* rfa_dtype */
+  int32_t R, rot_offset;
+  int32_t interleaved, conj;
+  int32_t naxes;           /* 1..4: axes of `positions` */
+  rfa_rotary_tensor t[2];
+  const float *inv_freq;   /* (R/2,) fp32, contiguous */
+  float scaling;           /* multiplies cos and sin; finite, > 0 */
+  int32_t pad;             /* 0 */
+  uint64_t freq_axis[4];   /* 2 bits per frequency: the axis it reads */
+  const int32_t *positions; /* (naxes, B, S) int32, or NULL: the map (naxes 1) */
+  int64_t pos_batch;       /* elements between two batch entries of positions (0 = shared) */
+  int64_t pos_axis;        /* elements between two axes of positions */
+  int64_t pos_offset;      /* added to positions[], or the map's first offset */
+  int32_t pos_stride, pos_split;
+  int64_t pos_offset2;
+} rfa_rotary_freqs_args;
+int rfa_rotary_freqs(const rfa_rotary_freqs_args *args, void *stream);
+
 /* Per-head RMSNorm of q and k fused with the rotary embedding (ring_flash_attn.apply_qk_norm_rotary; csrc/rfa_qknorm.hip) — what
  * Qwen3, Gemma-3 and OLMo-style models run in front of attention: q = rope(rmsnorm_D(q) * w_q), k likewise.  Up to two tensors of
  * one call share rows, positions and tables and go through ONE launch per direction; structs of their own, no existing struct

@@ -5,6 +5,7 @@
 #include "rfa_common.hpp"
 #include "rfa_seqhead_index.h"
 #include "rfa_rotary_index.h"
+#include "rfa_rotfreq_index.h"
 #include "rfa_qknorm_index.h"
 #include "rfa_qktoken_index.h"
 #include "rfa_maxlogit_band.h"
@@ -290,6 +291,29 @@ struct RotaryParams {
   int ntensors;
 };
 int launch_rotary(const RotaryParams& p, int dtype, bool table_f32, hipStream_t stream);
+
+// rotary position embedding with the angles formed in the kernel (rfa_rotfreq.hip; tiles of rows: rfa_rotfreq_index.h): up to
+// two tensors (q, k) per launch, one workgroup per tile of kRotFreqRows rows of a batch entry.  t[k].nunits is not used.
+// positions != NULL: frequency c of row i of batch entry b sits at pos_off + positions[axis(c) * pos_axis + b * pos_batch + i],
+// axis(c) the 2-bit code of c in freq_axis; NULL: every frequency at the position map, as in RotaryParams.  No clamp: there is
+// no table.
+struct RotFreqParams {
+  RotaryGeom g;
+  RotaryTensor t[2];
+  const void* src[2];
+  void* dst[2];             // == src[k]: in place
+  const float* inv_freq;    // (R/2,)
+  float scaling;            // multiplies cos and sin
+  const int32_t* positions;
+  int64_t pos_batch, pos_axis;
+  int64_t pos_off, pos_off2;
+  uint32_t pos_stride;
+  int32_t pos_split;
+  int32_t conj;             // s -> -s: the inverse rotation = the backward
+  int ntensors;
+  uint64_t freq_axis[4];    // 2 bits per frequency
+};
+int launch_rotary_freqs(const RotFreqParams& p, int dtype, hipStream_t stream);
 
 // per-head QK RMSNorm fused with the rotary embedding (rfa_qknorm.hip; index arithmetic: rfa_qknorm_index.h): up to two tensors
 // (q, k) per launch, one lane per 16-byte chunk, one (row, head) per lane group.  Positions as in RotaryParams; R == 0 (cos ==

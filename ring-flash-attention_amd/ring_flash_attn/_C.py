@@ -238,6 +238,33 @@ class RotaryArgs(C.Structure):
             self.struct_bytes = C.sizeof(RotaryArgs)
 
 
+class RotaryFreqsArgs(C.Structure):
+    """rfa_rotary_freqs_args: rotary embedding with the angles formed in the kernel (inv_freq, one to four position axes);
+    struct_bytes is filled in here"""
+    _fields_ = [
+        ("struct_bytes", C.c_uint32), ("reserved", C.c_uint32),
+        ("ntensors", C.c_int32),
+        ("B", C.c_int32), ("S", C.c_int32), ("D", C.c_int32),
+        ("dtype", C.c_int32),
+        ("R", C.c_int32), ("rot_offset", C.c_int32),
+        ("interleaved", C.c_int32), ("conj", C.c_int32),
+        ("naxes", C.c_int32),
+        ("t", RotaryTensor * 2),
+        ("inv_freq", C.c_void_p),
+        ("scaling", C.c_float), ("pad", C.c_int32),
+        ("freq_axis", C.c_uint64 * 4),
+        ("positions", C.c_void_p), ("pos_batch", C.c_int64), ("pos_axis", C.c_int64),
+        ("pos_offset", C.c_int64),
+        ("pos_stride", C.c_int32), ("pos_split", C.c_int32),
+        ("pos_offset2", C.c_int64),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if not self.struct_bytes:
+            self.struct_bytes = C.sizeof(RotaryFreqsArgs)
+
+
 QK_NORM_WEIGHT_F32 = 2            # RFA_QK_NORM_WEIGHT_F32: fp32 norm weights (otherwise the io dtype's code)
 
 _QK_NORM_HEAD = [
@@ -471,6 +498,7 @@ SYMBOLS = {
     "rfa_sink_grad_workspace_bytes": (C.c_int64, [C.POINTER(SinkGradArgs)]),
     "rfa_seq_head_copy": (C.c_int, [C.POINTER(SeqHeadArgs), C.c_void_p]),
     "rfa_rotary": (C.c_int, [C.POINTER(RotaryArgs), C.c_void_p]),
+    "rfa_rotary_freqs": (C.c_int, [C.POINTER(RotaryFreqsArgs), C.c_void_p]),
     "rfa_qk_norm_rotary_fwd": (C.c_int, [C.POINTER(QkNormRotaryArgs), C.c_void_p]),
     "rfa_qk_norm_rotary_bwd": (C.c_int, [C.POINTER(QkNormRotaryBwdArgs), C.c_void_p]),
     "rfa_qk_norm_rotary_bwd_workspace_bytes": (C.c_int64, [C.POINTER(QkNormRotaryBwdArgs)]),

@@ -99,6 +99,7 @@ class HipBackend:
     serves_row_ranges = True         # fwd / bwd take `row_ranges=(start, end, k_pos0)` (include/rfa.h: rfa_fwd_rr, rfa_bwd_rr): ring_flash_attn.with_row_ranges
     serves_block_mask = True         # fwd / bwd take `block_mask=(mask_view, k_blk0)` (include/rfa.h: rfa_fwd_bm, rfa_bwd_bm): ring_flash_attn.with_block_mask
     serves_rotary = True             # rotary (include/rfa.h: rfa_rotary): ring_flash_attn.apply_rotary
+    serves_rotary_freqs = True       # rotary_freqs (include/rfa.h: rfa_rotary_freqs): ring_flash_attn.apply_rotary_freqs
     serves_qk_norm = True            # qk_norm_rotary_fwd / _bwd (include/rfa.h: rfa_qk_norm_rotary_fwd / _bwd): ring_flash_attn.apply_qk_norm_rotary
     serves_qk_token_norm = True      # qk_token_norm_rotary_fwd / _bwd (include/rfa.h: rfa_qk_token_norm_rotary_fwd / _bwd): apply_qk_token_norm_rotary
     serves_dropout_positions = True  # `dropout=` takes the position maps (q_map, k_map): what dropout over a dense ring, zigzag or stripe schedule needs
@@ -733,6 +734,57 @@ class HipBackend:
         else:
             a.pos_stride, a.pos_split, a.pos_offset2 = int(stride), int(split), int(off2)
         _C.check(self.lib.rfa_rotary(C.byref(a), _stream(t0)), "rfa_rotary")
+
+    # ------------------------------------------------------------------ rotary embedding, angles in the kernel (apply_rotary_freqs)
+    def rotary_freqs(self, srcs, dsts, inv_freq, *, scaling=1.0, freq_axis=None, positions=None, pos_map=None, interleaved=False,
+                     rot_offset=0, conj=False):
+        """one launch of the rotary embedding that forms its own angles (include/rfa.h: rfa_rotary_freqs) for one or two tensors
+        that share rows and positions.  srcs / dsts as in `rotary`.  inv_freq: (R/2,) fp32 contiguous; scaling multiplies cos and
+        sin.  freq_axis None: positions int32 (S,) / (B,S) / (T,), row stride 1, or None: the rows sit at pos_map.  freq_axis a
+        sequence of R/2 axis numbers: positions int32 (A,S) / (A,B,S) / (A,T), A <= 4, and frequency c reads axis freq_axis[c].
+        pos_map's offset is added to tensor positions.  conj: the inverse rotation (the backward)."""
+        self._check_dev(inv_freq, positions, *srcs, *dsts)
+        t0 = srcs[0]
+        packed = t0.dim() == 3
+        a = _C.RotaryFreqsArgs()
+        a.ntensors = len(srcs)
+        a.B, a.S = (1, t0.shape[0]) if packed else (t0.shape[0], t0.shape[1])
+        a.D, a.dtype = t0.shape[-1], self._dtype(t0)
+        if inv_freq.dtype != torch.float32 or inv_freq.dim() != 1 or not inv_freq.is_contiguous():
+            raise ValueError("rotary_freqs: inv_freq is a contiguous fp32 (R/2,) tensor")
+        half = inv_freq.shape[0]
+        a.R, a.rot_offset = 2 * half, int(rot_offset)
+        a.interleaved, a.conj = int(bool(interleaved)), int(bool(conj))
+        a.inv_freq, a.scaling = inv_freq.data_ptr(), float(scaling)
+        for d, s, o in zip(a.t, srcs, dsts):
+            if s.dtype != t0.dtype or o.dtype != t0.dtype or s.shape != o.shape or s.stride(-1) != 1 or o.stride(-1) != 1:
+                raise ValueError("rotary_freqs: sources and destinations share one dtype and shape; last (head_dim) stride must be 1")
+            d.src, d.dst, d.H = s.data_ptr(), o.data_ptr(), s.shape[-2]
+            # (the stride of a dimension of length 1 is never used: 0, whatever torch reports for it)
+            ss, os_ = ([st if n > 1 else 0 for n, st in zip(t.shape, t.stride())] for t in (s, o))
+            d.src_batch, d.src_row, d.src_head = (0 if packed else ss[0]), ss[-3], ss[-2]
+            d.dst_batch, d.dst_row, d.dst_head = (0 if packed else os_[0]), os_[-3], os_[-2]
+        off, (stride, split, off2) = pos_map if pos_map is not None else (0, (1, 0, 0))
+        a.pos_offset = int(off)
+        a.naxes = 1
+        if freq_axis is not None:
+            if positions is None or positions.dim() < 2 or len(freq_axis) != half or half > 128:
+                raise ValueError("rotary_freqs: freq_axis has R/2 <= 128 entries and needs positions of shape (A, ...)")
+            a.naxes = positions.shape[0]
+            for c, ax in enumerate(freq_axis):
+                if not 0 <= int(ax) < 4:                           # (what 2 bits hold; rfa_rotary_freqs refuses a code >= naxes)
+                    raise ValueError(f"rotary_freqs: freq_axis[{c}] = {ax} is no axis code (0 .. 3)")
+                a.freq_axis[c // 32] |= int(ax) << (2 * (c % 32))
+        if positions is not None:
+            if positions.dtype != torch.int32 or (positions.stride(-1) != 1 and positions.shape[-1] != 1):
+                raise ValueError("rotary_freqs: positions are int32 with row stride 1")
+            a.positions = positions.data_ptr()
+            rest = positions if freq_axis is None else positions[0]
+            a.pos_axis = positions.stride(0) if freq_axis is not None and positions.shape[0] > 1 else 0
+            a.pos_batch = rest.stride(0) if rest.dim() == 2 and rest.shape[0] > 1 else 0
+        else:
+            a.pos_stride, a.pos_split, a.pos_offset2 = int(stride), int(split), int(off2)
+        _C.check(self.lib.rfa_rotary_freqs(C.byref(a), _stream(t0)), "rfa_rotary_freqs")
 
     # ------------------------------------------------------------------ QK RMSNorm + rotary (apply_qk_norm_rotary)
     def _qk_norm_args(self, a, xs, outs, weights, cos, sin, positions, pos_map, interleaved, rot_offset, eps, weight_offset):

@@ -1,4 +1,4 @@
-"""Rotary position embedding at GLOBAL positions for sharded q / k: `apply_rotary` and `local_positions`.
+"""Rotary position embedding at GLOBAL positions for sharded q / k: `apply_rotary`, `apply_rotary_freqs` and `local_positions`.
 
 Under context parallelism the rotation angle of local row i is its position in the unsharded sequence, and that depends on
 the schedule: a ring rank holds one contiguous run, a zigzag rank two distant chunks, a stripe rank every W-th token, the
@@ -6,8 +6,12 @@ packed families count inside each document.  The package already does this arith
 `with_block_mask` and ALiBi (_common.pos_map / zigzag_map / stripe_map); `local_positions(func, n_local)` hands it out as an
 int32 tensor for the sharding `func` expects, and `apply_rotary(q, k, cos, sin, layout=func)` rotates this rank's shards in
 one launch of one streaming kernel (HIP: csrc/rfa_rotary.hip) — the positions of the dense families travel as the four numbers
-of a position map, so no tensor is built.
+of a position map, so no tensor is built.  `apply_rotary_freqs` takes `inv_freq` in place of the tables and forms the angles in
+the kernel (HIP: csrc/rfa_rotfreq.hip): no table of the unsharded sequence on every rank, and rows with several positions
+(multi-axis M-RoPE), which no table describes.
 """
+import math
+
 import torch
 import torch.distributed as dist
 
@@ -309,3 +313,145 @@ def apply_rotary(q, k=None, cos=None, sin=None, *, layout=None, group=None, posi
 
 
 apply_rotary = _opaque(apply_rotary)
+
+
+# ---- apply_rotary_freqs -------------------------------------------------------------------------------------------------
+_POS_MAX = 2 ** 31 - 1
+
+
+class _RotaryFreqs(torch.autograd.Function):
+    """_Rotary with the angles formed in the kernel; backward: the same kernel with the conjugate flag on the incoming
+    gradients.  Saved: inv_freq, the positions (or the map's numbers) and the flags — neither inputs nor outputs."""
+
+    @staticmethod
+    def forward(ctx, q, k, inv_freq, positions, meta):
+        from .backend import get_backend
+
+        tensors = (q,) if k is None else (q, k)
+        ctx.meta = meta
+        ctx.save_for_backward(inv_freq, positions)
+        ctx.set_materialize_grads(False)
+        if meta["inplace"]:
+            ctx.mark_dirty(*tensors)
+            outs = list(tensors)
+        else:
+            outs = [torch.empty(t.shape, dtype=t.dtype, device=t.device) for t in tensors]
+        srcs = [t if _conforms(t) else t.contiguous() for t in tensors]        # (inplace: checked to conform before)
+        get_backend().rotary_freqs(srcs, outs, inv_freq, positions=positions, conj=False, **meta["launch"])
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        from .backend import get_backend
+
+        inv_freq, positions = ctx.saved_tensors
+        live = [g for g in grads if g is not None]
+        if live:
+            srcs = [g if _conforms(g) else g.contiguous() for g in live]
+            outs = [torch.empty(g.shape, dtype=g.dtype, device=g.device) for g in live]
+            get_backend().rotary_freqs(srcs, outs, inv_freq, positions=positions, conj=True, **ctx.meta["launch"])
+            it = iter(outs)
+            grads = tuple(next(it) if g is not None else None for g in grads)
+        return (grads[0], grads[1] if len(grads) > 1 else None, None, None, None)
+
+
+def apply_rotary_freqs(q, k=None, inv_freq=None, *, attention_scaling=1.0, freq_axis=None, layout=None, group=None,
+                       positions=None, offset=0, interleaved=False, rot_offset=0, inplace=False):
+    """`apply_rotary` without tables: the kernel forms the angles from `inv_freq` and the positions; returns the rotated q, or
+    (q, k).  Nothing of the size of the unsharded sequence is held, and a row may have up to four positions (M-RoPE).
+
+        q, k = apply_rotary_freqs(q, k, inv_freq, layout=zigzag_ring_flash_attn_func, group=group)
+        q, k = apply_rotary_freqs(q, k, inv_freq, positions=position_ids_thw, freq_axis=axes)      # Qwen2-VL / Qwen3-VL
+
+    q, k, `layout`, `group`, `positions`, `offset`, `interleaved`, `rot_offset` and `inplace` are apply_rotary's, with its checks.
+    inv_freq: fp32 (R/2,), contiguous, on q's device — with whatever Llama-3 / YaRN / NTK / linear scaling the model applies
+    already in it; R = 2 len(inv_freq) obeys apply_rotary's rules.  attention_scaling: a finite float > 0 that multiplies cos and
+    sin (Hugging Face's convention for YaRN / longrope).
+    freq_axis=None: one position per row — `positions` int32 (S,) / (B, S) / (T,), or `layout`, or neither (row i is position i).
+    freq_axis = a sequence or CPU int tensor of R/2 axis numbers in [0, A), 1 <= A <= 4: `positions` must be given, int32,
+    contiguous, (A, S), (A, B, S) or (A, T), and frequency c reads axis freq_axis[c]; `layout` is refused (a map yields one number
+    per row).  For R/2 = 64 and (t, h, w) position_ids:
+      Qwen2-VL, mrope_section [16, 24, 24]:   freq_axis = [0] * 16 + [1] * 24 + [2] * 24
+      Qwen3-VL, interleaved [24, 20, 20]:     freq_axis = [0] * 64; freq_axis[1:60:3] = [1] * 20; freq_axis[2:60:3] = [2] * 20
+    Per rotated pair, in fp32: ang = float(pos) * inv_freq[c] (one rounded multiply — what inv_freq.float() @
+    position_ids.float() gives), (s, c) = sincosf(ang) with full range reduction, both times attention_scaling, then
+    apply_rotary's expression, each result rounded once.  An element's bits depend on its values, its position(s), inv_freq and
+    the scaling alone.  Tensor positions may be any int32 and are not read on the host; a map (`layout` / `offset`) whose
+    positions leave [0, 2^31 - 1] is a ValueError.
+    Autograd: the backward is the same kernel with s -> -s on the incoming gradients; inv_freq gets no gradient.
+    Under torch.compile the call runs eagerly behind a graph break.
+    Raises, before anything is launched: NotImplementedError for a backend without `serves_rotary_freqs`; TypeError for a
+    `layout` as apply_rotary raises it; ValueError for everything else."""
+    from .backend import get_backend
+
+    who = "ring_flash_attn.apply_rotary_freqs"
+    be = get_backend()
+    if not getattr(be, "serves_rotary_freqs", False):
+        raise NotImplementedError(f"{who} needs a backend that serves `rotary_freqs`; "
+                                  f"{getattr(be, 'name', type(be).__name__)!r} does not")
+    if not isinstance(q, torch.Tensor) or (k is not None and not isinstance(k, torch.Tensor)):
+        raise ValueError(f"{who}: q and k must be tensors")
+    tensors = [q] if k is None else [q, k]
+    packed, D = _check_qk(who, q, k)
+    if not isinstance(inv_freq, torch.Tensor) or inv_freq.dtype != torch.float32 or inv_freq.dim() != 1 or \
+            not inv_freq.is_contiguous() or inv_freq.device != q.device:
+        raise ValueError(f"{who}: inv_freq must be a contiguous fp32 (R/2,) tensor on q's device")
+    interleaved = bool(interleaved)
+    half = inv_freq.shape[0]
+    R = 2 * half
+    if R < 1 or R % (8 if interleaved else 16):
+        raise ValueError(f"{who}: the rotary width R = {R} must be a positive multiple of {8 if interleaved else 16} "
+                         f"({'interleaved' if interleaved else 'halves'})")
+    if isinstance(attention_scaling, bool) or not isinstance(attention_scaling, (int, float)) or \
+            not math.isfinite(attention_scaling) or not attention_scaling > 0:
+        raise ValueError(f"{who}: attention_scaling must be a finite number > 0, got {attention_scaling!r}")
+    S = q.shape[0] if packed else q.shape[1]
+    if freq_axis is None:
+        # (apply_rotary's checks of rot_offset, layout and positions; no table: nothing bounds the positions there)
+        positions, pm, _, rot_offset = _check_tables_positions(who, q, packed, D, None, None, layout, group, positions, offset,
+                                                               interleaved, rot_offset)
+        if positions is None and S:
+            lo, hi = _map_bounds(pm, S)
+            if lo < 0 or hi > _POS_MAX:
+                raise ValueError(f"{who}: the rows sit at positions {lo} .. {hi}, outside 0 .. 2^31 - 1")
+    else:
+        if isinstance(freq_axis, torch.Tensor):
+            if freq_axis.is_floating_point() or freq_axis.device.type != "cpu" or freq_axis.dim() != 1:
+                raise ValueError(f"{who}: freq_axis must be a sequence or a 1-d CPU int tensor")
+            freq_axis = freq_axis.tolist()
+        freq_axis = tuple(freq_axis)
+        if len(freq_axis) != half or not all(isinstance(a, int) and not isinstance(a, bool) for a in freq_axis):
+            raise ValueError(f"{who}: freq_axis must hold R/2 = {half} ints, one axis number per frequency")
+        if layout is not None:
+            if _family(layout, "apply_rotary_freqs") not in _DENSE:
+                raise TypeError(f"{who}: `layout` serves the nine dense functions")
+            raise ValueError(f"{who}: `layout` yields one position per row and cannot serve freq_axis; pass positions= of shape (A, ...)")
+        _, pm, _, rot_offset = _check_tables_positions(who, q, packed, D, None, None, None, group, None, offset, interleaved,
+                                                       rot_offset)
+        lead = ((S,),) if packed else ((S,), (q.shape[0], S))
+        if not isinstance(positions, torch.Tensor) or positions.dtype != torch.int32 or positions.device != q.device or \
+                not positions.is_contiguous() or not 1 <= positions.shape[0] <= 4 or tuple(positions.shape[1:]) not in lead:
+            raise ValueError(f"{who}: with freq_axis, positions must be a contiguous int32 tensor of shape "
+                             f"{' or '.join(str(('A',) + w) for w in lead)}, 1 <= A <= 4, on q's device")
+        A = positions.shape[0]
+        if not all(0 <= a < A for a in freq_axis):
+            raise ValueError(f"{who}: freq_axis must name axes in [0, {A}), the first dimension of positions")
+    # (rot_offset is apply_rotary's by now: an int, a multiple of 8 inside D; the offset of tensor positions is bounded like a
+    # map's, where rfa_rotary_freqs would refuse it)
+    if rot_offset + R > D:
+        raise ValueError(f"{who}: rot_offset {rot_offset} must be a multiple of 8 with rot_offset + R = {rot_offset + R} <= D = {D}")
+    if positions is not None and abs(pm[0]) > _POS_MAX:
+        raise ValueError(f"{who}: offset {pm[0]} is outside -(2^31 - 1) .. 2^31 - 1")
+    inplace = bool(inplace)
+    if inplace and not all(_conforms(t) for t in tensors):
+        raise ValueError(f"{who}: inplace=True needs last stride 1, a 16-byte aligned start and strides that are multiples of 8")
+    launch = dict(scaling=float(attention_scaling), freq_axis=freq_axis, pos_map=pm, interleaved=interleaved, rot_offset=rot_offset)
+    meta = dict(inplace=inplace, launch=launch)
+    if inplace and k is not None and torch.is_grad_enabled() and any(t._is_view() for t in tensors):
+        # (autograd lets a Function that modifies a VIEW in place return one tensor only: q and k one after the other)
+        return tuple(_RotaryFreqs.apply(t, None, inv_freq, positions, meta)[0] for t in tensors)
+    outs = _RotaryFreqs.apply(q, k, inv_freq, positions, meta)
+    return outs[0] if k is None else outs
+
+
+apply_rotary_freqs = _opaque(apply_rotary_freqs)
