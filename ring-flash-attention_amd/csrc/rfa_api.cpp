@@ -1650,239 +1650,277 @@ int rfa_seq_head_copy(const rfa_seq_head_args* a, void* stream) {
   return launch_seq_head_copy(p, (hipStream_t)stream) ? RFA_ERR_LAUNCH : RFA_OK;
 }
 
-// ---- rotary position embedding (rfa.h; csrc/rfa_rotary.hip) ------------------------------------------------------------------
-int rfa_rotary(const rfa_rotary_args* a, void* stream) {
-  if (!a) return RFA_ERR_NULL;
-  if (a->struct_bytes != sizeof(rfa_rotary_args) || a->reserved != 0) return RFA_ERR_ARGS;
-  if (a->ntensors < 1 || a->ntensors > 2) return RFA_ERR_ARGS;
-  if (a->interleaved < 0 || a->interleaved > 1 || a->conj < 0 || a->conj > 1) return RFA_ERR_ARGS;
-  for (int k = 0; k < a->ntensors; ++k)
-    if (a->t[k].pad != 0) return RFA_ERR_ARGS;
-  if (a->dtype != RFA_BF16 && a->dtype != RFA_F16) return RFA_ERR_DTYPE;
-  if (a->table_dtype != a->dtype && a->table_dtype != RFA_ROTARY_TABLE_F32) return RFA_ERR_DTYPE;
-  if (a->D <= 0 || a->D > kMaxHeadDim || (a->D % 8) != 0) return RFA_ERR_HEAD_DIM;
-  if (a->R <= 0 || (a->R % (a->interleaved ? 8 : 16)) != 0) return RFA_ERR_HEAD_DIM;
-  if (a->rot_offset < 0 || (a->rot_offset % 8) != 0 || a->rot_offset > a->D - a->R) return RFA_ERR_HEAD_DIM;
-  if (a->B < 0 || a->S < 0 || a->P < 1) return RFA_ERR_SHAPE;
-  const int64_t rows = (int64_t)a->B * a->S;
-  if (rows > INT32_MAX) return RFA_ERR_SHAPE;
-  for (int k = 0; k < a->ntensors; ++k)                        // every tensor's heads before any tensor's unit count
-    if (a->t[k].H <= 0) return RFA_ERR_HEADS;
-  RotaryParams p{};
-  p.g.B = (uint32_t)a->B; p.g.S = (uint32_t)a->S; p.g.R = (uint32_t)a->R; p.g.rot_off = (uint32_t)a->rot_offset;
-  p.g.rot_units = (uint32_t)(a->interleaved ? a->R / 8 : a->R / 16);
-  p.g.interleaved = a->interleaved;
-  for (int k = 0; k < a->ntensors; ++k) {
-    const rfa_rotary_tensor& s = a->t[k];
-    const int64_t uph = rotary_units_per_head((uint32_t)a->D, (uint32_t)a->R, a->interleaved, s.dst == s.src);
-    // (rows and H fit 31 bits each, uph <= 32: the products fit 62 and 36 bits)
-    if (rows * s.H > INT32_MAX || rows * s.H * uph > INT32_MAX) return RFA_ERR_SHAPE;
-    RotaryTensor& t = p.t[k];
-    t.sb = s.src_batch; t.sr = s.src_row; t.sh = s.src_head;
-    t.db = s.dst_batch; t.dr = s.dst_row; t.dh = s.dst_head;
-    t.H = (uint32_t)s.H; t.uph = (uint32_t)uph; t.nunits = (uint32_t)(rows * s.H * uph);
-    p.src[k] = s.src; p.dst[k] = s.dst;
-  }
-  if (a->B == 0 || a->S == 0) return RFA_OK;
-  if (!a->cos || !a->sin) return RFA_ERR_NULL;
-  for (int k = 0; k < a->ntensors; ++k)
-    if (!a->t[k].src || !a->t[k].dst) return RFA_ERR_NULL;
-  if (!aligned16(a->cos) || !aligned16(a->sin)) return RFA_ERR_ALIGN;
-  for (int k = 0; k < a->ntensors; ++k) {
-    const rfa_rotary_tensor& s = a->t[k];
-    if (!aligned16(s.src) || !aligned16(s.dst) || (s.src_batch % 8) || (s.src_row % 8) || (s.src_head % 8) ||
-        (s.dst_batch % 8) || (s.dst_row % 8) || (s.dst_head % 8))
-      return RFA_ERR_ALIGN;
-  }
-  for (int k = 0; k < a->ntensors; ++k) {
-    const rfa_rotary_tensor& s = a->t[k];
-    if (s.dst == s.src && (s.src_batch != s.dst_batch || s.src_row != s.dst_row || s.src_head != s.dst_head)) return RFA_ERR_ARGS;
-  }
-  if (a->pos_batch < 0) return RFA_ERR_ARGS;
-  const uint32_t stride = a->pos_stride > 0 ? (uint32_t)a->pos_stride : 1u;
-  if (!a->positions) {
-    if (a->pos_stride < 0 || a->pos_split < 0 || a->pos_split > a->S - 1) return RFA_ERR_ARGS;
-    // the map's pieces are monotone: their ends bound every position
-    const uint32_t ends[4] = {0u, (uint32_t)(a->pos_split ? a->pos_split - 1 : a->S - 1), (uint32_t)a->pos_split, (uint32_t)(a->S - 1)};
-    // (an offset beyond 2^40 names no table row; refused here so that the sums below cannot overflow)
-    if (a->pos_offset < -(1ll << 40) || a->pos_offset > (1ll << 40) || a->pos_offset2 < -(1ll << 40) || a->pos_offset2 > (1ll << 40))
-      return RFA_ERR_ARGS;
-    for (int e = 0; e < 4; ++e) {
-      const int64_t pos = rotary_map_pos(a->pos_offset, stride, a->pos_split, a->pos_offset2, ends[e]);
-      if (pos < 0 || pos > a->P - 1) return RFA_ERR_ARGS;
-    }
-  }
-  p.cos = a->cos; p.sin = a->sin; p.P = a->P;
-  p.positions = a->positions; p.pos_batch = a->pos_batch;
-  p.pos_off = a->pos_offset; p.pos_off2 = a->pos_offset2; p.pos_stride = stride; p.pos_split = a->pos_split;
-  p.conj = a->conj;
-  p.ntensors = a->ntensors;
-  return launch_rotary(p, a->dtype, a->table_dtype == RFA_ROTARY_TABLE_F32, (hipStream_t)stream) ? RFA_ERR_LAUNCH : RFA_OK;
-}
-
-// ---- rotary position embedding, angles formed in the kernel (rfa.h; csrc/rfa_rotfreq.hip) -------------------------------------
-int rfa_rotary_freqs(const rfa_rotary_freqs_args* a, void* stream) {
-  if (!a) return RFA_ERR_NULL;
-  if (a->struct_bytes != sizeof(rfa_rotary_freqs_args) || a->reserved != 0) return RFA_ERR_ARGS;
-  if (a->ntensors < 1 || a->ntensors > 2) return RFA_ERR_ARGS;
-  if (a->interleaved < 0 || a->interleaved > 1 || a->conj < 0 || a->conj > 1) return RFA_ERR_ARGS;
-  for (int k = 0; k < a->ntensors; ++k)
-    if (a->t[k].pad != 0) return RFA_ERR_ARGS;
-  if (a->pad != 0 || a->naxes < 1 || a->naxes > 4) return RFA_ERR_ARGS;
-  if (!(a->scaling > 0.f) || !(a->scaling <= FLT_MAX)) return RFA_ERR_ARGS;
-  if (a->dtype != RFA_BF16 && a->dtype != RFA_F16) return RFA_ERR_DTYPE;
-  if (a->D <= 0 || a->D > kMaxHeadDim || (a->D % 8) != 0) return RFA_ERR_HEAD_DIM;
-  if (a->R <= 0 || (a->R % (a->interleaved ? 8 : 16)) != 0) return RFA_ERR_HEAD_DIM;
-  if (a->rot_offset < 0 || (a->rot_offset % 8) != 0 || a->rot_offset > a->D - a->R) return RFA_ERR_HEAD_DIM;
-  if (a->B < 0 || a->S < 0) return RFA_ERR_SHAPE;
-  const int64_t rows = (int64_t)a->B * a->S;
-  if (rows > INT32_MAX) return RFA_ERR_SHAPE;
-  for (int k = 0; k < a->ntensors; ++k)                        // every tensor's heads before any tensor's unit count
-    if (a->t[k].H <= 0) return RFA_ERR_HEADS;
-  RotFreqParams p{};
-  p.g.B = (uint32_t)a->B; p.g.S = (uint32_t)a->S; p.g.R = (uint32_t)a->R; p.g.rot_off = (uint32_t)a->rot_offset;
-  p.g.rot_units = (uint32_t)(a->interleaved ? a->R / 8 : a->R / 16);
-  p.g.interleaved = a->interleaved;
-  for (int k = 0; k < a->ntensors; ++k) {
-    const rfa_rotary_tensor& s = a->t[k];
-    const int64_t uph = rotary_units_per_head((uint32_t)a->D, (uint32_t)a->R, a->interleaved, s.dst == s.src);
-    // (a tile's units are a run of 32-bit unit indices: the bound of rfa_rotary holds here too)
-    if (rows * s.H > INT32_MAX || rows * s.H * uph > INT32_MAX) return RFA_ERR_SHAPE;
-    RotaryTensor& t = p.t[k];
-    t.sb = s.src_batch; t.sr = s.src_row; t.sh = s.src_head;
-    t.db = s.dst_batch; t.dr = s.dst_row; t.dh = s.dst_head;
-    t.H = (uint32_t)s.H; t.uph = (uint32_t)uph; t.nunits = (uint32_t)(rows * s.H * uph);
-    p.src[k] = s.src; p.dst[k] = s.dst;
-  }
-  for (uint32_t c = 0; c < 4 * 32; ++c) {                      // (R/2 <= 128 = the entries of the four words)
-    const uint32_t axis = rotfreq_axis(a->freq_axis[0], a->freq_axis[1], a->freq_axis[2], a->freq_axis[3], c);
-    if (axis >= (c < (uint32_t)a->R / 2 ? (uint32_t)a->naxes : 1u)) return RFA_ERR_ARGS;
-  }
-  if (a->B == 0 || a->S == 0) return RFA_OK;
-  if (!a->inv_freq) return RFA_ERR_NULL;
-  for (int k = 0; k < a->ntensors; ++k)
-    if (!a->t[k].src || !a->t[k].dst) return RFA_ERR_NULL;
-  if (reinterpret_cast<uintptr_t>(a->inv_freq) & 3) return RFA_ERR_ALIGN;
-  for (int k = 0; k < a->ntensors; ++k) {
-    const rfa_rotary_tensor& s = a->t[k];
-    if (!aligned16(s.src) || !aligned16(s.dst) || (s.src_batch % 8) || (s.src_row % 8) || (s.src_head % 8) ||
-        (s.dst_batch % 8) || (s.dst_row % 8) || (s.dst_head % 8))
-      return RFA_ERR_ALIGN;
-  }
-  for (int k = 0; k < a->ntensors; ++k) {
-    const rfa_rotary_tensor& s = a->t[k];
-    if (s.dst == s.src && (s.src_batch != s.dst_batch || s.src_row != s.dst_row || s.src_head != s.dst_head)) return RFA_ERR_ARGS;
-  }
-  if (a->pos_batch < 0 || a->pos_axis < 0) return RFA_ERR_ARGS;
-  // (an offset beyond 2^40 names no position that fp32 resolves; refused so that the sums here and in the kernel cannot overflow)
-  if (a->pos_offset < -(1ll << 40) || a->pos_offset > (1ll << 40)) return RFA_ERR_ARGS;
-  const uint32_t stride = a->pos_stride > 0 ? (uint32_t)a->pos_stride : 1u;
-  if (!a->positions) {
-    if (a->naxes > 1) return RFA_ERR_ARGS;
-    if (a->pos_stride < 0 || a->pos_split < 0 || a->pos_split > a->S - 1) return RFA_ERR_ARGS;
-    // the map's pieces are monotone: their ends bound every position
-    const uint32_t ends[4] = {0u, (uint32_t)(a->pos_split ? a->pos_split - 1 : a->S - 1), (uint32_t)a->pos_split, (uint32_t)(a->S - 1)};
-    if (a->pos_offset2 < -(1ll << 40) || a->pos_offset2 > (1ll << 40)) return RFA_ERR_ARGS;
-    for (int e = 0; e < 4; ++e) {
-      const int64_t pos = rotary_map_pos(a->pos_offset, stride, a->pos_split, a->pos_offset2, ends[e]);
-      if (pos < 0 || pos > INT32_MAX) return RFA_ERR_ARGS;
-    }
-  }
-  p.inv_freq = a->inv_freq; p.scaling = a->scaling;
-  p.positions = a->positions; p.pos_batch = a->pos_batch; p.pos_axis = a->pos_axis;
-  p.pos_off = a->pos_offset; p.pos_off2 = a->pos_offset2; p.pos_stride = stride; p.pos_split = a->pos_split;
-  p.conj = a->conj;
-  p.ntensors = a->ntensors;
-  for (int w = 0; w < 4; ++w) p.freq_axis[w] = a->freq_axis[w];
-  return launch_rotary_freqs(p, a->dtype, (hipStream_t)stream) ? RFA_ERR_LAUNCH : RFA_OK;
-}
-
-// ---- per-head QK RMSNorm + rotary (rfa.h; csrc/rfa_qknorm.hip) ---------------------------------------------------------------
+// ---- the row operators: rotary, rotary with its own angles, the two QK RMSNorms (rfa.h) ---------------------------------------
+// Every entry point runs the same stages, in the header's order of error codes: NULL (the struct), ARGS, DTYPE, HEAD_DIM, SHAPE,
+// HEADS, the per-tensor SHAPE bound, "no rows" (RFA_OK), NULL, ALIGN, the late ARGS (in place / dst == src, then the position
+// map).  One helper per stage; what an entry point checks on its own stands next to the stage of the same code.
 extern "C++" {
-// the checks the forward and the backward struct share, in the header's order: `upto` 0 stops in front of "no rows" (everything
-// that needs no pointer: what the workspace size depends on), 1 runs them all.  RFA_OK with *launch == false: nothing to do.
+// NULL, then ARGS: the struct itself and the fields every row operator has
 template <typename A>
-static int qk_norm_check(const A* a, int upto, QkNormParams* p, bool* launch) {
-  *launch = false;
+static int row_check_struct(const A* a) {
   if (!a) return RFA_ERR_NULL;
   if (a->struct_bytes != sizeof(A) || a->reserved != 0) return RFA_ERR_ARGS;
   if (a->ntensors < 1 || a->ntensors > 2) return RFA_ERR_ARGS;
   if (a->interleaved < 0 || a->interleaved > 1) return RFA_ERR_ARGS;
   for (int k = 0; k < a->ntensors; ++k)
     if (a->t[k].pad != 0) return RFA_ERR_ARGS;
-  if (!(a->eps >= 0.f) || !(a->eps <= FLT_MAX) || !(a->weight_offset >= -FLT_MAX && a->weight_offset <= FLT_MAX)) return RFA_ERR_ARGS;
+  return RFA_OK;
+}
+
+// DTYPE (the io dtype), HEAD_DIM, SHAPE, HEADS.  min_R: 1 where the rotation is the point, 0 where R == 0 is the norm alone;
+// P: the rows of the tables (1 where no table is looked at)
+template <typename A>
+static int row_check_dims(const A* a, int min_R, int64_t P) {
   if (a->dtype != RFA_BF16 && a->dtype != RFA_F16) return RFA_ERR_DTYPE;
-  if (a->table_dtype != a->dtype && a->table_dtype != RFA_ROTARY_TABLE_F32) return RFA_ERR_DTYPE;
-  if (a->weight_dtype != a->dtype && a->weight_dtype != RFA_QK_NORM_WEIGHT_F32) return RFA_ERR_DTYPE;
   if (a->D <= 0 || a->D > kMaxHeadDim || (a->D % 8) != 0) return RFA_ERR_HEAD_DIM;
-  if (a->R < 0 || (a->R % (a->interleaved ? 8 : 16)) != 0) return RFA_ERR_HEAD_DIM;
+  if (a->R < min_R || (a->R % (a->interleaved ? 8 : 16)) != 0) return RFA_ERR_HEAD_DIM;
   if (a->rot_offset < 0 || (a->rot_offset % 8) != 0 || a->rot_offset > a->D - a->R) return RFA_ERR_HEAD_DIM;
-  if (a->B < 0 || a->S < 0 || (a->R > 0 && a->P < 1)) return RFA_ERR_SHAPE;
-  const int64_t rows = (int64_t)a->B * a->S;
-  if (rows > INT32_MAX) return RFA_ERR_SHAPE;
-  for (int k = 0; k < a->ntensors; ++k)
+  if (a->B < 0 || a->S < 0 || P < 1) return RFA_ERR_SHAPE;
+  if ((int64_t)a->B * a->S > INT32_MAX) return RFA_ERR_SHAPE;
+  for (int k = 0; k < a->ntensors; ++k)                        // every tensor's heads before any tensor's own bound
     if (a->t[k].H <= 0) return RFA_ERR_HEADS;
+  return RFA_OK;
+}
+
+// RotaryGeom and RotaryTensor[] of RotaryParams / RotFreqParams, with the per-tensor SHAPE bound (a unit index is 32 bits in the
+// table kernel, and a tile's units are a run of them in the other)
+template <typename A, typename P>
+static int rotary_fill(const A* a, P* p) {
+  const int64_t rows = (int64_t)a->B * a->S;
+  p->g.B = (uint32_t)a->B; p->g.S = (uint32_t)a->S; p->g.R = (uint32_t)a->R; p->g.rot_off = (uint32_t)a->rot_offset;
+  p->g.rot_units = (uint32_t)(a->interleaved ? a->R / 8 : a->R / 16);
+  p->g.interleaved = a->interleaved;
   for (int k = 0; k < a->ntensors; ++k) {
-    if (rows * a->t[k].H > INT32_MAX) return RFA_ERR_SHAPE;
     const rfa_rotary_tensor& s = a->t[k];
-    QkNormTensor& t = p->t[k];
-    t.xb = s.src_batch; t.xr = s.src_row; t.xh = s.src_head;
-    t.ob = s.dst_batch; t.orow = s.dst_row; t.oh = s.dst_head;
-    t.H = (uint32_t)s.H; t.nitems = (uint32_t)(rows * s.H);
-    p->x[k] = s.src; p->out[k] = s.dst; p->weight[k] = a->weight[k];
+    const int64_t uph = rotary_units_per_head((uint32_t)a->D, (uint32_t)a->R, a->interleaved, s.dst == s.src);
+    // (rows and H fit 31 bits each, uph <= 32: the products fit 62 and 36 bits)
+    if (rows * s.H > INT32_MAX || rows * s.H * uph > INT32_MAX) return RFA_ERR_SHAPE;
+    RotaryTensor& t = p->t[k];
+    t.sb = s.src_batch; t.sr = s.src_row; t.sh = s.src_head;
+    t.db = s.dst_batch; t.dr = s.dst_row; t.dh = s.dst_head;
+    t.H = (uint32_t)s.H; t.uph = (uint32_t)uph; t.nunits = (uint32_t)(rows * s.H * uph);
+    p->src[k] = s.src; p->dst[k] = s.dst;
   }
-  QkNormGeom& g = p->g;
-  g.B = (uint32_t)a->B; g.S = (uint32_t)a->S; g.D = (uint32_t)a->D; g.R = (uint32_t)a->R; g.rot_off = (uint32_t)a->rot_offset;
-  g.interleaved = a->interleaved; g.chunks = g.D / 8; g.group = qknorm_group(g.D);
+  p->conj = a->conj;
   p->ntensors = a->ntensors;
-  for (int k = 0; k < a->ntensors; ++k) {
-    p->nparts[k] = qknorm_parts(p->t[k].nitems, g.group);
-    p->walk[k] = qknorm_walk(p->t[k].nitems, p->nparts[k], g.group);
-  }
-  p->eps = a->eps; p->weight_offset = a->weight_offset;
-  if (a->B == 0 || a->S == 0 || upto == 0) return RFA_OK;
-  *launch = true;
-  for (int k = 0; k < a->ntensors; ++k)
-    if (!a->t[k].src || !a->t[k].dst || !a->weight[k]) return RFA_ERR_NULL;
-  if (a->R > 0 && (!a->cos || !a->sin)) return RFA_ERR_NULL;
   return RFA_OK;
 }
 
-// the checks behind the NULL checks: alignment, then the rest
 template <typename A>
-static int qk_norm_check_rest(const A* a) {
-  if (a->R > 0 && (!aligned16(a->cos) || !aligned16(a->sin))) return RFA_ERR_ALIGN;
+static bool row_tensors_present(const A* a) {
+  for (int k = 0; k < a->ntensors; ++k)
+    if (!a->t[k].src || !a->t[k].dst) return false;
+  return true;
+}
+
+template <typename A>
+static bool row_tensors_aligned(const A* a) {
   for (int k = 0; k < a->ntensors; ++k) {
     const rfa_rotary_tensor& s = a->t[k];
-    if (!aligned16(s.src) || !aligned16(s.dst) || !aligned16(a->weight[k]) || (s.src_batch % 8) || (s.src_row % 8) ||
-        (s.src_head % 8) || (s.dst_batch % 8) || (s.dst_row % 8) || (s.dst_head % 8))
-      return RFA_ERR_ALIGN;
+    if (!aligned16(s.src) || !aligned16(s.dst) || (s.src_batch % 8) || (s.src_row % 8) || (s.src_head % 8) ||
+        (s.dst_batch % 8) || (s.dst_row % 8) || (s.dst_head % 8))
+      return false;
   }
-  return RFA_OK;
+  return true;
 }
 
+// a tensor rotated in place is read and written at the same strides
 template <typename A>
-static int qk_norm_check_map(const A* a, QkNormParams* p) {
-  for (int k = 0; k < a->ntensors; ++k)
-    if (a->t[k].dst == a->t[k].src) return RFA_ERR_ARGS;
+static bool rotary_inplace_ok(const A* a) {
+  for (int k = 0; k < a->ntensors; ++k) {
+    const rfa_rotary_tensor& s = a->t[k];
+    if (s.dst == s.src && (s.src_batch != s.dst_batch || s.src_row != s.dst_row || s.src_head != s.dst_head)) return false;
+  }
+  return true;
+}
+
+// the position fields of any *Params.  max_pos: the largest position a map may reach (the last table row; INT32_MAX where the
+// kernel forms the angle); use == false (the norm alone): nothing of the positions is read, checked or written but pos_batch
+template <typename A, typename P>
+static int row_pos_map(const A* a, P* p, int64_t max_pos, bool use) {
   if (a->pos_batch < 0) return RFA_ERR_ARGS;
+  if (!use) return RFA_OK;
   const uint32_t stride = a->pos_stride > 0 ? (uint32_t)a->pos_stride : 1u;
-  if (a->R > 0 && !a->positions) {
+  if (!a->positions) {
     if (a->pos_stride < 0 || a->pos_split < 0 || a->pos_split > a->S - 1) return RFA_ERR_ARGS;
+    // the map's pieces are monotone: their ends bound every position
     const uint32_t ends[4] = {0u, (uint32_t)(a->pos_split ? a->pos_split - 1 : a->S - 1), (uint32_t)a->pos_split, (uint32_t)(a->S - 1)};
+    // (an offset beyond 2^40 names no position; refused here so that the sums below cannot overflow)
     if (a->pos_offset < -(1ll << 40) || a->pos_offset > (1ll << 40) || a->pos_offset2 < -(1ll << 40) || a->pos_offset2 > (1ll << 40))
       return RFA_ERR_ARGS;
     for (int e = 0; e < 4; ++e) {
       const int64_t pos = rotary_map_pos(a->pos_offset, stride, a->pos_split, a->pos_offset2, ends[e]);
-      if (pos < 0 || pos > a->P - 1) return RFA_ERR_ARGS;
+      if (pos < 0 || pos > max_pos) return RFA_ERR_ARGS;
     }
   }
-  if (a->R > 0) {
-    p->cos = a->cos; p->sin = a->sin; p->P = a->P;
-    p->positions = a->positions; p->pos_batch = a->pos_batch;
-    p->pos_off = a->pos_offset; p->pos_off2 = a->pos_offset2; p->pos_stride = stride; p->pos_split = a->pos_split;
-  }
+  p->positions = a->positions; p->pos_batch = a->pos_batch;
+  p->pos_off = a->pos_offset; p->pos_off2 = a->pos_offset2; p->pos_stride = stride; p->pos_split = a->pos_split;
   return RFA_OK;
+}
+}  // extern "C++"
+
+// ---- rotary position embedding (csrc/rfa_rotary.hip) -------------------------------------------------------------------------
+int rfa_rotary(const rfa_rotary_args* a, void* stream) {
+  if (int rc = row_check_struct(a)) return rc;
+  if (a->conj < 0 || a->conj > 1) return RFA_ERR_ARGS;
+  if (a->table_dtype != a->dtype && a->table_dtype != RFA_ROTARY_TABLE_F32) return RFA_ERR_DTYPE;
+  if (int rc = row_check_dims(a, 1, a->P)) return rc;
+  RotaryParams p{};
+  if (int rc = rotary_fill(a, &p)) return rc;
+  if (a->B == 0 || a->S == 0) return RFA_OK;
+  if (!a->cos || !a->sin || !row_tensors_present(a)) return RFA_ERR_NULL;
+  if (!aligned16(a->cos) || !aligned16(a->sin) || !row_tensors_aligned(a)) return RFA_ERR_ALIGN;
+  if (!rotary_inplace_ok(a)) return RFA_ERR_ARGS;
+  if (int rc = row_pos_map(a, &p, a->P - 1, true)) return rc;
+  p.cos = a->cos; p.sin = a->sin; p.P = a->P;
+  return launch_rotary(p, a->dtype, a->table_dtype == RFA_ROTARY_TABLE_F32, (hipStream_t)stream) ? RFA_ERR_LAUNCH : RFA_OK;
+}
+
+// ---- rotary position embedding, angles formed in the kernel (csrc/rfa_rotfreq.hip) -------------------------------------------
+int rfa_rotary_freqs(const rfa_rotary_freqs_args* a, void* stream) {
+  if (int rc = row_check_struct(a)) return rc;
+  if (a->conj < 0 || a->conj > 1 || a->pad != 0 || a->naxes < 1 || a->naxes > 4) return RFA_ERR_ARGS;
+  if (!(a->scaling > 0.f) || !(a->scaling <= FLT_MAX)) return RFA_ERR_ARGS;
+  if (int rc = row_check_dims(a, 1, 1)) return rc;
+  RotFreqParams p{};
+  if (int rc = rotary_fill(a, &p)) return rc;
+  for (uint32_t c = 0; c < 4 * 32; ++c) {                      // (R/2 <= 128 = the entries of the four words)
+    const uint32_t axis = rotfreq_axis(a->freq_axis[0], a->freq_axis[1], a->freq_axis[2], a->freq_axis[3], c);
+    if (axis >= (c < (uint32_t)a->R / 2 ? (uint32_t)a->naxes : 1u)) return RFA_ERR_ARGS;
+  }
+  if (a->B == 0 || a->S == 0) return RFA_OK;
+  if (!a->inv_freq || !row_tensors_present(a)) return RFA_ERR_NULL;
+  if ((reinterpret_cast<uintptr_t>(a->inv_freq) & 3) || !row_tensors_aligned(a)) return RFA_ERR_ALIGN;
+  if (!rotary_inplace_ok(a) || a->pos_axis < 0) return RFA_ERR_ARGS;
+  // (an offset beyond 2^40 names no position that fp32 resolves; refused with tensor positions too, so that the kernel's sum
+  // cannot overflow.  A map yields one number per row: it serves one axis)
+  if (a->pos_offset < -(1ll << 40) || a->pos_offset > (1ll << 40) || (!a->positions && a->naxes > 1)) return RFA_ERR_ARGS;
+  if (int rc = row_pos_map(a, &p, INT32_MAX, true)) return rc;
+  p.inv_freq = a->inv_freq; p.scaling = a->scaling; p.pos_axis = a->pos_axis;
+  for (int w = 0; w < 4; ++w) p.freq_axis[w] = a->freq_axis[w];
+  return launch_rotary_freqs(p, a->dtype, (hipStream_t)stream) ? RFA_ERR_LAUNCH : RFA_OK;
+}
+
+// ---- the QK RMSNorms + rotary: per head (csrc/rfa_qknorm.hip) and over all heads of a token (csrc/rfa_qktoken.hip) ------------
+static_assert(RFA_QK_TOKEN_NORM_MAX_WIDTH == kQkTokenMaxWidth && RFA_QK_TOKEN_NORM_MAX_PARTS == kQkTokenMaxParts,
+              "rfa.h and rfa_qktoken_index.h state the same limits");
+extern "C++" {
+// the checks the forward and the backward struct of either norm share, up to the NULL checks: `upto` 0 stops in front of "no
+// rows" (everything that needs no pointer: what the workspace size depends on), 1 runs them all.  RFA_OK with *launch == false:
+// nothing to do.  own(a, p, rows): what the norm's own Geom and Tensor hold beyond the shared members, with its own bound.
+template <typename A, typename P, typename Own>
+static int qk_check(const A* a, int upto, P* p, bool* launch, Own own) {
+  *launch = false;
+  if (int rc = row_check_struct(a)) return rc;
+  if (!(a->eps >= 0.f) || !(a->eps <= FLT_MAX) || !(a->weight_offset >= -FLT_MAX && a->weight_offset <= FLT_MAX)) return RFA_ERR_ARGS;
+  if (a->table_dtype != a->dtype && a->table_dtype != RFA_ROTARY_TABLE_F32) return RFA_ERR_DTYPE;
+  if (a->weight_dtype != a->dtype && a->weight_dtype != RFA_QK_NORM_WEIGHT_F32) return RFA_ERR_DTYPE;
+  if (int rc = row_check_dims(a, 0, a->R > 0 ? a->P : 1)) return rc;
+  p->g.B = (uint32_t)a->B; p->g.S = (uint32_t)a->S; p->g.D = (uint32_t)a->D; p->g.R = (uint32_t)a->R;
+  p->g.rot_off = (uint32_t)a->rot_offset; p->g.interleaved = a->interleaved;
+  p->ntensors = a->ntensors;
+  for (int k = 0; k < a->ntensors; ++k) {
+    const rfa_rotary_tensor& s = a->t[k];
+    auto& t = p->t[k];
+    t.xb = s.src_batch; t.xr = s.src_row; t.xh = s.src_head;
+    t.ob = s.dst_batch; t.orow = s.dst_row; t.oh = s.dst_head;
+    t.H = (uint32_t)s.H;
+    p->x[k] = s.src; p->out[k] = s.dst; p->weight[k] = a->weight[k];
+  }
+  if (int rc = own(a, p, (int64_t)a->B * a->S)) return rc;
+  p->eps = a->eps; p->weight_offset = a->weight_offset;
+  if (a->B == 0 || a->S == 0 || upto == 0) return RFA_OK;
+  *launch = true;
+  for (int k = 0; k < a->ntensors; ++k)
+    if (!a->weight[k]) return RFA_ERR_NULL;
+  if (!row_tensors_present(a) || (a->R > 0 && (!a->cos || !a->sin))) return RFA_ERR_NULL;
+  return RFA_OK;
+}
+
+template <typename A>
+static int qk_norm_check(const A* a, int upto, QkNormParams* p, bool* launch) {
+  return qk_check(a, upto, p, launch, [](const A* a, QkNormParams* p, int64_t rows) -> int {
+    QkNormGeom& g = p->g;
+    g.chunks = g.D / 8; g.group = qknorm_group(g.D);
+    for (int k = 0; k < a->ntensors; ++k) {
+      if (rows * a->t[k].H > INT32_MAX) return RFA_ERR_SHAPE;
+      p->t[k].nitems = (uint32_t)(rows * a->t[k].H);
+      p->nparts[k] = qknorm_parts(p->t[k].nitems, g.group);
+      p->walk[k] = qknorm_walk(p->t[k].nitems, p->nparts[k], g.group);
+    }
+    return RFA_OK;
+  });
+}
+
+template <typename A>
+static int qk_token_check(const A* a, int upto, QkTokenParams* p, bool* launch) {
+  return qk_check(a, upto, p, launch, [](const A* a, QkTokenParams* p, int64_t rows) -> int {
+    for (int k = 0; k < a->ntensors; ++k)
+      if ((int64_t)a->t[k].H * a->D > kQkTokenMaxWidth) return RFA_ERR_HEADS;
+    p->g.hchunks = p->g.D / 8;
+    for (int k = 0; k < a->ntensors; ++k) {
+      QkTokenTensor& t = p->t[k];
+      t.N = t.H * p->g.D; t.chunks = t.N / 8; t.team = qktoken_team(t.N); t.rows = (uint32_t)rows;
+      p->nparts[k] = qktoken_parts(t.rows, t.team);
+      p->walk[k] = qktoken_walk(t.rows, p->nparts[k], t.team);
+    }
+    p->table_f32 = a->table_dtype == RFA_ROTARY_TABLE_F32; p->weight_f32 = a->weight_dtype == RFA_QK_NORM_WEIGHT_F32;
+    return RFA_OK;
+  });
+}
+
+// behind the NULL checks: ALIGN, then the late ARGS and the table and position fields (R == 0, the norm alone: none of them)
+template <typename A>
+static int qk_check_aligned(const A* a) {
+  if (a->R > 0 && (!aligned16(a->cos) || !aligned16(a->sin))) return RFA_ERR_ALIGN;
+  for (int k = 0; k < a->ntensors; ++k)
+    if (!aligned16(a->weight[k])) return RFA_ERR_ALIGN;
+  return row_tensors_aligned(a) ? RFA_OK : RFA_ERR_ALIGN;
+}
+
+template <typename A, typename P>
+static int qk_check_map(const A* a, P* p) {
+  for (int k = 0; k < a->ntensors; ++k)
+    if (a->t[k].dst == a->t[k].src) return RFA_ERR_ARGS;
+  if (int rc = row_pos_map(a, p, a->P - 1, a->R > 0)) return rc;
+  if (a->R > 0) { p->cos = a->cos; p->sin = a->sin; p->P = a->P; }
+  return RFA_OK;
+}
+
+// everything of a backward behind qk_*_check: the gradients, dweight and the workspace, stage by stage around the two above.
+// workspace_bytes(p): what the fold of p's partials needs
+template <typename A, typename P, typename Bytes>
+static int qk_bwd_tail(const A* a, P* p, Bytes workspace_bytes) {
+  bool any = false;
+  for (int k = 0; k < a->ntensors; ++k) {
+    if (!a->g[k].dout) return RFA_ERR_NULL;
+    any = any || a->dweight[k] != nullptr;
+  }
+  if (any && !a->workspace) return RFA_ERR_NULL;
+  if (int rc = qk_check_aligned(a)) return rc;
+  for (int k = 0; k < a->ntensors; ++k) {
+    const rfa_qk_norm_grad& g = a->g[k];
+    if (!aligned16(g.dout) || (g.dout_batch % 8) || (g.dout_row % 8) || (g.dout_head % 8)) return RFA_ERR_ALIGN;
+    if (a->dweight[k] && ((uintptr_t)a->dweight[k] % 4) != 0) return RFA_ERR_ALIGN;
+  }
+  if (any && !aligned16(a->workspace)) return RFA_ERR_ALIGN;
+  if (int rc = qk_check_map(a, p)) return rc;
+  for (int k = 0; k < a->ntensors; ++k) {
+    if (a->t[k].dst == a->g[k].dout) return RFA_ERR_ARGS;
+    p->dout[k] = a->g[k].dout;
+    p->t[k].gb = a->g[k].dout_batch; p->t[k].gr = a->g[k].dout_row; p->t[k].gh = a->g[k].dout_head;
+    p->dweight[k] = a->dweight[k];
+  }
+  if (any && a->workspace_bytes < workspace_bytes(*p)) return RFA_ERR_ARGS;
+  p->workspace = (float*)a->workspace;
+  return RFA_OK;
+}
+
+static int64_t qk_norm_workspace(const QkNormParams& p) { return qknorm_workspace_bytes(1, p.nparts[0] + p.nparts[1], p.g.D); }
+static int64_t qk_token_workspace(const QkTokenParams& p) {
+  int64_t bytes = 0;
+  for (int k = 0; k < p.ntensors; ++k) bytes += qktoken_workspace_bytes(p.nparts[k], p.t[k].N);
+  return bytes;
 }
 }  // extern "C++"
 
@@ -1891,8 +1929,7 @@ int rfa_qk_norm_rotary_fwd(const rfa_qk_norm_rotary_args* a, void* stream) {
   bool launch = false;
   int rc = qk_norm_check(a, 1, &p, &launch);
   if (rc != RFA_OK || !launch) return rc;
-  if ((rc = qk_norm_check_rest(a)) != RFA_OK) return rc;
-  if ((rc = qk_norm_check_map(a, &p)) != RFA_OK) return rc;
+  if ((rc = qk_check_aligned(a)) != RFA_OK || (rc = qk_check_map(a, &p)) != RFA_OK) return rc;
   return launch_qknorm_fwd(p, a->dtype, a->table_dtype == RFA_ROTARY_TABLE_F32, a->weight_dtype == RFA_QK_NORM_WEIGHT_F32,
                            (hipStream_t)stream) ? RFA_ERR_LAUNCH : RFA_OK;
 }
@@ -1900,8 +1937,7 @@ int rfa_qk_norm_rotary_fwd(const rfa_qk_norm_rotary_args* a, void* stream) {
 int64_t rfa_qk_norm_rotary_bwd_workspace_bytes(const rfa_qk_norm_rotary_bwd_args* a) {
   QkNormParams p{};
   bool launch = false;
-  if (qk_norm_check(a, 0, &p, &launch) != RFA_OK) return 0;
-  return qknorm_workspace_bytes(1, p.nparts[0] + p.nparts[1], p.g.D);
+  return qk_norm_check(a, 0, &p, &launch) == RFA_OK ? qk_norm_workspace(p) : 0;
 }
 
 int rfa_qk_norm_rotary_bwd(const rfa_qk_norm_rotary_bwd_args* a, void* stream) {
@@ -1909,130 +1945,24 @@ int rfa_qk_norm_rotary_bwd(const rfa_qk_norm_rotary_bwd_args* a, void* stream) {
   bool launch = false;
   int rc = qk_norm_check(a, 1, &p, &launch);
   if (rc != RFA_OK || !launch) return rc;
-  bool any = false;
-  for (int k = 0; k < a->ntensors; ++k) {
-    if (!a->g[k].dout) return RFA_ERR_NULL;
-    any = any || a->dweight[k] != nullptr;
-  }
-  if (any && !a->workspace) return RFA_ERR_NULL;
-  if ((rc = qk_norm_check_rest(a)) != RFA_OK) return rc;
-  for (int k = 0; k < a->ntensors; ++k) {
-    const rfa_qk_norm_grad& g = a->g[k];
-    if (!aligned16(g.dout) || (g.dout_batch % 8) || (g.dout_row % 8) || (g.dout_head % 8)) return RFA_ERR_ALIGN;
-    if (a->dweight[k] && ((uintptr_t)a->dweight[k] % 4) != 0) return RFA_ERR_ALIGN;
-  }
-  if (any && !aligned16(a->workspace)) return RFA_ERR_ALIGN;
-  if ((rc = qk_norm_check_map(a, &p)) != RFA_OK) return rc;
-  for (int k = 0; k < a->ntensors; ++k) {
-    if (a->t[k].dst == a->g[k].dout) return RFA_ERR_ARGS;
-    p.dout[k] = a->g[k].dout;
-    p.t[k].gb = a->g[k].dout_batch; p.t[k].gr = a->g[k].dout_row; p.t[k].gh = a->g[k].dout_head;
-    p.dweight[k] = a->dweight[k];
-  }
-  if (any && a->workspace_bytes < qknorm_workspace_bytes(1, p.nparts[0] + p.nparts[1], p.g.D)) return RFA_ERR_ARGS;
-  p.workspace = (float*)a->workspace;
+  if ((rc = qk_bwd_tail(a, &p, qk_norm_workspace)) != RFA_OK) return rc;
   return launch_qknorm_bwd(p, a->dtype, a->table_dtype == RFA_ROTARY_TABLE_F32, a->weight_dtype == RFA_QK_NORM_WEIGHT_F32,
                            (hipStream_t)stream) ? RFA_ERR_LAUNCH : RFA_OK;
 }
-
-// ---- token-wide QK RMSNorm + rotary (rfa.h; csrc/rfa_qktoken.hip) -------------------------------------------------------------
-static_assert(RFA_QK_TOKEN_NORM_MAX_WIDTH == kQkTokenMaxWidth && RFA_QK_TOKEN_NORM_MAX_PARTS == kQkTokenMaxParts,
-              "rfa.h and rfa_qktoken_index.h state the same limits");
-extern "C++" {
-// the checks the forward and the backward struct share, in the header's order: `upto` 0 stops in front of "no rows" (everything
-// that needs no pointer: what the workspace size depends on), 1 runs them all.  RFA_OK with *launch == false: nothing to do.
-template <typename A>
-static int qk_token_check(const A* a, int upto, QkTokenParams* p, bool* launch) {
-  *launch = false;
-  if (!a) return RFA_ERR_NULL;
-  if (a->struct_bytes != sizeof(A) || a->reserved != 0) return RFA_ERR_ARGS;
-  if (a->ntensors < 1 || a->ntensors > 2) return RFA_ERR_ARGS;
-  if (a->interleaved < 0 || a->interleaved > 1) return RFA_ERR_ARGS;
-  for (int k = 0; k < a->ntensors; ++k)
-    if (a->t[k].pad != 0) return RFA_ERR_ARGS;
-  if (!(a->eps >= 0.f) || !(a->eps <= FLT_MAX) || !(a->weight_offset >= -FLT_MAX && a->weight_offset <= FLT_MAX)) return RFA_ERR_ARGS;
-  if (a->dtype != RFA_BF16 && a->dtype != RFA_F16) return RFA_ERR_DTYPE;
-  if (a->table_dtype != a->dtype && a->table_dtype != RFA_ROTARY_TABLE_F32) return RFA_ERR_DTYPE;
-  if (a->weight_dtype != a->dtype && a->weight_dtype != RFA_QK_NORM_WEIGHT_F32) return RFA_ERR_DTYPE;
-  if (a->D <= 0 || a->D > kMaxHeadDim || (a->D % 8) != 0) return RFA_ERR_HEAD_DIM;
-  if (a->R < 0 || (a->R % (a->interleaved ? 8 : 16)) != 0) return RFA_ERR_HEAD_DIM;
-  if (a->rot_offset < 0 || (a->rot_offset % 8) != 0 || a->rot_offset > a->D - a->R) return RFA_ERR_HEAD_DIM;
-  if (a->B < 0 || a->S < 0 || (a->R > 0 && a->P < 1)) return RFA_ERR_SHAPE;
-  const int64_t rows = (int64_t)a->B * a->S;
-  if (rows > INT32_MAX) return RFA_ERR_SHAPE;
-  for (int k = 0; k < a->ntensors; ++k)
-    if (a->t[k].H <= 0 || (int64_t)a->t[k].H * a->D > kQkTokenMaxWidth) return RFA_ERR_HEADS;
-  QkTokenGeom& g = p->g;
-  g.B = (uint32_t)a->B; g.S = (uint32_t)a->S; g.D = (uint32_t)a->D; g.R = (uint32_t)a->R; g.rot_off = (uint32_t)a->rot_offset;
-  g.interleaved = a->interleaved; g.hchunks = g.D / 8;
-  p->ntensors = a->ntensors;
-  for (int k = 0; k < a->ntensors; ++k) {
-    const rfa_rotary_tensor& s = a->t[k];
-    QkTokenTensor& t = p->t[k];
-    t.xb = s.src_batch; t.xr = s.src_row; t.xh = s.src_head;
-    t.ob = s.dst_batch; t.orow = s.dst_row; t.oh = s.dst_head;
-    t.H = (uint32_t)s.H; t.N = t.H * g.D; t.chunks = t.N / 8; t.team = qktoken_team(t.N); t.rows = (uint32_t)rows;
-    p->x[k] = s.src; p->out[k] = s.dst; p->weight[k] = a->weight[k];
-    p->nparts[k] = qktoken_parts(t.rows, t.team);
-    p->walk[k] = qktoken_walk(t.rows, p->nparts[k], t.team);
-  }
-  p->eps = a->eps; p->weight_offset = a->weight_offset;
-  p->table_f32 = a->table_dtype == RFA_ROTARY_TABLE_F32; p->weight_f32 = a->weight_dtype == RFA_QK_NORM_WEIGHT_F32;
-  if (a->B == 0 || a->S == 0 || upto == 0) return RFA_OK;
-  *launch = true;
-  for (int k = 0; k < a->ntensors; ++k)
-    if (!a->t[k].src || !a->t[k].dst || !a->weight[k]) return RFA_ERR_NULL;
-  if (a->R > 0 && (!a->cos || !a->sin)) return RFA_ERR_NULL;
-  return RFA_OK;
-}
-
-// the map and the table fields behind the alignment checks (qk_norm_check_rest serves both norms)
-template <typename A>
-static int qk_token_check_map(const A* a, QkTokenParams* p) {
-  for (int k = 0; k < a->ntensors; ++k)
-    if (a->t[k].dst == a->t[k].src) return RFA_ERR_ARGS;
-  if (a->pos_batch < 0) return RFA_ERR_ARGS;
-  const uint32_t stride = a->pos_stride > 0 ? (uint32_t)a->pos_stride : 1u;
-  if (a->R > 0 && !a->positions) {
-    if (a->pos_stride < 0 || a->pos_split < 0 || a->pos_split > a->S - 1) return RFA_ERR_ARGS;
-    const uint32_t ends[4] = {0u, (uint32_t)(a->pos_split ? a->pos_split - 1 : a->S - 1), (uint32_t)a->pos_split, (uint32_t)(a->S - 1)};
-    if (a->pos_offset < -(1ll << 40) || a->pos_offset > (1ll << 40) || a->pos_offset2 < -(1ll << 40) || a->pos_offset2 > (1ll << 40))
-      return RFA_ERR_ARGS;
-    for (int e = 0; e < 4; ++e) {
-      const int64_t pos = rotary_map_pos(a->pos_offset, stride, a->pos_split, a->pos_offset2, ends[e]);
-      if (pos < 0 || pos > a->P - 1) return RFA_ERR_ARGS;
-    }
-  }
-  if (a->R > 0) {
-    p->cos = a->cos; p->sin = a->sin; p->P = a->P;
-    p->positions = a->positions; p->pos_batch = a->pos_batch;
-    p->pos_off = a->pos_offset; p->pos_off2 = a->pos_offset2; p->pos_stride = stride; p->pos_split = a->pos_split;
-  }
-  return RFA_OK;
-}
-
-static int64_t qk_token_workspace(const QkTokenParams& p) {
-  int64_t bytes = 0;
-  for (int k = 0; k < p.ntensors; ++k) bytes += qktoken_workspace_bytes(p.nparts[k], p.t[k].N);
-  return bytes;
-}
-}  // extern "C++"
 
 int rfa_qk_token_norm_rotary_fwd(const rfa_qk_token_norm_rotary_args* a, void* stream) {
   QkTokenParams p{};
   bool launch = false;
   int rc = qk_token_check(a, 1, &p, &launch);
   if (rc != RFA_OK || !launch) return rc;
-  if ((rc = qk_norm_check_rest(a)) != RFA_OK) return rc;
-  if ((rc = qk_token_check_map(a, &p)) != RFA_OK) return rc;
+  if ((rc = qk_check_aligned(a)) != RFA_OK || (rc = qk_check_map(a, &p)) != RFA_OK) return rc;
   return launch_qktoken_fwd(p, a->dtype, (hipStream_t)stream) ? RFA_ERR_LAUNCH : RFA_OK;
 }
 
 int64_t rfa_qk_token_norm_rotary_bwd_workspace_bytes(const rfa_qk_token_norm_rotary_bwd_args* a) {
   QkTokenParams p{};
   bool launch = false;
-  if (qk_token_check(a, 0, &p, &launch) != RFA_OK) return 0;
-  return qk_token_workspace(p);
+  return qk_token_check(a, 0, &p, &launch) == RFA_OK ? qk_token_workspace(p) : 0;
 }
 
 int rfa_qk_token_norm_rotary_bwd(const rfa_qk_token_norm_rotary_bwd_args* a, void* stream) {
@@ -2040,28 +1970,7 @@ int rfa_qk_token_norm_rotary_bwd(const rfa_qk_token_norm_rotary_bwd_args* a, voi
   bool launch = false;
   int rc = qk_token_check(a, 1, &p, &launch);
   if (rc != RFA_OK || !launch) return rc;
-  bool any = false;
-  for (int k = 0; k < a->ntensors; ++k) {
-    if (!a->g[k].dout) return RFA_ERR_NULL;
-    any = any || a->dweight[k] != nullptr;
-  }
-  if (any && !a->workspace) return RFA_ERR_NULL;
-  if ((rc = qk_norm_check_rest(a)) != RFA_OK) return rc;
-  for (int k = 0; k < a->ntensors; ++k) {
-    const rfa_qk_norm_grad& g = a->g[k];
-    if (!aligned16(g.dout) || (g.dout_batch % 8) || (g.dout_row % 8) || (g.dout_head % 8)) return RFA_ERR_ALIGN;
-    if (a->dweight[k] && ((uintptr_t)a->dweight[k] % 4) != 0) return RFA_ERR_ALIGN;
-  }
-  if (any && !aligned16(a->workspace)) return RFA_ERR_ALIGN;
-  if ((rc = qk_token_check_map(a, &p)) != RFA_OK) return rc;
-  for (int k = 0; k < a->ntensors; ++k) {
-    if (a->t[k].dst == a->g[k].dout) return RFA_ERR_ARGS;
-    p.dout[k] = a->g[k].dout;
-    p.t[k].gb = a->g[k].dout_batch; p.t[k].gr = a->g[k].dout_row; p.t[k].gh = a->g[k].dout_head;
-    p.dweight[k] = a->dweight[k];
-  }
-  if (any && a->workspace_bytes < qk_token_workspace(p)) return RFA_ERR_ARGS;
-  p.workspace = (float*)a->workspace;
+  if ((rc = qk_bwd_tail(a, &p, qk_token_workspace)) != RFA_OK) return rc;
   return launch_qktoken_bwd(p, a->dtype, (hipStream_t)stream) ? RFA_ERR_LAUNCH : RFA_OK;
 }
 

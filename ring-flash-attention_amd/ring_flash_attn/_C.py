@@ -25,6 +25,15 @@ class Strides(C.Structure):
     _fields_ = [("batch", C.c_int64), ("row", C.c_int64), ("head", C.c_int64)]
 
 
+class _SizedStructure(C.Structure):
+    """base of every struct whose first field is `struct_bytes`: filled in with the struct's own size unless the caller set it"""
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if not self.struct_bytes:
+            self.struct_bytes = C.sizeof(type(self))
+
+
 class FwdArgs(C.Structure):
     _fields_ = [
         ("q", C.c_void_p), ("k", C.c_void_p), ("v", C.c_void_p),
@@ -106,7 +115,7 @@ class BwdArgs(C.Structure):
     ]
 
 
-class ExtArgs(C.Structure):
+class ExtArgs(_SizedStructure):
     """rfa_ext_args: per-call features added after the ABI 8 structs were frozen (ALiBi, the soft cap); struct_bytes is
     filled in here"""
     _fields_ = [
@@ -114,11 +123,6 @@ class ExtArgs(C.Structure):
         ("alibi_slopes", C.c_void_p), ("alibi_batch_stride", C.c_int64), ("alibi_shift", C.c_int64),
         ("softcap", C.c_float), ("softcap_pad", C.c_uint32),
     ]
-
-    def __init__(self, *args, **kw):
-        super().__init__(*args, **kw)
-        if not self.struct_bytes:
-            self.struct_bytes = C.sizeof(ExtArgs)
 
 
 class MergeArgs(C.Structure):
@@ -183,7 +187,7 @@ class SeqHeadTensor(C.Structure):
     ]
 
 
-class SeqHeadArgs(C.Structure):
+class SeqHeadArgs(_SizedStructure):
     """rfa_seq_head_args: the layout change on either side of the Ulysses all-to-all; struct_bytes is filled in here"""
     _fields_ = [
         ("struct_bytes", C.c_uint32), ("reserved", C.c_uint32),
@@ -193,11 +197,6 @@ class SeqHeadArgs(C.Structure):
         ("t", SeqHeadTensor * 3),
         ("slots", C.c_void_p), ("slots_elems", C.c_int64),
     ]
-
-    def __init__(self, *args, **kw):
-        super().__init__(*args, **kw)
-        if not self.struct_bytes:
-            self.struct_bytes = C.sizeof(SeqHeadArgs)
 
 
 ROTARY_TABLE_F32 = 2              # RFA_ROTARY_TABLE_F32: fp32 cos / sin tables (otherwise the io dtype's code)
@@ -213,7 +212,7 @@ class RotaryTensor(C.Structure):
     ]
 
 
-class RotaryArgs(C.Structure):
+class RotaryArgs(_SizedStructure):
     """rfa_rotary_args: rotary position embedding of up to two tensors at global positions; struct_bytes is filled in here"""
     _fields_ = [
         ("struct_bytes", C.c_uint32), ("reserved", C.c_uint32),
@@ -232,13 +231,8 @@ class RotaryArgs(C.Structure):
         ("pos_offset2", C.c_int64),
     ]
 
-    def __init__(self, *args, **kw):
-        super().__init__(*args, **kw)
-        if not self.struct_bytes:
-            self.struct_bytes = C.sizeof(RotaryArgs)
 
-
-class RotaryFreqsArgs(C.Structure):
+class RotaryFreqsArgs(_SizedStructure):
     """rfa_rotary_freqs_args: rotary embedding with the angles formed in the kernel (inv_freq, one to four position axes);
     struct_bytes is filled in here"""
     _fields_ = [
@@ -258,11 +252,6 @@ class RotaryFreqsArgs(C.Structure):
         ("pos_stride", C.c_int32), ("pos_split", C.c_int32),
         ("pos_offset2", C.c_int64),
     ]
-
-    def __init__(self, *args, **kw):
-        super().__init__(*args, **kw)
-        if not self.struct_bytes:
-            self.struct_bytes = C.sizeof(RotaryFreqsArgs)
 
 
 QK_NORM_WEIGHT_F32 = 2            # RFA_QK_NORM_WEIGHT_F32: fp32 norm weights (otherwise the io dtype's code)
@@ -287,14 +276,9 @@ _QK_NORM_HEAD = [
 ]
 
 
-class QkNormRotaryArgs(C.Structure):
+class QkNormRotaryArgs(_SizedStructure):
     """rfa_qk_norm_rotary_args: per-head RMSNorm + rotary of up to two tensors, forward; struct_bytes is filled in here"""
     _fields_ = list(_QK_NORM_HEAD)
-
-    def __init__(self, *args, **kw):
-        super().__init__(*args, **kw)
-        if not self.struct_bytes:
-            self.struct_bytes = C.sizeof(QkNormRotaryArgs)
 
 
 class QkNormGrad(C.Structure):
@@ -302,49 +286,33 @@ class QkNormGrad(C.Structure):
     _fields_ = [("dout", C.c_void_p), ("dout_batch", C.c_int64), ("dout_row", C.c_int64), ("dout_head", C.c_int64)]
 
 
-class QkNormRotaryBwdArgs(C.Structure):
-    """rfa_qk_norm_rotary_bwd_args: the forward's fields, then the gradients, dweight and the workspace"""
-    _fields_ = list(_QK_NORM_HEAD) + [
-        ("g", QkNormGrad * 2),
-        ("dweight", C.c_void_p * 2),
-        ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
-    ]
+_QK_NORM_TAIL = [
+    ("g", QkNormGrad * 2),
+    ("dweight", C.c_void_p * 2),
+    ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+]
 
-    def __init__(self, *args, **kw):
-        super().__init__(*args, **kw)
-        if not self.struct_bytes:
-            self.struct_bytes = C.sizeof(QkNormRotaryBwdArgs)
+
+class QkNormRotaryBwdArgs(_SizedStructure):
+    """rfa_qk_norm_rotary_bwd_args: the forward's fields, then the gradients, dweight and the workspace"""
+    _fields_ = _QK_NORM_HEAD + _QK_NORM_TAIL
 
 
 QK_TOKEN_NORM_MAX_WIDTH = 16384   # RFA_QK_TOKEN_NORM_MAX_WIDTH: H * D of one tensor of the token-wide norm
 
 
-class QkTokenNormRotaryArgs(C.Structure):
+class QkTokenNormRotaryArgs(_SizedStructure):
     """rfa_qk_token_norm_rotary_args: RMSNorm over all heads of a token + rotary of up to two tensors, forward (the per-head
     struct's fields; weight[k] is (H_k * D,)); struct_bytes is filled in here"""
     _fields_ = list(_QK_NORM_HEAD)
 
-    def __init__(self, *args, **kw):
-        super().__init__(*args, **kw)
-        if not self.struct_bytes:
-            self.struct_bytes = C.sizeof(QkTokenNormRotaryArgs)
 
-
-class QkTokenNormRotaryBwdArgs(C.Structure):
+class QkTokenNormRotaryBwdArgs(_SizedStructure):
     """rfa_qk_token_norm_rotary_bwd_args: the forward's fields, then the gradients, dweight and the workspace"""
-    _fields_ = list(_QK_NORM_HEAD) + [
-        ("g", QkNormGrad * 2),
-        ("dweight", C.c_void_p * 2),
-        ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
-    ]
-
-    def __init__(self, *args, **kw):
-        super().__init__(*args, **kw)
-        if not self.struct_bytes:
-            self.struct_bytes = C.sizeof(QkTokenNormRotaryBwdArgs)
+    _fields_ = _QK_NORM_HEAD + _QK_NORM_TAIL
 
 
-class MaxLogitArgs(C.Structure):
+class MaxLogitArgs(_SizedStructure):
     """rfa_max_logit_args: the per-head max attention logit of one block call; struct_bytes is filled in here"""
     _fields_ = [
         ("struct_bytes", C.c_uint32), ("reserved", C.c_uint32),
@@ -364,11 +332,6 @@ class MaxLogitArgs(C.Structure):
         ("max_logit", C.c_void_p),
         ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
     ]
-
-    def __init__(self, *args, **kw):
-        super().__init__(*args, **kw)
-        if not self.struct_bytes:
-            self.struct_bytes = C.sizeof(MaxLogitArgs)
 
 
 class BwdPreLseArgs(C.Structure):
@@ -417,20 +380,15 @@ class MergePairBwdArgs(C.Structure):
     ]
 
 
-class VdimArgs(C.Structure):
+class VdimArgs(_SizedStructure):
     """rfa_vdim_args: the V head dim of a call whose QK head dim (the base struct's D) differs; struct_bytes is filled in here"""
     _fields_ = [
         ("struct_bytes", C.c_uint32), ("reserved", C.c_uint32),
         ("head_dim_v", C.c_int32), ("pad", C.c_int32),
     ]
 
-    def __init__(self, *args, **kw):
-        super().__init__(*args, **kw)
-        if not self.struct_bytes:
-            self.struct_bytes = C.sizeof(VdimArgs)
 
-
-class RowRangeArgs(C.Structure):
+class RowRangeArgs(_SizedStructure):
     """rfa_rowrange_args: per-row key ranges of a block call (start / end: int32 (B, Sq) global key positions, k_pos0: the
     global position of the block's key row 0, tile_bounds: the backward's workspace); struct_bytes is filled in here"""
     _fields_ = [
@@ -440,16 +398,11 @@ class RowRangeArgs(C.Structure):
         ("tile_bounds", C.c_void_p),
     ]
 
-    def __init__(self, *args, **kw):
-        super().__init__(*args, **kw)
-        if not self.struct_bytes:
-            self.struct_bytes = C.sizeof(RowRangeArgs)
-
 
 BLOCK_MASK_SIZE = 128             # RFA_BLOCK_MASK_SIZE: query rows / keys per byte of a block mask
 
 
-class BlockMaskArgs(C.Structure):
+class BlockMaskArgs(_SizedStructure):
     """rfa_blockmask_args: the block-sparse mask of a block call (mask: uint8 (Bm, Hm, nq, nk_blocks), one byte per pair of
     128 query rows and 128 keys; the strides in bytes, 0 = broadcast; k_blk0: the column of the block's key row 0);
     struct_bytes is filled in here"""
@@ -460,11 +413,6 @@ class BlockMaskArgs(C.Structure):
         ("nk_blocks", C.c_int64), ("k_blk0", C.c_int64),
         ("workspace", C.c_void_p),
     ]
-
-    def __init__(self, *args, **kw):
-        super().__init__(*args, **kw)
-        if not self.struct_bytes:
-            self.struct_bytes = C.sizeof(BlockMaskArgs)
 
 
 # every symbol include/rfa.h declares: name -> (restype, argtypes)

@@ -696,6 +696,47 @@ class HipBackend:
             raise ValueError("seq_head_copy: the slot buffer must be contiguous")
         _C.check(self.lib.rfa_seq_head_copy(C.byref(a), _stream(slots)), "rfa_seq_head_copy")
 
+    # ------------------------------------------------------------------ the row operators: what their argument structs share
+    def _row_tensors(self, a, refusal, srcs, dsts):
+        """a.ntensors, a.B, a.S, a.D, a.dtype and a.t[k] of a row operator's struct: the pointers, heads and element strides of
+        what is read (srcs) and written (dsts); ValueError(refusal) for a tensor off the contract.  Returns `packed`."""
+        t0 = srcs[0]
+        packed = t0.dim() == 3
+        a.ntensors = len(srcs)
+        a.B, a.S = (1, t0.shape[0]) if packed else (t0.shape[0], t0.shape[1])
+        a.D, a.dtype = t0.shape[-1], self._dtype(t0)
+        for d, s, o in zip(a.t, srcs, dsts):
+            if s.dtype != t0.dtype or o.dtype != t0.dtype or s.shape != o.shape or s.stride(-1) != 1 or o.stride(-1) != 1:
+                raise ValueError(refusal)
+            d.src, d.dst, d.H = s.data_ptr(), o.data_ptr(), s.shape[-2]
+            # (the stride of a dimension of length 1 is never used: 0, whatever torch reports for it)
+            ss, os_ = ([st if n > 1 else 0 for n, st in zip(t.shape, t.stride())] for t in (s, o))
+            d.src_batch, d.src_row, d.src_head = (0 if packed else ss[0]), ss[-3], ss[-2]
+            d.dst_batch, d.dst_row, d.dst_head = (0 if packed else os_[0]), os_[-3], os_[-2]
+        return packed
+
+    def _row_tables(self, a, who, cos, sin):
+        """a.R, a.P, a.cos, a.sin, a.table_dtype from the (P, R/2) tables"""
+        if not cos.is_contiguous() or not sin.is_contiguous() or cos.shape != sin.shape or cos.dtype != sin.dtype:
+            raise ValueError(f"{who}: cos and sin are contiguous (P, R/2) tensors of one shape and dtype")
+        a.R, a.P = 2 * cos.shape[1], cos.shape[0]
+        a.cos, a.sin = cos.data_ptr(), sin.data_ptr()
+        a.table_dtype = _C.ROTARY_TABLE_F32 if cos.dtype == torch.float32 else self._dtype(cos)
+
+    @staticmethod
+    def _row_positions(a, who, positions, pos_map):
+        """a.pos_offset, then a.positions / a.pos_batch of an int32 (S,) / (B,S) / (T,) tensor, or the other three numbers of
+        pos_map = (offset, (stride, split, offset2)) (_common.pos_map)"""
+        off, (stride, split, off2) = pos_map if pos_map is not None else (0, (1, 0, 0))
+        a.pos_offset = int(off)
+        if positions is None:
+            a.pos_stride, a.pos_split, a.pos_offset2 = int(stride), int(split), int(off2)
+            return
+        if positions.dtype != torch.int32 or (positions.stride(-1) != 1 and positions.shape[-1] != 1):
+            raise ValueError(f"{who}: positions are int32 with row stride 1")
+        a.positions = positions.data_ptr()
+        a.pos_batch = positions.stride(0) if positions.dim() == 2 and positions.shape[0] > 1 else 0
+
     # ------------------------------------------------------------------ rotary embedding (apply_rotary)
     def rotary(self, srcs, dsts, cos, sin, *, positions=None, pos_map=None, interleaved=False, rot_offset=0, conj=False):
         """one launch of the rotary embedding (include/rfa.h: rfa_rotary) for one or two tensors that share rows and positions.
@@ -704,36 +745,13 @@ class HipBackend:
         row stride 1, to which pos_map's offset is added — or None: the rows sit at pos_map = (offset, (stride, split,
         offset2)) (_common.pos_map).  conj: the inverse rotation (the backward)."""
         self._check_dev(cos, sin, positions, *srcs, *dsts)
-        t0 = srcs[0]
-        packed = t0.dim() == 3
         a = _C.RotaryArgs()
-        a.ntensors = len(srcs)
-        a.B, a.S = (1, t0.shape[0]) if packed else (t0.shape[0], t0.shape[1])
-        a.D, a.dtype = t0.shape[-1], self._dtype(t0)
-        a.R, a.rot_offset = 2 * cos.shape[1], int(rot_offset)
-        a.interleaved, a.conj = int(bool(interleaved)), int(bool(conj))
-        a.table_dtype = _C.ROTARY_TABLE_F32 if cos.dtype == torch.float32 else self._dtype(cos)
-        if not cos.is_contiguous() or not sin.is_contiguous() or cos.shape != sin.shape or cos.dtype != sin.dtype:
-            raise ValueError("rotary: cos and sin are contiguous (P, R/2) tensors of one shape and dtype")
-        for d, s, o in zip(a.t, srcs, dsts):
-            if s.dtype != t0.dtype or o.dtype != t0.dtype or s.shape != o.shape or s.stride(-1) != 1 or o.stride(-1) != 1:
-                raise ValueError("rotary: sources and destinations share one dtype and shape; last (head_dim) stride must be 1")
-            d.src, d.dst, d.H = s.data_ptr(), o.data_ptr(), s.shape[-2]
-            # (the stride of a dimension of length 1 is never used: 0, whatever torch reports for it)
-            ss, os_ = ([st if n > 1 else 0 for n, st in zip(t.shape, t.stride())] for t in (s, o))
-            d.src_batch, d.src_row, d.src_head = (0 if packed else ss[0]), ss[-3], ss[-2]
-            d.dst_batch, d.dst_row, d.dst_head = (0 if packed else os_[0]), os_[-3], os_[-2]
-        a.cos, a.sin, a.P = cos.data_ptr(), sin.data_ptr(), cos.shape[0]
-        off, (stride, split, off2) = pos_map if pos_map is not None else (0, (1, 0, 0))
-        a.pos_offset = int(off)
-        if positions is not None:
-            if positions.dtype != torch.int32 or (positions.stride(-1) != 1 and positions.shape[-1] != 1):
-                raise ValueError("rotary: positions are int32 with row stride 1")
-            a.positions = positions.data_ptr()
-            a.pos_batch = positions.stride(0) if positions.dim() == 2 and positions.shape[0] > 1 else 0
-        else:
-            a.pos_stride, a.pos_split, a.pos_offset2 = int(stride), int(split), int(off2)
-        _C.check(self.lib.rfa_rotary(C.byref(a), _stream(t0)), "rfa_rotary")
+        self._row_tensors(a, "rotary: sources and destinations share one dtype and shape; last (head_dim) stride must be 1",
+                          srcs, dsts)
+        self._row_tables(a, "rotary", cos, sin)
+        a.rot_offset, a.interleaved, a.conj = int(rot_offset), int(bool(interleaved)), int(bool(conj))
+        self._row_positions(a, "rotary", positions, pos_map)
+        _C.check(self.lib.rfa_rotary(C.byref(a), _stream(srcs[0])), "rfa_rotary")
 
     # ------------------------------------------------------------------ rotary embedding, angles in the kernel (apply_rotary_freqs)
     def rotary_freqs(self, srcs, dsts, inv_freq, *, scaling=1.0, freq_axis=None, positions=None, pos_map=None, interleaved=False,
@@ -744,28 +762,15 @@ class HipBackend:
         sequence of R/2 axis numbers: positions int32 (A,S) / (A,B,S) / (A,T), A <= 4, and frequency c reads axis freq_axis[c].
         pos_map's offset is added to tensor positions.  conj: the inverse rotation (the backward)."""
         self._check_dev(inv_freq, positions, *srcs, *dsts)
-        t0 = srcs[0]
-        packed = t0.dim() == 3
         a = _C.RotaryFreqsArgs()
-        a.ntensors = len(srcs)
-        a.B, a.S = (1, t0.shape[0]) if packed else (t0.shape[0], t0.shape[1])
-        a.D, a.dtype = t0.shape[-1], self._dtype(t0)
         if inv_freq.dtype != torch.float32 or inv_freq.dim() != 1 or not inv_freq.is_contiguous():
             raise ValueError("rotary_freqs: inv_freq is a contiguous fp32 (R/2,) tensor")
         half = inv_freq.shape[0]
+        self._row_tensors(a, "rotary_freqs: sources and destinations share one dtype and shape; last (head_dim) stride must be 1",
+                          srcs, dsts)
         a.R, a.rot_offset = 2 * half, int(rot_offset)
         a.interleaved, a.conj = int(bool(interleaved)), int(bool(conj))
         a.inv_freq, a.scaling = inv_freq.data_ptr(), float(scaling)
-        for d, s, o in zip(a.t, srcs, dsts):
-            if s.dtype != t0.dtype or o.dtype != t0.dtype or s.shape != o.shape or s.stride(-1) != 1 or o.stride(-1) != 1:
-                raise ValueError("rotary_freqs: sources and destinations share one dtype and shape; last (head_dim) stride must be 1")
-            d.src, d.dst, d.H = s.data_ptr(), o.data_ptr(), s.shape[-2]
-            # (the stride of a dimension of length 1 is never used: 0, whatever torch reports for it)
-            ss, os_ = ([st if n > 1 else 0 for n, st in zip(t.shape, t.stride())] for t in (s, o))
-            d.src_batch, d.src_row, d.src_head = (0 if packed else ss[0]), ss[-3], ss[-2]
-            d.dst_batch, d.dst_row, d.dst_head = (0 if packed else os_[0]), os_[-3], os_[-2]
-        off, (stride, split, off2) = pos_map if pos_map is not None else (0, (1, 0, 0))
-        a.pos_offset = int(off)
         a.naxes = 1
         if freq_axis is not None:
             if positions is None or positions.dim() < 2 or len(freq_axis) != half or half > 128:
@@ -775,60 +780,60 @@ class HipBackend:
                 if not 0 <= int(ax) < 4:                           # (what 2 bits hold; rfa_rotary_freqs refuses a code >= naxes)
                     raise ValueError(f"rotary_freqs: freq_axis[{c}] = {ax} is no axis code (0 .. 3)")
                 a.freq_axis[c // 32] |= int(ax) << (2 * (c % 32))
-        if positions is not None:
-            if positions.dtype != torch.int32 or (positions.stride(-1) != 1 and positions.shape[-1] != 1):
-                raise ValueError("rotary_freqs: positions are int32 with row stride 1")
-            a.positions = positions.data_ptr()
-            rest = positions if freq_axis is None else positions[0]
-            a.pos_axis = positions.stride(0) if freq_axis is not None and positions.shape[0] > 1 else 0
-            a.pos_batch = rest.stride(0) if rest.dim() == 2 and rest.shape[0] > 1 else 0
-        else:
-            a.pos_stride, a.pos_split, a.pos_offset2 = int(stride), int(split), int(off2)
-        _C.check(self.lib.rfa_rotary_freqs(C.byref(a), _stream(t0)), "rfa_rotary_freqs")
+            a.pos_axis = positions.stride(0) if positions.shape[0] > 1 else 0
+            positions = positions[0]                               # (axis 0: the same first element, the shape of one axis)
+        self._row_positions(a, "rotary_freqs", positions, pos_map)
+        _C.check(self.lib.rfa_rotary_freqs(C.byref(a), _stream(srcs[0])), "rfa_rotary_freqs")
 
-    # ------------------------------------------------------------------ QK RMSNorm + rotary (apply_qk_norm_rotary)
-    def _qk_norm_args(self, a, xs, outs, weights, cos, sin, positions, pos_map, interleaved, rot_offset, eps, weight_offset):
-        """the fields rfa_qk_norm_rotary_args and rfa_qk_norm_rotary_bwd_args share"""
+    # ------------------------------------------------------------------ QK RMSNorm + rotary (apply_qk_norm_rotary, apply_qk_token_norm_rotary)
+    def _qk_norm_args(self, a, xs, outs, weights, cos, sin, positions, pos_map, interleaved, rot_offset, eps, weight_offset,
+                      weight_numel=None):
+        """the fields the forward and the backward struct of either norm share.  weight_numel: the elements of each tensor's 1-d
+        weight (None: D, the per-head norm's)"""
         self._check_dev(cos, sin, positions, *xs, *outs, *weights)
-        t0 = xs[0]
-        packed = t0.dim() == 3
-        a.ntensors = len(xs)
-        a.B, a.S = (1, t0.shape[0]) if packed else (t0.shape[0], t0.shape[1])
-        a.D, a.dtype = t0.shape[-1], self._dtype(t0)
+        packed = self._row_tensors(a, "qk_norm_rotary: inputs and outputs share one dtype and shape; last (head_dim) stride "
+                                      "must be 1", xs, outs)
         a.rot_offset, a.interleaved = int(rot_offset), int(bool(interleaved))
         a.eps, a.weight_offset = float(eps), float(weight_offset)
         if (cos is None) != (sin is None):
             raise ValueError("qk_norm_rotary: cos and sin come together (both None: the norm alone)")
         if cos is not None:
-            if not cos.is_contiguous() or not sin.is_contiguous() or cos.shape != sin.shape or cos.dtype != sin.dtype:
-                raise ValueError("qk_norm_rotary: cos and sin are contiguous (P, R/2) tensors of one shape and dtype")
-            a.R, a.P = 2 * cos.shape[1], cos.shape[0]
-            a.cos, a.sin = cos.data_ptr(), sin.data_ptr()
-            a.table_dtype = _C.ROTARY_TABLE_F32 if cos.dtype == torch.float32 else self._dtype(cos)
+            self._row_tables(a, "qk_norm_rotary", cos, sin)
         else:
             a.table_dtype = a.dtype
         w0 = weights[0]
         a.weight_dtype = _C.QK_NORM_WEIGHT_F32 if w0.dtype == torch.float32 else self._dtype(w0)
-        for k, (d, s, o, w) in enumerate(zip(a.t, xs, outs, weights)):
-            if s.dtype != t0.dtype or o.dtype != t0.dtype or s.shape != o.shape or s.stride(-1) != 1 or o.stride(-1) != 1:
-                raise ValueError("qk_norm_rotary: inputs and outputs share one dtype and shape; last (head_dim) stride must be 1")
-            if w.dtype != w0.dtype or tuple(w.shape) != (a.D,) or not w.is_contiguous():
+        for k, w in enumerate(weights):
+            if w.dtype != w0.dtype or tuple(w.shape) != (weight_numel[k] if weight_numel else a.D,) or not w.is_contiguous():
                 raise ValueError("qk_norm_rotary: the weights are contiguous (D,) tensors of one dtype")
-            d.src, d.dst, d.H = s.data_ptr(), o.data_ptr(), s.shape[-2]
             a.weight[k] = w.data_ptr()
-            ss, os_ = ([st if n > 1 else 0 for n, st in zip(t.shape, t.stride())] for t in (s, o))
-            d.src_batch, d.src_row, d.src_head = (0 if packed else ss[0]), ss[-3], ss[-2]
-            d.dst_batch, d.dst_row, d.dst_head = (0 if packed else os_[0]), os_[-3], os_[-2]
-        off, (stride, split, off2) = pos_map if pos_map is not None else (0, (1, 0, 0))
-        a.pos_offset = int(off)
-        if positions is not None:
-            if positions.dtype != torch.int32 or (positions.stride(-1) != 1 and positions.shape[-1] != 1):
-                raise ValueError("qk_norm_rotary: positions are int32 with row stride 1")
-            a.positions = positions.data_ptr()
-            a.pos_batch = positions.stride(0) if positions.dim() == 2 and positions.shape[0] > 1 else 0
-        else:
-            a.pos_stride, a.pos_split, a.pos_offset2 = int(stride), int(split), int(off2)
+        self._row_positions(a, "qk_norm_rotary", positions, pos_map)
         return packed
+
+    def _qk_norm_bwd(self, a, who, workspace_bytes, bwd, packed, xs, douts, dweights, dweight_ok, dweight_refusal):
+        """the backward of either norm behind _qk_norm_args: a.g[k], a.dweight[k], the workspace, the launch.  workspace_bytes /
+        bwd: the names of the two library symbols; dweight_ok(dw, x): whether dw has the shape of x's weight gradient"""
+        self._check_dev(*douts, *[d for d in dweights if d is not None])
+        for k, (g, x, dw) in enumerate(zip(douts, xs, dweights)):
+            if g.dtype != x.dtype or g.shape != x.shape or g.stride(-1) != 1:
+                raise ValueError(f"{who}: a gradient has its tensor's dtype and shape; last (head_dim) stride must be 1")
+            gs = [st if n > 1 else 0 for n, st in zip(g.shape, g.stride())]
+            a.g[k].dout = g.data_ptr()
+            a.g[k].dout_batch, a.g[k].dout_row, a.g[k].dout_head = (0 if packed else gs[0]), gs[-3], gs[-2]
+            if dw is not None:
+                if dw.dtype != torch.float32 or not dweight_ok(dw, x) or not dw.is_contiguous():
+                    raise ValueError(f"{who}: {dweight_refusal}")
+                a.dweight[k] = dw.data_ptr()
+        ws = None
+        if any(d is not None for d in dweights):
+            need = int(getattr(self.lib, workspace_bytes)(C.byref(a)))
+            ws = torch.empty(max(need, 16), dtype=torch.uint8, device=xs[0].device)
+            a.workspace, a.workspace_bytes = ws.data_ptr(), need
+        _C.check(getattr(self.lib, bwd)(C.byref(a), _stream(xs[0])), bwd)
+        if a.B == 0 or a.S == 0:                                   # (nothing was launched: an empty sum)
+            for dw in dweights:
+                if dw is not None:
+                    dw.zero_()
 
     def qk_norm_rotary_fwd(self, xs, outs, weights, cos, sin, *, positions=None, pos_map=None, interleaved=False, rot_offset=0,
                            eps=1e-6, weight_offset=0.0):
@@ -845,44 +850,19 @@ class HipBackend:
         fp32 (D,) tensor that is overwritten with this call's weight gradient, or None.  The workspace is allocated here."""
         a = _C.QkNormRotaryBwdArgs()
         packed = self._qk_norm_args(a, xs, dxs, weights, cos, sin, positions, pos_map, interleaved, rot_offset, eps, weight_offset)
-        self._check_dev(*douts, *[d for d in dweights if d is not None])
-        for k, (g, x, dw) in enumerate(zip(douts, xs, dweights)):
-            if g.dtype != x.dtype or g.shape != x.shape or g.stride(-1) != 1:
-                raise ValueError("qk_norm_rotary: a gradient has its tensor's dtype and shape; last (head_dim) stride must be 1")
-            gs = [st if n > 1 else 0 for n, st in zip(g.shape, g.stride())]
-            a.g[k].dout = g.data_ptr()
-            a.g[k].dout_batch, a.g[k].dout_row, a.g[k].dout_head = (0 if packed else gs[0]), gs[-3], gs[-2]
-            if dw is not None:
-                if dw.dtype != torch.float32 or tuple(dw.shape) != (a.D,) or not dw.is_contiguous():
-                    raise ValueError("qk_norm_rotary: dweight is a contiguous fp32 (D,) tensor")
-                a.dweight[k] = dw.data_ptr()
-        ws = None
-        if any(d is not None for d in dweights):
-            need = int(self.lib.rfa_qk_norm_rotary_bwd_workspace_bytes(C.byref(a)))
-            ws = torch.empty(max(need, 16), dtype=torch.uint8, device=xs[0].device)
-            a.workspace, a.workspace_bytes = ws.data_ptr(), need
-        _C.check(self.lib.rfa_qk_norm_rotary_bwd(C.byref(a), _stream(xs[0])), "rfa_qk_norm_rotary_bwd")
-        if a.B == 0 or a.S == 0:                                   # (nothing was launched: an empty sum)
-            for dw in dweights:
-                if dw is not None:
-                    dw.zero_()
+        self._qk_norm_bwd(a, "qk_norm_rotary", "rfa_qk_norm_rotary_bwd_workspace_bytes", "rfa_qk_norm_rotary_bwd", packed, xs,
+                          douts, dweights, lambda dw, x: tuple(dw.shape) == (x.shape[-1],), "dweight is a contiguous fp32 (D,) tensor")
 
-    # ------------------------------------------------------------------ token-wide QK RMSNorm + rotary (apply_qk_token_norm_rotary)
     def _qk_token_norm_args(self, a, xs, outs, weights, cos, sin, positions, pos_map, interleaved, rot_offset, eps, weight_offset):
-        """the fields rfa_qk_token_norm_rotary_args and _bwd_args share: the per-head call's, with (H * D,) weights (the view
-        handed to _qk_norm_args stands in for the (D,) check there)"""
+        """the fields rfa_qk_token_norm_rotary_args and _bwd_args share: the per-head call's, with (H * D,) weights"""
         for x, w in zip(xs, weights):
             if w.numel() != x.shape[-2] * x.shape[-1] or not w.is_contiguous() or w.dim() not in (1, 2) or \
                     (w.dim() == 2 and tuple(w.shape) != tuple(x.shape[-2:])):
                 raise ValueError("qk_token_norm_rotary: the weights are contiguous (H * D,) or (H, D) tensors of one dtype")
             if x.shape[-2] * x.shape[-1] > _C.QK_TOKEN_NORM_MAX_WIDTH:
                 raise ValueError(f"qk_token_norm_rotary: H * D is at most {_C.QK_TOKEN_NORM_MAX_WIDTH}")
-        D = xs[0].shape[-1]
-        packed = self._qk_norm_args(a, xs, outs, [w.reshape(-1)[:D] for w in weights], cos, sin, positions, pos_map, interleaved,
-                                    rot_offset, eps, weight_offset)
-        for k, w in enumerate(weights):
-            a.weight[k] = w.data_ptr()
-        return packed
+        return self._qk_norm_args(a, xs, outs, [w.reshape(-1) for w in weights], cos, sin, positions, pos_map, interleaved,
+                                  rot_offset, eps, weight_offset, weight_numel=[x.shape[-2] * x.shape[-1] for x in xs])
 
     def qk_token_norm_rotary_fwd(self, xs, outs, weights, cos, sin, *, positions=None, pos_map=None, interleaved=False,
                                  rot_offset=0, eps=1e-6, weight_offset=0.0):
@@ -901,27 +881,9 @@ class HipBackend:
         a = _C.QkTokenNormRotaryBwdArgs()
         packed = self._qk_token_norm_args(a, xs, dxs, weights, cos, sin, positions, pos_map, interleaved, rot_offset, eps,
                                           weight_offset)
-        self._check_dev(*douts, *[d for d in dweights if d is not None])
-        for k, (g, x, dw) in enumerate(zip(douts, xs, dweights)):
-            if g.dtype != x.dtype or g.shape != x.shape or g.stride(-1) != 1:
-                raise ValueError("qk_token_norm_rotary: a gradient has its tensor's dtype and shape; last (head_dim) stride must be 1")
-            gs = [st if n > 1 else 0 for n, st in zip(g.shape, g.stride())]
-            a.g[k].dout = g.data_ptr()
-            a.g[k].dout_batch, a.g[k].dout_row, a.g[k].dout_head = (0 if packed else gs[0]), gs[-3], gs[-2]
-            if dw is not None:
-                if dw.dtype != torch.float32 or dw.numel() != x.shape[-2] * x.shape[-1] or not dw.is_contiguous():
-                    raise ValueError("qk_token_norm_rotary: dweight is a contiguous fp32 tensor of H * D elements")
-                a.dweight[k] = dw.data_ptr()
-        ws = None
-        if any(d is not None for d in dweights):
-            need = int(self.lib.rfa_qk_token_norm_rotary_bwd_workspace_bytes(C.byref(a)))
-            ws = torch.empty(max(need, 16), dtype=torch.uint8, device=xs[0].device)
-            a.workspace, a.workspace_bytes = ws.data_ptr(), need
-        _C.check(self.lib.rfa_qk_token_norm_rotary_bwd(C.byref(a), _stream(xs[0])), "rfa_qk_token_norm_rotary_bwd")
-        if a.B == 0 or a.S == 0:                                   # (nothing was launched: an empty sum)
-            for dw in dweights:
-                if dw is not None:
-                    dw.zero_()
+        self._qk_norm_bwd(a, "qk_token_norm_rotary", "rfa_qk_token_norm_rotary_bwd_workspace_bytes", "rfa_qk_token_norm_rotary_bwd",
+                          packed, xs, douts, dweights, lambda dw, x: dw.numel() == x.shape[-2] * x.shape[-1],
+                          "dweight is a contiguous fp32 tensor of H * D elements")
 
     def sum_slots(self, src: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
         """dst[...] = sum over dim 0 of src (io dtype, summed in fp32).  src: (W, B, S, H, D) or (W, T, H, D), each slot

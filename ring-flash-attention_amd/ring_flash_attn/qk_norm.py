@@ -12,14 +12,16 @@ import math
 
 import torch
 
+from . import _C
 from ._api import _opaque
 from ._common import pos_map
 from .rotary import _check_qk, _check_tables_positions, _conforms
 
 
-class _QkNormRotary(torch.autograd.Function):
-    """norm + rotation of one or two tensors in one launch.  Saved: the inputs, the weights, the tables and the positions (or
-    the map's numbers) — neither rstd, which the backward recomputes with the forward's own code, nor the outputs."""
+class _NormRotary(torch.autograd.Function):
+    """norm (per head or over the token: meta["fwd"] / meta["bwd"] name the backend's methods) + rotation of one or two tensors
+    in one launch.  Saved: the inputs, the weights, the tables and the positions (or the map's numbers) — neither rstd, which
+    the backward recomputes with the forward's own code, nor the outputs."""
 
     @staticmethod
     def forward(ctx, q, k, wq, wk, cos, sin, positions, meta):
@@ -27,11 +29,9 @@ class _QkNormRotary(torch.autograd.Function):
 
         tensors = (q,) if k is None else (q, k)
         weights = (wq,) if k is None else (wq, wk)
-        pm, interleaved, rot_offset, eps, weight_offset = meta
         srcs = [t if _conforms(t) else t.contiguous() for t in tensors]
         outs = [torch.empty(t.shape, dtype=t.dtype, device=t.device) for t in tensors]
-        get_backend().qk_norm_rotary_fwd(srcs, outs, list(weights), cos, sin, positions=positions, pos_map=pm,
-                                         interleaved=interleaved, rot_offset=rot_offset, eps=eps, weight_offset=weight_offset)
+        getattr(get_backend(), meta["fwd"])(srcs, outs, list(weights), cos, sin, positions=positions, **meta["launch"])
         ctx.meta = meta
         ctx.n = len(tensors)
         ctx.save_for_backward(cos, sin, positions, *srcs, *weights)
@@ -45,7 +45,6 @@ class _QkNormRotary(torch.autograd.Function):
         cos, sin, positions, *rest = ctx.saved_tensors
         n = ctx.n
         xs, ws = rest[:n], rest[n:]
-        pm, interleaved, rot_offset, eps, weight_offset = ctx.meta
         need_w = (ctx.needs_input_grad[2], ctx.needs_input_grad[3])
         dx, dw = [None, None], [None, None]
         live = [i for i in range(n) if grads[i] is not None]
@@ -53,13 +52,49 @@ class _QkNormRotary(torch.autograd.Function):
             douts = [grads[i] if _conforms(grads[i]) else grads[i].contiguous() for i in live]
             dxs = [torch.empty(xs[i].shape, dtype=xs[i].dtype, device=xs[i].device) for i in live]
             dws = [torch.empty(ws[i].shape, dtype=torch.float32, device=ws[i].device) if need_w[i] else None for i in live]
-            get_backend().qk_norm_rotary_bwd([xs[i] for i in live], douts, dxs, [ws[i] for i in live], dws, cos, sin,
-                                             positions=positions, pos_map=pm, interleaved=interleaved, rot_offset=rot_offset,
-                                             eps=eps, weight_offset=weight_offset)
+            getattr(get_backend(), ctx.meta["bwd"])([xs[i] for i in live], douts, dxs, [ws[i] for i in live], dws, cos, sin,
+                                                    positions=positions, **ctx.meta["launch"])
             for j, i in enumerate(live):
                 dx[i] = dxs[j]
                 dw[i] = dws[j].to(ws[i].dtype) if dws[j] is not None else None          # rounded once from the fp32 sum
         return (dx[0], dx[1], dw[0], dw[1], None, None, None, None)
+
+
+def _norm_rotary(who, feature, check_weight, q, k, q_weight, k_weight, cos, sin, eps, weight_offset, layout, group, positions,
+                 offset, interleaved, rot_offset):
+    """what apply_qk_norm_rotary and apply_qk_token_norm_rotary share: every check in front of the launch, in one order, and the
+    node.  feature: `qk_norm` / `qk_token_norm` (the backend's serves_* flag and the stem of its two methods);
+    check_weight(x, w, D): ValueError unless w is a weight of tensor x."""
+    from .backend import get_backend
+
+    be = get_backend()
+    if not getattr(be, f"serves_{feature}", False):
+        raise NotImplementedError(f"{who} needs a backend that serves `{feature}`; {getattr(be, 'name', type(be).__name__)!r} "
+                                  "does not")
+    if not isinstance(q, torch.Tensor) or (k is not None and not isinstance(k, torch.Tensor)):
+        raise ValueError(f"{who}: q and k must be tensors")
+    if (k is None) != (k_weight is None):
+        raise ValueError(f"{who}: k and k_weight come together (both None: one tensor)")
+    if (cos is None) != (sin is None):
+        raise ValueError(f"{who}: cos and sin come together (both None: the norm alone)")
+    if cos is not None and (not isinstance(cos, torch.Tensor) or not isinstance(sin, torch.Tensor)):
+        raise ValueError(f"{who}: cos and sin must be tensors of shape (P, R/2)")
+    packed, D = _check_qk(who, q, k)
+    for x, w in [(q, q_weight)] if k is None else [(q, q_weight), (k, k_weight)]:
+        check_weight(x, w, D)
+    eps, weight_offset = float(eps), float(weight_offset)
+    if not math.isfinite(eps) or eps < 0:
+        raise ValueError(f"{who}: eps must be finite and not negative, got {eps}")
+    if not math.isfinite(weight_offset):
+        raise ValueError(f"{who}: weight_offset must be finite, got {weight_offset}")
+    positions, pm, interleaved, rot_offset = _check_tables_positions(who, q, packed, D, cos, sin, layout, group, positions, offset,
+                                                                      interleaved, rot_offset)
+    if cos is None:                                    # (the norm alone has no angle: nothing of the positions is used)
+        positions, pm = None, pos_map(0)
+    meta = dict(fwd=f"{feature}_rotary_fwd", bwd=f"{feature}_rotary_bwd",
+                launch=dict(pos_map=pm, interleaved=interleaved, rot_offset=rot_offset, eps=eps, weight_offset=weight_offset))
+    outs = _NormRotary.apply(q, k, q_weight, k_weight, cos, sin, positions, meta)
+    return outs[0] if k is None else outs
 
 
 def apply_qk_norm_rotary(q, k, q_weight, k_weight, cos=None, sin=None, *, eps=1e-6, weight_offset=0.0, layout=None, group=None,
@@ -87,90 +122,18 @@ def apply_qk_norm_rotary(q, k, q_weight, k_weight, cos=None, sin=None, *, eps=1e
     Under torch.compile the call runs eagerly behind a graph break.
     Raises, before anything is launched: NotImplementedError for a backend without `serves_qk_norm`; TypeError for a `layout`
     that is not one of the nine dense attention functions; ValueError for everything else."""
-    from .backend import get_backend
-
     who = "ring_flash_attn.apply_qk_norm_rotary"
-    be = get_backend()
-    if not getattr(be, "serves_qk_norm", False):
-        raise NotImplementedError(f"{who} needs a backend that serves `qk_norm`; {getattr(be, 'name', type(be).__name__)!r} "
-                                  "does not")
-    if not isinstance(q, torch.Tensor) or (k is not None and not isinstance(k, torch.Tensor)):
-        raise ValueError(f"{who}: q and k must be tensors")
-    if (k is None) != (k_weight is None):
-        raise ValueError(f"{who}: k and k_weight come together (both None: one tensor)")
-    if (cos is None) != (sin is None):
-        raise ValueError(f"{who}: cos and sin come together (both None: the norm alone)")
-    if cos is not None and (not isinstance(cos, torch.Tensor) or not isinstance(sin, torch.Tensor)):
-        raise ValueError(f"{who}: cos and sin must be tensors of shape (P, R/2)")
-    packed, D = _check_qk(who, q, k)
-    weights = [q_weight] if k is None else [q_weight, k_weight]
-    for w in weights:
+
+    def check_weight(x, w, D):
         if not isinstance(w, torch.Tensor) or tuple(w.shape) != (D,) or not w.is_contiguous() or w.device != q.device or \
-                w.dtype not in (torch.float32, q.dtype) or w.dtype != weights[0].dtype:
+                w.dtype not in (torch.float32, q.dtype) or w.dtype != q_weight.dtype:
             raise ValueError(f"{who}: the weights must be contiguous (D,) = ({D},) tensors on q's device, both fp32 or both {q.dtype}")
-    eps, weight_offset = float(eps), float(weight_offset)
-    if not math.isfinite(eps) or eps < 0:
-        raise ValueError(f"{who}: eps must be finite and not negative, got {eps}")
-    if not math.isfinite(weight_offset):
-        raise ValueError(f"{who}: weight_offset must be finite, got {weight_offset}")
-    positions, pm, interleaved, rot_offset = _check_tables_positions(who, q, packed, D, cos, sin, layout, group, positions, offset,
-                                                                      interleaved, rot_offset)
-    if cos is None:                                    # (the norm alone has no angle: nothing of the positions is used)
-        positions, pm = None, pos_map(0)
-    meta = (pm, interleaved, rot_offset, eps, weight_offset)
-    outs = _QkNormRotary.apply(q, k, q_weight, k_weight, cos, sin, positions, meta)
-    return outs[0] if k is None else outs
+
+    return _norm_rotary(who, "qk_norm", check_weight, q, k, q_weight, k_weight, cos, sin, eps, weight_offset, layout, group,
+                        positions, offset, interleaved, rot_offset)
 
 
 apply_qk_norm_rotary = _opaque(apply_qk_norm_rotary)
-
-
-class _QkTokenNormRotary(torch.autograd.Function):
-    """the norm over all heads of a token + rotation of one or two tensors in one launch.  Saved: the inputs, the weights, the
-    tables and the positions (or the map's numbers) — neither rstd nor the outputs."""
-
-    @staticmethod
-    def forward(ctx, q, k, wq, wk, cos, sin, positions, meta):
-        from .backend import get_backend
-
-        tensors = (q,) if k is None else (q, k)
-        weights = (wq,) if k is None else (wq, wk)
-        pm, interleaved, rot_offset, eps, weight_offset = meta
-        srcs = [t if _conforms(t) else t.contiguous() for t in tensors]
-        outs = [torch.empty(t.shape, dtype=t.dtype, device=t.device) for t in tensors]
-        get_backend().qk_token_norm_rotary_fwd(srcs, outs, list(weights), cos, sin, positions=positions, pos_map=pm,
-                                               interleaved=interleaved, rot_offset=rot_offset, eps=eps, weight_offset=weight_offset)
-        ctx.meta = meta
-        ctx.n = len(tensors)
-        ctx.save_for_backward(cos, sin, positions, *srcs, *weights)
-        ctx.set_materialize_grads(False)
-        return tuple(outs)
-
-    @staticmethod
-    def backward(ctx, *grads):
-        from .backend import get_backend
-
-        cos, sin, positions, *rest = ctx.saved_tensors
-        n = ctx.n
-        xs, ws = rest[:n], rest[n:]
-        pm, interleaved, rot_offset, eps, weight_offset = ctx.meta
-        need_w = (ctx.needs_input_grad[2], ctx.needs_input_grad[3])
-        dx, dw = [None, None], [None, None]
-        live = [i for i in range(n) if grads[i] is not None]
-        if live:
-            douts = [grads[i] if _conforms(grads[i]) else grads[i].contiguous() for i in live]
-            dxs = [torch.empty(xs[i].shape, dtype=xs[i].dtype, device=xs[i].device) for i in live]
-            dws = [torch.empty(ws[i].shape, dtype=torch.float32, device=ws[i].device) if need_w[i] else None for i in live]
-            get_backend().qk_token_norm_rotary_bwd([xs[i] for i in live], douts, dxs, [ws[i] for i in live], dws, cos, sin,
-                                                   positions=positions, pos_map=pm, interleaved=interleaved,
-                                                   rot_offset=rot_offset, eps=eps, weight_offset=weight_offset)
-            for j, i in enumerate(live):
-                dx[i] = dxs[j]
-                dw[i] = dws[j].to(ws[i].dtype) if dws[j] is not None else None          # rounded once from the fp32 sum
-        return (dx[0], dx[1], dw[0], dw[1], None, None, None, None)
-
-
-TOKEN_NORM_MAX_WIDTH = 16384          # H * D (and Hk * D) that `apply_qk_token_norm_rotary` serves: include/rfa.h
 
 
 def apply_qk_token_norm_rotary(q, k, q_weight, k_weight, cos=None, sin=None, *, eps=1e-6, weight_offset=0.0, layout=None,
@@ -200,43 +163,20 @@ def apply_qk_token_norm_rotary(q, k, q_weight, k_weight, cos=None, sin=None, *, 
     Under torch.compile the call runs eagerly behind a graph break.
     Raises, before anything is launched: NotImplementedError for a backend without `serves_qk_token_norm`; TypeError for a
     `layout` that is not one of the nine dense attention functions; ValueError for everything else."""
-    from .backend import get_backend
-
     who = "ring_flash_attn.apply_qk_token_norm_rotary"
-    be = get_backend()
-    if not getattr(be, "serves_qk_token_norm", False):
-        raise NotImplementedError(f"{who} needs a backend that serves `qk_token_norm`; "
-                                  f"{getattr(be, 'name', type(be).__name__)!r} does not")
-    if not isinstance(q, torch.Tensor) or (k is not None and not isinstance(k, torch.Tensor)):
-        raise ValueError(f"{who}: q and k must be tensors")
-    if (k is None) != (k_weight is None):
-        raise ValueError(f"{who}: k and k_weight come together (both None: one tensor)")
-    if (cos is None) != (sin is None):
-        raise ValueError(f"{who}: cos and sin come together (both None: the norm alone)")
-    if cos is not None and (not isinstance(cos, torch.Tensor) or not isinstance(sin, torch.Tensor)):
-        raise ValueError(f"{who}: cos and sin must be tensors of shape (P, R/2)")
-    packed, D = _check_qk(who, q, k)
-    pairs = [(q, q_weight)] if k is None else [(q, q_weight), (k, k_weight)]
-    for x, w in pairs:
+    width = _C.QK_TOKEN_NORM_MAX_WIDTH                 # H * D (and Hk * D) that is served: include/rfa.h
+
+    def check_weight(x, w, D):
         H = x.shape[-2]
-        if H * D > TOKEN_NORM_MAX_WIDTH:
-            raise ValueError(f"{who}: H * D = {H * D} is more than the {TOKEN_NORM_MAX_WIDTH} columns a token row may have")
+        if H * D > width:
+            raise ValueError(f"{who}: H * D = {H * D} is more than the {width} columns a token row may have")
         if not isinstance(w, torch.Tensor) or tuple(w.shape) not in ((H * D,), (H, D)) or not w.is_contiguous() or \
                 w.device != q.device or w.dtype not in (torch.float32, q.dtype) or w.dtype != q_weight.dtype:
             raise ValueError(f"{who}: the weights must be contiguous (H * D,) = ({H * D},) or (H, D) = ({H}, {D}) tensors on q's "
                              f"device, both fp32 or both {q.dtype}")
-    eps, weight_offset = float(eps), float(weight_offset)
-    if not math.isfinite(eps) or eps < 0:
-        raise ValueError(f"{who}: eps must be finite and not negative, got {eps}")
-    if not math.isfinite(weight_offset):
-        raise ValueError(f"{who}: weight_offset must be finite, got {weight_offset}")
-    positions, pm, interleaved, rot_offset = _check_tables_positions(who, q, packed, D, cos, sin, layout, group, positions, offset,
-                                                                      interleaved, rot_offset)
-    if cos is None:                                    # (the norm alone has no angle: nothing of the positions is used)
-        positions, pm = None, pos_map(0)
-    meta = (pm, interleaved, rot_offset, eps, weight_offset)
-    outs = _QkTokenNormRotary.apply(q, k, q_weight, k_weight, cos, sin, positions, meta)
-    return outs[0] if k is None else outs
+
+    return _norm_rotary(who, "qk_token_norm", check_weight, q, k, q_weight, k_weight, cos, sin, eps, weight_offset, layout, group,
+                        positions, offset, interleaved, rot_offset)
 
 
 apply_qk_token_norm_rotary = _opaque(apply_qk_token_norm_rotary)

@@ -215,44 +215,56 @@ def _check_tables_positions(who, q, packed, D, cos, sin, layout, group, position
 
 
 class _Rotary(torch.autograd.Function):
-    """the rotation of one or two tensors in one launch; backward: the same kernel with the conjugate flag on the incoming
-    gradients.  Saved: cos, sin, the positions (or the map's numbers) and the flags — neither inputs nor outputs."""
+    """the rotation of one or two tensors in one launch of the backend method meta["method"] — `rotary` with tables = (cos, sin),
+    `rotary_freqs` with tables = (inv_freq,); backward: the same kernel with the conjugate flag on the incoming gradients.
+    Saved: the tables, the positions (or the map's numbers) and the flags — neither inputs nor outputs."""
 
     @staticmethod
-    def forward(ctx, q, k, cos, sin, positions, meta):
+    def forward(ctx, q, k, positions, meta, *tables):
         from .backend import get_backend
 
         # (q comes first: where autograd rewrites the history of a VIEW modified in place it takes the view for input 0)
         tensors = (q,) if k is None else (q, k)
-        pm, interleaved, rot_offset, inplace = meta
         ctx.meta = meta
-        ctx.save_for_backward(cos, sin, positions)
+        ctx.save_for_backward(*tables, positions)
         ctx.set_materialize_grads(False)
-        if inplace:
+        if meta["inplace"]:
             ctx.mark_dirty(*tensors)
             outs = list(tensors)
         else:
             outs = [torch.empty(t.shape, dtype=t.dtype, device=t.device) for t in tensors]
         srcs = [t if _conforms(t) else t.contiguous() for t in tensors]        # (inplace: checked to conform before)
-        get_backend().rotary(srcs, outs, cos, sin, positions=positions, pos_map=pm, interleaved=interleaved,
-                             rot_offset=rot_offset, conj=False)
+        getattr(get_backend(), meta["method"])(srcs, outs, *tables, positions=positions, conj=False, **meta["launch"])
         return tuple(outs)
 
     @staticmethod
     def backward(ctx, *grads):
         from .backend import get_backend
 
-        cos, sin, positions = ctx.saved_tensors
-        pm, interleaved, rot_offset, _ = ctx.meta
+        *tables, positions = ctx.saved_tensors
         live = [g for g in grads if g is not None]
         if live:
             srcs = [g if _conforms(g) else g.contiguous() for g in live]
             outs = [torch.empty(g.shape, dtype=g.dtype, device=g.device) for g in live]
-            get_backend().rotary(srcs, outs, cos, sin, positions=positions, pos_map=pm, interleaved=interleaved,
-                                 rot_offset=rot_offset, conj=True)
+            getattr(get_backend(), ctx.meta["method"])(srcs, outs, *tables, positions=positions, conj=True, **ctx.meta["launch"])
             it = iter(outs)
             grads = tuple(next(it) if g is not None else None for g in grads)
-        return (grads[0], grads[1] if len(grads) > 1 else None, None, None, None, None)
+        return (grads[0], grads[1] if len(grads) > 1 else None, None, None) + (None,) * len(tables)
+
+
+def _rotate(who, method, q, k, tables, positions, inplace, launch):
+    """the end of apply_rotary and apply_rotary_freqs: the check of `inplace`, then the node on q and k"""
+    tensors = [q] if k is None else [q, k]
+    inplace = bool(inplace)
+    if inplace and not all(_conforms(t) for t in tensors):
+        raise ValueError(f"{who}: inplace=True needs last stride 1, a 16-byte aligned start and strides that are multiples of 8")
+    meta = dict(method=method, inplace=inplace, launch=launch)
+    if inplace and k is not None and torch.is_grad_enabled() and any(t._is_view() for t in tensors):
+        # (autograd lets a Function that modifies a VIEW in place return one tensor only: q and k one after the other — the
+        #  bits do not depend on it)
+        return tuple(_Rotary.apply(t, None, positions, meta, *tables)[0] for t in tensors)
+    outs = _Rotary.apply(q, k, positions, meta, *tables)
+    return outs[0] if k is None else outs
 
 
 def apply_rotary(q, k=None, cos=None, sin=None, *, layout=None, group=None, positions=None, offset=0, interleaved=False,
@@ -296,20 +308,11 @@ def apply_rotary(q, k=None, cos=None, sin=None, *, layout=None, group=None, posi
         raise ValueError(f"{who}: q and k must be tensors")
     if not isinstance(cos, torch.Tensor) or not isinstance(sin, torch.Tensor):
         raise ValueError(f"{who}: cos and sin must be tensors of shape (P, R/2)")
-    tensors = [q] if k is None else [q, k]
     packed, D = _check_qk(who, q, k)
     positions, pm, interleaved, rot_offset = _check_tables_positions(who, q, packed, D, cos, sin, layout, group, positions, offset,
                                                                       interleaved, rot_offset)
-    inplace = bool(inplace)
-    if inplace and not all(_conforms(t) for t in tensors):
-        raise ValueError(f"{who}: inplace=True needs last stride 1, a 16-byte aligned start and strides that are multiples of 8")
-    meta = (pm, interleaved, rot_offset, inplace)
-    if inplace and k is not None and torch.is_grad_enabled() and any(t._is_view() for t in tensors):
-        # (autograd lets a Function that modifies a VIEW in place return one tensor only: q and k one after the other — the
-        #  bits do not depend on it)
-        return tuple(_Rotary.apply(t, None, cos, sin, positions, meta)[0] for t in tensors)
-    outs = _Rotary.apply(q, k, cos, sin, positions, meta)
-    return outs[0] if k is None else outs
+    return _rotate(who, "rotary", q, k, (cos, sin), positions, inplace,
+                   dict(pos_map=pm, interleaved=interleaved, rot_offset=rot_offset))
 
 
 apply_rotary = _opaque(apply_rotary)
@@ -317,42 +320,6 @@ apply_rotary = _opaque(apply_rotary)
 
 # ---- apply_rotary_freqs -------------------------------------------------------------------------------------------------
 _POS_MAX = 2 ** 31 - 1
-
-
-class _RotaryFreqs(torch.autograd.Function):
-    """_Rotary with the angles formed in the kernel; backward: the same kernel with the conjugate flag on the incoming
-    gradients.  Saved: inv_freq, the positions (or the map's numbers) and the flags — neither inputs nor outputs."""
-
-    @staticmethod
-    def forward(ctx, q, k, inv_freq, positions, meta):
-        from .backend import get_backend
-
-        tensors = (q,) if k is None else (q, k)
-        ctx.meta = meta
-        ctx.save_for_backward(inv_freq, positions)
-        ctx.set_materialize_grads(False)
-        if meta["inplace"]:
-            ctx.mark_dirty(*tensors)
-            outs = list(tensors)
-        else:
-            outs = [torch.empty(t.shape, dtype=t.dtype, device=t.device) for t in tensors]
-        srcs = [t if _conforms(t) else t.contiguous() for t in tensors]        # (inplace: checked to conform before)
-        get_backend().rotary_freqs(srcs, outs, inv_freq, positions=positions, conj=False, **meta["launch"])
-        return tuple(outs)
-
-    @staticmethod
-    def backward(ctx, *grads):
-        from .backend import get_backend
-
-        inv_freq, positions = ctx.saved_tensors
-        live = [g for g in grads if g is not None]
-        if live:
-            srcs = [g if _conforms(g) else g.contiguous() for g in live]
-            outs = [torch.empty(g.shape, dtype=g.dtype, device=g.device) for g in live]
-            get_backend().rotary_freqs(srcs, outs, inv_freq, positions=positions, conj=True, **ctx.meta["launch"])
-            it = iter(outs)
-            grads = tuple(next(it) if g is not None else None for g in grads)
-        return (grads[0], grads[1] if len(grads) > 1 else None, None, None, None)
 
 
 def apply_rotary_freqs(q, k=None, inv_freq=None, *, attention_scaling=1.0, freq_axis=None, layout=None, group=None,
@@ -391,7 +358,6 @@ def apply_rotary_freqs(q, k=None, inv_freq=None, *, attention_scaling=1.0, freq_
                                   f"{getattr(be, 'name', type(be).__name__)!r} does not")
     if not isinstance(q, torch.Tensor) or (k is not None and not isinstance(k, torch.Tensor)):
         raise ValueError(f"{who}: q and k must be tensors")
-    tensors = [q] if k is None else [q, k]
     packed, D = _check_qk(who, q, k)
     if not isinstance(inv_freq, torch.Tensor) or inv_freq.dtype != torch.float32 or inv_freq.dim() != 1 or \
             not inv_freq.is_contiguous() or inv_freq.device != q.device:
@@ -442,16 +408,9 @@ def apply_rotary_freqs(q, k=None, inv_freq=None, *, attention_scaling=1.0, freq_
         raise ValueError(f"{who}: rot_offset {rot_offset} must be a multiple of 8 with rot_offset + R = {rot_offset + R} <= D = {D}")
     if positions is not None and abs(pm[0]) > _POS_MAX:
         raise ValueError(f"{who}: offset {pm[0]} is outside -(2^31 - 1) .. 2^31 - 1")
-    inplace = bool(inplace)
-    if inplace and not all(_conforms(t) for t in tensors):
-        raise ValueError(f"{who}: inplace=True needs last stride 1, a 16-byte aligned start and strides that are multiples of 8")
-    launch = dict(scaling=float(attention_scaling), freq_axis=freq_axis, pos_map=pm, interleaved=interleaved, rot_offset=rot_offset)
-    meta = dict(inplace=inplace, launch=launch)
-    if inplace and k is not None and torch.is_grad_enabled() and any(t._is_view() for t in tensors):
-        # (autograd lets a Function that modifies a VIEW in place return one tensor only: q and k one after the other)
-        return tuple(_RotaryFreqs.apply(t, None, inv_freq, positions, meta)[0] for t in tensors)
-    outs = _RotaryFreqs.apply(q, k, inv_freq, positions, meta)
-    return outs[0] if k is None else outs
+    return _rotate(who, "rotary_freqs", q, k, (inv_freq,), positions, inplace,
+                   dict(scaling=float(attention_scaling), freq_axis=freq_axis, pos_map=pm, interleaved=interleaved,
+                        rot_offset=rot_offset))
 
 
 apply_rotary_freqs = _opaque(apply_rotary_freqs)
