@@ -1804,7 +1804,13 @@ int rfa_rotary_freqs(const rfa_rotary_freqs_args* a, void* stream) {
 // ---- the QK RMSNorms + rotary: per head (csrc/rfa_qknorm.hip) and over all heads of a token (csrc/rfa_qktoken.hip) ------------
 static_assert(RFA_QK_TOKEN_NORM_MAX_WIDTH == kQkTokenMaxWidth && RFA_QK_TOKEN_NORM_MAX_PARTS == kQkTokenMaxParts,
               "rfa.h and rfa_qktoken_index.h state the same limits");
+static_assert(RFA_QK_NORM_FREQS_TILE_ROWS == kQkNfRows, "rfa.h and rfa_qknormfreq_index.h state the same tile height");
 extern "C++" {
+// the structs of the per-head norm that forms its own angles (csrc/rfa_qknormfreq.hip): where the others have tables, these
+// have rfa_rotary_freqs's inv_freq, scaling, naxes and freq_axis, checked where rfa_rotary_freqs checks them
+template <typename A>
+constexpr bool kOwnAngles = std::is_same_v<A, rfa_qk_norm_rotary_freqs_args> || std::is_same_v<A, rfa_qk_norm_rotary_freqs_bwd_args>;
+
 // the checks the forward and the backward struct of either norm share, up to the NULL checks: `upto` 0 stops in front of "no
 // rows" (everything that needs no pointer: what the workspace size depends on), 1 runs them all.  RFA_OK with *launch == false:
 // nothing to do.  own(a, p, rows): what the norm's own Geom and Tensor hold beyond the shared members, with its own bound.
@@ -1813,9 +1819,17 @@ static int qk_check(const A* a, int upto, P* p, bool* launch, Own own) {
   *launch = false;
   if (int rc = row_check_struct(a)) return rc;
   if (!(a->eps >= 0.f) || !(a->eps <= FLT_MAX) || !(a->weight_offset >= -FLT_MAX && a->weight_offset <= FLT_MAX)) return RFA_ERR_ARGS;
-  if (a->table_dtype != a->dtype && a->table_dtype != RFA_ROTARY_TABLE_F32) return RFA_ERR_DTYPE;
+  if constexpr (kOwnAngles<A>) {
+    if (a->pad != 0 || a->naxes < 1 || a->naxes > 4 || !(a->scaling > 0.f) || !(a->scaling <= FLT_MAX)) return RFA_ERR_ARGS;
+  } else {
+    if (a->table_dtype != a->dtype && a->table_dtype != RFA_ROTARY_TABLE_F32) return RFA_ERR_DTYPE;
+  }
   if (a->weight_dtype != a->dtype && a->weight_dtype != RFA_QK_NORM_WEIGHT_F32) return RFA_ERR_DTYPE;
-  if (int rc = row_check_dims(a, 0, a->R > 0 ? a->P : 1)) return rc;
+  if constexpr (kOwnAngles<A>) {
+    if (int rc = row_check_dims(a, 1, 1)) return rc;
+  } else {
+    if (int rc = row_check_dims(a, 0, a->R > 0 ? a->P : 1)) return rc;
+  }
   p->g.B = (uint32_t)a->B; p->g.S = (uint32_t)a->S; p->g.D = (uint32_t)a->D; p->g.R = (uint32_t)a->R;
   p->g.rot_off = (uint32_t)a->rot_offset; p->g.interleaved = a->interleaved;
   p->ntensors = a->ntensors;
@@ -1833,7 +1847,12 @@ static int qk_check(const A* a, int upto, P* p, bool* launch, Own own) {
   *launch = true;
   for (int k = 0; k < a->ntensors; ++k)
     if (!a->weight[k]) return RFA_ERR_NULL;
-  if (!row_tensors_present(a) || (a->R > 0 && (!a->cos || !a->sin))) return RFA_ERR_NULL;
+  if (!row_tensors_present(a)) return RFA_ERR_NULL;
+  if constexpr (kOwnAngles<A>) {
+    if (!a->inv_freq) return RFA_ERR_NULL;
+  } else {
+    if (a->R > 0 && (!a->cos || !a->sin)) return RFA_ERR_NULL;
+  }
   return RFA_OK;
 }
 
@@ -1848,6 +1867,25 @@ static int qk_norm_check(const A* a, int upto, QkNormParams* p, bool* launch) {
       p->nparts[k] = qknorm_parts(p->t[k].nitems, g.group);
       p->walk[k] = qknorm_walk(p->t[k].nitems, p->nparts[k], g.group);
     }
+    return RFA_OK;
+  });
+}
+
+template <typename A>
+static int qk_freqs_check(const A* a, int upto, QkNormFreqParams* p, bool* launch) {
+  return qk_check(a, upto, p, launch, [](const A* a, QkNormFreqParams* p, int64_t rows) -> int {
+    QkNormGeom& g = p->g;
+    g.chunks = g.D / 8; g.group = qknorm_group(g.D);
+    for (int k = 0; k < a->ntensors; ++k) {                    // (a tile's items are counted in 32 bits)
+      if (rows * a->t[k].H > INT32_MAX || (int64_t)kQkNfRows * a->t[k].H > INT32_MAX) return RFA_ERR_SHAPE;
+      p->t[k].nitems = (uint32_t)(rows * a->t[k].H);
+    }
+    for (uint32_t c = 0; c < 4 * 32; ++c) {                    // (R/2 <= 128 = the entries of the four words)
+      const uint32_t axis = rotfreq_axis(a->freq_axis[0], a->freq_axis[1], a->freq_axis[2], a->freq_axis[3], c);
+      if (axis >= (c < (uint32_t)a->R / 2 ? (uint32_t)a->naxes : 1u)) return RFA_ERR_ARGS;
+    }
+    p->nparts = qknf_parts(qknf_tiles(g.B, g.S));
+    p->walk = qknf_walk(qknf_tiles(g.B, g.S), p->nparts);
     return RFA_OK;
   });
 }
@@ -1872,7 +1910,11 @@ static int qk_token_check(const A* a, int upto, QkTokenParams* p, bool* launch) 
 // behind the NULL checks: ALIGN, then the late ARGS and the table and position fields (R == 0, the norm alone: none of them)
 template <typename A>
 static int qk_check_aligned(const A* a) {
-  if (a->R > 0 && (!aligned16(a->cos) || !aligned16(a->sin))) return RFA_ERR_ALIGN;
+  if constexpr (kOwnAngles<A>) {
+    if (reinterpret_cast<uintptr_t>(a->inv_freq) & 3) return RFA_ERR_ALIGN;
+  } else {
+    if (a->R > 0 && (!aligned16(a->cos) || !aligned16(a->sin))) return RFA_ERR_ALIGN;
+  }
   for (int k = 0; k < a->ntensors; ++k)
     if (!aligned16(a->weight[k])) return RFA_ERR_ALIGN;
   return row_tensors_aligned(a) ? RFA_OK : RFA_ERR_ALIGN;
@@ -1882,8 +1924,17 @@ template <typename A, typename P>
 static int qk_check_map(const A* a, P* p) {
   for (int k = 0; k < a->ntensors; ++k)
     if (a->t[k].dst == a->t[k].src) return RFA_ERR_ARGS;
-  if (int rc = row_pos_map(a, p, a->P - 1, a->R > 0)) return rc;
-  if (a->R > 0) { p->cos = a->cos; p->sin = a->sin; p->P = a->P; }
+  if constexpr (kOwnAngles<A>) {
+    // (rfa_rotary_freqs's late checks: an offset beyond 2^40 names no position that fp32 resolves; a map serves one axis)
+    if (a->pos_axis < 0 || a->pos_offset < -(1ll << 40) || a->pos_offset > (1ll << 40) || (!a->positions && a->naxes > 1))
+      return RFA_ERR_ARGS;
+    if (int rc = row_pos_map(a, p, INT32_MAX, true)) return rc;
+    p->inv_freq = a->inv_freq; p->scaling = a->scaling; p->pos_axis = a->pos_axis;
+    for (int w = 0; w < 4; ++w) p->freq_axis[w] = a->freq_axis[w];
+  } else {
+    if (int rc = row_pos_map(a, p, a->P - 1, a->R > 0)) return rc;
+    if (a->R > 0) { p->cos = a->cos; p->sin = a->sin; p->P = a->P; }
+  }
   return RFA_OK;
 }
 
@@ -1917,6 +1968,7 @@ static int qk_bwd_tail(const A* a, P* p, Bytes workspace_bytes) {
 }
 
 static int64_t qk_norm_workspace(const QkNormParams& p) { return qknorm_workspace_bytes(1, p.nparts[0] + p.nparts[1], p.g.D); }
+static int64_t qk_freqs_workspace(const QkNormFreqParams& p) { return qknorm_workspace_bytes(p.ntensors, p.nparts, p.g.D); }
 static int64_t qk_token_workspace(const QkTokenParams& p) {
   int64_t bytes = 0;
   for (int k = 0; k < p.ntensors; ++k) bytes += qktoken_workspace_bytes(p.nparts[k], p.t[k].N);
@@ -1948,6 +2000,31 @@ int rfa_qk_norm_rotary_bwd(const rfa_qk_norm_rotary_bwd_args* a, void* stream) {
   if ((rc = qk_bwd_tail(a, &p, qk_norm_workspace)) != RFA_OK) return rc;
   return launch_qknorm_bwd(p, a->dtype, a->table_dtype == RFA_ROTARY_TABLE_F32, a->weight_dtype == RFA_QK_NORM_WEIGHT_F32,
                            (hipStream_t)stream) ? RFA_ERR_LAUNCH : RFA_OK;
+}
+
+// ---- the per-head norm with the angles formed in the kernel (csrc/rfa_qknormfreq.hip) ------------------------------------------
+int rfa_qk_norm_rotary_freqs_fwd(const rfa_qk_norm_rotary_freqs_args* a, void* stream) {
+  QkNormFreqParams p{};
+  bool launch = false;
+  int rc = qk_freqs_check(a, 1, &p, &launch);
+  if (rc != RFA_OK || !launch) return rc;
+  if ((rc = qk_check_aligned(a)) != RFA_OK || (rc = qk_check_map(a, &p)) != RFA_OK) return rc;
+  return launch_qknormfreq_fwd(p, a->dtype, a->weight_dtype == RFA_QK_NORM_WEIGHT_F32, (hipStream_t)stream) ? RFA_ERR_LAUNCH : RFA_OK;
+}
+
+int64_t rfa_qk_norm_rotary_freqs_bwd_workspace_bytes(const rfa_qk_norm_rotary_freqs_bwd_args* a) {
+  QkNormFreqParams p{};
+  bool launch = false;
+  return qk_freqs_check(a, 0, &p, &launch) == RFA_OK ? qk_freqs_workspace(p) : 0;
+}
+
+int rfa_qk_norm_rotary_freqs_bwd(const rfa_qk_norm_rotary_freqs_bwd_args* a, void* stream) {
+  QkNormFreqParams p{};
+  bool launch = false;
+  int rc = qk_freqs_check(a, 1, &p, &launch);
+  if (rc != RFA_OK || !launch) return rc;
+  if ((rc = qk_bwd_tail(a, &p, qk_freqs_workspace)) != RFA_OK) return rc;
+  return launch_qknormfreq_bwd(p, a->dtype, a->weight_dtype == RFA_QK_NORM_WEIGHT_F32, (hipStream_t)stream) ? RFA_ERR_LAUNCH : RFA_OK;
 }
 
 int rfa_qk_token_norm_rotary_fwd(const rfa_qk_token_norm_rotary_args* a, void* stream) {

@@ -7,6 +7,7 @@
 #include "rfa_rotary_index.h"
 #include "rfa_rotfreq_index.h"
 #include "rfa_qknorm_index.h"
+#include "rfa_qknormfreq_index.h"
 #include "rfa_qktoken_index.h"
 #include "rfa_maxlogit_band.h"
 #include "rfa_rowrange.h"
@@ -341,6 +342,35 @@ struct QkNormParams {
 };
 int launch_qknorm_fwd(const QkNormParams& p, int dtype, bool table_f32, bool weight_f32, hipStream_t stream);
 int launch_qknorm_bwd(const QkNormParams& p, int dtype, bool table_f32, bool weight_f32, hipStream_t stream);
+
+// per-head QK RMSNorm fused with a rotary embedding whose angles are formed in the kernel (rfa_qknormfreq.hip; index
+// arithmetic: rfa_qknormfreq_index.h): up to two tensors (q, k) per launch, one workgroup per tile of kQkNfRows rows of a batch
+// entry, one (row, head) per lane group.  Tensors and weights as in QkNormParams, angles and positions as in RotFreqParams
+// (R > 0 always).  Backward (the kernel conjugates the rotation itself): nparts workgroups per tensor walk `walk` tiles each (both functions of B and S alone); workspace:
+// tensor 0's nparts partials of D floats, then tensor 1's; then the fold launch.
+struct QkNormFreqParams {
+  QkNormGeom g;
+  QkNormTensor t[2];
+  const void* x[2];
+  void* out[2];             // forward: y; backward: dx
+  const void* dout[2];      // backward only
+  const void* weight[2];    // (D,), fp32 or the io dtype
+  float* dweight[2];        // backward: fp32 (D,) or NULL
+  float* workspace;
+  uint32_t nparts, walk;
+  float eps, weight_offset;
+  const float* inv_freq;    // (R/2,)
+  float scaling;            // multiplies cos and sin
+  const int32_t* positions;
+  int64_t pos_batch, pos_axis;
+  int64_t pos_off, pos_off2;
+  uint32_t pos_stride;
+  int32_t pos_split;
+  int ntensors;
+  uint64_t freq_axis[4];    // 2 bits per frequency
+};
+int launch_qknormfreq_fwd(const QkNormFreqParams& p, int dtype, bool weight_f32, hipStream_t stream);
+int launch_qknormfreq_bwd(const QkNormFreqParams& p, int dtype, bool weight_f32, hipStream_t stream);
 
 // token-wide QK RMSNorm (one rstd per token over all H * D columns; OLMo-2) fused with the rotary embedding (rfa_qktoken.hip;
 // index arithmetic: rfa_qktoken_index.h): up to two tensors (q, k) per launch, one team of 1, 2 or 4 waves per token row.

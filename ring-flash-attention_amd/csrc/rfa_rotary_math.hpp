@@ -1,4 +1,4 @@
-// rfa_rotary_math.hpp — the arithmetic that rfa_rotary.hip and rfa_qknorm.hip share: ONE expression for a rotated pair and the
+// rfa_rotary_math.hpp — the arithmetic that the rotary and QK norm kernels share: ONE expression for a rotated pair and the
 // load of a run of cos / sin values, so that a pair rotated behind the QK norm has the bits the plain rotation gives it.
 #ifndef RFA_ROTARY_MATH_HPP_
 #define RFA_ROTARY_MATH_HPP_
@@ -9,6 +9,13 @@ namespace rfa {
 __device__ __forceinline__ void rot(float x1, float x2, float c, float s, float& o1, float& o2) {
   o1 = __builtin_fmaf(x1, c, -(x2 * s));
   o2 = __builtin_fmaf(x2, c, x1 * s);
+}
+
+// a product rounded once to fp32 and never contracted into a neighbouring add, whatever -ffp-contract the file is built with
+// (the angle of the kernels that form their own: rfa_rotfreq.hip, rfa_qknormfreq.hip)
+__device__ __forceinline__ float mul_rn(float x, float y) {
+#pragma clang fp contract(off)
+  return x * y;
 }
 
 // N consecutive values of a cos / sin row as fp32 (N * sizeof(TT) bytes, aligned to that)

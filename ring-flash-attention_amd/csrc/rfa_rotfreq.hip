@@ -25,18 +25,12 @@
 // grid: x = B * ceil(S / kRotFreqRows).  LDS: 2 * kRotFreqRows * 128 * 4 = 2 KiB, static.
 #include "rfa_common.hpp"
 #include "rfa_kernels.hpp"
-#include "rfa_rotary_math.hpp"     // rot()
+#include "rfa_rotary_math.hpp"     // rot(), mul_rn()
 
 namespace rfa {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x8 __attribute__((ext_vector_type(8)));
-
-// a product rounded once to fp32 and never contracted into a neighbouring add, whatever -ffp-contract the file is built with
-__device__ __forceinline__ float mul_rn(float x, float y) {
-#pragma clang fp contract(off)
-  return x * y;
-}
 
 // VAR: measurement switches of tools/rotfreq_variants.hip — what the kernel costs WITHOUT one of its phases.  Every shipped
 // instance has VAR == 0 and ROWS == kRotFreqRows; the switched-off code is dead there.  A variant's results are wrong on

@@ -298,6 +298,39 @@ class QkNormRotaryBwdArgs(_SizedStructure):
     _fields_ = _QK_NORM_HEAD + _QK_NORM_TAIL
 
 
+_QK_NORM_FREQS_HEAD = [
+    ("struct_bytes", C.c_uint32), ("reserved", C.c_uint32),
+    ("ntensors", C.c_int32),
+    ("B", C.c_int32), ("S", C.c_int32), ("D", C.c_int32),
+    ("dtype", C.c_int32),
+    ("R", C.c_int32), ("rot_offset", C.c_int32),
+    ("interleaved", C.c_int32),
+    ("naxes", C.c_int32), ("weight_dtype", C.c_int32),
+    ("eps", C.c_float), ("weight_offset", C.c_float),
+    ("t", RotaryTensor * 2),
+    ("weight", C.c_void_p * 2),
+    ("inv_freq", C.c_void_p),
+    ("scaling", C.c_float), ("pad", C.c_int32),
+    ("freq_axis", C.c_uint64 * 4),
+    ("positions", C.c_void_p), ("pos_batch", C.c_int64), ("pos_axis", C.c_int64),
+    ("pos_offset", C.c_int64),
+    ("pos_stride", C.c_int32), ("pos_split", C.c_int32),
+    ("pos_offset2", C.c_int64),
+]
+QK_NORM_FREQS_TILE_ROWS = 4       # RFA_QK_NORM_FREQS_TILE_ROWS: rows of a batch entry whose angles one workgroup forms
+
+
+class QkNormRotaryFreqsArgs(_SizedStructure):
+    """rfa_qk_norm_rotary_freqs_args: per-head RMSNorm + rotary with the angles formed in the kernel, forward — the norm's
+    fields of rfa_qk_norm_rotary_args, the angle's of rfa_rotary_freqs_args; struct_bytes is filled in here"""
+    _fields_ = list(_QK_NORM_FREQS_HEAD)
+
+
+class QkNormRotaryFreqsBwdArgs(_SizedStructure):
+    """rfa_qk_norm_rotary_freqs_bwd_args: the forward's fields, then the gradients, dweight and the workspace"""
+    _fields_ = _QK_NORM_FREQS_HEAD + _QK_NORM_TAIL
+
+
 QK_TOKEN_NORM_MAX_WIDTH = 16384   # RFA_QK_TOKEN_NORM_MAX_WIDTH: H * D of one tensor of the token-wide norm
 
 
@@ -450,6 +483,9 @@ SYMBOLS = {
     "rfa_qk_norm_rotary_fwd": (C.c_int, [C.POINTER(QkNormRotaryArgs), C.c_void_p]),
     "rfa_qk_norm_rotary_bwd": (C.c_int, [C.POINTER(QkNormRotaryBwdArgs), C.c_void_p]),
     "rfa_qk_norm_rotary_bwd_workspace_bytes": (C.c_int64, [C.POINTER(QkNormRotaryBwdArgs)]),
+    "rfa_qk_norm_rotary_freqs_fwd": (C.c_int, [C.POINTER(QkNormRotaryFreqsArgs), C.c_void_p]),
+    "rfa_qk_norm_rotary_freqs_bwd": (C.c_int, [C.POINTER(QkNormRotaryFreqsBwdArgs), C.c_void_p]),
+    "rfa_qk_norm_rotary_freqs_bwd_workspace_bytes": (C.c_int64, [C.POINTER(QkNormRotaryFreqsBwdArgs)]),
     "rfa_qk_token_norm_rotary_fwd": (C.c_int, [C.POINTER(QkTokenNormRotaryArgs), C.c_void_p]),
     "rfa_qk_token_norm_rotary_bwd": (C.c_int, [C.POINTER(QkTokenNormRotaryBwdArgs), C.c_void_p]),
     "rfa_qk_token_norm_rotary_bwd_workspace_bytes": (C.c_int64, [C.POINTER(QkTokenNormRotaryBwdArgs)]),

@@ -89,6 +89,9 @@ from .rotary import apply_rotary_freqs
 # per-head QK RMSNorm (Qwen3, Gemma-3, OLMo) fused with that rotation: apply_qk_norm_rotary(q, k, w_q, w_k, cos, sin,
 # layout=func, group=group) is one launch per direction, one rounding, and a reproducible weight gradient
 from .qk_norm import apply_qk_norm_rotary
+# ... and with the angles formed in the kernel, up to four position axes per row (Qwen3-VL; Qwen3 / Gemma-3 without tables):
+# apply_qk_norm_rotary_freqs(q, k, w_q, w_k, inv_freq, positions=pos_thw, freq_axis=axes)
+from .qk_norm import apply_qk_norm_rotary_freqs
 # the same fused with ONE statistic per token over all heads (OLMo-2 / OLMo-3 normalise the whole projection width):
 # apply_qk_token_norm_rotary(q, k, w_q, w_k, cos, sin, layout=func, group=group), weights of H * D entries
 from .qk_norm import apply_qk_token_norm_rotary

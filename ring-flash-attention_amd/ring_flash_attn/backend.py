@@ -101,6 +101,7 @@ class HipBackend:
     serves_rotary = True             # rotary (include/rfa.h: rfa_rotary): ring_flash_attn.apply_rotary
     serves_rotary_freqs = True       # rotary_freqs (include/rfa.h: rfa_rotary_freqs): ring_flash_attn.apply_rotary_freqs
     serves_qk_norm = True            # qk_norm_rotary_fwd / _bwd (include/rfa.h: rfa_qk_norm_rotary_fwd / _bwd): ring_flash_attn.apply_qk_norm_rotary
+    serves_qk_norm_freqs = True      # qk_norm_freqs_rotary_fwd / _bwd (include/rfa.h: rfa_qk_norm_rotary_freqs_fwd / _bwd): apply_qk_norm_rotary_freqs
     serves_qk_token_norm = True      # qk_token_norm_rotary_fwd / _bwd (include/rfa.h: rfa_qk_token_norm_rotary_fwd / _bwd): apply_qk_token_norm_rotary
     serves_dropout_positions = True  # `dropout=` takes the position maps (q_map, k_map): what dropout over a dense ring, zigzag or stripe schedule needs
 
@@ -770,26 +771,33 @@ class HipBackend:
                           srcs, dsts)
         a.R, a.rot_offset = 2 * half, int(rot_offset)
         a.interleaved, a.conj = int(bool(interleaved)), int(bool(conj))
+        self._row_freqs(a, "rotary_freqs", inv_freq, scaling, freq_axis, positions, pos_map)
+        _C.check(self.lib.rfa_rotary_freqs(C.byref(a), _stream(srcs[0])), "rfa_rotary_freqs")
+
+    def _row_freqs(self, a, who, inv_freq, scaling, freq_axis, positions, pos_map):
+        """a.inv_freq, a.scaling, a.naxes, a.freq_axis, a.pos_axis and the position fields of a struct whose kernel forms its
+        own angles (a.R is set: 2 len(inv_freq))"""
+        half = a.R // 2
         a.inv_freq, a.scaling = inv_freq.data_ptr(), float(scaling)
         a.naxes = 1
         if freq_axis is not None:
             if positions is None or positions.dim() < 2 or len(freq_axis) != half or half > 128:
-                raise ValueError("rotary_freqs: freq_axis has R/2 <= 128 entries and needs positions of shape (A, ...)")
+                raise ValueError(f"{who}: freq_axis has R/2 <= 128 entries and needs positions of shape (A, ...)")
             a.naxes = positions.shape[0]
             for c, ax in enumerate(freq_axis):
-                if not 0 <= int(ax) < 4:                           # (what 2 bits hold; rfa_rotary_freqs refuses a code >= naxes)
-                    raise ValueError(f"rotary_freqs: freq_axis[{c}] = {ax} is no axis code (0 .. 3)")
+                if not 0 <= int(ax) < 4:                           # (what 2 bits hold; the library refuses a code >= naxes)
+                    raise ValueError(f"{who}: freq_axis[{c}] = {ax} is no axis code (0 .. 3)")
                 a.freq_axis[c // 32] |= int(ax) << (2 * (c % 32))
             a.pos_axis = positions.stride(0) if positions.shape[0] > 1 else 0
             positions = positions[0]                               # (axis 0: the same first element, the shape of one axis)
-        self._row_positions(a, "rotary_freqs", positions, pos_map)
-        _C.check(self.lib.rfa_rotary_freqs(C.byref(a), _stream(srcs[0])), "rfa_rotary_freqs")
+        self._row_positions(a, who, positions, pos_map)
 
     # ------------------------------------------------------------------ QK RMSNorm + rotary (apply_qk_norm_rotary, apply_qk_token_norm_rotary)
     def _qk_norm_args(self, a, xs, outs, weights, cos, sin, positions, pos_map, interleaved, rot_offset, eps, weight_offset,
-                      weight_numel=None):
+                      weight_numel=None, tables=True):
         """the fields the forward and the backward struct of either norm share.  weight_numel: the elements of each tensor's 1-d
-        weight (None: D, the per-head norm's)"""
+        weight (None: D, the per-head norm's); tables=False: a struct without table and position fields of this kind (the
+        kernel forms its angles: _qk_norm_freqs_args fills its own)"""
         self._check_dev(cos, sin, positions, *xs, *outs, *weights)
         packed = self._row_tensors(a, "qk_norm_rotary: inputs and outputs share one dtype and shape; last (head_dim) stride "
                                       "must be 1", xs, outs)
@@ -799,7 +807,7 @@ class HipBackend:
             raise ValueError("qk_norm_rotary: cos and sin come together (both None: the norm alone)")
         if cos is not None:
             self._row_tables(a, "qk_norm_rotary", cos, sin)
-        else:
+        elif tables:
             a.table_dtype = a.dtype
         w0 = weights[0]
         a.weight_dtype = _C.QK_NORM_WEIGHT_F32 if w0.dtype == torch.float32 else self._dtype(w0)
@@ -807,7 +815,8 @@ class HipBackend:
             if w.dtype != w0.dtype or tuple(w.shape) != (weight_numel[k] if weight_numel else a.D,) or not w.is_contiguous():
                 raise ValueError("qk_norm_rotary: the weights are contiguous (D,) tensors of one dtype")
             a.weight[k] = w.data_ptr()
-        self._row_positions(a, "qk_norm_rotary", positions, pos_map)
+        if tables:
+            self._row_positions(a, "qk_norm_rotary", positions, pos_map)
         return packed
 
     def _qk_norm_bwd(self, a, who, workspace_bytes, bwd, packed, xs, douts, dweights, dweight_ok, dweight_refusal):
@@ -852,6 +861,40 @@ class HipBackend:
         packed = self._qk_norm_args(a, xs, dxs, weights, cos, sin, positions, pos_map, interleaved, rot_offset, eps, weight_offset)
         self._qk_norm_bwd(a, "qk_norm_rotary", "rfa_qk_norm_rotary_bwd_workspace_bytes", "rfa_qk_norm_rotary_bwd", packed, xs,
                           douts, dweights, lambda dw, x: tuple(dw.shape) == (x.shape[-1],), "dweight is a contiguous fp32 (D,) tensor")
+
+    def _qk_norm_freqs_args(self, a, xs, outs, weights, inv_freq, positions, pos_map, interleaved, rot_offset, eps, weight_offset,
+                            scaling, freq_axis):
+        """the fields rfa_qk_norm_rotary_freqs_args and _bwd_args share: the tensors and weights of _qk_norm_args (no tables),
+        then the angle's of rotary_freqs"""
+        if inv_freq.dtype != torch.float32 or inv_freq.dim() != 1 or not inv_freq.is_contiguous():
+            raise ValueError("qk_norm_freqs_rotary: inv_freq is a contiguous fp32 (R/2,) tensor")
+        self._check_dev(inv_freq, positions)
+        packed = self._qk_norm_args(a, xs, outs, weights, None, None, None, None, interleaved, rot_offset, eps, weight_offset,
+                                    tables=False)
+        a.R = 2 * inv_freq.shape[0]
+        self._row_freqs(a, "qk_norm_freqs_rotary", inv_freq, scaling, freq_axis, positions, pos_map)
+        return packed
+
+    def qk_norm_freqs_rotary_fwd(self, xs, outs, weights, inv_freq, _sin=None, *, positions=None, pos_map=None, interleaved=False,
+                                 rot_offset=0, eps=1e-6, weight_offset=0.0, scaling=1.0, freq_axis=None):
+        """one launch of the per-head RMSNorm + rotary with the angles formed in the kernel (include/rfa.h:
+        rfa_qk_norm_rotary_freqs_fwd).  xs / outs / weights as in qk_norm_rotary_fwd; inv_freq, scaling, freq_axis, positions and
+        pos_map as in rotary_freqs.  (_sin: the place of the second table in the shared autograd node; always None)"""
+        a = _C.QkNormRotaryFreqsArgs()
+        self._qk_norm_freqs_args(a, xs, outs, weights, inv_freq, positions, pos_map, interleaved, rot_offset, eps, weight_offset,
+                                 scaling, freq_axis)
+        _C.check(self.lib.rfa_qk_norm_rotary_freqs_fwd(C.byref(a), _stream(xs[0])), "rfa_qk_norm_rotary_freqs_fwd")
+
+    def qk_norm_freqs_rotary_bwd(self, xs, douts, dxs, weights, dweights, inv_freq, _sin=None, *, positions=None, pos_map=None,
+                                 interleaved=False, rot_offset=0, eps=1e-6, weight_offset=0.0, scaling=1.0, freq_axis=None):
+        """the backward (include/rfa.h: rfa_qk_norm_rotary_freqs_bwd): dxs[k] from xs[k] and douts[k] in one launch; dweights[k]
+        an fp32 (D,) tensor that is overwritten with this call's weight gradient, or None.  The workspace is allocated here."""
+        a = _C.QkNormRotaryFreqsBwdArgs()
+        packed = self._qk_norm_freqs_args(a, xs, dxs, weights, inv_freq, positions, pos_map, interleaved, rot_offset, eps,
+                                          weight_offset, scaling, freq_axis)
+        self._qk_norm_bwd(a, "qk_norm_freqs_rotary", "rfa_qk_norm_rotary_freqs_bwd_workspace_bytes", "rfa_qk_norm_rotary_freqs_bwd",
+                          packed, xs, douts, dweights, lambda dw, x: tuple(dw.shape) == (x.shape[-1],),
+                          "dweight is a contiguous fp32 (D,) tensor")
 
     def _qk_token_norm_args(self, a, xs, outs, weights, cos, sin, positions, pos_map, interleaved, rot_offset, eps, weight_offset):
         """the fields rfa_qk_token_norm_rotary_args and _bwd_args share: the per-head call's, with (H * D,) weights"""

@@ -1,5 +1,6 @@
-"""QK RMSNorm fused with the rotary embedding at GLOBAL positions: per head (`apply_qk_norm_rotary`) and over all heads of a
-token (`apply_qk_token_norm_rotary`, at the end of this file).
+"""QK RMSNorm fused with the rotary embedding at GLOBAL positions: per head with tables (`apply_qk_norm_rotary`), per head with the
+angles formed in the kernel (`apply_qk_norm_rotary_freqs`) and over all heads of a token (`apply_qk_token_norm_rotary`, at the
+end of this file).
 
 Qwen3, Gemma-3 and OLMo-style models put an RMSNorm over each head of q and k directly in front of RoPE,
     q = rope(rmsnorm_D(q_proj(x)) * w_q),   k = rope(rmsnorm_D(k_proj(x)) * w_k).
@@ -15,13 +16,14 @@ import torch
 from . import _C
 from ._api import _opaque
 from ._common import pos_map
-from .rotary import _check_qk, _check_tables_positions, _conforms
+from .rotary import _check_freqs, _check_qk, _check_tables_positions, _conforms
 
 
 class _NormRotary(torch.autograd.Function):
     """norm (per head or over the token: meta["fwd"] / meta["bwd"] name the backend's methods) + rotation of one or two tensors
-    in one launch.  Saved: the inputs, the weights, the tables and the positions (or the map's numbers) — neither rstd, which
-    the backward recomputes with the forward's own code, nor the outputs."""
+    in one launch.  Saved: the inputs, the weights, the tables — or, where the kernel forms its angles, inv_freq in the place of
+    cos, sin None — and the positions (or the map's numbers): neither rstd, which the backward recomputes with the forward's own
+    code, nor the outputs."""
 
     @staticmethod
     def forward(ctx, q, k, wq, wk, cos, sin, positions, meta):
@@ -61,10 +63,11 @@ class _NormRotary(torch.autograd.Function):
 
 
 def _norm_rotary(who, feature, check_weight, q, k, q_weight, k_weight, cos, sin, eps, weight_offset, layout, group, positions,
-                 offset, interleaved, rot_offset):
-    """what apply_qk_norm_rotary and apply_qk_token_norm_rotary share: every check in front of the launch, in one order, and the
-    node.  feature: `qk_norm` / `qk_token_norm` (the backend's serves_* flag and the stem of its two methods);
-    check_weight(x, w, D): ValueError unless w is a weight of tensor x."""
+                 offset, interleaved, rot_offset, freqs=None):
+    """what the three norm + rotary calls share: every check in front of the launch, in one order, and the node.  feature:
+    `qk_norm` / `qk_norm_freqs` / `qk_token_norm` (the backend's serves_* flag and the stem of its two methods);
+    check_weight(x, w, D): ValueError unless w is a weight of tensor x; freqs = (inv_freq, attention_scaling, freq_axis): the
+    kernel forms the angles, there are no tables (cos = sin = None) and the angle's checks are apply_rotary_freqs's."""
     from .backend import get_backend
 
     be = get_backend()
@@ -87,12 +90,16 @@ def _norm_rotary(who, feature, check_weight, q, k, q_weight, k_weight, cos, sin,
         raise ValueError(f"{who}: eps must be finite and not negative, got {eps}")
     if not math.isfinite(weight_offset):
         raise ValueError(f"{who}: weight_offset must be finite, got {weight_offset}")
-    positions, pm, interleaved, rot_offset = _check_tables_positions(who, q, packed, D, cos, sin, layout, group, positions, offset,
-                                                                      interleaved, rot_offset)
-    if cos is None:                                    # (the norm alone has no angle: nothing of the positions is used)
-        positions, pm = None, pos_map(0)
-    meta = dict(fwd=f"{feature}_rotary_fwd", bwd=f"{feature}_rotary_bwd",
-                launch=dict(pos_map=pm, interleaved=interleaved, rot_offset=rot_offset, eps=eps, weight_offset=weight_offset))
+    if freqs is not None:
+        positions, launch = _check_freqs(who, q, packed, D, *freqs, layout, group, positions, offset, interleaved, rot_offset)
+        cos = freqs[0]
+    else:
+        positions, pm, interleaved, rot_offset = _check_tables_positions(who, q, packed, D, cos, sin, layout, group, positions,
+                                                                          offset, interleaved, rot_offset)
+        if cos is None:                                # (the norm alone has no angle: nothing of the positions is used)
+            positions, pm = None, pos_map(0)
+        launch = dict(pos_map=pm, interleaved=interleaved, rot_offset=rot_offset)
+    meta = dict(fwd=f"{feature}_rotary_fwd", bwd=f"{feature}_rotary_bwd", launch=dict(launch, eps=eps, weight_offset=weight_offset))
     outs = _NormRotary.apply(q, k, q_weight, k_weight, cos, sin, positions, meta)
     return outs[0] if k is None else outs
 
@@ -134,6 +141,48 @@ def apply_qk_norm_rotary(q, k, q_weight, k_weight, cos=None, sin=None, *, eps=1e
 
 
 apply_qk_norm_rotary = _opaque(apply_qk_norm_rotary)
+
+
+def apply_qk_norm_rotary_freqs(q, k, q_weight, k_weight, inv_freq, *, eps=1e-6, weight_offset=0.0, attention_scaling=1.0,
+                               freq_axis=None, layout=None, group=None, positions=None, offset=0, interleaved=False,
+                               rot_offset=0):
+    """`apply_qk_norm_rotary` without tables: the per-head RMSNorm and a rotation whose angles the kernel forms from `inv_freq`
+    and the positions, fused (HIP: csrc/rfa_qknormfreq.hip); returns the new q, or (q, k).  Nothing of the size of the unsharded
+    sequence is held, and a row may have up to four positions (M-RoPE).
+
+        q, k = apply_qk_norm_rotary_freqs(q, k, w_q, w_k, inv_freq, layout=zigzag_ring_flash_attn_func, group=group)   # Qwen3
+        q, k = apply_qk_norm_rotary_freqs(q, k, w_q, w_k, inv_freq, positions=pos_thw, freq_axis=axes)                 # Qwen3-VL
+
+    q, k, q_weight, k_weight, eps, weight_offset, rot_offset and k=None with k_weight=None are `apply_qk_norm_rotary`'s, with
+    its checks; inv_freq, attention_scaling, freq_axis, layout, group, positions, offset and interleaved are
+    `apply_rotary_freqs`'s, with its checks (at most four axes; `layout` with freq_axis is a ValueError, and so is a map that
+    leaves [0, 2^31 - 1]).  R = 2 len(inv_freq); the columns [rot_offset, rot_offset + R) are rotated, the norm always runs over
+    all D columns.
+    Per (row, head), in fp32 with ONE rounding to the io dtype at the end: `apply_qk_norm_rotary`'s norm, the angle
+    ang = float(pos[axis(c)]) * inv_freq[c] as one rounded multiply, the precise sincosf, both times attention_scaling, then
+    `apply_rotary`'s expression.  An element's bits depend on the row's values, the weight, the position(s), inv_freq and the
+    scaling alone: every rank's shard is the shard of the single-device result, bit for bit, which the two calls this one
+    replaces (the norm alone, then `apply_rotary_freqs`) do not give — they round to the io dtype in between.
+    Autograd: one backward launch (plus a small fold) gives dq, dk and both weight gradients; kept are q, k, the weights,
+    inv_freq and the positions or the map — neither rstd nor the outputs; the weight gradient is summed in fp32 in a fixed order
+    without atomics (two runs: the same bits) and rounded once to the weight's dtype; inv_freq gets no gradient; a weight that
+    does not require grad, or a tensor whose incoming gradient is None, skips that work.  Over several ranks the weight gradient
+    is THIS RANK'S PARTIAL, like `sinks.grad`.  There is no in-place mode.
+    Under torch.compile the call runs eagerly behind a graph break.
+    Raises, before anything is launched: NotImplementedError for a backend without `serves_qk_norm_freqs`; TypeError for a
+    `layout` that is not one of the nine dense attention functions; ValueError for everything else."""
+    who = "ring_flash_attn.apply_qk_norm_rotary_freqs"
+
+    def check_weight(x, w, D):
+        if not isinstance(w, torch.Tensor) or tuple(w.shape) != (D,) or not w.is_contiguous() or w.device != q.device or \
+                w.dtype not in (torch.float32, q.dtype) or w.dtype != q_weight.dtype:
+            raise ValueError(f"{who}: the weights must be contiguous (D,) = ({D},) tensors on q's device, both fp32 or both {q.dtype}")
+
+    return _norm_rotary(who, "qk_norm_freqs", check_weight, q, k, q_weight, k_weight, None, None, eps, weight_offset, layout, group,
+                        positions, offset, interleaved, rot_offset, freqs=(inv_freq, attention_scaling, freq_axis))
+
+
+apply_qk_norm_rotary_freqs = _opaque(apply_qk_norm_rotary_freqs)
 
 
 def apply_qk_token_norm_rotary(q, k, q_weight, k_weight, cos=None, sin=None, *, eps=1e-6, weight_offset=0.0, layout=None,

@@ -322,6 +322,64 @@ apply_rotary = _opaque(apply_rotary)
 _POS_MAX = 2 ** 31 - 1
 
 
+def _check_freqs(who, q, packed, D, inv_freq, attention_scaling, freq_axis, layout, group, positions, offset, interleaved,
+                 rot_offset):
+    """the checks of inv_freq, the scaling, freq_axis and the positions that apply_rotary_freqs and apply_qk_norm_rotary_freqs
+    share, in apply_rotary_freqs's order.  Returns (positions, launch): the positions as the backend takes them and its
+    keywords scaling, freq_axis, pos_map, interleaved, rot_offset."""
+    if not isinstance(inv_freq, torch.Tensor) or inv_freq.dtype != torch.float32 or inv_freq.dim() != 1 or \
+            not inv_freq.is_contiguous() or inv_freq.device != q.device:
+        raise ValueError(f"{who}: inv_freq must be a contiguous fp32 (R/2,) tensor on q's device")
+    interleaved = bool(interleaved)
+    half = inv_freq.shape[0]
+    R = 2 * half
+    if R < 1 or R % (8 if interleaved else 16):
+        raise ValueError(f"{who}: the rotary width R = {R} must be a positive multiple of {8 if interleaved else 16} "
+                         f"({'interleaved' if interleaved else 'halves'})")
+    if isinstance(attention_scaling, bool) or not isinstance(attention_scaling, (int, float)) or \
+            not math.isfinite(attention_scaling) or not attention_scaling > 0:
+        raise ValueError(f"{who}: attention_scaling must be a finite number > 0, got {attention_scaling!r}")
+    S = q.shape[0] if packed else q.shape[1]
+    if freq_axis is None:
+        # (apply_rotary's checks of rot_offset, layout and positions; no table: nothing bounds the positions there)
+        positions, pm, _, rot_offset = _check_tables_positions(who, q, packed, D, None, None, layout, group, positions, offset,
+                                                               interleaved, rot_offset)
+        if positions is None and S:
+            lo, hi = _map_bounds(pm, S)
+            if lo < 0 or hi > _POS_MAX:
+                raise ValueError(f"{who}: the rows sit at positions {lo} .. {hi}, outside 0 .. 2^31 - 1")
+    else:
+        if isinstance(freq_axis, torch.Tensor):
+            if freq_axis.is_floating_point() or freq_axis.device.type != "cpu" or freq_axis.dim() != 1:
+                raise ValueError(f"{who}: freq_axis must be a sequence or a 1-d CPU int tensor")
+            freq_axis = freq_axis.tolist()
+        freq_axis = tuple(freq_axis)
+        if len(freq_axis) != half or not all(isinstance(a, int) and not isinstance(a, bool) for a in freq_axis):
+            raise ValueError(f"{who}: freq_axis must hold R/2 = {half} ints, one axis number per frequency")
+        if layout is not None:
+            if _family(layout, who.rsplit(".", 1)[-1]) not in _DENSE:
+                raise TypeError(f"{who}: `layout` serves the nine dense functions")
+            raise ValueError(f"{who}: `layout` yields one position per row and cannot serve freq_axis; pass positions= of shape (A, ...)")
+        _, pm, _, rot_offset = _check_tables_positions(who, q, packed, D, None, None, None, group, None, offset, interleaved,
+                                                       rot_offset)
+        lead = ((S,),) if packed else ((S,), (q.shape[0], S))
+        if not isinstance(positions, torch.Tensor) or positions.dtype != torch.int32 or positions.device != q.device or \
+                not positions.is_contiguous() or not 1 <= positions.shape[0] <= 4 or tuple(positions.shape[1:]) not in lead:
+            raise ValueError(f"{who}: with freq_axis, positions must be a contiguous int32 tensor of shape "
+                             f"{' or '.join(str(('A',) + w) for w in lead)}, 1 <= A <= 4, on q's device")
+        A = positions.shape[0]
+        if not all(0 <= a < A for a in freq_axis):
+            raise ValueError(f"{who}: freq_axis must name axes in [0, {A}), the first dimension of positions")
+    # (rot_offset is apply_rotary's by now: an int, a multiple of 8 inside D; the offset of tensor positions is bounded like a
+    # map's, where rfa_rotary_freqs would refuse it)
+    if rot_offset + R > D:
+        raise ValueError(f"{who}: rot_offset {rot_offset} must be a multiple of 8 with rot_offset + R = {rot_offset + R} <= D = {D}")
+    if positions is not None and abs(pm[0]) > _POS_MAX:
+        raise ValueError(f"{who}: offset {pm[0]} is outside -(2^31 - 1) .. 2^31 - 1")
+    return positions, dict(scaling=float(attention_scaling), freq_axis=freq_axis, pos_map=pm, interleaved=interleaved,
+                           rot_offset=rot_offset)
+
+
 def apply_rotary_freqs(q, k=None, inv_freq=None, *, attention_scaling=1.0, freq_axis=None, layout=None, group=None,
                        positions=None, offset=0, interleaved=False, rot_offset=0, inplace=False):
     """`apply_rotary` without tables: the kernel forms the angles from `inv_freq` and the positions; returns the rotated q, or
@@ -359,58 +417,9 @@ def apply_rotary_freqs(q, k=None, inv_freq=None, *, attention_scaling=1.0, freq_
     if not isinstance(q, torch.Tensor) or (k is not None and not isinstance(k, torch.Tensor)):
         raise ValueError(f"{who}: q and k must be tensors")
     packed, D = _check_qk(who, q, k)
-    if not isinstance(inv_freq, torch.Tensor) or inv_freq.dtype != torch.float32 or inv_freq.dim() != 1 or \
-            not inv_freq.is_contiguous() or inv_freq.device != q.device:
-        raise ValueError(f"{who}: inv_freq must be a contiguous fp32 (R/2,) tensor on q's device")
-    interleaved = bool(interleaved)
-    half = inv_freq.shape[0]
-    R = 2 * half
-    if R < 1 or R % (8 if interleaved else 16):
-        raise ValueError(f"{who}: the rotary width R = {R} must be a positive multiple of {8 if interleaved else 16} "
-                         f"({'interleaved' if interleaved else 'halves'})")
-    if isinstance(attention_scaling, bool) or not isinstance(attention_scaling, (int, float)) or \
-            not math.isfinite(attention_scaling) or not attention_scaling > 0:
-        raise ValueError(f"{who}: attention_scaling must be a finite number > 0, got {attention_scaling!r}")
-    S = q.shape[0] if packed else q.shape[1]
-    if freq_axis is None:
-        # (apply_rotary's checks of rot_offset, layout and positions; no table: nothing bounds the positions there)
-        positions, pm, _, rot_offset = _check_tables_positions(who, q, packed, D, None, None, layout, group, positions, offset,
-                                                               interleaved, rot_offset)
-        if positions is None and S:
-            lo, hi = _map_bounds(pm, S)
-            if lo < 0 or hi > _POS_MAX:
-                raise ValueError(f"{who}: the rows sit at positions {lo} .. {hi}, outside 0 .. 2^31 - 1")
-    else:
-        if isinstance(freq_axis, torch.Tensor):
-            if freq_axis.is_floating_point() or freq_axis.device.type != "cpu" or freq_axis.dim() != 1:
-                raise ValueError(f"{who}: freq_axis must be a sequence or a 1-d CPU int tensor")
-            freq_axis = freq_axis.tolist()
-        freq_axis = tuple(freq_axis)
-        if len(freq_axis) != half or not all(isinstance(a, int) and not isinstance(a, bool) for a in freq_axis):
-            raise ValueError(f"{who}: freq_axis must hold R/2 = {half} ints, one axis number per frequency")
-        if layout is not None:
-            if _family(layout, "apply_rotary_freqs") not in _DENSE:
-                raise TypeError(f"{who}: `layout` serves the nine dense functions")
-            raise ValueError(f"{who}: `layout` yields one position per row and cannot serve freq_axis; pass positions= of shape (A, ...)")
-        _, pm, _, rot_offset = _check_tables_positions(who, q, packed, D, None, None, None, group, None, offset, interleaved,
-                                                       rot_offset)
-        lead = ((S,),) if packed else ((S,), (q.shape[0], S))
-        if not isinstance(positions, torch.Tensor) or positions.dtype != torch.int32 or positions.device != q.device or \
-                not positions.is_contiguous() or not 1 <= positions.shape[0] <= 4 or tuple(positions.shape[1:]) not in lead:
-            raise ValueError(f"{who}: with freq_axis, positions must be a contiguous int32 tensor of shape "
-                             f"{' or '.join(str(('A',) + w) for w in lead)}, 1 <= A <= 4, on q's device")
-        A = positions.shape[0]
-        if not all(0 <= a < A for a in freq_axis):
-            raise ValueError(f"{who}: freq_axis must name axes in [0, {A}), the first dimension of positions")
-    # (rot_offset is apply_rotary's by now: an int, a multiple of 8 inside D; the offset of tensor positions is bounded like a
-    # map's, where rfa_rotary_freqs would refuse it)
-    if rot_offset + R > D:
-        raise ValueError(f"{who}: rot_offset {rot_offset} must be a multiple of 8 with rot_offset + R = {rot_offset + R} <= D = {D}")
-    if positions is not None and abs(pm[0]) > _POS_MAX:
-        raise ValueError(f"{who}: offset {pm[0]} is outside -(2^31 - 1) .. 2^31 - 1")
-    return _rotate(who, "rotary_freqs", q, k, (inv_freq,), positions, inplace,
-                   dict(scaling=float(attention_scaling), freq_axis=freq_axis, pos_map=pm, interleaved=interleaved,
-                        rot_offset=rot_offset))
+    positions, launch = _check_freqs(who, q, packed, D, inv_freq, attention_scaling, freq_axis, layout, group, positions, offset,
+                                     interleaved, rot_offset)
+    return _rotate(who, "rotary_freqs", q, k, (inv_freq,), positions, inplace, launch)
 
 
 apply_rotary_freqs = _opaque(apply_rotary_freqs)
