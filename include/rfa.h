@@ -930,6 +930,88 @@ int rfa_qk_token_norm_rotary_fwd(const rfa_qk_token_norm_rotary_args *args, void
 int rfa_qk_token_norm_rotary_bwd(const rfa_qk_token_norm_rotary_bwd_args *args, void *stream);
 int64_t rfa_qk_token_norm_rotary_bwd_workspace_bytes(const rfa_qk_token_norm_rotary_bwd_args *args);
 
+/* RMSNorm of q and k over ALL heads of a token fused with a rotary embedding whose angles are formed in the kernel, one to four
+ * position axes per row (ring_flash_attn.apply_qk_token_norm_rotary_freqs; csrc/rfa_qktokenfreq.hip) — OLMo-2 / OLMo-3 under
+ * context parallelism without tables of the unsharded sequence, and a token-wide norm in front of an M-RoPE.  Entry points and
+ * structs of their own; no existing struct, kernel or refusal changes (ABI 8 revision 1 stays).  Tensors, weights ((t[k].H * D,)),
+ * eps, weight_offset, the gradients, dweight, the partials and the workspace are rfa_qk_token_norm_rotary's, with its arithmetic
+ * for the norm and its backward (the same device functions: rstd has that kernel's bits); inv_freq, scaling, naxes, freq_axis
+ * and the position fields are rfa_rotary_freqs's, with its arithmetic for the angle (one rounded multiply, the precise sincosf,
+ * times scaling).  There is no conj: the backward conjugates the rotation itself.  R is positive: the norm alone is
+ * rfa_qk_token_norm_rotary's.  A token row's team forms the row's R/2 angles once for all heads; one launch per direction, plus
+ * the fold of the weight gradient partials (a fixed order, no atomics: two runs give the same bits).  The bits of an element
+ * depend on its token row's values, the weight, the position(s), inv_freq and the scaling alone.
+ *   workspace: rfa_qk_token_norm_rotary_freqs_bwd_workspace_bytes(args) bytes = rfa_qk_token_norm_rotary_bwd_workspace_bytes of
+ *   the same shapes (0 for arguments the checks below refuse before a pointer is needed), 16-byte aligned, needed where a
+ *   dweight is asked for.
+ * Checks, in this order and before any pointer is read: NULL struct RFA_ERR_NULL; struct_bytes != sizeof, reserved != 0,
+ * ntensors outside 1..2, interleaved outside 0..1, a non-zero pad (of a tensor or the struct's), naxes outside 1..4, a scaling
+ * that is not finite or not > 0, an eps that is negative or not finite, a weight_offset that is not finite RFA_ERR_ARGS; dtype,
+ * a weight_dtype that is neither dtype nor RFA_QK_NORM_WEIGHT_F32 RFA_ERR_DTYPE; D not a multiple of 8 in 8..256, R not a
+ * positive multiple of 16 (interleaved: of 8), rot_offset negative or not a multiple of 8, rot_offset + R > D
+ * RFA_ERR_HEAD_DIM; B < 0, S < 0, B * S above 2^31 - 1 RFA_ERR_SHAPE; an H <= 0, or an H * D above
+ * RFA_QK_TOKEN_NORM_MAX_WIDTH, of any tensor RFA_ERR_HEADS; an axis code >= naxes among the first R/2, or a non-zero bit behind
+ * them, RFA_ERR_ARGS; B == 0 or S == 0: RFA_OK, nothing is launched or written; NULL src, dst, weight or inv_freq (backward:
+ * dout; a dweight without a workspace) RFA_ERR_NULL; pointers or strides off the 16-byte contract (inv_freq and a dweight: 4
+ * bytes) RFA_ERR_ALIGN; dst == src (backward also dst == dout), a negative pos_batch or pos_axis, a pos_offset beyond +-2^40,
+ * naxes > 1 with positions == NULL, with the map a negative pos_stride, a pos_split outside 0..S-1 or a position outside
+ * [0, 2^31 - 1], a workspace_bytes below the stated size RFA_ERR_ARGS. */
+typedef struct {
+  uint32_t struct_bytes;   /* sizeof(rfa_qk_token_norm_rotary_freqs_args) */
+  uint32_t reserved;       /* 0 */
+  int32_t ntensors;        /* 1..2 */
+  int32_t B, S, D;         /* packed input: B = 1, S = T */
+  int32_t dtype;           /* rfa_dtype */
+  int32_t R, rot_offset;
+  int32_t interleaved;
+  int32_t naxes;           /* 1..4: axes of `positions` */
+  int32_t weight_dtype;    /* dtype, or RFA_QK_NORM_WEIGHT_F32 */
+  float eps, weight_offset;
+  rfa_rotary_tensor t[2];  /* src = x, dst = the output */
+  const void *weight[2];   /* (t[k].H * D,) */
+  const float *inv_freq;   /* (R/2,) fp32, contiguous */
+  float scaling;           /* multiplies cos and sin; finite, > 0 */
+  int32_t pad;             /* 0 */
+  uint64_t freq_axis[4];   /* 2 bits per frequency: the axis it reads */
+  const int32_t *positions; /* (naxes, B, S) int32, or NULL: the map (naxes 1) */
+  int64_t pos_batch;
+  int64_t pos_axis;
+  int64_t pos_offset;
+  int32_t pos_stride, pos_split;
+  int64_t pos_offset2;
+} rfa_qk_token_norm_rotary_freqs_args;
+typedef struct {
+  uint32_t struct_bytes;   /* sizeof(rfa_qk_token_norm_rotary_freqs_bwd_args) */
+  uint32_t reserved;       /* 0 */
+  int32_t ntensors;
+  int32_t B, S, D;
+  int32_t dtype;
+  int32_t R, rot_offset;
+  int32_t interleaved;
+  int32_t naxes;
+  int32_t weight_dtype;
+  float eps, weight_offset;
+  rfa_rotary_tensor t[2];  /* src = x, dst = dx */
+  const void *weight[2];
+  const float *inv_freq;
+  float scaling;
+  int32_t pad;
+  uint64_t freq_axis[4];
+  const int32_t *positions;
+  int64_t pos_batch;
+  int64_t pos_axis;
+  int64_t pos_offset;
+  int32_t pos_stride, pos_split;
+  int64_t pos_offset2;
+  rfa_qk_norm_grad g[2];
+  float *dweight[2];       /* fp32 (t[k].H * D,), overwritten; NULL: not wanted */
+  void *workspace;
+  int64_t workspace_bytes;
+} rfa_qk_token_norm_rotary_freqs_bwd_args;
+int rfa_qk_token_norm_rotary_freqs_fwd(const rfa_qk_token_norm_rotary_freqs_args *args, void *stream);
+int rfa_qk_token_norm_rotary_freqs_bwd(const rfa_qk_token_norm_rotary_freqs_bwd_args *args, void *stream);
+int64_t rfa_qk_token_norm_rotary_freqs_bwd_workspace_bytes(const rfa_qk_token_norm_rotary_freqs_bwd_args *args);
+
 /* Per-head max attention logit (QK-Clip / MuonClip; Transformer Engine's and Megatron's `max_logit`): for every query head h
  *     max_logit[h] = max over batch b, query row i and the keys j that row i SEES of  softmax_scale * q[b,i,h,:] . k[b,j,h/G,:]
  * for one block call — the raw scaled dot product (no soft cap, bias, dropout or sink enters it), -inf for a head that sees no

@@ -1801,15 +1801,28 @@ int rfa_rotary_freqs(const rfa_rotary_freqs_args* a, void* stream) {
   return launch_rotary_freqs(p, a->dtype, (hipStream_t)stream) ? RFA_ERR_LAUNCH : RFA_OK;
 }
 
-// ---- the QK RMSNorms + rotary: per head (csrc/rfa_qknorm.hip) and over all heads of a token (csrc/rfa_qktoken.hip) ------------
+// ---- the QK RMSNorms + rotary: per head (csrc/rfa_qknorm.hip, rfa_qknormfreq.hip) and over all heads of a token
+// ---- (csrc/rfa_qktoken.hip, rfa_qktokenfreq.hip) ---------------------------------------------------------------------------
 static_assert(RFA_QK_TOKEN_NORM_MAX_WIDTH == kQkTokenMaxWidth && RFA_QK_TOKEN_NORM_MAX_PARTS == kQkTokenMaxParts,
               "rfa.h and rfa_qktoken_index.h state the same limits");
 static_assert(RFA_QK_NORM_FREQS_TILE_ROWS == kQkNfRows, "rfa.h and rfa_qknormfreq_index.h state the same tile height");
 extern "C++" {
-// the structs of the per-head norm that forms its own angles (csrc/rfa_qknormfreq.hip): where the others have tables, these
-// have rfa_rotary_freqs's inv_freq, scaling, naxes and freq_axis, checked where rfa_rotary_freqs checks them
+// the structs of the norms that form their own angles (csrc/rfa_qknormfreq.hip, rfa_qktokenfreq.hip): where the others have
+// tables, these have rfa_rotary_freqs's inv_freq, scaling, naxes and freq_axis, checked where rfa_rotary_freqs checks them
 template <typename A>
-constexpr bool kOwnAngles = std::is_same_v<A, rfa_qk_norm_rotary_freqs_args> || std::is_same_v<A, rfa_qk_norm_rotary_freqs_bwd_args>;
+constexpr bool kOwnAngles = std::is_same_v<A, rfa_qk_norm_rotary_freqs_args> || std::is_same_v<A, rfa_qk_norm_rotary_freqs_bwd_args> ||
+                            std::is_same_v<A, rfa_qk_token_norm_rotary_freqs_args> ||
+                            std::is_same_v<A, rfa_qk_token_norm_rotary_freqs_bwd_args>;
+
+// every frequency of the call reads an axis that `positions` has, and no bit is set behind the R/2 codes
+template <typename A>
+static int qk_axis_codes(const A* a) {
+  for (uint32_t c = 0; c < 4 * 32; ++c) {                      // (R/2 <= 128 = the entries of the four words)
+    const uint32_t axis = rotfreq_axis(a->freq_axis[0], a->freq_axis[1], a->freq_axis[2], a->freq_axis[3], c);
+    if (axis >= (c < (uint32_t)a->R / 2 ? (uint32_t)a->naxes : 1u)) return RFA_ERR_ARGS;
+  }
+  return RFA_OK;
+}
 
 // the checks the forward and the backward struct of either norm share, up to the NULL checks: `upto` 0 stops in front of "no
 // rows" (everything that needs no pointer: what the workspace size depends on), 1 runs them all.  RFA_OK with *launch == false:
@@ -1880,30 +1893,43 @@ static int qk_freqs_check(const A* a, int upto, QkNormFreqParams* p, bool* launc
       if (rows * a->t[k].H > INT32_MAX || (int64_t)kQkNfRows * a->t[k].H > INT32_MAX) return RFA_ERR_SHAPE;
       p->t[k].nitems = (uint32_t)(rows * a->t[k].H);
     }
-    for (uint32_t c = 0; c < 4 * 32; ++c) {                    // (R/2 <= 128 = the entries of the four words)
-      const uint32_t axis = rotfreq_axis(a->freq_axis[0], a->freq_axis[1], a->freq_axis[2], a->freq_axis[3], c);
-      if (axis >= (c < (uint32_t)a->R / 2 ? (uint32_t)a->naxes : 1u)) return RFA_ERR_ARGS;
-    }
+    if (int rc = qk_axis_codes(a)) return rc;
     p->nparts = qknf_parts(qknf_tiles(g.B, g.S));
     p->walk = qknf_walk(qknf_tiles(g.B, g.S), p->nparts);
     return RFA_OK;
   });
 }
 
+// what a token-wide norm's Geom and Tensors hold beyond the shared members: teams, partials and walk, functions of the shapes
+template <typename A>
+static int qk_token_own(const A* a, QkTokenParams* p, int64_t rows) {
+  for (int k = 0; k < a->ntensors; ++k)
+    if ((int64_t)a->t[k].H * a->D > kQkTokenMaxWidth) return RFA_ERR_HEADS;
+  p->g.hchunks = p->g.D / 8;
+  for (int k = 0; k < a->ntensors; ++k) {
+    QkTokenTensor& t = p->t[k];
+    t.N = t.H * p->g.D; t.chunks = t.N / 8; t.team = qktoken_team(t.N); t.rows = (uint32_t)rows;
+    p->nparts[k] = qktoken_parts(t.rows, t.team);
+    p->walk[k] = qktoken_walk(t.rows, p->nparts[k], t.team);
+  }
+  p->weight_f32 = a->weight_dtype == RFA_QK_NORM_WEIGHT_F32;
+  return RFA_OK;
+}
+
 template <typename A>
 static int qk_token_check(const A* a, int upto, QkTokenParams* p, bool* launch) {
   return qk_check(a, upto, p, launch, [](const A* a, QkTokenParams* p, int64_t rows) -> int {
-    for (int k = 0; k < a->ntensors; ++k)
-      if ((int64_t)a->t[k].H * a->D > kQkTokenMaxWidth) return RFA_ERR_HEADS;
-    p->g.hchunks = p->g.D / 8;
-    for (int k = 0; k < a->ntensors; ++k) {
-      QkTokenTensor& t = p->t[k];
-      t.N = t.H * p->g.D; t.chunks = t.N / 8; t.team = qktoken_team(t.N); t.rows = (uint32_t)rows;
-      p->nparts[k] = qktoken_parts(t.rows, t.team);
-      p->walk[k] = qktoken_walk(t.rows, p->nparts[k], t.team);
-    }
-    p->table_f32 = a->table_dtype == RFA_ROTARY_TABLE_F32; p->weight_f32 = a->weight_dtype == RFA_QK_NORM_WEIGHT_F32;
+    if (int rc = qk_token_own(a, p, rows)) return rc;
+    p->table_f32 = a->table_dtype == RFA_ROTARY_TABLE_F32;
     return RFA_OK;
+  });
+}
+
+template <typename A>
+static int qk_token_freqs_check(const A* a, int upto, QkTokenFreqParams* p, bool* launch) {
+  return qk_check(a, upto, p, launch, [](const A* a, QkTokenFreqParams* p, int64_t rows) -> int {
+    if (int rc = qk_token_own(a, p, rows)) return rc;
+    return qk_axis_codes(a);
   });
 }
 
@@ -2049,6 +2075,31 @@ int rfa_qk_token_norm_rotary_bwd(const rfa_qk_token_norm_rotary_bwd_args* a, voi
   if (rc != RFA_OK || !launch) return rc;
   if ((rc = qk_bwd_tail(a, &p, qk_token_workspace)) != RFA_OK) return rc;
   return launch_qktoken_bwd(p, a->dtype, (hipStream_t)stream) ? RFA_ERR_LAUNCH : RFA_OK;
+}
+
+// ---- the token-wide norm with the angles formed in the kernel (csrc/rfa_qktokenfreq.hip) -------------------------------------
+int rfa_qk_token_norm_rotary_freqs_fwd(const rfa_qk_token_norm_rotary_freqs_args* a, void* stream) {
+  QkTokenFreqParams p{};
+  bool launch = false;
+  int rc = qk_token_freqs_check(a, 1, &p, &launch);
+  if (rc != RFA_OK || !launch) return rc;
+  if ((rc = qk_check_aligned(a)) != RFA_OK || (rc = qk_check_map(a, &p)) != RFA_OK) return rc;
+  return launch_qktokenfreq_fwd(p, a->dtype, (hipStream_t)stream) ? RFA_ERR_LAUNCH : RFA_OK;
+}
+
+int64_t rfa_qk_token_norm_rotary_freqs_bwd_workspace_bytes(const rfa_qk_token_norm_rotary_freqs_bwd_args* a) {
+  QkTokenFreqParams p{};
+  bool launch = false;
+  return qk_token_freqs_check(a, 0, &p, &launch) == RFA_OK ? qk_token_workspace(p) : 0;
+}
+
+int rfa_qk_token_norm_rotary_freqs_bwd(const rfa_qk_token_norm_rotary_freqs_bwd_args* a, void* stream) {
+  QkTokenFreqParams p{};
+  bool launch = false;
+  int rc = qk_token_freqs_check(a, 1, &p, &launch);
+  if (rc != RFA_OK || !launch) return rc;
+  if ((rc = qk_bwd_tail(a, &p, qk_token_workspace)) != RFA_OK) return rc;
+  return launch_qktokenfreq_bwd(p, a->dtype, (hipStream_t)stream) ? RFA_ERR_LAUNCH : RFA_OK;
 }
 
 // ---- per-head max attention logit (rfa.h; csrc/rfa_maxlogit.hip) ------------------------------------------------------------

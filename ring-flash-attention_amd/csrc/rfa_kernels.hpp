@@ -399,6 +399,20 @@ struct QkTokenParams {
 };
 int launch_qktoken_fwd(const QkTokenParams& p, int dtype, hipStream_t stream);
 int launch_qktoken_bwd(const QkTokenParams& p, int dtype, hipStream_t stream);
+int launch_qktoken_fold(const QkTokenParams& p, hipStream_t stream);   // the second launch of a backward: partials -> dweight
+
+// token-wide QK RMSNorm fused with a rotary embedding whose angles are formed in the kernel (rfa_qktokenfreq.hip; ownership and
+// partials: rfa_qktoken_index.h, unchanged): QkTokenParams' tensors, weights, partials and position map — cos, sin, P and
+// table_f32 stay zero — with the angle's fields of RotFreqParams (R > 0 always; positions may have up to four axes).  The
+// backward conjugates the rotation itself; its partials are folded by launch_qktoken_fold.
+struct QkTokenFreqParams : QkTokenParams {
+  const float* inv_freq;    // (R/2,)
+  float scaling;            // multiplies cos and sin
+  int64_t pos_axis;
+  uint64_t freq_axis[4];    // 2 bits per frequency
+};
+int launch_qktokenfreq_fwd(const QkTokenFreqParams& p, int dtype, hipStream_t stream);
+int launch_qktokenfreq_bwd(const QkTokenFreqParams& p, int dtype, hipStream_t stream);
 
 // per-head max attention logit (rfa_maxlogit.hip; tile arithmetic: rfa_maxlogit_band.h): the forward's S phase alone.
 // Workgroup (batch b, query block qb, head h) stores the max of its UNSCALED visible scores to

@@ -34,82 +34,18 @@
 //     Longest chain: walk + slots + ceil(nparts/8) + 8 additions.  No atomics; nparts = min(ceil(rows/slots), 512) is a
 //     function of the tensor's shape alone, so its weight gradient's bits do not depend on the tensor that rides along.
 // grid: forward x = max over tensors of ceil(rows/slots), y = tensor; backward x = max over tensors of nparts, y = tensor.
+// The row sums' stages, rstd, the scale, rotate8, the lane roles and the hand-over of a workgroup's dw partial are
+// rfa_qktoken_math.hpp's, shared with rfa_qktokenfreq.hip (the same kernels with the angles formed in place of the table fetch:
+// its rstd, rotated pairs and partials have these kernels' bits); launch_qktoken_fold serves both sources' partials.
 #include "rfa_common.hpp"
 #include "rfa_kernels.hpp"
 #include "rfa_rotary_math.hpp"
+#include "rfa_qktoken_math.hpp"
 
 namespace rfa {
 namespace {
 
-enum { kTokNone = 0, kTokHalves = 1, kTokInterleaved = 2 };
-constexpr uint32_t kStageBytes = 32768;       // 16 B x (4 rows x 128 | 2 rows x 512 | 1 row x 2048) chunks
-constexpr uint32_t kTabFloats = 128;          // R / 2 <= 128
-constexpr uint32_t kMaxSlots = 4;
-
-typedef float f32x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-template <typename T>
-__device__ __forceinline__ void widen(const vec8<T>& v, float (&f)[8]) {
-#pragma unroll
-  for (int e = 0; e < 8; ++e) f[e] = (float)v[e];
-}
-
-template <typename T>
-__device__ __forceinline__ void store8(T* p, const float (&f)[8]) {
-  f32x8 v;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) v[e] = f[e];
-  *(vec8<T>*)p = __builtin_convertvector(v, vec8<T>);
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int m = 32; m; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-
-// the team's sum of the per-wave sums in `red` (written in front of the last barrier), in wave order
-__device__ __forceinline__ float team_total(const float* red, uint32_t team, uint32_t wave) {
-  const uint32_t nw = team >> 6, fw = wave & ~(nw - 1);
-  float total = red[fw];
-  for (uint32_t j = 1; j < nw; ++j) total += red[fw + j];
-  return total;
-}
-
-__device__ __forceinline__ float row_rstd(float ss, uint32_t N, float eps) { return rsqrtf(ss / (float)N + eps); }
-
-// a_c = weight_offset + w_c of the 8 columns of chunk c
-template <typename T>
-__device__ __forceinline__ void load_scale(const QkTokenParams& p, const void* weight, uint32_t c, float (&a)[8]) {
-  if (p.weight_f32) {
-    float lo[4], hi[4];
-    load_tab<float, 4>((const float*)weight + 8 * (size_t)c, lo);
-    load_tab<float, 4>((const float*)weight + 8 * (size_t)c + 4, hi);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      a[e] = p.weight_offset + lo[e];
-      a[4 + e] = p.weight_offset + hi[e];
-    }
-  } else {
-    float w[8];
-    load_tab<T, 8>((const T*)weight + 8 * (size_t)c, w);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) a[e] = p.weight_offset + w[e];
-  }
-}
-
-// a wave-uniform 64-bit value held in vector registers.  The backward keeps more uniform values live across its walk than there
-// are scalar registers; strides and position offsets only ever enter per-lane (vector) arithmetic, so they live there
-__device__ __forceinline__ int64_t in_vgpr(int64_t v) {
-  asm volatile("" : "+v"(v));
-  return v;
-}
-
-__device__ __forceinline__ uint32_t in_vgpr(uint32_t v) {
-  asm volatile("" : "+v"(v));
-  return v;
-}
+using namespace qktoken_math;         // wave_sum, team_total, row_rstd, load_scale, rotate8, lane_roles, store_dw_partial
 
 // the row's cos / sin values into tab[0 / 1][slot][0 .. R/2), widened; by the row's own team, once for all its heads
 template <typename T>
@@ -130,44 +66,6 @@ __device__ __forceinline__ void stage_tables(const QkTokenParams& p, float (*tab
       tab[0][slot][j] = (float)((const T*)p.cos)[at + j];
       tab[1][slot][j] = (float)((const T*)p.sin)[at + j];
     }
-  }
-}
-
-// the chunk's 8 columns after the rotation (CONJ: the inverse one); v the chunk's values, pv its partner's (halves only)
-template <int MODE, bool CONJ>
-__device__ __forceinline__ void rotate8(const float (&v)[8], const float (&pv)[8], float (&o)[8], int kind, const float* c,
-                                        const float* s) {
-  if constexpr (MODE == kTokHalves) {
-    const bool lo = kind == kQkTokenLo;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      float o1, o2;
-      rot(lo ? v[e] : pv[e], lo ? pv[e] : v[e], c[e], CONJ ? -s[e] : s[e], o1, o2);
-      o[e] = lo ? o1 : o2;
-    }
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) rot(v[2 * e], v[2 * e + 1], c[e], CONJ ? -s[e] : s[e], o[2 * e], o[2 * e + 1]);
-  }
-}
-
-// lane tl's j-th chunk, tl + j * team, exists: a uniform test for all j but one (every lane has its first chunks / team ones)
-__device__ __forceinline__ bool has_chunk(uint32_t j, uint32_t tl, uint32_t jfull, uint32_t tail) {
-  return j < jfull || (j == jfull && tl < tail);
-}
-
-// (head << 16 | first column) and (kind << 16 | table column) of the lane's chunks: functions of the chunk alone
-template <int K>
-__device__ __forceinline__ void lane_roles(const QkTokenGeom& g, const QkTokenTensor& t, uint32_t tl, uint32_t (&hc)[K],
-                                           uint32_t (&kt)[K]) {
-#pragma unroll
-  for (int j = 0; j < K; ++j) {
-    const uint32_t c = tl + j * t.team;
-    QkTokenRole r{};
-    r.kind = kQkTokenPass;
-    if (c < t.chunks) qktoken_role(g, c, &r);
-    hc[j] = r.head << 16 | r.col;
-    kt[j] = (uint32_t)r.kind << 16 | r.tcol;
   }
 }
 
@@ -361,38 +259,7 @@ __global__ __launch_bounds__(256) void qktoken_bwd_kernel(const QkTokenParams p)
   }
   if (in_vgpr(wantv) == 0) return;                                          // (uniform over the workgroup)
   // the teams of the workgroup, in slot order: slots 1 .. hand theirs over through LDS ((slots - 1) N floats <= 16 KiB)
-  float* hand = (float*)stage_raw;
-  if (slots > 1) {
-    __syncthreads();                                             // (the last step's reads of `stage` are done)
-    if (slot > 0) {
-#pragma unroll
-      for (int j = 0; j < K; ++j) {
-        const uint32_t c = tl + j * teamv;
-        if (!has_chunk(j, tl, jfull, tail)) continue;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) hand[(size_t)(slot - 1) * t.N + 8 * c + e] = acc[j][e];
-      }
-    }
-    __syncthreads();
-  }
-  if (slot > 0) return;
-  float* part = p.workspace + (k ? (size_t)p.nparts[0] * p.t[0].N : (size_t)0) + (size_t)blockIdx.x * t.N;
-#pragma unroll
-  for (int j = 0; j < K; ++j) {
-    const uint32_t c = tl + j * teamv;
-    if (!has_chunk(j, tl, jfull, tail)) continue;
-    for (uint32_t s = 1; s < slots; ++s)
-#pragma unroll
-      for (int e = 0; e < 8; ++e) acc[j][e] += hand[(size_t)(s - 1) * t.N + 8 * c + e];
-    f32x4 lo, hi;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      lo[e] = acc[j][e];
-      hi[e] = acc[j][4 + e];
-    }
-    *(f32x4*)(part + 8 * c) = lo;
-    *(f32x4*)(part + 8 * c + 4) = hi;
-  }
+  store_dw_partial<K>(p, k, t.N, (float*)stage_raw, acc, slots, slot, tl, teamv, jfull, tail);
 }
 
 // dweight[k][c] = the nparts partials of column c: 8 runs of consecutive partials, then the runs in order
@@ -466,6 +333,12 @@ int launch_qktoken_bwd(const QkTokenParams& p, int dtype, hipStream_t stream) {
   if (dtype == 0) launch_t<bf16_t>(p, true, grid, stream);
   else launch_t<f16_t>(p, true, grid, stream);
   if (hipGetLastError() != hipSuccess) return -1;
+  return launch_qktoken_fold(p, stream);
+}
+
+// the fold of the weight gradient partials that a backward launch left in p.workspace (this file's, or rfa_qktokenfreq.hip's:
+// the same partial layout); reads p.t[k].N, p.nparts, p.dweight, p.workspace and p.ntensors alone
+int launch_qktoken_fold(const QkTokenParams& p, hipStream_t stream) {
   uint32_t widest = 0;
   for (int i = 0; i < p.ntensors; ++i)
     if (p.dweight[i]) widest = p.t[i].N > widest ? p.t[i].N : widest;

@@ -345,6 +345,17 @@ class QkTokenNormRotaryBwdArgs(_SizedStructure):
     _fields_ = _QK_NORM_HEAD + _QK_NORM_TAIL
 
 
+class QkTokenNormRotaryFreqsArgs(_SizedStructure):
+    """rfa_qk_token_norm_rotary_freqs_args: RMSNorm over all heads of a token + rotary with the angles formed in the kernel,
+    forward (the fields of rfa_qk_norm_rotary_freqs_args; weight[k] is (H_k * D,)); struct_bytes is filled in here"""
+    _fields_ = list(_QK_NORM_FREQS_HEAD)
+
+
+class QkTokenNormRotaryFreqsBwdArgs(_SizedStructure):
+    """rfa_qk_token_norm_rotary_freqs_bwd_args: the forward's fields, then the gradients, dweight and the workspace"""
+    _fields_ = _QK_NORM_FREQS_HEAD + _QK_NORM_TAIL
+
+
 class MaxLogitArgs(_SizedStructure):
     """rfa_max_logit_args: the per-head max attention logit of one block call; struct_bytes is filled in here"""
     _fields_ = [
@@ -489,6 +500,9 @@ SYMBOLS = {
     "rfa_qk_token_norm_rotary_fwd": (C.c_int, [C.POINTER(QkTokenNormRotaryArgs), C.c_void_p]),
     "rfa_qk_token_norm_rotary_bwd": (C.c_int, [C.POINTER(QkTokenNormRotaryBwdArgs), C.c_void_p]),
     "rfa_qk_token_norm_rotary_bwd_workspace_bytes": (C.c_int64, [C.POINTER(QkTokenNormRotaryBwdArgs)]),
+    "rfa_qk_token_norm_rotary_freqs_fwd": (C.c_int, [C.POINTER(QkTokenNormRotaryFreqsArgs), C.c_void_p]),
+    "rfa_qk_token_norm_rotary_freqs_bwd": (C.c_int, [C.POINTER(QkTokenNormRotaryFreqsBwdArgs), C.c_void_p]),
+    "rfa_qk_token_norm_rotary_freqs_bwd_workspace_bytes": (C.c_int64, [C.POINTER(QkTokenNormRotaryFreqsBwdArgs)]),
     "rfa_max_logit": (C.c_int, [C.POINTER(MaxLogitArgs), C.c_void_p]),
     "rfa_max_logit_workspace_bytes": (C.c_int64, [C.POINTER(MaxLogitArgs)]),
     "rfa_bwd_preprocess_lse": (C.c_int, [C.POINTER(BwdPreLseArgs), C.c_void_p]),

@@ -95,3 +95,6 @@ from .qk_norm import apply_qk_norm_rotary_freqs
 # the same fused with ONE statistic per token over all heads (OLMo-2 / OLMo-3 normalise the whole projection width):
 # apply_qk_token_norm_rotary(q, k, w_q, w_k, cos, sin, layout=func, group=group), weights of H * D entries
 from .qk_norm import apply_qk_token_norm_rotary
+# ... and with the angles formed in the kernel (OLMo under context parallelism without tables; a token-wide norm in front of an
+# M-RoPE): apply_qk_token_norm_rotary_freqs(q, k, w_q, w_k, inv_freq, layout=func, group=group)
+from .qk_norm import apply_qk_token_norm_rotary_freqs

@@ -103,6 +103,7 @@ class HipBackend:
     serves_qk_norm = True            # qk_norm_rotary_fwd / _bwd (include/rfa.h: rfa_qk_norm_rotary_fwd / _bwd): ring_flash_attn.apply_qk_norm_rotary
     serves_qk_norm_freqs = True      # qk_norm_freqs_rotary_fwd / _bwd (include/rfa.h: rfa_qk_norm_rotary_freqs_fwd / _bwd): apply_qk_norm_rotary_freqs
     serves_qk_token_norm = True      # qk_token_norm_rotary_fwd / _bwd (include/rfa.h: rfa_qk_token_norm_rotary_fwd / _bwd): apply_qk_token_norm_rotary
+    serves_qk_token_norm_freqs = True  # qk_token_norm_freqs_rotary_fwd / _bwd (rfa_qk_token_norm_rotary_freqs_fwd / _bwd): apply_qk_token_norm_rotary_freqs
     serves_dropout_positions = True  # `dropout=` takes the position maps (q_map, k_map): what dropout over a dense ring, zigzag or stripe schedule needs
 
     def __init__(self):
@@ -863,16 +864,17 @@ class HipBackend:
                           douts, dweights, lambda dw, x: tuple(dw.shape) == (x.shape[-1],), "dweight is a contiguous fp32 (D,) tensor")
 
     def _qk_norm_freqs_args(self, a, xs, outs, weights, inv_freq, positions, pos_map, interleaved, rot_offset, eps, weight_offset,
-                            scaling, freq_axis):
-        """the fields rfa_qk_norm_rotary_freqs_args and _bwd_args share: the tensors and weights of _qk_norm_args (no tables),
-        then the angle's of rotary_freqs"""
+                            scaling, freq_axis, weight_numel=None, who="qk_norm_freqs_rotary"):
+        """the fields the structs of a norm that forms its own angles share (rfa_qk_norm_rotary_freqs_args, the token-wide
+        rfa_qk_token_norm_rotary_freqs_args and their _bwd_args): the tensors and weights of _qk_norm_args (no tables), then the
+        angle's of rotary_freqs"""
         if inv_freq.dtype != torch.float32 or inv_freq.dim() != 1 or not inv_freq.is_contiguous():
-            raise ValueError("qk_norm_freqs_rotary: inv_freq is a contiguous fp32 (R/2,) tensor")
+            raise ValueError(f"{who}: inv_freq is a contiguous fp32 (R/2,) tensor")
         self._check_dev(inv_freq, positions)
         packed = self._qk_norm_args(a, xs, outs, weights, None, None, None, None, interleaved, rot_offset, eps, weight_offset,
-                                    tables=False)
+                                    weight_numel=weight_numel, tables=False)
         a.R = 2 * inv_freq.shape[0]
-        self._row_freqs(a, "qk_norm_freqs_rotary", inv_freq, scaling, freq_axis, positions, pos_map)
+        self._row_freqs(a, who, inv_freq, scaling, freq_axis, positions, pos_map)
         return packed
 
     def qk_norm_freqs_rotary_fwd(self, xs, outs, weights, inv_freq, _sin=None, *, positions=None, pos_map=None, interleaved=False,
@@ -896,16 +898,22 @@ class HipBackend:
                           packed, xs, douts, dweights, lambda dw, x: tuple(dw.shape) == (x.shape[-1],),
                           "dweight is a contiguous fp32 (D,) tensor")
 
-    def _qk_token_norm_args(self, a, xs, outs, weights, cos, sin, positions, pos_map, interleaved, rot_offset, eps, weight_offset):
-        """the fields rfa_qk_token_norm_rotary_args and _bwd_args share: the per-head call's, with (H * D,) weights"""
+    @staticmethod
+    def _qk_token_weights(xs, weights):
+        """the weights of a token-wide norm as 1-d tensors, and their element counts H_k * D"""
         for x, w in zip(xs, weights):
             if w.numel() != x.shape[-2] * x.shape[-1] or not w.is_contiguous() or w.dim() not in (1, 2) or \
                     (w.dim() == 2 and tuple(w.shape) != tuple(x.shape[-2:])):
                 raise ValueError("qk_token_norm_rotary: the weights are contiguous (H * D,) or (H, D) tensors of one dtype")
             if x.shape[-2] * x.shape[-1] > _C.QK_TOKEN_NORM_MAX_WIDTH:
                 raise ValueError(f"qk_token_norm_rotary: H * D is at most {_C.QK_TOKEN_NORM_MAX_WIDTH}")
-        return self._qk_norm_args(a, xs, outs, [w.reshape(-1) for w in weights], cos, sin, positions, pos_map, interleaved,
-                                  rot_offset, eps, weight_offset, weight_numel=[x.shape[-2] * x.shape[-1] for x in xs])
+        return [w.reshape(-1) for w in weights], [x.shape[-2] * x.shape[-1] for x in xs]
+
+    def _qk_token_norm_args(self, a, xs, outs, weights, cos, sin, positions, pos_map, interleaved, rot_offset, eps, weight_offset):
+        """the fields rfa_qk_token_norm_rotary_args and _bwd_args share: the per-head call's, with (H * D,) weights"""
+        flat, numel = self._qk_token_weights(xs, weights)
+        return self._qk_norm_args(a, xs, outs, flat, cos, sin, positions, pos_map, interleaved, rot_offset, eps, weight_offset,
+                                  weight_numel=numel)
 
     def qk_token_norm_rotary_fwd(self, xs, outs, weights, cos, sin, *, positions=None, pos_map=None, interleaved=False,
                                  rot_offset=0, eps=1e-6, weight_offset=0.0):
@@ -927,6 +935,31 @@ class HipBackend:
         self._qk_norm_bwd(a, "qk_token_norm_rotary", "rfa_qk_token_norm_rotary_bwd_workspace_bytes", "rfa_qk_token_norm_rotary_bwd",
                           packed, xs, douts, dweights, lambda dw, x: dw.numel() == x.shape[-2] * x.shape[-1],
                           "dweight is a contiguous fp32 tensor of H * D elements")
+
+    def qk_token_norm_freqs_rotary_fwd(self, xs, outs, weights, inv_freq, _sin=None, *, positions=None, pos_map=None,
+                                       interleaved=False, rot_offset=0, eps=1e-6, weight_offset=0.0, scaling=1.0, freq_axis=None):
+        """one launch of the RMSNorm over all heads of a token + rotary with the angles formed in the kernel (include/rfa.h:
+        rfa_qk_token_norm_rotary_freqs_fwd).  xs / outs / weights as in qk_token_norm_rotary_fwd; inv_freq, scaling, freq_axis,
+        positions and pos_map as in rotary_freqs.  (_sin: the place of the second table in the shared autograd node; always None)"""
+        a = _C.QkTokenNormRotaryFreqsArgs()
+        flat, numel = self._qk_token_weights(xs, weights)
+        self._qk_norm_freqs_args(a, xs, outs, flat, inv_freq, positions, pos_map, interleaved, rot_offset, eps, weight_offset,
+                                 scaling, freq_axis, weight_numel=numel, who="qk_token_norm_freqs_rotary")
+        _C.check(self.lib.rfa_qk_token_norm_rotary_freqs_fwd(C.byref(a), _stream(xs[0])), "rfa_qk_token_norm_rotary_freqs_fwd")
+
+    def qk_token_norm_freqs_rotary_bwd(self, xs, douts, dxs, weights, dweights, inv_freq, _sin=None, *, positions=None,
+                                       pos_map=None, interleaved=False, rot_offset=0, eps=1e-6, weight_offset=0.0, scaling=1.0,
+                                       freq_axis=None):
+        """the backward (include/rfa.h: rfa_qk_token_norm_rotary_freqs_bwd): dxs[k] from xs[k] and douts[k] in one launch;
+        dweights[k] a contiguous fp32 tensor of H_k * D elements that is overwritten with this call's weight gradient, or None.
+        The workspace is allocated here."""
+        a = _C.QkTokenNormRotaryFreqsBwdArgs()
+        flat, numel = self._qk_token_weights(xs, weights)
+        packed = self._qk_norm_freqs_args(a, xs, dxs, flat, inv_freq, positions, pos_map, interleaved, rot_offset, eps,
+                                          weight_offset, scaling, freq_axis, weight_numel=numel, who="qk_token_norm_freqs_rotary")
+        self._qk_norm_bwd(a, "qk_token_norm_freqs_rotary", "rfa_qk_token_norm_rotary_freqs_bwd_workspace_bytes",
+                          "rfa_qk_token_norm_rotary_freqs_bwd", packed, xs, douts, dweights,
+                          lambda dw, x: dw.numel() == x.shape[-2] * x.shape[-1], "dweight is a contiguous fp32 tensor of H * D elements")
 
     def sum_slots(self, src: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
         """dst[...] = sum over dim 0 of src (io dtype, summed in fp32).  src: (W, B, S, H, D) or (W, T, H, D), each slot

@@ -1,6 +1,7 @@
 """QK RMSNorm fused with the rotary embedding at GLOBAL positions: per head with tables (`apply_qk_norm_rotary`), per head with the
-angles formed in the kernel (`apply_qk_norm_rotary_freqs`) and over all heads of a token (`apply_qk_token_norm_rotary`, at the
-end of this file).
+angles formed in the kernel (`apply_qk_norm_rotary_freqs`) and over all heads of a token, with tables
+(`apply_qk_token_norm_rotary`) or with the angles formed in the kernel (`apply_qk_token_norm_rotary_freqs`, both at the end of
+this file).
 
 Qwen3, Gemma-3 and OLMo-style models put an RMSNorm over each head of q and k directly in front of RoPE,
     q = rope(rmsnorm_D(q_proj(x)) * w_q),   k = rope(rmsnorm_D(k_proj(x)) * w_k).
@@ -64,8 +65,8 @@ class _NormRotary(torch.autograd.Function):
 
 def _norm_rotary(who, feature, check_weight, q, k, q_weight, k_weight, cos, sin, eps, weight_offset, layout, group, positions,
                  offset, interleaved, rot_offset, freqs=None):
-    """what the three norm + rotary calls share: every check in front of the launch, in one order, and the node.  feature:
-    `qk_norm` / `qk_norm_freqs` / `qk_token_norm` (the backend's serves_* flag and the stem of its two methods);
+    """what the four norm + rotary calls share: every check in front of the launch, in one order, and the node.  feature:
+    `qk_norm` / `qk_norm_freqs` / `qk_token_norm` / `qk_token_norm_freqs` (the backend's serves_* flag and the stem of its two methods);
     check_weight(x, w, D): ValueError unless w is a weight of tensor x; freqs = (inv_freq, attention_scaling, freq_axis): the
     kernel forms the angles, there are no tables (cos = sin = None) and the angle's checks are apply_rotary_freqs's."""
     from .backend import get_backend
@@ -185,6 +186,22 @@ def apply_qk_norm_rotary_freqs(q, k, q_weight, k_weight, inv_freq, *, eps=1e-6, 
 apply_qk_norm_rotary_freqs = _opaque(apply_qk_norm_rotary_freqs)
 
 
+def _token_weight_check(who, q, q_weight):
+    """check_weight of the token-wide norms: w is (H * D,) or (H, D) for tensor x, and H * D is a width that is served"""
+    width = _C.QK_TOKEN_NORM_MAX_WIDTH                 # H * D (and Hk * D) that is served: include/rfa.h
+
+    def check_weight(x, w, D):
+        H = x.shape[-2]
+        if H * D > width:
+            raise ValueError(f"{who}: H * D = {H * D} is more than the {width} columns a token row may have")
+        if not isinstance(w, torch.Tensor) or tuple(w.shape) not in ((H * D,), (H, D)) or not w.is_contiguous() or \
+                w.device != q.device or w.dtype not in (torch.float32, q.dtype) or w.dtype != q_weight.dtype:
+            raise ValueError(f"{who}: the weights must be contiguous (H * D,) = ({H * D},) or (H, D) = ({H}, {D}) tensors on q's "
+                             f"device, both fp32 or both {q.dtype}")
+
+    return check_weight
+
+
 def apply_qk_token_norm_rotary(q, k, q_weight, k_weight, cos=None, sin=None, *, eps=1e-6, weight_offset=0.0, layout=None,
                                group=None, positions=None, offset=0, interleaved=False, rot_offset=0):
     """RMSNorm of this rank's q (and k) over ALL heads of a token — OLMo-2 / OLMo-3 normalise q_proj(x) and k_proj(x) over the
@@ -213,19 +230,47 @@ def apply_qk_token_norm_rotary(q, k, q_weight, k_weight, cos=None, sin=None, *, 
     Raises, before anything is launched: NotImplementedError for a backend without `serves_qk_token_norm`; TypeError for a
     `layout` that is not one of the nine dense attention functions; ValueError for everything else."""
     who = "ring_flash_attn.apply_qk_token_norm_rotary"
-    width = _C.QK_TOKEN_NORM_MAX_WIDTH                 # H * D (and Hk * D) that is served: include/rfa.h
-
-    def check_weight(x, w, D):
-        H = x.shape[-2]
-        if H * D > width:
-            raise ValueError(f"{who}: H * D = {H * D} is more than the {width} columns a token row may have")
-        if not isinstance(w, torch.Tensor) or tuple(w.shape) not in ((H * D,), (H, D)) or not w.is_contiguous() or \
-                w.device != q.device or w.dtype not in (torch.float32, q.dtype) or w.dtype != q_weight.dtype:
-            raise ValueError(f"{who}: the weights must be contiguous (H * D,) = ({H * D},) or (H, D) = ({H}, {D}) tensors on q's "
-                             f"device, both fp32 or both {q.dtype}")
-
-    return _norm_rotary(who, "qk_token_norm", check_weight, q, k, q_weight, k_weight, cos, sin, eps, weight_offset, layout, group,
+    return _norm_rotary(who, "qk_token_norm", _token_weight_check(who, q, q_weight), q, k, q_weight, k_weight, cos, sin, eps, weight_offset, layout, group,
                         positions, offset, interleaved, rot_offset)
 
 
 apply_qk_token_norm_rotary = _opaque(apply_qk_token_norm_rotary)
+
+
+def apply_qk_token_norm_rotary_freqs(q, k, q_weight, k_weight, inv_freq, *, eps=1e-6, weight_offset=0.0, attention_scaling=1.0,
+                                     freq_axis=None, layout=None, group=None, positions=None, offset=0, interleaved=False,
+                                     rot_offset=0):
+    """`apply_qk_token_norm_rotary` without tables: the RMSNorm over ALL heads of a token and a rotation whose angles the kernel
+    forms from `inv_freq` and the positions, fused (HIP: csrc/rfa_qktokenfreq.hip); returns the new q, or (q, k).  Nothing of
+    the size of the unsharded sequence is held, and a row may have up to four positions (M-RoPE).
+
+        q, k = apply_qk_token_norm_rotary_freqs(q, k, w_q, w_k, inv_freq, layout=zigzag_ring_flash_attn_func, group=group)  # OLMo-2
+        q, k = apply_qk_token_norm_rotary_freqs(q, k, w_q, w_k, inv_freq, positions=pos_thw, freq_axis=axes)
+
+    q, k, q_weight ((H * D,) or (H, D)), k_weight, eps, weight_offset, rot_offset and k=None with k_weight=None are
+    `apply_qk_token_norm_rotary`'s, with its checks (H * D and Hk * D at most 16384); inv_freq, attention_scaling, freq_axis,
+    layout, group, positions, offset and interleaved are `apply_rotary_freqs`'s, with its checks (at most four axes; `layout`
+    with freq_axis is a ValueError, and so is a map that leaves [0, 2^31 - 1]).  R = 2 len(inv_freq); the columns [rot_offset,
+    rot_offset + R) of every head are rotated, the norm always runs over all H * D columns.
+    Per token row, in fp32 with ONE rounding to the io dtype at the end: `apply_qk_token_norm_rotary`'s norm (the same device
+    functions: rstd has that kernel's bits), the angle ang = float(pos[axis(c)]) * inv_freq[c] as one rounded multiply, the
+    precise sincosf, both times attention_scaling, then `apply_rotary`'s expression.  An element's bits depend on its token
+    row's values, the weight, the position(s), inv_freq and the scaling alone: every rank's shard is the shard of the
+    single-device result, bit for bit, which the two calls this one replaces (the token norm alone, then `apply_rotary_freqs`)
+    do not give — they round to the io dtype in between.
+    Autograd: one backward launch (plus a small fold) gives dq, dk and both weight gradients; kept are q, k, the weights,
+    inv_freq and the positions or the map — neither rstd nor the outputs; the weight gradient is summed in fp32 in a fixed order
+    without atomics (two runs: the same bits) and rounded once to the weight's dtype; inv_freq gets no gradient; a weight that
+    does not require grad, or a tensor whose incoming gradient is None, skips that work.  Over several ranks the weight gradient
+    is THIS RANK'S PARTIAL, like `sinks.grad`.  Head-parallel callers (a `with_ulysses` region among them) split the token row
+    across ranks and are not served.  There is no in-place mode.
+    Under torch.compile the call runs eagerly behind a graph break.
+    Raises, before anything is launched: NotImplementedError for a backend without `serves_qk_token_norm_freqs`; TypeError for a
+    `layout` that is not one of the nine dense attention functions; ValueError for everything else."""
+    who = "ring_flash_attn.apply_qk_token_norm_rotary_freqs"
+    return _norm_rotary(who, "qk_token_norm_freqs", _token_weight_check(who, q, q_weight), q, k, q_weight, k_weight, None, None,
+                        eps, weight_offset, layout, group, positions, offset, interleaved, rot_offset,
+                        freqs=(inv_freq, attention_scaling, freq_axis))
+
+
+apply_qk_token_norm_rotary_freqs = _opaque(apply_qk_token_norm_rotary_freqs)
