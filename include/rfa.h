@@ -1012,6 +1012,77 @@ int rfa_qk_token_norm_rotary_freqs_fwd(const rfa_qk_token_norm_rotary_freqs_args
 int rfa_qk_token_norm_rotary_freqs_bwd(const rfa_qk_token_norm_rotary_freqs_bwd_args *args, void *stream);
 int64_t rfa_qk_token_norm_rotary_freqs_bwd_workspace_bytes(const rfa_qk_token_norm_rotary_freqs_bwd_args *args);
 
+/* The K / V assembly of multi-head latent attention fused with the rotary embedding at GLOBAL positions
+ * (ring_flash_attn.apply_mla_rotary; csrc/rfa_mlarope.hip) — what a DeepSeek-V2 / V3 / Kimi K2 layer runs between its
+ * projections and an attention call with a QK head dim of Dn + Dr and a value head dim of Dv (rfa_fwd_vd).  Structs of their
+ * own; no attention kernel, refusal or existing struct changes (ABI 8 revision 1 stays).  Per row (B, S; packed input: B = 1,
+ * S = T) the forward reads q (Hq, Dn + Dr), kv (H, Dn + Dv) = [k_nope | v] and k_pe (Dr), ONE rope key for all heads, and writes
+ *     q_out[h]  = [ q[h, :Dn]  | rope(q[h, Dn:]) ]                 Hq == 0: there is no q, q and q_out are not looked at
+ *     k[h]      = [ kv[h, :Dn] | rope(k_pe) ]                      the same rope bits for every head
+ *     v[h]      =   kv[h, Dn:]
+ * in one launch; rope is rfa_rotary's rotation of Dr columns — pairing by `interleaved`, cos / sin (P, Dr/2), positions or the
+ * position map, the clamp into the tables, fp32 arithmetic and one rounding all as stated there: the bits rfa_rotary gives with
+ * R = Dr, rot_offset = Dn.  Copied columns keep their bits.  The backward takes the gradients of the three outputs and writes
+ *     dq[h]     = [ dq_out[h, :Dn] | rope^-1(dq_out[h, Dn:]) ]     Hq == 0: neither is looked at
+ *     dkv[h]    = [ dk[h, :Dn] | dv[h] ]                           dk NULL or dv NULL: that part of dkv is not written;
+ *                                                                  dkv NULL: none of it is
+ *     dk_pe     = rope^-1( sum_h dk[h, Dn:] )                      dk_pe NULL: not computed
+ * in one launch, with no workspace and no atomics: the sum is taken in fp32 in an order that depends on H and Dr alone
+ * (csrc/rfa_mlarope_index.h), rotated after it is complete and rounded once; two calls give the same bits.
+ *   Each tensor: element strides (batch, row, head), last stride 1, rows 16-byte aligned; k_pe / dk_pe have no head stride (0).
+ *   An output must not overlap any other tensor of the call.
+ * Checks, in this order and before any pointer is read: NULL struct RFA_ERR_NULL; struct_bytes != sizeof, reserved != 0,
+ * interleaved outside 0..1 RFA_ERR_ARGS; dtype, or a table_dtype that is neither dtype nor RFA_ROTARY_TABLE_F32, RFA_ERR_DTYPE; Dn
+ * negative or not a multiple of 8, Dr not a positive multiple of 16 (interleaved: of 8), Dv not a positive multiple of 8,
+ * Dn + Dr or Dv above 256 RFA_ERR_HEAD_DIM; B < 0, S < 0, P < 1, B * S above 2^31 - 1 RFA_ERR_SHAPE; H <= 0 or Hq < 0
+ * RFA_ERR_HEADS; B S H (Dn + Dr + Dv) / 8 or rfa_rotary's unit count of q above 2^31 - 1 RFA_ERR_SHAPE; B == 0 or S == 0: RFA_OK,
+ * nothing is launched; NULL cos or sin, forward: a NULL kv, k_pe, k or v, or with Hq > 0 q or q_out, backward: with Hq > 0 a NULL
+ * dq_out or dq, a dkv with neither dk nor dv, a dk_pe without dk, or nothing to do at all (Hq == 0, no dkv, no dk_pe)
+ * RFA_ERR_NULL; pointers or strides off the 16-byte contract RFA_ERR_ALIGN; a negative pos_batch, and with the map a negative
+ * pos_stride, a pos_split outside 0..S-1 or a position outside [0, P - 1] RFA_ERR_ARGS. */
+typedef struct {
+  void *ptr;               /* read or written, by its role */
+  int64_t batch, row, head; /* element strides */
+} rfa_mla_rotary_tensor;
+typedef struct {
+  uint32_t struct_bytes;   /* sizeof(rfa_mla_rotary_args) */
+  uint32_t reserved;       /* 0 */
+  int32_t B, S;            /* packed input: B = 1, S = T */
+  int32_t dtype;           /* rfa_dtype */
+  int32_t Dn, Dr, Dv;
+  int32_t H, Hq;           /* heads of kv / k / v; of q (0: no q) */
+  int32_t interleaved;
+  int32_t table_dtype;     /* dtype, or RFA_ROTARY_TABLE_F32 */
+  rfa_mla_rotary_tensor q, q_out, kv, k_pe, k, v;
+  const void *cos, *sin;   /* (P, Dr/2), 16-byte aligned */
+  int64_t P;
+  const int32_t *positions; /* (B, S) / (S,) int32, or NULL: the map */
+  int64_t pos_batch;       /* elements between two batch entries of positions (0 = shared) */
+  int64_t pos_offset;      /* added to positions[], or the map's first offset */
+  int32_t pos_stride, pos_split;
+  int64_t pos_offset2;
+} rfa_mla_rotary_args;
+typedef struct {
+  uint32_t struct_bytes;   /* sizeof(rfa_mla_rotary_bwd_args) */
+  uint32_t reserved;       /* 0 */
+  int32_t B, S;
+  int32_t dtype;
+  int32_t Dn, Dr, Dv;
+  int32_t H, Hq;           /* Hq 0: no dq_out / dq */
+  int32_t interleaved;
+  int32_t table_dtype;
+  rfa_mla_rotary_tensor dq_out, dq, dk, dv, dkv, dk_pe; /* dq_out, dk, dv read; dq, dkv, dk_pe written */
+  const void *cos, *sin;
+  int64_t P;
+  const int32_t *positions;
+  int64_t pos_batch;
+  int64_t pos_offset;
+  int32_t pos_stride, pos_split;
+  int64_t pos_offset2;
+} rfa_mla_rotary_bwd_args;
+int rfa_mla_rotary_fwd(const rfa_mla_rotary_args *args, void *stream);
+int rfa_mla_rotary_bwd(const rfa_mla_rotary_bwd_args *args, void *stream);
+
 /* Per-head max attention logit (QK-Clip / MuonClip; Transformer Engine's and Megatron's `max_logit`): for every query head h
  *     max_logit[h] = max over batch b, query row i and the keys j that row i SEES of  softmax_scale * q[b,i,h,:] . k[b,j,h/G,:]
  * for one block call — the raw scaled dot product (no soft cap, bias, dropout or sink enters it), -inf for a head that sees no

@@ -1801,6 +1801,91 @@ int rfa_rotary_freqs(const rfa_rotary_freqs_args* a, void* stream) {
   return launch_rotary_freqs(p, a->dtype, (hipStream_t)stream) ? RFA_ERR_LAUNCH : RFA_OK;
 }
 
+// ---- MLA K / V assembly fused with the rotary embedding (csrc/rfa_mlarope.hip) -----------------------------------------------
+extern "C++" {
+static MlaRopeTensor mla_strides(const rfa_mla_rotary_tensor& t) { return MlaRopeTensor{t.batch, t.row, t.head}; }
+
+static bool mla_aligned(const rfa_mla_rotary_tensor& t) {
+  return !t.ptr || (aligned16(t.ptr) && (t.batch % 8) == 0 && (t.row % 8) == 0 && (t.head % 8) == 0);
+}
+
+// the stages both directions share, in the header's order, up to "no rows": *go is false where the call is done.  Fills the
+// geometry of p; q_src / q_dst: the tensors of the q stream (strides only — no pointer is read)
+template <typename A>
+static int mla_check(const A* a, const rfa_mla_rotary_tensor A::*q_src, const rfa_mla_rotary_tensor A::*q_dst, MlaRopeParams* p, bool* go) {
+  *go = false;
+  if (!a) return RFA_ERR_NULL;
+  if (a->struct_bytes != sizeof(A) || a->reserved != 0) return RFA_ERR_ARGS;
+  if (a->interleaved < 0 || a->interleaved > 1) return RFA_ERR_ARGS;
+  if (a->dtype != RFA_BF16 && a->dtype != RFA_F16) return RFA_ERR_DTYPE;
+  if (a->table_dtype != a->dtype && a->table_dtype != RFA_ROTARY_TABLE_F32) return RFA_ERR_DTYPE;
+  if (a->Dn < 0 || (a->Dn % 8) != 0 || a->Dr <= 0 || (a->Dr % (a->interleaved ? 8 : 16)) != 0 || a->Dv <= 0 || (a->Dv % 8) != 0)
+    return RFA_ERR_HEAD_DIM;
+  if (a->Dn > kMlaRopeMaxRot - a->Dr || a->Dr > kMlaRopeMaxRot || a->Dv > kMlaRopeMaxRot) return RFA_ERR_HEAD_DIM;
+  if (a->B < 0 || a->S < 0 || a->P < 1) return RFA_ERR_SHAPE;
+  const int64_t rows = (int64_t)a->B * a->S;
+  if (rows > INT32_MAX) return RFA_ERR_SHAPE;
+  if (a->H <= 0 || a->Hq < 0) return RFA_ERR_HEADS;
+  const int64_t quph = rotary_units_per_head((uint32_t)(a->Dn + a->Dr), (uint32_t)a->Dr, a->interleaved, false);
+  // (rows, H and Hq fit 31 bits each, the units per head 6: the products fit 62 and 37 bits)
+  if (rows * a->H > INT32_MAX || rows * a->H * ((a->Dn + a->Dr + a->Dv) / 8) > INT32_MAX) return RFA_ERR_SHAPE;
+  if (rows * a->Hq > INT32_MAX || rows * a->Hq * quph > INT32_MAX) return RFA_ERR_SHAPE;
+  p->g.B = (uint32_t)a->B; p->g.S = (uint32_t)a->S; p->g.H = (uint32_t)a->H;
+  p->g.Dn = (uint32_t)a->Dn; p->g.Dr = (uint32_t)a->Dr; p->g.Dv = (uint32_t)a->Dv;
+  p->g.rot_units = (uint32_t)(a->interleaved ? a->Dr / 8 : a->Dr / 16);
+  p->g.interleaved = a->interleaved;
+  p->gq.B = p->g.B; p->gq.S = p->g.S; p->gq.R = p->g.Dr; p->gq.rot_off = p->g.Dn; p->gq.rot_units = p->g.rot_units;
+  p->gq.interleaved = a->interleaved;
+  const rfa_mla_rotary_tensor &s = a->*q_src, &d = a->*q_dst;
+  p->tq.sb = s.batch; p->tq.sr = s.row; p->tq.sh = s.head;
+  p->tq.db = d.batch; p->tq.dr = d.row; p->tq.dh = d.head;
+  p->tq.H = (uint32_t)a->Hq; p->tq.uph = (uint32_t)quph; p->tq.nunits = (uint32_t)(rows * a->Hq * quph);
+  *go = a->B != 0 && a->S != 0;
+  return RFA_OK;
+}
+}  // extern "C++"
+
+int rfa_mla_rotary_fwd(const rfa_mla_rotary_args* a, void* stream) {
+  MlaRopeParams p{};
+  bool go;
+  if (int rc = mla_check(a, &rfa_mla_rotary_args::q, &rfa_mla_rotary_args::q_out, &p, &go)) return rc;
+  if (!go) return RFA_OK;
+  if (!a->cos || !a->sin || !a->kv.ptr || !a->k_pe.ptr || !a->k.ptr || !a->v.ptr) return RFA_ERR_NULL;
+  if (a->Hq > 0 && (!a->q.ptr || !a->q_out.ptr)) return RFA_ERR_NULL;
+  if (!aligned16(a->cos) || !aligned16(a->sin) || !mla_aligned(a->kv) || !mla_aligned(a->k_pe) || !mla_aligned(a->k) || !mla_aligned(a->v))
+    return RFA_ERR_ALIGN;
+  if (a->Hq > 0 && (!mla_aligned(a->q) || !mla_aligned(a->q_out))) return RFA_ERR_ALIGN;
+  if (int rc = row_pos_map(a, &p, a->P - 1, true)) return rc;
+  if (a->Hq > 0) { p.q = a->q.ptr; p.q_out = a->q_out.ptr; }
+  p.kv = a->kv.ptr; p.k_pe = a->k_pe.ptr; p.k = a->k.ptr; p.v = a->v.ptr;
+  p.kv_st = mla_strides(a->kv); p.k_pe_st = mla_strides(a->k_pe); p.k_st = mla_strides(a->k); p.v_st = mla_strides(a->v);
+  p.k_pe_st.sh = 0;
+  p.cos = a->cos; p.sin = a->sin; p.P = a->P;
+  return launch_mla_rotary_fwd(p, a->dtype, a->table_dtype == RFA_ROTARY_TABLE_F32, (hipStream_t)stream) ? RFA_ERR_LAUNCH : RFA_OK;
+}
+
+int rfa_mla_rotary_bwd(const rfa_mla_rotary_bwd_args* a, void* stream) {
+  MlaRopeParams p{};
+  bool go;
+  if (int rc = mla_check(a, &rfa_mla_rotary_bwd_args::dq_out, &rfa_mla_rotary_bwd_args::dq, &p, &go)) return rc;
+  if (!go) return RFA_OK;
+  if (!a->cos || !a->sin) return RFA_ERR_NULL;
+  if (a->Hq > 0 && (!a->dq_out.ptr || !a->dq.ptr)) return RFA_ERR_NULL;
+  if (a->dkv.ptr && !a->dk.ptr && !a->dv.ptr) return RFA_ERR_NULL;
+  if (a->dk_pe.ptr && !a->dk.ptr) return RFA_ERR_NULL;
+  if (a->Hq == 0 && !a->dkv.ptr && !a->dk_pe.ptr) return RFA_ERR_NULL;
+  if (!aligned16(a->cos) || !aligned16(a->sin) || !mla_aligned(a->dk) || !mla_aligned(a->dv) || !mla_aligned(a->dkv) || !mla_aligned(a->dk_pe))
+    return RFA_ERR_ALIGN;
+  if (a->Hq > 0 && (!mla_aligned(a->dq_out) || !mla_aligned(a->dq))) return RFA_ERR_ALIGN;
+  if (int rc = row_pos_map(a, &p, a->P - 1, true)) return rc;
+  if (a->Hq > 0) { p.q = a->dq_out.ptr; p.q_out = a->dq.ptr; }
+  p.kv = a->dkv.ptr; p.k_pe = a->dk_pe.ptr; p.k = a->dk.ptr; p.v = a->dv.ptr;
+  p.kv_st = mla_strides(a->dkv); p.k_pe_st = mla_strides(a->dk_pe); p.k_st = mla_strides(a->dk); p.v_st = mla_strides(a->dv);
+  p.k_pe_st.sh = 0;
+  p.cos = a->cos; p.sin = a->sin; p.P = a->P;
+  return launch_mla_rotary_bwd(p, a->dtype, a->table_dtype == RFA_ROTARY_TABLE_F32, (hipStream_t)stream) ? RFA_ERR_LAUNCH : RFA_OK;
+}
+
 // ---- the QK RMSNorms + rotary: per head (csrc/rfa_qknorm.hip, rfa_qknormfreq.hip) and over all heads of a token
 // ---- (csrc/rfa_qktoken.hip, rfa_qktokenfreq.hip) ---------------------------------------------------------------------------
 static_assert(RFA_QK_TOKEN_NORM_MAX_WIDTH == kQkTokenMaxWidth && RFA_QK_TOKEN_NORM_MAX_PARTS == kQkTokenMaxParts,

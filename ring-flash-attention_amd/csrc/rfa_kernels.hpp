@@ -9,6 +9,7 @@
 #include "rfa_qknorm_index.h"
 #include "rfa_qknormfreq_index.h"
 #include "rfa_qktoken_index.h"
+#include "rfa_mlarope_index.h"
 #include "rfa_maxlogit_band.h"
 #include "rfa_rowrange.h"
 #include "rfa_blockmask.h"
@@ -413,6 +414,30 @@ struct QkTokenFreqParams : QkTokenParams {
 };
 int launch_qktokenfreq_fwd(const QkTokenFreqParams& p, int dtype, hipStream_t stream);
 int launch_qktokenfreq_bwd(const QkTokenFreqParams& p, int dtype, hipStream_t stream);
+
+// MLA K / V assembly fused with the rotary embedding (rfa_mlarope.hip; tiles, units and the head sum: rfa_mlarope_index.h).
+// Forward: q -> q_out (gq / tq: rotary_unit()'s geometry with R = Dr, rot_off = Dn; tq.H == 0: no q), kv and k_pe read, k and v
+// written.  Backward: the same fields name the gradients — q = dq_out read, q_out = dq written (tq.H == 0: neither), k = dk and
+// v = dv read, kv = dkv and k_pe = dk_pe written; k NULL / v NULL: that half of dkv is left alone, kv NULL: no dkv stream,
+// k_pe NULL: no head sum.  Positions and tables as in RotaryParams.
+struct MlaRopeParams {
+  MlaRopeGeom g;
+  RotaryGeom gq;
+  RotaryTensor tq;
+  const void* q;
+  void* q_out;
+  MlaRopeTensor kv_st, k_pe_st, k_st, v_st;
+  void *kv, *k_pe, *k, *v;
+  const void *cos, *sin;    // (P, Dr/2), contiguous, fp32 or the io dtype
+  int64_t P;
+  const int32_t* positions;
+  int64_t pos_batch;
+  int64_t pos_off, pos_off2;
+  uint32_t pos_stride;
+  int32_t pos_split;
+};
+int launch_mla_rotary_fwd(const MlaRopeParams& p, int dtype, bool table_f32, hipStream_t stream);
+int launch_mla_rotary_bwd(const MlaRopeParams& p, int dtype, bool table_f32, hipStream_t stream);
 
 // per-head max attention logit (rfa_maxlogit.hip; tile arithmetic: rfa_maxlogit_band.h): the forward's S phase alone.
 // Workgroup (batch b, query block qb, head h) stores the max of its UNSCALED visible scores to

@@ -356,6 +356,40 @@ class QkTokenNormRotaryFreqsBwdArgs(_SizedStructure):
     _fields_ = _QK_NORM_FREQS_HEAD + _QK_NORM_TAIL
 
 
+class MlaRotaryTensor(C.Structure):
+    """rfa_mla_rotary_tensor: one tensor of an MLA rotary call, read or written by its role"""
+    _fields_ = [("ptr", C.c_void_p), ("batch", C.c_int64), ("row", C.c_int64), ("head", C.c_int64)]
+
+
+_MLA_ROTARY_HEAD = [
+    ("struct_bytes", C.c_uint32), ("reserved", C.c_uint32),
+    ("B", C.c_int32), ("S", C.c_int32),
+    ("dtype", C.c_int32),
+    ("Dn", C.c_int32), ("Dr", C.c_int32), ("Dv", C.c_int32),
+    ("H", C.c_int32), ("Hq", C.c_int32),
+    ("interleaved", C.c_int32),
+    ("table_dtype", C.c_int32),
+]
+_MLA_ROTARY_TAIL = [
+    ("cos", C.c_void_p), ("sin", C.c_void_p),
+    ("P", C.c_int64),
+    ("positions", C.c_void_p), ("pos_batch", C.c_int64),
+    ("pos_offset", C.c_int64),
+    ("pos_stride", C.c_int32), ("pos_split", C.c_int32),
+    ("pos_offset2", C.c_int64),
+]
+
+
+class MlaRotaryArgs(_SizedStructure):
+    """rfa_mla_rotary_args: MLA's k / v assembly fused with the rotary embedding, forward; struct_bytes is filled in here"""
+    _fields_ = _MLA_ROTARY_HEAD + [(n, MlaRotaryTensor) for n in ("q", "q_out", "kv", "k_pe", "k", "v")] + _MLA_ROTARY_TAIL
+
+
+class MlaRotaryBwdArgs(_SizedStructure):
+    """rfa_mla_rotary_bwd_args: the same fields with the gradients in the tensors' places"""
+    _fields_ = _MLA_ROTARY_HEAD + [(n, MlaRotaryTensor) for n in ("dq_out", "dq", "dk", "dv", "dkv", "dk_pe")] + _MLA_ROTARY_TAIL
+
+
 class MaxLogitArgs(_SizedStructure):
     """rfa_max_logit_args: the per-head max attention logit of one block call; struct_bytes is filled in here"""
     _fields_ = [
@@ -503,6 +537,8 @@ SYMBOLS = {
     "rfa_qk_token_norm_rotary_freqs_fwd": (C.c_int, [C.POINTER(QkTokenNormRotaryFreqsArgs), C.c_void_p]),
     "rfa_qk_token_norm_rotary_freqs_bwd": (C.c_int, [C.POINTER(QkTokenNormRotaryFreqsBwdArgs), C.c_void_p]),
     "rfa_qk_token_norm_rotary_freqs_bwd_workspace_bytes": (C.c_int64, [C.POINTER(QkTokenNormRotaryFreqsBwdArgs)]),
+    "rfa_mla_rotary_fwd": (C.c_int, [C.POINTER(MlaRotaryArgs), C.c_void_p]),
+    "rfa_mla_rotary_bwd": (C.c_int, [C.POINTER(MlaRotaryBwdArgs), C.c_void_p]),
     "rfa_max_logit": (C.c_int, [C.POINTER(MaxLogitArgs), C.c_void_p]),
     "rfa_max_logit_workspace_bytes": (C.c_int64, [C.POINTER(MaxLogitArgs)]),
     "rfa_bwd_preprocess_lse": (C.c_int, [C.POINTER(BwdPreLseArgs), C.c_void_p]),
@@ -575,6 +611,10 @@ def load():
     # ... and the rotary embedding (a struct of its own)
     if not hasattr(lib, "rfa_rotary"):
         raise RuntimeError("ring_flash_attn: librfa_hip.so has no rfa_rotary (the rotary embedding entry point); rebuild")
+    # ... and MLA's k / v assembly fused with it (structs of their own)
+    for name in ("rfa_mla_rotary_fwd", "rfa_mla_rotary_bwd"):
+        if not hasattr(lib, name):
+            raise RuntimeError(f"ring_flash_attn: librfa_hip.so has no {name} (the MLA rotary entry points); rebuild")
     for name, (res, args) in SYMBOLS.items():
         fn = getattr(lib, name)  # AttributeError if the .so is stale
         fn.restype = res

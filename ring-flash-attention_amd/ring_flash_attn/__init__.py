@@ -98,3 +98,7 @@ from .qk_norm import apply_qk_token_norm_rotary
 # ... and with the angles formed in the kernel (OLMo under context parallelism without tables; a token-wide norm in front of an
 # M-RoPE): apply_qk_token_norm_rotary_freqs(q, k, w_q, w_k, inv_freq, layout=func, group=group)
 from .qk_norm import apply_qk_token_norm_rotary_freqs
+# multi-head latent attention (DeepSeek-V2 / V3, Kimi K2) between its projections and the 192 / 128 attention call:
+# apply_mla_rotary(q, kv, k_pe, cos, sin, layout=func, group=group) rotates q's rope columns and assembles k = [k_nope | rope(k_pe)]
+# and v from kv in one launch per direction, with a reproducible sum over heads for dk_pe
+from .mla import apply_mla_rotary

@@ -104,6 +104,7 @@ class HipBackend:
     serves_qk_norm_freqs = True      # qk_norm_freqs_rotary_fwd / _bwd (include/rfa.h: rfa_qk_norm_rotary_freqs_fwd / _bwd): apply_qk_norm_rotary_freqs
     serves_qk_token_norm = True      # qk_token_norm_rotary_fwd / _bwd (include/rfa.h: rfa_qk_token_norm_rotary_fwd / _bwd): apply_qk_token_norm_rotary
     serves_qk_token_norm_freqs = True  # qk_token_norm_freqs_rotary_fwd / _bwd (rfa_qk_token_norm_rotary_freqs_fwd / _bwd): apply_qk_token_norm_rotary_freqs
+    serves_mla_rotary = True         # mla_rotary_fwd / _bwd (include/rfa.h: rfa_mla_rotary_fwd / _bwd): ring_flash_attn.apply_mla_rotary
     serves_dropout_positions = True  # `dropout=` takes the position maps (q_map, k_map): what dropout over a dense ring, zigzag or stripe schedule needs
 
     def __init__(self):
@@ -754,6 +755,65 @@ class HipBackend:
         a.rot_offset, a.interleaved, a.conj = int(rot_offset), int(bool(interleaved)), int(bool(conj))
         self._row_positions(a, "rotary", positions, pos_map)
         _C.check(self.lib.rfa_rotary(C.byref(a), _stream(srcs[0])), "rfa_rotary")
+
+    # ------------------------------------------------------------------ MLA k / v assembly + rotary (apply_mla_rotary)
+    @staticmethod
+    def _mla_tensor(d, who, t, lead, heads, width, dtype):
+        """one rfa_mla_rotary_tensor from `t` of shape lead + (heads, width), or lead + (width,) for heads = None; a tensor
+        that is None stays NULL"""
+        if t is None:
+            return
+        want = tuple(lead) + ((width,) if heads is None else (heads, width))
+        if t.dtype != dtype or t.stride(-1) != 1 or (tuple(t.shape) != want and not (heads is None and tuple(t.shape) == tuple(lead) + (1, width))):
+            raise ValueError(f"{who}: expected a {dtype} tensor of shape {want} with last stride 1, got {tuple(t.shape)} {t.dtype}")
+        # (the stride of a dimension of length 1 is never used: 0, whatever torch reports for it)
+        st = [s_ if n > 1 else 0 for n, s_ in zip(t.shape, t.stride())]
+        d.ptr = t.data_ptr()
+        d.batch, d.row = (st[0] if len(lead) == 2 else 0), st[len(lead) - 1]
+        d.head = 0 if heads is None else st[len(lead)]
+
+    def _mla_rotary(self, a, who, names, tensors, heads, cos, sin, dims, positions, pos_map, interleaved):
+        """the fields both directions share: dims = (Dn, Dv); heads = (Hq, H); tensors in the struct's order, the first two q's"""
+        first = next(t for t in tensors if t is not None)              # (never k_pe / dk_pe: a tensor with heads precedes them)
+        self._check_dev(cos, sin, positions, *tensors)
+        self._row_tables(a, who, cos, sin)                             # (a.R: not a field of these structs — their Dr, below)
+        Dn, Dv = int(dims[0]), int(dims[1])
+        Hq, H = int(heads[0]), int(heads[1])
+        lead = tuple(first.shape[:-2])
+        if len(lead) not in (1, 2):
+            raise ValueError(f"{who}: tensors are (B, S, H, D) or packed (T, H, D)")
+        a.B, a.S = (1, lead[0]) if len(lead) == 1 else lead
+        a.dtype, a.Dn, a.Dr, a.Dv, a.H, a.Hq, a.interleaved = self._dtype(first), Dn, a.R, Dv, H, Hq, int(bool(interleaved))
+        shapes = [(Hq, Dn + a.R), (Hq, Dn + a.R), (H, Dn + Dv), (None, a.R), (H, Dn + a.R), (H, Dv)]
+        if names[0] == "dq_out":                                       # backward: dq_out, dq, dk, dv, dkv, dk_pe
+            shapes = [shapes[0], shapes[1], shapes[4], shapes[5], shapes[2], shapes[3]]
+        for name, t, (h, w) in zip(names, tensors, shapes):
+            self._mla_tensor(getattr(a, name), f"{who}: {name}", t, lead, h, w, first.dtype)
+        self._row_positions(a, who, positions, pos_map)
+        return first
+
+    def mla_rotary_fwd(self, q, q_out, kv, k_pe, k, v, cos, sin, *, nope_dim, positions=None, pos_map=None, interleaved=False):
+        """one launch of MLA's k / v assembly fused with the rotary embedding (include/rfa.h: rfa_mla_rotary_fwd).  q / q_out
+        (.., Hq, Dn + Dr) or both None; kv (.., H, Dn + Dv); k_pe (.., 1, Dr) or (.., Dr); k (.., H, Dn + Dr), v (.., H, Dv) are
+        written; `..` is (B, S) or packed (T,).  Any strides with last stride 1 and 16-byte aligned rows.  cos / sin, positions
+        and pos_map as in `rotary`; Dn = nope_dim, Dr from the tables, Dv from kv."""
+        a = _C.MlaRotaryArgs()
+        names = ("q", "q_out", "kv", "k_pe", "k", "v")
+        first = self._mla_rotary(a, "mla_rotary_fwd", names, [q, q_out, kv, k_pe, k, v], (0 if q is None else q.shape[-2], kv.shape[-2]),
+                                 cos, sin, (nope_dim, kv.shape[-1] - int(nope_dim)), positions, pos_map, interleaved)
+        _C.check(self.lib.rfa_mla_rotary_fwd(C.byref(a), _stream(first)), "rfa_mla_rotary_fwd")
+
+    def mla_rotary_bwd(self, dq_out, dq, dk, dv, dkv, dk_pe, cos, sin, *, nope_dim, v_dim, heads, positions=None, pos_map=None,
+                       interleaved=False):
+        """one launch of its backward (include/rfa.h: rfa_mla_rotary_bwd): dq_out -> dq (both None: no q), dk and dv -> dkv (a
+        None dk or dv leaves that part of dkv alone; dkv None: nothing of it), dk -> dk_pe = the conjugate rotation of the sum
+        over heads of dk's rope columns (None: not computed).  heads: H of dk / dv / dkv."""
+        a = _C.MlaRotaryBwdArgs()
+        names = ("dq_out", "dq", "dk", "dv", "dkv", "dk_pe")
+        first = self._mla_rotary(a, "mla_rotary_bwd", names, [dq_out, dq, dk, dv, dkv, dk_pe],
+                                 (0 if dq_out is None else dq_out.shape[-2], heads), cos, sin, (nope_dim, v_dim), positions, pos_map,
+                                 interleaved)
+        _C.check(self.lib.rfa_mla_rotary_bwd(C.byref(a), _stream(first)), "rfa_mla_rotary_bwd")
 
     # ------------------------------------------------------------------ rotary embedding, angles in the kernel (apply_rotary_freqs)
     def rotary_freqs(self, srcs, dsts, inv_freq, *, scaling=1.0, freq_axis=None, positions=None, pos_map=None, interleaved=False,
