@@ -1083,6 +1083,68 @@ typedef struct {
 int rfa_mla_rotary_fwd(const rfa_mla_rotary_args *args, void *stream);
 int rfa_mla_rotary_bwd(const rfa_mla_rotary_bwd_args *args, void *stream);
 
+/* The K / V assembly of multi-head latent attention fused with a rotary embedding whose angles are formed in the kernel
+ * (ring_flash_attn.apply_mla_rotary_freqs; csrc/rfa_mlaropefreq.hip) — DeepSeek-V2 / V3 / R1 and Kimi K2 with their YaRN
+ * attention_scaling and without (P, Dr/2) tables of the unsharded sequence on every rank.  Structs of their own; no existing
+ * struct, kernel or refusal changes (ABI 8 revision 1 stays).  Tensors, Dn / Dr / Dv, H / Hq, what each direction reads and
+ * writes, the NULL gradients, the order of the head sum and the stride contract are rfa_mla_rotary_fwd / _bwd's; inv_freq
+ * (Dr/2 fp32 numbers), scaling and the position fields are rfa_rotary_freqs's with ONE position per row (no axes), and so is
+ * the arithmetic of the angle: ang = (float)pos * inv_freq[c] rounded once, the precise cosf / sinf, times scaling, then
+ * rfa_rotary's rotation, each result rounded once (the backward conjugates the rotation itself).  q_out has the bits
+ * rfa_rotary_freqs gives with R = Dr, rot_offset = Dn; k's rope columns those it gives for k_pe, the same for every head.
+ * positions: int32, any value, not clamped — there is no table.  One launch per direction, no workspace, no atomics; two
+ * backward calls give the same bits.
+ * Checks, in this order and before any pointer is read: NULL struct RFA_ERR_NULL; struct_bytes != sizeof, reserved != 0,
+ * interleaved outside 0..1, a non-zero pad0 or pad, a scaling that is not finite or not > 0 RFA_ERR_ARGS; dtype RFA_ERR_DTYPE;
+ * Dn negative or not a multiple of 8, Dr not a positive multiple of 16 (interleaved: of 8), Dv not a positive multiple of 8,
+ * Dn + Dr or Dv above 256 RFA_ERR_HEAD_DIM; B < 0, S < 0, B * S above 2^31 - 1 RFA_ERR_SHAPE; H <= 0 or Hq < 0 RFA_ERR_HEADS;
+ * B S H (Dn + Dr + Dv) / 8 or rfa_rotary's unit count of q above 2^31 - 1 RFA_ERR_SHAPE; B == 0 or S == 0: RFA_OK, nothing is
+ * launched; a NULL inv_freq, forward: a NULL kv, k_pe, k or v, or with Hq > 0 q or q_out, backward: with Hq > 0 a NULL dq_out or
+ * dq, a dkv with neither dk nor dv, a dk_pe without dk, or nothing to do at all (Hq == 0, no dkv, no dk_pe) RFA_ERR_NULL; tensor
+ * pointers or strides off the 16-byte contract, or an inv_freq off 4 bytes, RFA_ERR_ALIGN; a pos_offset beyond +-2^40, a
+ * negative pos_batch, and with the map a negative pos_stride, a pos_split outside 0..S-1 or a position outside [0, 2^31 - 1]
+ * RFA_ERR_ARGS. */
+typedef struct {
+  uint32_t struct_bytes;   /* sizeof(rfa_mla_rotary_freqs_args) */
+  uint32_t reserved;       /* 0 */
+  int32_t B, S;            /* packed input: B = 1, S = T */
+  int32_t dtype;           /* rfa_dtype */
+  int32_t Dn, Dr, Dv;
+  int32_t H, Hq;           /* heads of kv / k / v; of q (0: no q) */
+  int32_t interleaved;
+  int32_t pad0;            /* 0 (where rfa_mla_rotary_args has table_dtype) */
+  rfa_mla_rotary_tensor q, q_out, kv, k_pe, k, v;
+  const float *inv_freq;   /* (Dr/2,) fp32, contiguous */
+  float scaling;           /* multiplies cos and sin; finite, > 0 */
+  int32_t pad;             /* 0 */
+  const int32_t *positions; /* (B, S) / (S,) int32, or NULL: the map */
+  int64_t pos_batch;       /* elements between two batch entries of positions (0 = shared) */
+  int64_t pos_offset;      /* added to positions[], or the map's first offset */
+  int32_t pos_stride, pos_split;
+  int64_t pos_offset2;
+} rfa_mla_rotary_freqs_args;
+typedef struct {
+  uint32_t struct_bytes;   /* sizeof(rfa_mla_rotary_freqs_bwd_args) */
+  uint32_t reserved;       /* 0 */
+  int32_t B, S;
+  int32_t dtype;
+  int32_t Dn, Dr, Dv;
+  int32_t H, Hq;           /* Hq 0: no dq_out / dq */
+  int32_t interleaved;
+  int32_t pad0;
+  rfa_mla_rotary_tensor dq_out, dq, dk, dv, dkv, dk_pe; /* dq_out, dk, dv read; dq, dkv, dk_pe written */
+  const float *inv_freq;
+  float scaling;
+  int32_t pad;
+  const int32_t *positions;
+  int64_t pos_batch;
+  int64_t pos_offset;
+  int32_t pos_stride, pos_split;
+  int64_t pos_offset2;
+} rfa_mla_rotary_freqs_bwd_args;
+int rfa_mla_rotary_freqs_fwd(const rfa_mla_rotary_freqs_args *args, void *stream);
+int rfa_mla_rotary_freqs_bwd(const rfa_mla_rotary_freqs_bwd_args *args, void *stream);
+
 /* Per-head max attention logit (QK-Clip / MuonClip; Transformer Engine's and Megatron's `max_logit`): for every query head h
  *     max_logit[h] = max over batch b, query row i and the keys j that row i SEES of  softmax_scale * q[b,i,h,:] . k[b,j,h/G,:]
  * for one block call — the raw scaled dot product (no soft cap, bias, dropout or sink enters it), -inf for a head that sees no

@@ -28,9 +28,9 @@ SELFTEST_BIN = os.path.join(ROOT, "tests", "native", "selftest")
 
 HIP_SOURCES = ["rfa_fwd.hip", "rfa_bwd.hip", "rfa_bigd.hip", "rfa_dqs.hip", "rfa_aux.hip", "rfa_sink.hip", "rfa_seqhead.hip",
                "rfa_maxlogit.hip", "rfa_mergepair.hip", "rfa_vdim.hip", "rfa_rotary.hip", "rfa_qknorm.hip", "rfa_qktoken.hip",
-               "rfa_rotfreq.hip", "rfa_qknormfreq.hip", "rfa_qktokenfreq.hip", "rfa_mlarope.hip"]
+               "rfa_rotfreq.hip", "rfa_qknormfreq.hip", "rfa_qktokenfreq.hip", "rfa_mlarope.hip", "rfa_mlaropefreq.hip"]
 API_SOURCE = "rfa_api.cpp"
-HEADERS = ["rfa_common.hpp", "rfa_kernels.hpp", "rfa_seqhead_index.h", "rfa_rotary_index.h", "rfa_rotary_math.hpp", "rfa_rotfreq_index.h", "rfa_qknorm_index.h", "rfa_qknorm_math.hpp", "rfa_qknormfreq_index.h", "rfa_qktoken_index.h", "rfa_qktoken_math.hpp", "rfa_mlarope_index.h", "rfa_maxlogit_band.h", "rfa_rowrange.h", "rfa_blockmask.h", os.path.join(ROOT, "include", "rfa.h")]
+HEADERS = ["rfa_common.hpp", "rfa_kernels.hpp", "rfa_seqhead_index.h", "rfa_rotary_index.h", "rfa_rotary_math.hpp", "rfa_rotfreq_index.h", "rfa_qknorm_index.h", "rfa_qknorm_math.hpp", "rfa_qknormfreq_index.h", "rfa_qktoken_index.h", "rfa_qktoken_math.hpp", "rfa_mlarope_index.h", "rfa_mlarope_stream.hpp", "rfa_maxlogit_band.h", "rfa_rowrange.h", "rfa_blockmask.h", os.path.join(ROOT, "include", "rfa.h")]
 EXPORTS_MAP = "rfa_exports.map"          # linker version script: only rfa_* is bindable
 
 

@@ -1809,20 +1809,27 @@ static bool mla_aligned(const rfa_mla_rotary_tensor& t) {
   return !t.ptr || (aligned16(t.ptr) && (t.batch % 8) == 0 && (t.row % 8) == 0 && (t.head % 8) == 0);
 }
 
-// the stages both directions share, in the header's order, up to "no rows": *go is false where the call is done.  Fills the
-// geometry of p; q_src / q_dst: the tensors of the q stream (strides only — no pointer is read)
+// NULL, then ARGS: the struct itself
 template <typename A>
-static int mla_check(const A* a, const rfa_mla_rotary_tensor A::*q_src, const rfa_mla_rotary_tensor A::*q_dst, MlaRopeParams* p, bool* go) {
-  *go = false;
+static int mla_check_struct(const A* a) {
   if (!a) return RFA_ERR_NULL;
   if (a->struct_bytes != sizeof(A) || a->reserved != 0) return RFA_ERR_ARGS;
   if (a->interleaved < 0 || a->interleaved > 1) return RFA_ERR_ARGS;
+  return RFA_OK;
+}
+
+// the stages all four entry points share behind it, in the header's order, up to "no rows": *go is false where the call is done.
+// P: the rows of the tables (1 where no table is looked at).  Fills the geometry of p; q_src / q_dst: the tensors of the q
+// stream (strides only — no pointer is read)
+template <typename A>
+static int mla_check_dims(const A* a, const rfa_mla_rotary_tensor A::*q_src, const rfa_mla_rotary_tensor A::*q_dst, int64_t P,
+                          MlaRopeParams* p, bool* go) {
+  *go = false;
   if (a->dtype != RFA_BF16 && a->dtype != RFA_F16) return RFA_ERR_DTYPE;
-  if (a->table_dtype != a->dtype && a->table_dtype != RFA_ROTARY_TABLE_F32) return RFA_ERR_DTYPE;
   if (a->Dn < 0 || (a->Dn % 8) != 0 || a->Dr <= 0 || (a->Dr % (a->interleaved ? 8 : 16)) != 0 || a->Dv <= 0 || (a->Dv % 8) != 0)
     return RFA_ERR_HEAD_DIM;
   if (a->Dn > kMlaRopeMaxRot - a->Dr || a->Dr > kMlaRopeMaxRot || a->Dv > kMlaRopeMaxRot) return RFA_ERR_HEAD_DIM;
-  if (a->B < 0 || a->S < 0 || a->P < 1) return RFA_ERR_SHAPE;
+  if (a->B < 0 || a->S < 0 || P < 1) return RFA_ERR_SHAPE;
   const int64_t rows = (int64_t)a->B * a->S;
   if (rows > INT32_MAX) return RFA_ERR_SHAPE;
   if (a->H <= 0 || a->Hq < 0) return RFA_ERR_HEADS;
@@ -1843,47 +1850,106 @@ static int mla_check(const A* a, const rfa_mla_rotary_tensor A::*q_src, const rf
   *go = a->B != 0 && a->S != 0;
   return RFA_OK;
 }
+
+// the tensors of a forward (table or freqs struct): NULL, ALIGN, and their place in p
+template <typename A>
+static int mla_fwd_tensors(const A* a, bool tables_present, bool tables_aligned, MlaRopeParams* p) {
+  if (!tables_present || !a->kv.ptr || !a->k_pe.ptr || !a->k.ptr || !a->v.ptr) return RFA_ERR_NULL;
+  if (a->Hq > 0 && (!a->q.ptr || !a->q_out.ptr)) return RFA_ERR_NULL;
+  if (!tables_aligned || !mla_aligned(a->kv) || !mla_aligned(a->k_pe) || !mla_aligned(a->k) || !mla_aligned(a->v)) return RFA_ERR_ALIGN;
+  if (a->Hq > 0 && (!mla_aligned(a->q) || !mla_aligned(a->q_out))) return RFA_ERR_ALIGN;
+  if (a->Hq > 0) { p->q = a->q.ptr; p->q_out = a->q_out.ptr; }
+  p->kv = a->kv.ptr; p->k_pe = a->k_pe.ptr; p->k = a->k.ptr; p->v = a->v.ptr;
+  p->kv_st = mla_strides(a->kv); p->k_pe_st = mla_strides(a->k_pe); p->k_st = mla_strides(a->k); p->v_st = mla_strides(a->v);
+  p->k_pe_st.sh = 0;
+  return RFA_OK;
+}
+
+// ... and of a backward
+template <typename A>
+static int mla_bwd_tensors(const A* a, bool tables_present, bool tables_aligned, MlaRopeParams* p) {
+  if (!tables_present) return RFA_ERR_NULL;
+  if (a->Hq > 0 && (!a->dq_out.ptr || !a->dq.ptr)) return RFA_ERR_NULL;
+  if (a->dkv.ptr && !a->dk.ptr && !a->dv.ptr) return RFA_ERR_NULL;
+  if (a->dk_pe.ptr && !a->dk.ptr) return RFA_ERR_NULL;
+  if (a->Hq == 0 && !a->dkv.ptr && !a->dk_pe.ptr) return RFA_ERR_NULL;
+  if (!tables_aligned || !mla_aligned(a->dk) || !mla_aligned(a->dv) || !mla_aligned(a->dkv) || !mla_aligned(a->dk_pe)) return RFA_ERR_ALIGN;
+  if (a->Hq > 0 && (!mla_aligned(a->dq_out) || !mla_aligned(a->dq))) return RFA_ERR_ALIGN;
+  if (a->Hq > 0) { p->q = a->dq_out.ptr; p->q_out = a->dq.ptr; }
+  p->kv = a->dkv.ptr; p->k_pe = a->dk_pe.ptr; p->k = a->dk.ptr; p->v = a->dv.ptr;
+  p->kv_st = mla_strides(a->dkv); p->k_pe_st = mla_strides(a->dk_pe); p->k_st = mla_strides(a->dk); p->v_st = mla_strides(a->dv);
+  p->k_pe_st.sh = 0;
+  return RFA_OK;
+}
+
+// the table entry points: everything up to the launch.  tensors: mla_fwd_tensors / mla_bwd_tensors
+template <typename A, typename F>
+static int mla_tables(const A* a, const rfa_mla_rotary_tensor A::*q_src, const rfa_mla_rotary_tensor A::*q_dst, F tensors, MlaRopeParams* p,
+                      bool* go) {
+  *go = false;
+  if (int rc = mla_check_struct(a)) return rc;
+  if (a->table_dtype != a->dtype && a->table_dtype != RFA_ROTARY_TABLE_F32) return RFA_ERR_DTYPE;   // (dtype itself: below, the same code)
+  if (int rc = mla_check_dims(a, q_src, q_dst, a->P, p, go)) return rc;
+  if (!*go) return RFA_OK;
+  if (int rc = tensors(a, a->cos && a->sin, aligned16(a->cos) && aligned16(a->sin), p)) return rc;
+  if (int rc = row_pos_map(a, p, a->P - 1, true)) return rc;
+  p->cos = a->cos; p->sin = a->sin; p->P = a->P;
+  return RFA_OK;
+}
+
+// the entry points whose kernel forms the angles (csrc/rfa_mlaropefreq.hip): rfa_rotary_freqs's rules where the tables were
+template <typename A, typename F>
+static int mla_freqs(const A* a, const rfa_mla_rotary_tensor A::*q_src, const rfa_mla_rotary_tensor A::*q_dst, F tensors,
+                     MlaRopeFreqParams* p, bool* go) {
+  *go = false;
+  if (int rc = mla_check_struct(a)) return rc;
+  if (a->pad0 != 0 || a->pad != 0 || !(a->scaling > 0.f) || !(a->scaling <= FLT_MAX)) return RFA_ERR_ARGS;
+  if (int rc = mla_check_dims(a, q_src, q_dst, 1, p, go)) return rc;
+  if (!*go) return RFA_OK;
+  if (int rc = tensors(a, a->inv_freq != nullptr, (reinterpret_cast<uintptr_t>(a->inv_freq) & 3) == 0, p)) return rc;
+  // (an offset beyond 2^40 names no position that fp32 resolves; refused with tensor positions too, so that the kernel's sum
+  // cannot overflow)
+  if (a->pos_offset < -(1ll << 40) || a->pos_offset > (1ll << 40)) return RFA_ERR_ARGS;
+  if (int rc = row_pos_map(a, p, INT32_MAX, true)) return rc;
+  p->inv_freq = a->inv_freq; p->scaling = a->scaling;
+  return RFA_OK;
+}
 }  // extern "C++"
 
 int rfa_mla_rotary_fwd(const rfa_mla_rotary_args* a, void* stream) {
   MlaRopeParams p{};
   bool go;
-  if (int rc = mla_check(a, &rfa_mla_rotary_args::q, &rfa_mla_rotary_args::q_out, &p, &go)) return rc;
+  if (int rc = mla_tables(a, &rfa_mla_rotary_args::q, &rfa_mla_rotary_args::q_out, mla_fwd_tensors<rfa_mla_rotary_args>, &p, &go)) return rc;
   if (!go) return RFA_OK;
-  if (!a->cos || !a->sin || !a->kv.ptr || !a->k_pe.ptr || !a->k.ptr || !a->v.ptr) return RFA_ERR_NULL;
-  if (a->Hq > 0 && (!a->q.ptr || !a->q_out.ptr)) return RFA_ERR_NULL;
-  if (!aligned16(a->cos) || !aligned16(a->sin) || !mla_aligned(a->kv) || !mla_aligned(a->k_pe) || !mla_aligned(a->k) || !mla_aligned(a->v))
-    return RFA_ERR_ALIGN;
-  if (a->Hq > 0 && (!mla_aligned(a->q) || !mla_aligned(a->q_out))) return RFA_ERR_ALIGN;
-  if (int rc = row_pos_map(a, &p, a->P - 1, true)) return rc;
-  if (a->Hq > 0) { p.q = a->q.ptr; p.q_out = a->q_out.ptr; }
-  p.kv = a->kv.ptr; p.k_pe = a->k_pe.ptr; p.k = a->k.ptr; p.v = a->v.ptr;
-  p.kv_st = mla_strides(a->kv); p.k_pe_st = mla_strides(a->k_pe); p.k_st = mla_strides(a->k); p.v_st = mla_strides(a->v);
-  p.k_pe_st.sh = 0;
-  p.cos = a->cos; p.sin = a->sin; p.P = a->P;
   return launch_mla_rotary_fwd(p, a->dtype, a->table_dtype == RFA_ROTARY_TABLE_F32, (hipStream_t)stream) ? RFA_ERR_LAUNCH : RFA_OK;
 }
 
 int rfa_mla_rotary_bwd(const rfa_mla_rotary_bwd_args* a, void* stream) {
   MlaRopeParams p{};
   bool go;
-  if (int rc = mla_check(a, &rfa_mla_rotary_bwd_args::dq_out, &rfa_mla_rotary_bwd_args::dq, &p, &go)) return rc;
+  if (int rc = mla_tables(a, &rfa_mla_rotary_bwd_args::dq_out, &rfa_mla_rotary_bwd_args::dq, mla_bwd_tensors<rfa_mla_rotary_bwd_args>, &p, &go))
+    return rc;
   if (!go) return RFA_OK;
-  if (!a->cos || !a->sin) return RFA_ERR_NULL;
-  if (a->Hq > 0 && (!a->dq_out.ptr || !a->dq.ptr)) return RFA_ERR_NULL;
-  if (a->dkv.ptr && !a->dk.ptr && !a->dv.ptr) return RFA_ERR_NULL;
-  if (a->dk_pe.ptr && !a->dk.ptr) return RFA_ERR_NULL;
-  if (a->Hq == 0 && !a->dkv.ptr && !a->dk_pe.ptr) return RFA_ERR_NULL;
-  if (!aligned16(a->cos) || !aligned16(a->sin) || !mla_aligned(a->dk) || !mla_aligned(a->dv) || !mla_aligned(a->dkv) || !mla_aligned(a->dk_pe))
-    return RFA_ERR_ALIGN;
-  if (a->Hq > 0 && (!mla_aligned(a->dq_out) || !mla_aligned(a->dq))) return RFA_ERR_ALIGN;
-  if (int rc = row_pos_map(a, &p, a->P - 1, true)) return rc;
-  if (a->Hq > 0) { p.q = a->dq_out.ptr; p.q_out = a->dq.ptr; }
-  p.kv = a->dkv.ptr; p.k_pe = a->dk_pe.ptr; p.k = a->dk.ptr; p.v = a->dv.ptr;
-  p.kv_st = mla_strides(a->dkv); p.k_pe_st = mla_strides(a->dk_pe); p.k_st = mla_strides(a->dk); p.v_st = mla_strides(a->dv);
-  p.k_pe_st.sh = 0;
-  p.cos = a->cos; p.sin = a->sin; p.P = a->P;
   return launch_mla_rotary_bwd(p, a->dtype, a->table_dtype == RFA_ROTARY_TABLE_F32, (hipStream_t)stream) ? RFA_ERR_LAUNCH : RFA_OK;
+}
+
+int rfa_mla_rotary_freqs_fwd(const rfa_mla_rotary_freqs_args* a, void* stream) {
+  MlaRopeFreqParams p{};
+  bool go;
+  if (int rc = mla_freqs(a, &rfa_mla_rotary_freqs_args::q, &rfa_mla_rotary_freqs_args::q_out, mla_fwd_tensors<rfa_mla_rotary_freqs_args>, &p, &go))
+    return rc;
+  if (!go) return RFA_OK;
+  return launch_mla_rotary_freqs_fwd(p, a->dtype, (hipStream_t)stream) ? RFA_ERR_LAUNCH : RFA_OK;
+}
+
+int rfa_mla_rotary_freqs_bwd(const rfa_mla_rotary_freqs_bwd_args* a, void* stream) {
+  MlaRopeFreqParams p{};
+  bool go;
+  if (int rc = mla_freqs(a, &rfa_mla_rotary_freqs_bwd_args::dq_out, &rfa_mla_rotary_freqs_bwd_args::dq,
+                         mla_bwd_tensors<rfa_mla_rotary_freqs_bwd_args>, &p, &go))
+    return rc;
+  if (!go) return RFA_OK;
+  return launch_mla_rotary_freqs_bwd(p, a->dtype, (hipStream_t)stream) ? RFA_ERR_LAUNCH : RFA_OK;
 }
 
 // ---- the QK RMSNorms + rotary: per head (csrc/rfa_qknorm.hip, rfa_qknormfreq.hip) and over all heads of a token

@@ -439,6 +439,16 @@ struct MlaRopeParams {
 int launch_mla_rotary_fwd(const MlaRopeParams& p, int dtype, bool table_f32, hipStream_t stream);
 int launch_mla_rotary_bwd(const MlaRopeParams& p, int dtype, bool table_f32, hipStream_t stream);
 
+// MLA K / V assembly fused with a rotary embedding whose angles are formed in the kernel (rfa_mlaropefreq.hip; streams and head
+// sum: rfa_mlarope_stream.hpp, unchanged): MlaRopeParams' tensors, geometry and position map — cos, sin and P stay zero, and no
+// position is clamped — with the angle's fields of RotFreqParams, one position per row.
+struct MlaRopeFreqParams : MlaRopeParams {
+  const float* inv_freq;    // (Dr/2,)
+  float scaling;            // multiplies cos and sin
+};
+int launch_mla_rotary_freqs_fwd(const MlaRopeFreqParams& p, int dtype, hipStream_t stream);
+int launch_mla_rotary_freqs_bwd(const MlaRopeFreqParams& p, int dtype, hipStream_t stream);
+
 // per-head max attention logit (rfa_maxlogit.hip; tile arithmetic: rfa_maxlogit_band.h): the forward's S phase alone.
 // Workgroup (batch b, query block qb, head h) stores the max of its UNSCALED visible scores to
 // partial[h * nparts + b * nqblk + qb] (-inf: it saw nothing), nparts = B * nqblk; maxlogit_finish_kernel folds a head's

@@ -390,6 +390,22 @@ class MlaRotaryBwdArgs(_SizedStructure):
     _fields_ = _MLA_ROTARY_HEAD + [(n, MlaRotaryTensor) for n in ("dq_out", "dq", "dk", "dv", "dkv", "dk_pe")] + _MLA_ROTARY_TAIL
 
 
+_MLA_ROTARY_FREQS_HEAD = _MLA_ROTARY_HEAD[:-1] + [("pad0", C.c_int32)]
+_MLA_ROTARY_FREQS_TAIL = [("inv_freq", C.c_void_p), ("scaling", C.c_float), ("pad", C.c_int32)] + _MLA_ROTARY_TAIL[3:]
+
+
+class MlaRotaryFreqsArgs(_SizedStructure):
+    """rfa_mla_rotary_freqs_args: MLA's k / v assembly fused with a rotary embedding whose angles the kernel forms, forward —
+    rfa_mla_rotary_args with inv_freq, scaling and zero pads where the tables were; struct_bytes is filled in here"""
+    _fields_ = _MLA_ROTARY_FREQS_HEAD + [(n, MlaRotaryTensor) for n in ("q", "q_out", "kv", "k_pe", "k", "v")] + _MLA_ROTARY_FREQS_TAIL
+
+
+class MlaRotaryFreqsBwdArgs(_SizedStructure):
+    """rfa_mla_rotary_freqs_bwd_args: the same fields with the gradients in the tensors' places"""
+    _fields_ = _MLA_ROTARY_FREQS_HEAD + [(n, MlaRotaryTensor) for n in ("dq_out", "dq", "dk", "dv", "dkv", "dk_pe")] + \
+        _MLA_ROTARY_FREQS_TAIL
+
+
 class MaxLogitArgs(_SizedStructure):
     """rfa_max_logit_args: the per-head max attention logit of one block call; struct_bytes is filled in here"""
     _fields_ = [
@@ -539,6 +555,8 @@ SYMBOLS = {
     "rfa_qk_token_norm_rotary_freqs_bwd_workspace_bytes": (C.c_int64, [C.POINTER(QkTokenNormRotaryFreqsBwdArgs)]),
     "rfa_mla_rotary_fwd": (C.c_int, [C.POINTER(MlaRotaryArgs), C.c_void_p]),
     "rfa_mla_rotary_bwd": (C.c_int, [C.POINTER(MlaRotaryBwdArgs), C.c_void_p]),
+    "rfa_mla_rotary_freqs_fwd": (C.c_int, [C.POINTER(MlaRotaryFreqsArgs), C.c_void_p]),
+    "rfa_mla_rotary_freqs_bwd": (C.c_int, [C.POINTER(MlaRotaryFreqsBwdArgs), C.c_void_p]),
     "rfa_max_logit": (C.c_int, [C.POINTER(MaxLogitArgs), C.c_void_p]),
     "rfa_max_logit_workspace_bytes": (C.c_int64, [C.POINTER(MaxLogitArgs)]),
     "rfa_bwd_preprocess_lse": (C.c_int, [C.POINTER(BwdPreLseArgs), C.c_void_p]),
@@ -612,7 +630,7 @@ def load():
     if not hasattr(lib, "rfa_rotary"):
         raise RuntimeError("ring_flash_attn: librfa_hip.so has no rfa_rotary (the rotary embedding entry point); rebuild")
     # ... and MLA's k / v assembly fused with it (structs of their own)
-    for name in ("rfa_mla_rotary_fwd", "rfa_mla_rotary_bwd"):
+    for name in ("rfa_mla_rotary_fwd", "rfa_mla_rotary_bwd", "rfa_mla_rotary_freqs_fwd", "rfa_mla_rotary_freqs_bwd"):
         if not hasattr(lib, name):
             raise RuntimeError(f"ring_flash_attn: librfa_hip.so has no {name} (the MLA rotary entry points); rebuild")
     for name, (res, args) in SYMBOLS.items():

@@ -101,4 +101,6 @@ from .qk_norm import apply_qk_token_norm_rotary_freqs
 # multi-head latent attention (DeepSeek-V2 / V3, Kimi K2) between its projections and the 192 / 128 attention call:
 # apply_mla_rotary(q, kv, k_pe, cos, sin, layout=func, group=group) rotates q's rope columns and assembles k = [k_nope | rope(k_pe)]
 # and v from kv in one launch per direction, with a reproducible sum over heads for dk_pe
-from .mla import apply_mla_rotary
+# apply_mla_rotary_freqs(q, kv, k_pe, inv_freq, attention_scaling=..., layout=func, group=group) is the same call without tables: the
+# kernel forms the angles (YaRN's attention_scaling; no table of the unsharded sequence on every rank)
+from .mla import apply_mla_rotary, apply_mla_rotary_freqs

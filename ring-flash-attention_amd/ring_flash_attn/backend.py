@@ -105,6 +105,7 @@ class HipBackend:
     serves_qk_token_norm = True      # qk_token_norm_rotary_fwd / _bwd (include/rfa.h: rfa_qk_token_norm_rotary_fwd / _bwd): apply_qk_token_norm_rotary
     serves_qk_token_norm_freqs = True  # qk_token_norm_freqs_rotary_fwd / _bwd (rfa_qk_token_norm_rotary_freqs_fwd / _bwd): apply_qk_token_norm_rotary_freqs
     serves_mla_rotary = True         # mla_rotary_fwd / _bwd (include/rfa.h: rfa_mla_rotary_fwd / _bwd): ring_flash_attn.apply_mla_rotary
+    serves_mla_rotary_freqs = True   # mla_rotary_freqs_fwd / _bwd (include/rfa.h: rfa_mla_rotary_freqs_fwd / _bwd): ring_flash_attn.apply_mla_rotary_freqs
     serves_dropout_positions = True  # `dropout=` takes the position maps (q_map, k_map): what dropout over a dense ring, zigzag or stripe schedule needs
 
     def __init__(self):
@@ -772,11 +773,18 @@ class HipBackend:
         d.batch, d.row = (st[0] if len(lead) == 2 else 0), st[len(lead) - 1]
         d.head = 0 if heads is None else st[len(lead)]
 
-    def _mla_rotary(self, a, who, names, tensors, heads, cos, sin, dims, positions, pos_map, interleaved):
-        """the fields both directions share: dims = (Dn, Dv); heads = (Hq, H); tensors in the struct's order, the first two q's"""
+    def _mla_rotary(self, a, who, names, tensors, heads, tables, dims, positions, pos_map, interleaved, scaling=None):
+        """the fields both directions share: dims = (Dn, Dv); heads = (Hq, H); tensors in the struct's order, the first two q's;
+        tables = (cos, sin), or (inv_freq,) with `scaling` for the structs whose kernel forms the angles"""
         first = next(t for t in tensors if t is not None)              # (never k_pe / dk_pe: a tensor with heads precedes them)
-        self._check_dev(cos, sin, positions, *tensors)
-        self._row_tables(a, who, cos, sin)                             # (a.R: not a field of these structs — their Dr, below)
+        self._check_dev(*tables, positions, *tensors)
+        if len(tables) == 2:
+            self._row_tables(a, who, *tables)                          # (a.R: not a field of these structs — their Dr, below)
+        else:
+            inv_freq, = tables
+            if inv_freq.dtype != torch.float32 or inv_freq.dim() != 1 or not inv_freq.is_contiguous():
+                raise ValueError(f"{who}: inv_freq is a contiguous fp32 (Dr/2,) tensor")
+            a.R, a.inv_freq, a.scaling = 2 * inv_freq.shape[0], inv_freq.data_ptr(), float(scaling)
         Dn, Dv = int(dims[0]), int(dims[1])
         Hq, H = int(heads[0]), int(heads[1])
         lead = tuple(first.shape[:-2])
@@ -800,7 +808,7 @@ class HipBackend:
         a = _C.MlaRotaryArgs()
         names = ("q", "q_out", "kv", "k_pe", "k", "v")
         first = self._mla_rotary(a, "mla_rotary_fwd", names, [q, q_out, kv, k_pe, k, v], (0 if q is None else q.shape[-2], kv.shape[-2]),
-                                 cos, sin, (nope_dim, kv.shape[-1] - int(nope_dim)), positions, pos_map, interleaved)
+                                 (cos, sin), (nope_dim, kv.shape[-1] - int(nope_dim)), positions, pos_map, interleaved)
         _C.check(self.lib.rfa_mla_rotary_fwd(C.byref(a), _stream(first)), "rfa_mla_rotary_fwd")
 
     def mla_rotary_bwd(self, dq_out, dq, dk, dv, dkv, dk_pe, cos, sin, *, nope_dim, v_dim, heads, positions=None, pos_map=None,
@@ -811,9 +819,32 @@ class HipBackend:
         a = _C.MlaRotaryBwdArgs()
         names = ("dq_out", "dq", "dk", "dv", "dkv", "dk_pe")
         first = self._mla_rotary(a, "mla_rotary_bwd", names, [dq_out, dq, dk, dv, dkv, dk_pe],
-                                 (0 if dq_out is None else dq_out.shape[-2], heads), cos, sin, (nope_dim, v_dim), positions, pos_map,
+                                 (0 if dq_out is None else dq_out.shape[-2], heads), (cos, sin), (nope_dim, v_dim), positions, pos_map,
                                  interleaved)
         _C.check(self.lib.rfa_mla_rotary_bwd(C.byref(a), _stream(first)), "rfa_mla_rotary_bwd")
+
+    # ------------------------------------------------------------------ ... with the angles formed in the kernel (apply_mla_rotary_freqs)
+    def mla_rotary_freqs_fwd(self, q, q_out, kv, k_pe, k, v, inv_freq, *, nope_dim, scaling=1.0, positions=None, pos_map=None,
+                             interleaved=False):
+        """`mla_rotary_fwd` without tables (include/rfa.h: rfa_mla_rotary_freqs_fwd): the tensors are its own; inv_freq (Dr/2,)
+        fp32 contiguous, scaling multiplies cos and sin, positions int32 (S,) / (B,S) / (T,) of any value or None: pos_map, as
+        in `rotary_freqs` with one axis."""
+        a = _C.MlaRotaryFreqsArgs()
+        names = ("q", "q_out", "kv", "k_pe", "k", "v")
+        first = self._mla_rotary(a, "mla_rotary_freqs_fwd", names, [q, q_out, kv, k_pe, k, v],
+                                 (0 if q is None else q.shape[-2], kv.shape[-2]), (inv_freq,), (nope_dim, kv.shape[-1] - int(nope_dim)),
+                                 positions, pos_map, interleaved, scaling)
+        _C.check(self.lib.rfa_mla_rotary_freqs_fwd(C.byref(a), _stream(first)), "rfa_mla_rotary_freqs_fwd")
+
+    def mla_rotary_freqs_bwd(self, dq_out, dq, dk, dv, dkv, dk_pe, inv_freq, *, nope_dim, v_dim, heads, scaling=1.0, positions=None,
+                             pos_map=None, interleaved=False):
+        """one launch of its backward (include/rfa.h: rfa_mla_rotary_freqs_bwd): `mla_rotary_bwd`'s gradients and None rules"""
+        a = _C.MlaRotaryFreqsBwdArgs()
+        names = ("dq_out", "dq", "dk", "dv", "dkv", "dk_pe")
+        first = self._mla_rotary(a, "mla_rotary_freqs_bwd", names, [dq_out, dq, dk, dv, dkv, dk_pe],
+                                 (0 if dq_out is None else dq_out.shape[-2], heads), (inv_freq,), (nope_dim, v_dim), positions, pos_map,
+                                 interleaved, scaling)
+        _C.check(self.lib.rfa_mla_rotary_freqs_bwd(C.byref(a), _stream(first)), "rfa_mla_rotary_freqs_bwd")
 
     # ------------------------------------------------------------------ rotary embedding, angles in the kernel (apply_rotary_freqs)
     def rotary_freqs(self, srcs, dsts, inv_freq, *, scaling=1.0, freq_axis=None, positions=None, pos_map=None, interleaved=False,
